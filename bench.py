@@ -12,8 +12,20 @@ row update of both tables.  One retrieval "step" = Q queries against the whole
 catalog with per-query exclusion lists, k = 20.  Inputs are resident in HBM when the
 timed region starts.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: set-up, spin-up, W warm-up training steps, ONE timed
+region of exactly K training steps (no kernel timing events inside it), the outputs if asked for, the JSON line.
+``--full`` adds everything else the benchmark measures: the headline region repeated (median of MF_BENCH_REPS regions of K
+steps), the cold leg, HIP-event kernel spans and rooflines, the top-k retrieval leg, the SURVEY 8(d) matrix (``--no-extras``
+leaves it out) and the CPU baseline (``--no-cpu-baseline`` leaves it out).
+
+``--dump-outputs DIR``: after the timed steps, what the timed training step left its caller in the last step -- the loss
+it returned and rows of both tables it updated (the batch's own rows and a fixed seeded sample of each table, float32,
+~16 MB at the defaults, <= 64 MB in all) -- as ``DIR/<name>.npy``; with ``--full`` also the last timed top-k call's
+scores and indices.  Inputs are seeded: the same arguments give the same inputs on every run, so two builds can be
+compared output for output.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment: this process starts the N ranks itself, as FRESH child
 processes (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set), before it has made any GPU call, waits for them
@@ -29,8 +41,8 @@ the leg's dominant kernels on scratch data right in front of the W warm-up steps
 and the optimizer's moment tables are allocated at construction; K = 20 / W = 3 then reads the same 1.16 ms per step
 as K = 100 (without it: 1.26).  Defaults: K = 100, W = 10.
 
-Prints ONE JSON line (rank 0).  `value` is train pairs/s over all ranks; the top-k
-leg is reported beside it (`topk`), each with the roofline of its dominant kernel,
+Prints ONE JSON line (rank 0).  `value` is train pairs/s over all ranks, `ms_per_step` the milliseconds of one timed
+training step; with --full the top-k leg is reported beside it (`topk`), each with the roofline of its dominant kernel,
 and the CPU baseline (the oracle's restatement of the same step, torch CPU, all host
 cores, bounded sample) on rank 0 at N = 1.
 """
@@ -102,9 +114,14 @@ def parse_args():
     ap.add_argument("--queries", type=int, default=1024, help="queries per GPU per retrieval step")
     ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam")
     ap.add_argument("--num-negatives", type=int, default=0, help="0 = all in-batch negatives (sampled softmax)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline legs (no SURVEY 8(d) matrix)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline legs (no SURVEY 8(d) matrix)")
     ap.add_argument("--cpu-steps", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also repeat the timed region, time the cold leg, kernel spans / rooflines, the top-k leg, the SURVEY 8(d) "
+                         "matrix and the CPU baseline (a plain run times K training steps once and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     return ap.parse_args()
 
 
@@ -313,15 +330,59 @@ def spread(ms: list) -> dict:
     return {"n": len(ms), "median": round(srt[len(srt) // 2], 4), "min": round(srt[0], 4), "max": round(srt[-1], 4)}
 
 
+DUMP_BYTES = 64 << 20              # --dump-outputs writes at most this much in all
+DUMP_BATCH_ROWS = 16384            # rows of a table the last batch touched, at most (a fixed seeded sample beyond)
+DUMP_SAMPLE_ROWS = 4096            # rows of each whole table (a fixed seeded sample)
+
+
+def sample_rows(t: torch.Tensor, n: int, seed: int) -> torch.Tensor:
+    """A fixed seeded sample of `n` rows of `t` in row order (all of them when it has no more than `n`)."""
+    if t.shape[0] <= n:
+        return t
+    g = torch.Generator().manual_seed(seed)
+    return t[torch.randperm(t.shape[0], generator=g)[:n].sort().values.to(t.device)]
+
+
+def train_outputs(tables: dict, batch, loss) -> dict:
+    """What a caller of the timed training step holds after its last step: the loss it returned, the rows of both tables
+    that step's batch touched, as its update left them, and a fixed seeded sample of each whole table.  `batch`: None when
+    its ids are not rows of `tables` (a rank's shards)."""
+    out = {"loss": loss.detach().float().reshape(1)}
+    for seed, (side, table) in enumerate(tables.items()):
+        w = table.detach()
+        if batch is not None:
+            out[f"{side}_batch_rows"] = sample_rows(w[batch[side]], DUMP_BATCH_ROWS, 100 + seed)
+        out[f"{side}_table_sample"] = sample_rows(w, DUMP_SAMPLE_ROWS, 200 + seed)
+    return out
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """`arrays` as DIR/<name>.npy: floating point as float32 (float64 kept), integers as float64 (exact below 2^53)."""
+    import numpy as np
+
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (at most {DUMP_BYTES})")
+    d = pathlib.Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in host.items():
+        np.save(d / f"{name}.npy", a)
+
+
 def run_train_leg(mf, lib, device, *, batch: int, steps: int, warmup: int, optimizer: str = "adam", num_negatives: int = 0,
                   loss: str = "InfomationNoiseContrastiveEstimationLoss", num_users: int = NUM_USERS, num_items: int = NUM_ITEMS,
                   dim: int = DIM, pos_pad: int = POS_PAD, use_logq: bool = True, spin: bool = True, graph: bool = False,
-                  seed: int = 1000, reps: int = 1, batches=None, num_hashes: int = 0, id_space=None) -> dict:
+                  seed: int = 1000, reps: int = 1, batches=None, num_hashes: int = 0, id_space=None, kernel_spans: bool = True) -> dict:
     """One single-GPU training leg: fresh tables, `warmup` untimed steps, then `reps` timed regions of `steps` steps each
-    (the reported ms / step is the MEDIAN region); HIP-event spans of the dominant kernels every time_every(launches)-th launch.
+    (the reported ms / step is the MEDIAN region); HIP-event spans of the dominant kernels every time_every(launches)-th launch
+    (kernel_spans=False: none, no event inside the timed region).
     graph=True: the step is captured in a hipGraph and replayed.  `batches`: pre-built flat batches (else synthetic padded
     ones); `id_space` = (users, items): ranges the synthetic ids are drawn from when they differ from the table heights
-    (hash towers: ids far beyond the bucket counts)."""
+    (hash towers: ids far beyond the bucket counts).  `last_loss` / `last_batch`: the loss and batch of the last timed step."""
     n_batches = min(steps + warmup, 8)
     if batches is None:
         nu, ni = id_space if id_space is not None else (num_users, num_items)
@@ -337,17 +398,22 @@ def run_train_leg(mf, lib, device, *, batch: int, steps: int, warmup: int, optim
     for i in range(warmup):
         step(batches[i % n_batches])
     lib.mf_timing_reset()
-    if not graph:                                   # (event records inside a replayed graph would time nothing)
+    if kernel_spans and not graph:                  # (event records inside a replayed graph would time nothing)
         lib.mf_timing_enable(time_every(steps * max(reps, 1)))
-    ms = []
+    ms, last = [], {}
+
+    def timed_step(j):
+        last["batch"] = batches[j % n_batches]
+        last["loss"] = step(last["batch"])
+
     for r in range(reps):
-        dt = timed(lambda i, r=r: step(batches[(warmup + r * steps + i) % n_batches]), steps, False)
+        dt = timed(lambda i, r=r: timed_step(warmup + r * steps + i), steps, False)
         ms.append(dt / steps * 1e3)
     lib.mf_timing_enable(0)
-    spans = {n: kernel_span(lib, n)[0] for n in TRAIN_KERNELS}
+    spans = {n: kernel_span(lib, n)[0] for n in TRAIN_KERNELS} if kernel_spans else {}
     med = sorted(ms)[len(ms) // 2]
     return {"ms_per_step": med, "pairs_per_s": batch / (med * 1e-3), "reps_ms": ms, "spans": {k: v for k, v in spans.items() if v},
-            "trainer": trainer, "batches": batches}
+            "trainer": trainer, "batches": batches, "last_loss": last.get("loss"), "last_batch": last.get("batch")}
 
 
 def train_roofline(spans: dict, batch: int, dim: int, world: int, optimizer: str, update_launches: int = 1):
@@ -674,7 +740,8 @@ def main() -> None:
     mf = importlib.import_module("matrix-factorization-torch_amd")
     lib = mf._lib.lib()
     B, Q, K, W = args.batch, args.queries, args.steps, args.warmup
-    extras = {}
+    reps = REPS if args.full else 1             # timed regions of K steps (a plain run: exactly K timed steps)
+    extras, last = {}, {}
 
     # ------------------------------------------------------------------ training leg --
     cold_ms = None
@@ -703,7 +770,8 @@ def main() -> None:
             for b in batches:
                 b["user"] = trainer.user_lo + b["user"] % span_u
         # the sharded step prefetches the exchange plan of the batch after it (ids are known ahead)
-        run_step = lambda j: trainer.step(batches[j % n_batches], next_b=batches[(j + 1) % n_batches])  # noqa: E731
+        def run_step(j):
+            last["loss"] = trainer.step(batches[j % n_batches], next_b=batches[(j + 1) % n_batches])
         # everything that would stall the first sharded step happens before the spin-up: RCCL's lazy
         # initialisation (first collective) and the first batch's exchange plan (a host sync)
         warm = torch.zeros(world, dtype=torch.int64, device=device)
@@ -714,20 +782,25 @@ def main() -> None:
         for i in range(W):
             run_step(i)
         lib.mf_timing_reset()
-        lib.mf_timing_enable(time_every(K * REPS))
-        train_reps = [timed(lambda i, r=r: run_step(W + r * K + i), K, dist_on) / K * 1e3 for r in range(REPS)]
+        if args.full:
+            lib.mf_timing_enable(time_every(K * reps))
+        train_reps = [timed(lambda i, r=r: run_step(W + r * K + i), K, dist_on) / K * 1e3 for r in range(reps)]
         dt_train = sorted(train_reps)[len(train_reps) // 2] * K / 1e3
         lib.mf_timing_enable(0)
         trainer.finish()                        # deferred error flags (id range / exchange capacity) of the timed steps
         spans = {n: kernel_span(lib, n)[0] for n in TRAIN_KERNELS}
         spans = {k: v for k, v in spans.items() if v}
+        if args.dump_outputs and rank == 0:
+            write_outputs(args.dump_outputs, train_outputs({"user": trainer.user_table, "item": trainer.item_table}, None,
+                                                           last["loss"]))
     else:
-        # cold first: what a step costs right after the device has idled (no spin-up; DESIGN.md 4, "post-idle ramp")
-        time.sleep(0.05)
-        cold = run_train_leg(mf, lib, device, batch=B, steps=min(K, 20), warmup=min(W, 3), optimizer=args.optimizer,
-                             num_negatives=args.num_negatives, spin=False)
-        cold_ms = cold["ms_per_step"]
-        del cold
+        if args.full:
+            # cold first: what a step costs right after the device has idled (no spin-up; DESIGN.md 4, "post-idle ramp")
+            time.sleep(0.05)
+            cold = run_train_leg(mf, lib, device, batch=B, steps=min(K, 20), warmup=min(W, 3), optimizer=args.optimizer,
+                                 num_negatives=args.num_negatives, spin=False)
+            cold_ms = cold["ms_per_step"]
+            del cold
         # the reference's own inputs when the box has them (there is no network here, so normally it has not): the ids of a
         # MovieLens ratings file through the device batch producer, CSR positives, table heights from the data
         ml_batches, data_tag, ml_meta = None, "synthetic", None
@@ -738,13 +811,42 @@ def main() -> None:
             ml_batches = [flat_batch(sampler.batch(j)) for j in range(8)]
             data_tag = "movielens"
         leg = run_train_leg(mf, lib, device, batch=B, steps=K, warmup=W, optimizer=args.optimizer,
-                            num_negatives=args.num_negatives, spin=True, reps=REPS, batches=ml_batches,
+                            num_negatives=args.num_negatives, spin=True, reps=reps, batches=ml_batches, kernel_spans=args.full,
                             **({} if ml_meta is None else {"num_users": ml_meta["num_users"], "num_items": ml_meta["num_items"],
                                                            "use_logq": False}))
         dt_train, spans, trainer, batches = leg["ms_per_step"] * K / 1e3, leg["spans"], leg["trainer"], leg["batches"]
         train_reps = leg["reps_ms"]
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, train_outputs({s: trainer.towers[s].weight for s in ("user", "item")},
+                                                           leg["last_batch"], leg["last_loss"]))
+        del leg
     pairs_per_s = world * B * K / dt_train
     N = 2 * B
+    line = {
+        "metric": "train pairs/sec + full-catalog top-k queries/sec, ML-25M d=128",
+        "value": round(pairs_per_s, 1), "unit": "pairs/s", "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": round(dt_train / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": data_tag,
+        "config": {"workload": (f"MovieLens ratings file {ml_meta['path']} ({ml_meta['num_users'] - 1:,} users x "
+                                f"{ml_meta['num_items'] - 1:,} items, {ml_meta['train_pairs']:,} train pairs), d=128, InfoNCE, CSR positives, "
+                                if ml_meta else
+                                "C3: MovieLens-25M shape (162,541 users x 62,423 items), d=128, InfoNCE + logQ, ") +
+                               f"num_negatives={args.num_negatives}, row-{args.optimizer} update",
+                   "batch_per_gpu": B, "items_per_step": N, "pos_pad": POS_PAD,
+                   "parallelism": f"dp{world}" + (f" + both tables row-sharded, {trainer.user_mode} users" if dist_on else "")},
+        "rccl_ranks": trainer.comm.rccl_ranks if dist_on else None,
+        "transport": trainer.comm.transport if dist_on else "none (one process, one GPU)",
+        **({"comm_note": comm_note} if dist_on and comm_note else {}),
+        "full": args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist_on:
+            torch.distributed.destroy_process_group()
+        return
+
+    # ------------------------------------------------------------ --full from here on --
     train_roof = train_roofline(spans, B, DIM, world, args.optimizer, update_launches=2 if dist_on else 1)
 
     # ----------------------------------------------------------------- retrieval leg --
@@ -765,18 +867,25 @@ def main() -> None:
     if dist_on:
         searcher = mf.distributed.ShardedIndex(trainer.item_shard(), trainer.item_offset(), n_items_leg, stride=trainer.item_stride(),
                                                comm=trainer.comm)
-        run_topk = lambda i: searcher.search(queries, TOP_K, exclude_csr=csr)   # noqa: E731
+        search = searcher.search
     else:
         index = mf.retrieval.ItemIndex(items)
-        run_topk = lambda i: index.search(queries, TOP_K, exclude_csr=csr)      # noqa: E731
+        search = index.search
+
+    def run_topk(i):
+        last["topk"] = search(queries, TOP_K, exclude_csr=csr)
+
     spin_up(mf, device, "topk", index=mf.retrieval.ItemIndex(trainer.item_shard()) if dist_on else index)
     for i in range(W):
         run_topk(i)
     lib.mf_timing_reset()
-    lib.mf_timing_enable(time_every(K * REPS))
-    topk_reps = [timed(run_topk, K, dist_on) / K * 1e3 for _ in range(REPS)]
+    lib.mf_timing_enable(time_every(K * reps))
+    topk_reps = [timed(run_topk, K, dist_on) / K * 1e3 for _ in range(reps)]
     dt_topk = sorted(topk_reps)[len(topk_reps) // 2] * K / 1e3
     lib.mf_timing_enable(0)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"topk_scores": sample_rows(last["topk"][0], DUMP_BATCH_ROWS, 300),
+                                          "topk_indices": sample_rows(last["topk"][1], DUMP_BATCH_ROWS, 300)})
     qps = world * Q * K / dt_topk
     span, _n = kernel_span(lib, "topk_select")
     span_bf, _nb = kernel_span(lib, "topk_bf3")
@@ -925,22 +1034,8 @@ def main() -> None:
         cpu = cpu_baselines(args, cb, queries.cpu(), items.cpu(), pieces)
 
     if rank == 0:
-        line = {
-            "metric": "train pairs/sec + full-catalog top-k queries/sec, ML-25M d=128",
-            "value": round(pairs_per_s, 1), "unit": "pairs/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": round(dt_train / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": data_tag,
+        line.update({
             "reps_ms_per_step": spread(train_reps),      # REPS timed regions of K steps each; value / ms_per_step = the median one
-            "config": {"workload": (f"MovieLens ratings file {ml_meta['path']} ({ml_meta['num_users'] - 1:,} users x "
-                                    f"{ml_meta['num_items'] - 1:,} items, {ml_meta['train_pairs']:,} train pairs), d=128, InfoNCE, CSR positives, "
-                                    if ml_meta else
-                                    "C3: MovieLens-25M shape (162,541 users x 62,423 items), d=128, InfoNCE + logQ, ") +
-                                   f"num_negatives={args.num_negatives}, row-{args.optimizer} update",
-                       "batch_per_gpu": B, "items_per_step": N, "pos_pad": POS_PAD,
-                       "parallelism": f"dp{world}" + (f" + both tables row-sharded, {trainer.user_mode} users" if dist_on else "")},
-            "rccl_ranks": trainer.comm.rccl_ranks if dist_on else None,
-            "transport": trainer.comm.transport if dist_on else "none (one process, one GPU)",
-            **({"comm_note": comm_note} if dist_on and comm_note else {}),
             "cold_ms_per_step": None if cold_ms is None else round(cold_ms, 4),
             "roofline": train_roof,
             "topk": {"value": round(qps, 1), "unit": "queries/s", "ms_per_step": round(dt_topk / K * 1e3, 4),
@@ -948,7 +1043,7 @@ def main() -> None:
                      "roofline": topk_roof},
             "extras": extras,
             "cpu_baseline": cpu,
-        }
+        })
         # the second half of the headline metric and the other figures with a bar attached, as TOP-LEVEL scalars at the END
         # of the line: the driver's record keeps top-level scalars and the last 2 kB
         def dig(obj, *path):

@@ -1,8 +1,8 @@
 """Mean SQ counters per dispatch and kernel from a rocprofv3 PMC pass (rocpd database):
 
     rocprofv3 --pmc SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_ANY \
-              SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d gpurun_out/pmcS -o r -- python3 bench.py --steps 3 --warmup 1
-    python tools/pmc_sq.py gpurun_out/pmcS/r_results.db > profiles/r02_pmc_sq_summary.json
+              SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d out/pmcS -o r -- python3 bench.py --full --steps 3 --warmup 1
+    python tools/pmc_sq.py out/pmcS/r_results.db > profiles/r02_pmc_sq_summary.json
 
 mfma_pipe_busy_frac = MFMA busy cycles / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs).
 """

@@ -1,8 +1,8 @@
 """HBM traffic per launch from two rocprofv3 PMC passes (rocpd databases):
 
-    rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmcF -o r -- python3 bench.py --steps 3 --warmup 1
-    rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmcW -o r -- python3 bench.py --steps 3 --warmup 1
-    python tools/pmc_traffic.py gpurun_out/pmcF/r_results.db gpurun_out/pmcW/r_results.db > profiles/r02_traffic.json
+    rocprofv3 --pmc FETCH_SIZE -d out/pmcF -o r -- python3 bench.py --full --steps 3 --warmup 1
+    rocprofv3 --pmc WRITE_SIZE -d out/pmcW -o r -- python3 bench.py --full --steps 3 --warmup 1
+    python tools/pmc_traffic.py out/pmcF/r_results.db out/pmcW/r_results.db > profiles/r02_traffic.json
 
 FETCH_SIZE is doubled as MI355X_MICROARCH.md prescribes for gfx950 (128-byte requests of a wide
 coalesced stream are tallied at 64 B); both counters are in KiB.  Kernels are grouped under the names

@@ -178,6 +178,10 @@ int mf_loss_bwd(int64_t B, int64_t N, int d, int P, int num_negatives, float sig
  * to compare the two on small shapes); mode 0: the fp32 search everywhere.  MF_MINE_BF=0|1|2 in the environment sets the initial
  * mode.  Process-wide; not a per-stream setting. */
 void mf_set_mining_prefilter(int mode);
+/* Host-only view of the prefilter's plan for a shape (nothing is launched, no GPU needed): out[8] = {ok (it can serve the
+ * shape), pays (mode 1 uses it), item chunks, tiles per chunk, rescoring lanes per chunk, lists per user, capacity of the
+ * rescoring wave's key array, its LDS bytes}.  d outside {64, 128}: ok = 0 and the last two are 0. */
+int mf_mining_prefilter_plan(int64_t B, int64_t N, int d, int k, int64_t* out);
 
 /* API parity with the public helper methods of EmbeddingLoss, on caller-provided tensors (not the
  * hot path): negative_masks (losses.py:92-110) -> out_mask[B,N] bytes, 1 = valid negative;

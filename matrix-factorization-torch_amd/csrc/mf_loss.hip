@@ -1580,10 +1580,10 @@ static void mine_bf_launch(const LossWs& w, const MinedRowParams& fin, const flo
     }
     {
         MineRescore mr{u, v, w.nu, w.nv, w.lii, w.sgn, w.logq, w.maskW, B, w.Bp, N, m.Xq, sigma, m.nlists, k,
-                       m.lpc, MineRescoreGeom<D>::keys_cap(m.nlists), w.mbf_plist, w.mbf_pcnt, w.mbf_flag, w.mbf_spill, w.mbf_spill_cnt, w.mbf_gate, w.mbf_rep, w.mbf_copybits, w.mbf_lastcopy, m.blk, w.cand, w.cand_cnt, w.plan.rowcap,
+                       m.lpc, MineRescoreGeom<D>::keys_cap(m.nlists, k), w.mbf_plist, w.mbf_pcnt, w.mbf_flag, w.mbf_spill, w.mbf_spill_cnt, w.mbf_gate, w.mbf_rep, w.mbf_copybits, w.mbf_lastcopy, m.blk, w.cand, w.cand_cnt, w.plan.rowcap,
                        g_mine_dbg};
         auto fn = mine_rescore_kernel<D, MinedRowFinish>;
-        const int bytes = MineRescoreGeom<D>::bytes(m.nlists);      // (at most 8 KB rows + 9.3 KB keys + 1.5 KB: below the 64 KB that need no attribute)
+        const int bytes = MineRescoreGeom<D>::bytes(m.nlists, k);      // (at most 4 KB rows + 9.3 KB keys + 1.5 KB: below the 64 KB that need no attribute)
         MBF_TIMED("mining_rescore", s, (fn<<<dim3((unsigned)w.Bp), 64, bytes, s>>>(mr, fin)));
     }
 }
@@ -1609,21 +1609,33 @@ static int mine_bf_run(const LossWs& w, const MiningPolicy::Params& mp, const Se
     if (whole) mf_timing_end("mining_prefilter", s);
     return MF_OK;
 }
-// tools/lab/mined_timeline.py: [0] candidates rescored, [1] users, [2] users walked exactly, since the last call
-extern "C" int mf_probe_mining_prefilter(unsigned long long* out3, int enable) {
+// tools/lab/mined_timeline.py, tests/test_gpu_mining_prefilter.py: sixteen counters since the last call -- [0] candidates
+// rescored, [1] users, [2] users walked exactly, [3] .. [7] (mf_mine_bf.h), [8] the largest copy-expansion pool (keys)
+extern "C" int mf_probe_mining_prefilter(unsigned long long* out16, int enable) {
     static unsigned long long* buf = nullptr;
     if (!buf) {
-        if (hipMalloc(reinterpret_cast<void**>(&buf), 64) != hipSuccess) return -1;
-        (void)hipMemset(buf, 0, 64);
+        if (hipMalloc(reinterpret_cast<void**>(&buf), 128) != hipSuccess) return -1;
+        (void)hipMemset(buf, 0, 128);
     }
     (void)hipDeviceSynchronize();
-    if (out3) (void)hipMemcpy(out3, buf, 64, hipMemcpyDeviceToHost);      // (eight counters)
-    (void)hipMemset(buf, 0, 64);
+    if (out16) (void)hipMemcpy(out16, buf, 128, hipMemcpyDeviceToHost);
+    (void)hipMemset(buf, 0, 128);
     g_mine_dbg = enable ? buf : nullptr;
     return 0;
 }
 // 1 = the prefilter where it pays (default), 2 = wherever it can serve (tests), 0 = select_kernel only
 extern "C" void mf_set_mining_prefilter(int mode) { g_mine_bf_mode = mode <= 0 ? 0 : (mode >= 2 ? 2 : 1); }
+// host-only: the prefilter's plan for a shape, as mine_bf_launch would use it (nothing is launched)
+extern "C" int mf_mining_prefilter_plan(int64_t B, int64_t N, int d, int k, int64_t* out8) {
+    if (!out8) return mf_set_error(MF_EINVAL, "mf_mining_prefilter_plan: out is NULL");
+    const MineBfPlan m = mine_bf_plan(B, N, d, k);
+    int64_t kc = 0, lds = 0;
+    if (d == 64) { kc = MineRescoreGeom<64>::keys_cap(m.nlists, k); lds = MineRescoreGeom<64>::bytes(m.nlists, k); }
+    else if (d == 128) { kc = MineRescoreGeom<128>::keys_cap(m.nlists, k); lds = MineRescoreGeom<128>::bytes(m.nlists, k); }
+    const int64_t o[8] = {m.ok ? 1 : 0, m.pays ? 1 : 0, m.nchunk, m.tpc, m.lpc, m.nlists, kc, lds};
+    for (int i = 0; i < 8; ++i) out8[i] = o[i];
+    return MF_OK;
+}
 
 static int pos_src_check(const char* what, const PosSrc& src) {
     if (src.pos_off) {

@@ -78,8 +78,10 @@ static inline MineBfPlan mine_bf_plan(int64_t B, int64_t N, int d, int k) {
     p.nchunk = (p.NT + p.tpc - 1) / p.tpc;
     p.lpc = k > 16 ? 4 : 2;                              // (~4 k columns per user pass at k = 32, most of them among the batch's first half)
     p.nlists = p.lpc * p.nchunk;
-    // (the seeding pass of mf_select_plan exists from 64 tiles on; below that, and for short batches, select_kernel is fast anyway)
-    p.ok = (d == 64 || d == 128) && B >= 256 && N >= 2048 && k >= 1 && k <= 32 && (int64_t)p.tpc * 32 * p.rowb <= (int64_t)MF_SRD_MAX_BYTES;
+    // (the seeding pass of mf_select_plan exists from 64 tiles on; below that, and for short batches, select_kernel is fast anyway;
+    // a scan hit packs its column into 24 bits -- mine_scan_kernel --, so N < 2^24)
+    p.ok = (d == 64 || d == 128) && B >= 256 && N >= 2048 && N < (int64_t(1) << 24) && k >= 1 && k <= 32 &&
+           (int64_t)p.tpc * 32 * p.rowb <= (int64_t)MF_SRD_MAX_BYTES;
     // B = 8192, N = 16,384, d = 128 (us per step, prefilter / fp32 search; profiles/r04_mined_shapes.log): k = 4: 389 / 677,
     // k = 8: 456 / 737, k = 16: 614 / 855 (2048 hits buffered per wave and chunk; 512 overflowed there), k = 32: 1043 / 1142 (four
     // rescoring lanes per chunk and a quarter-sample seed: ~150 columns per user are rescored); at B = 2048 there are too few user
@@ -582,7 +584,7 @@ struct MineRescore {
     int64_t B, Bp, N, Xq;
     float sigma;
     int nlists, k;
-    int lpc, keys_cap;               // lanes per chunk; capacity of keys[] (16 nlists + MBF_SPILL + 8)
+    int lpc, keys_cap;               // lanes per chunk; capacity of keys[] (MineRescoreGeom::keys_cap)
     const uint32_t* plist;
     const uint32_t* pcnt;
     const int32_t* rowflag;
@@ -596,7 +598,7 @@ struct MineRescore {
     unsigned long long* cand;
     int32_t* cand_cnt;
     int rowcap;
-    unsigned long long* dbg;         // lab: [0] += candidates rescored, [1] += rows, [2] += rows walked exactly (NULL: off)
+    unsigned long long* dbg;         // lab: [0] += candidates rescored, [1] += rows, [2] += rows walked exactly, [8] = max pool (NULL: off)
 };
 template <int D>
 struct MineRescoreGeom {
@@ -605,8 +607,13 @@ struct MineRescoreGeom {
     static constexpr int RB = 8;                        // candidates per round (a user has ~20: three rounds; LDS is this kernel's occupancy limit -- 32 per round: 69 us)
     static constexpr int NI = RB / RPI;
     static constexpr int LMAX = MBF_MAXLISTS * MBF_CAPL + MBF_SPILL;
-    static constexpr int keys_cap(int nlists) { return nlists * MBF_CAPL + MBF_SPILL + 8; }      // (+ the stand-in of a masked diagonal)
-    static constexpr int bytes(int nlists) { return RB * D * 4 + keys_cap(nlists) * 8 + 2 * 64 * 8 + D * 4; }      // rows | keys | win, sorted | the user's row
+    // keys[] holds the listed candidates (+ the stand-in of a masked diagonal), and later the copy-expansion pool: the k winners
+    // and, behind the winner at position t, up to k - 1 - t copies -- k (k + 1) / 2 keys, more than the lists at few chunks
+    // (k = 32, B = 65,536: 2 chunks, 8 lists, 264 list slots for a pool of 528)
+    static constexpr int keys_cap(int nlists, int k) {
+        return nlists * MBF_CAPL + MBF_SPILL + 8 > k * (k + 1) / 2 ? nlists * MBF_CAPL + MBF_SPILL + 8 : k * (k + 1) / 2;
+    }
+    static constexpr int bytes(int nlists, int k) { return RB * D * 4 + keys_cap(nlists, k) * 8 + 2 * 64 * 8 + D * 4; }      // rows | keys | win, sorted | the user's row
 };
 
 // the exact key of (user, column) from the chain product -- MiningPolicy::key, word for word
@@ -832,6 +839,7 @@ __global__ __launch_bounds__(64) void mine_rescore_kernel(MineRescore p, typenam
                 });
             }
             mf_row_topk_sync<true>();
+            if (p.dbg && lane == 0) atomicMax(p.dbg + 8, (unsigned long long)n_pool);
             if (n_pool <= 64) m = mf_row_topk<1, true>(keys, n_pool, p.k, win, sorted);
             else m = mf_row_topk<G::LMAX / 64, true>(keys, n_pool, p.k, win, sorted);
         }

@@ -499,8 +499,8 @@ __global__ __launch_bounds__(64 * mf_nw(D), T >= 32 ? 1 : mf_wg_per_cu(D)) void 
 // compiler is enough.
 template <bool WAVE_LOCAL>
 __device__ __forceinline__ void mf_row_topk_sync() {
-    if (WAVE_LOCAL) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
-    else mf_row_topk_sync<WAVE_LOCAL>();
+    if constexpr (WAVE_LOCAL) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
+    else __syncthreads();
 }
 template <int KPL, bool WAVE_LOCAL = false>
 __device__ __forceinline__ int mf_row_topk(const unsigned long long* __restrict__ src, int n, int k,

@@ -452,12 +452,12 @@ class PairwiseHingeLoss(PairwiseEmbeddingLoss):  # losses.py:357-359 (default tr
 
 @torch.no_grad()
 def negative_mask(user_embed, item_embed, target, *, item_idx, pos_idx=None, num_negatives=0, sigma=1.0,
-                  logq=None, pos_csr=None) -> torch.Tensor:
+                  logq=None, pos_csr=None, logq_table=None) -> torch.Tensor:
     """Boolean ``[B, N]`` mask of the negatives that enter the loss: ``negative_masks``
     followed by ``semi_hard_mining`` (losses.py:92-162), computed by the HIP path
     (``out_mask_bits`` of ``mf_loss_fwd``).  Diagnostic / test helper."""
     check_inputs(user_embed, item_embed, target)
-    u, v, t, ii, pi, p, (lq, lq_rows), d, dp = _prepare(user_embed, item_embed, target, item_idx, pos_idx, logq)
+    u, v, t, ii, pi, p, (lq, lq_rows), d, dp = _prepare(user_embed, item_embed, target, item_idx, pos_idx, logq, logq_table)
     b, n = u.shape[0], v.shape[0]
     nw = (n + 31) // 32
     lib = _lib.lib()
@@ -474,5 +474,7 @@ def negative_mask(user_embed, item_embed, target, *, item_idx, pos_idx=None, num
         _lib.check(lib.mf_loss_fwd_csr(b, n, dp, int(num_negatives), float(sigma), 1.0, 1 << 1, _lib.ptr(u), _lib.ptr(v),
                                        _lib.ptr(t), _lib.ptr(ii), _lib.ptr(uid), _lib.ptr(off), _lib.ptr(items), nu, _lib.ptr(lq),
                                        lq_rows, flags, _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.ptr(bits), _lib.stream_ptr()))
-    shifts = torch.arange(32, device=u.device, dtype=torch.int32)
-    return ((bits[:, :, None] >> shifts) & 1).bool().reshape(b, nw * 32)[:, :n]
+    # (through bytes: word w's byte q holds columns 32 w + 8 q .. -- little-endian words, as on every target; a [B, N] int32
+    # temporary would be 4 x the mask)
+    shifts = torch.arange(8, device=u.device, dtype=torch.uint8)
+    return ((bits.view(torch.uint8)[:, :, None] >> shifts) & 1).bool().reshape(b, nw * 32)[:, :n]

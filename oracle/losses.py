@@ -41,37 +41,41 @@ def logits_fn(u, v, target, sigma: float, logq: torch.Tensor | None = None) -> t
 
 
 @torch.no_grad()
-def negative_masks(item_idx: torch.Tensor, pos_idx: torch.Tensor | None, batch: int) -> torch.Tensor:
+def negative_masks(item_idx: torch.Tensor, pos_idx: torch.Tensor | None, batch: int,
+                   rows: torch.Tensor | None = None) -> torch.Tensor:
     """M[i, j] = not(item_idx[i] == item_idx[j] or item_idx[j] in pos_idx[i, :])
     (losses.py:92-110).  No special case for the 0 padding: like the reference, a
-    padded 0 matches a column whose item id is 0."""
+    padded 0 matches a column whose item id is 0.  ``rows``: only these users' rows,
+    in that order (the full mask's ``[rows]``; for batches too large to hold B x N)."""
     n = item_idx.numel()
+    sel = torch.arange(batch) if rows is None else torch.as_tensor(rows, dtype=torch.int64)
     order = torch.argsort(item_idx, stable=True)
     skeys = item_idx[order]
-    keys = item_idx[:batch, None]
+    keys = item_idx[sel, None]
     if pos_idx is not None:
-        keys = torch.cat([keys, pos_idx.to(item_idx.dtype)], dim=1)
+        keys = torch.cat([keys, pos_idx[sel].to(item_idx.dtype)], dim=1)
     lo = torch.searchsorted(skeys, keys.contiguous(), right=False)
     hi = torch.searchsorted(skeys, keys.contiguous(), right=True)
     cnt = (hi - lo).reshape(-1)
-    rows = torch.arange(batch).repeat_interleave(keys.shape[1]).repeat_interleave(cnt)
+    at = torch.arange(sel.numel()).repeat_interleave(keys.shape[1]).repeat_interleave(cnt)
     start = lo.reshape(-1).repeat_interleave(cnt)
     within = torch.arange(int(cnt.sum())) - (cnt.cumsum(0) - cnt).repeat_interleave(cnt)
     cols = order[start + within]
-    hit = torch.zeros(batch, n, dtype=torch.bool)
-    hit[rows, cols] = True
+    hit = torch.zeros(sel.numel(), n, dtype=torch.bool)
+    hit[at, cols] = True
     return ~hit
 
 
 @torch.no_grad()
-def semi_hard_mining(lg: torch.Tensor, neg: torch.Tensor, k: int) -> torch.Tensor:
+def semi_hard_mining(lg: torch.Tensor, neg: torch.Tensor, k: int, diag: torch.Tensor | None = None) -> torch.Tensor:
     """losses.py:134-162.  Keeps, per row, the min(k, #valid) valid negatives that
     come first in: semi-hard (L_ij < L_ii) by descending L, then hard by ascending
-    L, lowest column on exact ties (the refinement documented in mf_numerics.h)."""
+    L, lowest column on exact ties (the refinement documented in mf_numerics.h).
+    ``diag``: each row's own logit L_ii, for a subset of the rows (default: lg's diagonal)."""
     n = lg.shape[1]
     if k <= 0 or k >= n:
         return neg
-    dm = lg - lg.diagonal()[:, None]
+    dm = lg - (lg.diagonal() if diag is None else diag)[:, None]
     cls = torch.where(dm < 0, 2, 1) * neg.to(torch.int64)      # 2 semi, 1 hard, 0 masked
     val = torch.where(dm < 0, dm, -dm)
     o1 = torch.argsort(val, dim=1, descending=True, stable=True)

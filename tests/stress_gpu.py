@@ -228,8 +228,9 @@ def mining_case():
     from tests import test_gpu_parity as tp
 
     d = [64, 128][ri(0, 1)]
-    b = [ri(256, 600), ri(600, 1500)][ri(0, 1)]
-    n = max(b, [ri(2048, 3000), ri(3000, 7000)][ri(0, 1)])
+    big = ri(0, 7) == 0                                       # one case in eight: a batch the default mode (1) serves
+    b = ri(4096, 8192) if big else [ri(256, 600), ri(600, 1500)][ri(0, 1)]
+    n = max(b, [ri(2048, 3000), ri(3000, 7000)][ri(0, 1)], ri(b, 2 * b) if big else 0)
     k = [ri(1, 4), ri(5, 16), ri(17, 32)][ri(0, 2)]
     sigma = [1.0, 0.3, 30.0, 1000.0][ri(0, 3)]
     n_items = [n // 8, n // 2, 4 * n][ri(0, 2)]
@@ -249,7 +250,7 @@ def mining_case():
     logq = None if ri(0, 1) else torch.log(torch.rand(n, generator=g) * 0.9 + 0.05)
     kind = ["PairwiseHingeLoss", "PairwiseLogisticLoss", "InfomationNoiseContrastiveEstimationLoss"][ri(0, 2)]
     res = []
-    for mode in (0, 2):                                       # (2: the prefilter wherever it can serve)
+    for mode in (0, 1 if big else 2):                         # (2: the prefilter wherever it can serve; 1: where it pays, B >= 4096)
         lib.mf_set_mining_prefilter(mode)
         mask = mf.losses.negative_mask(t["u"].to(dev), t["v"].to(dev), t["target"].to(dev), item_idx=t["item_idx"].to(dev),
                                        pos_idx=t["pos_idx"].to(dev), num_negatives=k, sigma=sigma).cpu()
@@ -261,7 +262,7 @@ def mining_case():
     same = torch.equal(res[0][0], res[1][0]) and (res[0][1] == res[1][1] or (res[0][1] != res[0][1] and res[1][1] != res[1][1])) \
         and torch.equal(res[0][2], res[1][2]) and torch.equal(res[0][3], res[1][3])
     if not same:
-        print(f"MINING PREFILTER MISMATCH b={b} n={n} d={d} k={k} sigma={sigma} flavour={flavour} n_items={n_items} logq={logq is not None} "
+        print(f"MINING PREFILTER MISMATCH b={b} n={n} big={big} d={d} k={k} sigma={sigma} flavour={flavour} n_items={n_items} logq={logq is not None} "
               f"kind={kind} mask rows off {int((res[0][0] != res[1][0]).any(1).sum())} loss {res[0][1]} vs {res[1][1]}", flush=True)
     return same
 

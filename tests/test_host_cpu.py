@@ -54,6 +54,45 @@ def test_descriptor_limits_are_enforced_on_the_host(mf):
     assert rc == mf._lib.MF_ENOTSUP and b"exclusion words" in lib.mf_last_error()
 
 
+def test_mining_prefilter_plan_holds_what_its_kernels_write(mf):
+    """The split-bf16 mining prefilter (csrc/mf_mine_bf.h) is planned on the host, and its limits are host arithmetic: the
+    rescoring wave's key array must hold the copy-expansion pool (the k winners and, behind the winner at position t, up to
+    k - 1 - t copies: k (k + 1) / 2 keys -- more than the lists hold once the batch is large enough for few item chunks),
+    its LDS must fit one workgroup, and a scan hit packs its column into 24 bits.  Swept over the batch sizes the default
+    mode serves (B >= 4096) up to 2^20, ragged ones included, and catalogs on both sides of 2^24."""
+    import ctypes
+
+    lib = mf._lib.lib()
+    out = (ctypes.c_int64 * 8)()
+    bs = [1 << e for e in range(8, 21)] + [300, 4100, 5000, 12_289, 33_000, 70_001, 131_000, 600_000]
+    served = {"near 2^24": 0, "few chunks, k > 16": 0}
+    for b in bs:
+        for n in (b, 2 * b, (1 << 24) - 32, (1 << 24) + 32):
+            for d in (64, 128):
+                for k in range(1, 33):
+                    assert lib.mf_mining_prefilter_plan(b, n, d, k, out) == 0
+                    ok, pays, nchunk, tpc, lpc, nlists, keys_cap, lds = out
+                    what = dict(B=b, N=n, d=d, k=k, plan=list(out))
+                    assert pays == (ok and b >= 4096), what
+                    if n >= 1 << 24:
+                        assert not ok, what               # columns would alias in the scan's 24-bit hit words
+                    if not ok:
+                        continue
+                    assert nchunk * tpc * 32 >= n and lpc == (4 if k > 16 else 2) and nlists == lpc * nchunk <= 64, what
+                    assert keys_cap >= 16 * nlists + 128 + 1, what          # the lists, the spill list, a diagonal's stand-in
+                    assert keys_cap >= k * (k + 1) // 2, what               # the copy-expansion pool
+                    assert lds <= 64 * 1024 and lds >= keys_cap * 8, what
+                    served["near 2^24"] += n == (1 << 24) - 32
+                    served["few chunks, k > 16"] += nchunk < 16 and k > 16
+    assert all(served.values()), served                  # (the sweep reaches the cases it is about)
+    # the geometries the GPU tests (tests/test_gpu_mining_prefilter.py) rely on
+    for b, d, k, nchunk, lpc in ((16_384, 128, 32, 8, 4), (32_768, 64, 32, 4, 4), (65_536, 64, 24, 2, 4), (65_536, 64, 32, 2, 4),
+                                 (8_192, 128, 4, 16, 2)):
+        assert lib.mf_mining_prefilter_plan(b, b if b > 8192 else 2 * b, d, k, out) == 0
+        assert out[0] == 1 and out[2] == nchunk and out[4] == lpc, (b, d, k, list(out))
+    assert lib.mf_mining_prefilter_plan(8192, 16384, 32, 4, out) == 0 and out[0] == 0     # d = 32: never served
+
+
 def test_no_product_kernel_spills():
     """vgpr_spill_count == 0 and no scratch for every kernel of the training step, its set-up and the retrieval paths
     (read from the code objects' notes: tools/kernel_resources.py).  Spills in update_fused_kernel<*, Adam> and

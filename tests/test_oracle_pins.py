@@ -142,6 +142,33 @@ def test_retrieval_metrics_hand_worked_torchmetrics_formulas():
 
 
 # ------------------------------------------------------------------ key order --
+def test_mining_on_a_subset_of_rows_is_those_rows_of_the_full_mining():
+    """negative_masks(rows=) / semi_hard_mining(diag=) (what the GPU tests use on batches too large for a B x N mask on
+    the host): the chosen users' rows of the whole-batch result, bit for bit -- duplicate ids, padding 0s in the positives,
+    rows listed out of order and twice."""
+    from oracle import losses as ol
+
+    g = torch.Generator().manual_seed(4)
+    b, n, d, k = 40, 97, 8, 5
+    u = torch.nn.functional.normalize(torch.randn(b, d, generator=g), dim=-1)
+    v = torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)
+    target = torch.randint(-2, 4, (b,), generator=g)
+    item_idx = torch.randint(0, 30, (n,), generator=g)
+    pos_idx = torch.randint(0, 30, (b, 3), generator=g)
+    pos_idx[::4, 0] = 0
+    lg = torch.from_numpy(chain.logits(u.numpy(), v.numpy(), target.numpy(), 3.0))
+    full_neg = ol.negative_masks(item_idx, pos_idx, b)
+    full = ol.semi_hard_mining(lg, full_neg, k)
+    rows = torch.tensor([31, 0, 7, 7, 39, 12])
+    neg = ol.negative_masks(item_idx, pos_idx, b, rows=rows)
+    assert torch.equal(neg, full_neg[rows])
+    sub = torch.from_numpy(chain.logits(u[rows].numpy(), v.numpy(), target[rows].numpy(), 3.0))
+    assert torch.equal(sub, lg[rows])
+    got = ol.semi_hard_mining(sub, neg, k, diag=sub[torch.arange(rows.numel()), rows])
+    assert torch.equal(got, full[rows]) and int(got.sum()) == k * rows.numel()
+    assert not torch.equal(ol.semi_hard_mining(sub, neg, k), full[rows])     # (the diagonal matters: the default is wrong here)
+
+
 def _orderable(x: float) -> int:          # independent of mf_numerics.h: order-preserving map via struct packing
     import struct
 

@@ -29,10 +29,13 @@ for (dim, k, users, items, B) in [c for c in ((128, 4, bench.NUM_USERS, bench.NU
         out.append((time.perf_counter() - t0) / 100 * 1e6)
         trained.append(tr)
     lib.mf_set_mining_prefilter(1)
+    # the two searches give the same bits, so the two trainers' tables are the same after the same steps (else a time means nothing)
+    for (name, p0), p2 in zip(trained[1].towers.state_dict().items(), trained[0].towers.state_dict().values()):
+        assert torch.equal(p0, p2), f"d={dim} num_negatives={k} B={B}: {name} differs between the two searches"
     extra = ""
     if os.environ.get("MF_MINE_DBG") and hasattr(lib, "mf_probe_mining_prefilter"):
         import ctypes
-        buf = (ctypes.c_ulonglong * 8)()
+        buf = (ctypes.c_ulonglong * 16)()
         lib.mf_probe_mining_prefilter(None, 1)
         lib.mf_set_mining_prefilter(2)
         trained[0].step(batches[0])

@@ -57,7 +57,7 @@ if os.environ.get("MF_MINE_DBG"):
     import ctypes
     if hasattr(lib, "mf_probe_mining_prefilter"):
         import struct
-        buf = (ctypes.c_ulonglong * 8)()
+        buf = (ctypes.c_ulonglong * 16)()
         for bi in range(8):
             lib.mf_probe_mining_prefilter(None, 1)
             tr.step(batches[bi])

@@ -351,6 +351,38 @@ int mf_comm_all_to_all_rows(void* comm, const void* send, const int64_t* send_ro
                             const int64_t* recv_rows_host, int64_t row_bytes, mf_stream_t stream);
 int mf_comm_all_gather(void* comm, const void* send, void* recv, int64_t bytes, mf_stream_t stream);
 
+/* ------------------------------------------------------------ history-pooled user tower ---
+ * The id-only counterpart of PoolingTransformer.forward (xfmr_rec/models.py:81-84, pooling_mode "mean" / "max",
+ * models.py:24, then Normalize, models.py:59) over the item rows of a user's history (prepare.py:285-299).  User b's list
+ * is items[start[b], end[b]) (clamped to [0, n_items)); ids outside [1, n_rows) are padding; max_history > 0 keeps the last
+ * max_history valid entries.  r_e = norm_item ? W[id] / max(|W[id]|, 1e-12) : W[id]; p_b = mean_e r_e (mode 0) or the
+ * channel-wise max (mode 1: ties go to the first entry); u_b = norm_user ? p_b / max(|p_b|, 1e-12) : p_b; an empty list
+ * gives u_b = 0.  n_entries >= sum_b (end[b] - start[b]) sizes the workspace (mf_pool_ws_bytes).  Outputs: out_u [B, d],
+ * out_inv [B] (1 / max(|p_b|, 1e-12), or 1), out_count [B] (valid entries), out_lo [B] (first position pooled), out_off [B + 1]
+ * (exclusive prefix of end - lo: the entry numbering of the backward), out_arg [B, d] (mode 1: the winning entry's offset
+ * from out_lo, -1 for an empty list).  Deterministic: fixed chunking and combination order, no atomics.  MF_ENOTSUP above
+ * 2^20 table rows. */
+size_t mf_pool_ws_bytes(int64_t B, int64_t n_entries, int d, int mode);
+int mf_pool_forward(const float* table, int64_t n_rows, int d, const int64_t* seg_start, const int64_t* seg_end,
+                    const int64_t* items, int64_t n_items, int64_t B, int64_t n_entries, int max_history, int mode,
+                    int norm_item, int norm_user, float* out_u, float* out_inv, int32_t* out_count, int64_t* out_lo,
+                    int64_t* out_off, int32_t* out_arg, void* ws, size_t ws_bytes, mf_stream_t stream);
+/* Backward, coalesced with the rows other towers parked on the same table: grad_p [B, d] = dL/dp (after the normalise
+ * backward, mf_normalize_backward); entry e of user b gets grad_p[b] / count[b] (mode 0) or grad_p[b] on the channels it won
+ * (mode 1); the extra rows (extra_ids [n_extra], extra_grad [n_extra, d]; valid ids [0, n_rows)) join them.  Every entry is
+ * summed per id in entry order (extras first) -- a stable radix sort by id, linear in the entries, no float atomics, no host
+ * round trip.  out_ids [capacity] = the unique ids ascending, then -1; out_grad [capacity, d] their summed rows (rows of a -1
+ * slot are not written).  capacity must be min(n_rows, n_extra + n_entries). */
+size_t mf_pool_backward_ws_bytes(int64_t n_extra, int64_t n_entries, int d);
+int mf_pool_backward(int64_t n_rows, int d, int mode, const int64_t* items, int64_t B, const int64_t* lo, const int64_t* ent_off,
+                     const int32_t* count, const int32_t* arg, const float* grad_p, int64_t n_entries, const int64_t* extra_ids,
+                     const float* extra_grad, int64_t n_extra, int64_t capacity, int64_t* out_ids, float* out_grad, void* ws,
+                     size_t ws_bytes, mf_stream_t stream);
+/* The history window of each example mf_sample_batch puts in row r (same Feistel permutation, same seed and start):
+ * out_start[r] = pair_hist_lo[e], out_end[r] = pair_hist_hi[e] (InteractionTable.history_lo / history_hi of the train pairs). */
+int mf_sample_history(const int64_t* pair_hist_lo, const int64_t* pair_hist_hi, int64_t n_pairs, uint64_t seed, int64_t start,
+                      int64_t B, int64_t* out_start, int64_t* out_end, mf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

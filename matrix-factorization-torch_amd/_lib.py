@@ -82,6 +82,13 @@ SIGNATURES = {
     "mf_topk_bf3_build": (c_int, [c_vp, c_i64, c_int, c_vp, c_sz, c_vp]),
     "mf_topk_bf3_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "mf_topk_bf3": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "mf_pool_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
+    "mf_pool_forward": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mf_pool_backward_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
+    "mf_pool_backward": (c_int, [c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
+                                 c_vp, c_vp, c_sz, c_vp]),
+    "mf_sample_history": (c_int, [c_vp, c_vp, c_i64, ctypes.c_uint64, c_i64, c_i64, c_vp, c_vp, c_vp]),
 }
 
 MF_OK, MF_EINVAL, MF_ENOSPC, MF_ELAUNCH, MF_ENOTSUP = 0, -1, -2, -3, -4       # return codes (include/mf_hip.h)

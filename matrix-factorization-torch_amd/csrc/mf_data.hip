@@ -72,3 +72,29 @@ extern "C" int mf_sample_batch(const int64_t* pair_user, const int64_t* pair_ite
         out_target, out_pos);
     return mf_check_launch("mf_sample_batch");
 }
+
+// The history window of every example of the same stream: row r of a batch gets (out_start[r], out_end[r]) =
+// (pair_hist_lo[e], pair_hist_hi[e]) of the pair e that mf_sample_batch puts in row r (same Feistel permutation, same
+// (seed, start)).  The windows index the caller's item list (InteractionTable.sorted_item): nothing is copied.
+__global__ __launch_bounds__(256) void sample_history_kernel(const int64_t* __restrict__ pair_hist_lo, const int64_t* __restrict__ pair_hist_hi,
+                                                             int64_t n_pairs, int half_bits, unsigned long long seed, int64_t start, int64_t B,
+                                                             int64_t* __restrict__ out_start, int64_t* __restrict__ out_end) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= B) return;
+    const unsigned long long p = (unsigned long long)(start + r);
+    const unsigned long long e = mf_feistel_perm(p % (unsigned long long)n_pairs, (unsigned long long)n_pairs, half_bits,
+                                                 p / (unsigned long long)n_pairs, seed);
+    out_start[r] = pair_hist_lo[e];
+    out_end[r] = pair_hist_hi[e];
+}
+
+extern "C" int mf_sample_history(const int64_t* pair_hist_lo, const int64_t* pair_hist_hi, int64_t n_pairs, uint64_t seed, int64_t start,
+                                 int64_t B, int64_t* out_start, int64_t* out_end, mf_stream_t stream) {
+    if (!pair_hist_lo || !pair_hist_hi || !out_start || !out_end || n_pairs <= 0 || start < 0 || B <= 0)
+        return mf_set_error(MF_EINVAL, "mf_sample_history: bad argument");
+    int bits = 1;
+    while ((1ll << bits) < n_pairs) ++bits;
+    sample_history_kernel<<<dim3((unsigned)((B + 255) / 256)), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        pair_hist_lo, pair_hist_hi, n_pairs, (bits + 1) / 2, seed, start, B, out_start, out_end);
+    return mf_check_launch("mf_sample_history");
+}

@@ -240,10 +240,16 @@ class InteractionTable:
                 (t_off, self.sorted_item[t_mask], self.sorted_rating[t_mask].to(torch.float32)))
 
     def sampler(self, *, num_items: int, batch_size: int = BATCH_SIZE, seed: int = 0, device="cuda", pos_pad: int | None = None,
-                user_range: tuple[int, int] | None = None) -> "DeviceInteractionSampler":
+                user_range: tuple[int, int] | None = None, history: bool = False) -> "DeviceInteractionSampler":
+        """``history=True``: batches also carry ``user.history = (start, end, sorted_item)``, the rolling window of every
+        example (``history_lo / history_hi`` of the train pairs) -- the input of ``models.HistoryPoolingTower``."""
+        hist = {}
+        if history:
+            tr = self.sorted_train
+            hist = {"pair_hist_lo": self.history_lo[tr], "pair_hist_hi": self.history_hi[tr], "hist_items": self.sorted_item}
         return DeviceInteractionSampler(self.pair_user, self.pair_item, self.pair_target, self.pos_off, self.pos_items,
                                         num_items=num_items, batch_size=batch_size, pos_pad=pos_pad, seed=seed, device=device,
-                                        user_range=user_range)
+                                        user_range=user_range, **hist)
 
 
 class DeviceInteractionSampler:
@@ -261,21 +267,45 @@ class DeviceInteractionSampler:
     30,000-column matrix.  ``pos_pad=P``: the reference's layout, ``user.pos_idx[B, P]`` 0-padded on the right; a P shorter
     than the longest list of the data would silently turn positives into negatives and is refused unless
     ``truncate_positives=True`` says that this is wanted.  ``user_range=(lo, hi)`` keeps only the pairs of users
-    ``lo <= u < hi``: the per-rank stream of a user-partitioned job (``distributed.ShardedTrainer(user_mode="partitioned")``)."""
+    ``lo <= u < hi``: the per-rank stream of a user-partitioned job (``distributed.ShardedTrainer(user_mode="partitioned")``).
+
+    History.  ``pair_hist_lo / pair_hist_hi`` (one window per pair) and ``hist_items``: every batch also carries
+    ``user.history = (start [B], end [B], hist_items)`` -- the window of the pair in each row (``mf_sample_history``, the same
+    permutation as ``mf_sample_batch``); ``user_range`` filters the windows with their pairs."""
 
     def __init__(self, pair_user, pair_item, pair_target, pos_off, pos_items, *, num_items: int,
                  batch_size: int = BATCH_SIZE, pos_pad: int | None = None, seed: int = 0, device="cuda",
-                 user_range: tuple[int, int] | None = None, truncate_positives: bool = False) -> None:
+                 user_range: tuple[int, int] | None = None, truncate_positives: bool = False, pair_hist_lo=None, pair_hist_hi=None,
+                 hist_items=None) -> None:
         from . import _lib
 
         self._lib = _lib
         i64 = lambda t: torch.as_tensor(t, dtype=torch.int64).to(device).contiguous()  # noqa: E731
         self.pair_user, self.pair_item = i64(pair_user), i64(pair_item)
         self.pair_target = torch.as_tensor(pair_target, dtype=torch.float32).to(device).contiguous()
+        given = [t is not None for t in (pair_hist_lo, pair_hist_hi, hist_items)]
+        if any(given) and not all(given):
+            msg = "pair_hist_lo, pair_hist_hi and hist_items go together"
+            raise ValueError(msg)
+        self.pair_hist_lo = self.pair_hist_hi = self.hist_items = None
+        if all(given):
+            self.pair_hist_lo, self.pair_hist_hi, self.hist_items = i64(pair_hist_lo), i64(pair_hist_hi), i64(hist_items)
+            if not (self.pair_hist_lo.numel() == self.pair_hist_hi.numel() == self.pair_user.numel()):
+                msg = (f"one history window per pair: {self.pair_hist_lo.numel() = }, {self.pair_hist_hi.numel() = }, "
+                       f"{self.pair_user.numel() = }")
+                raise ValueError(msg)
+            if self.pair_hist_lo.numel() and (int(self.pair_hist_lo.min()) < 0 or int(self.pair_hist_hi.max()) > self.hist_items.numel()
+                                              or bool((self.pair_hist_hi < self.pair_hist_lo).any())):
+                msg = f"history windows must satisfy 0 <= lo <= hi <= len(hist_items) = {self.hist_items.numel()}"
+                raise ValueError(msg)
+            if self.hist_items.numel() == 0:
+                self.hist_items = torch.zeros(1, dtype=torch.int64, device=device)
         if user_range is not None:
             keep = (self.pair_user >= user_range[0]) & (self.pair_user < user_range[1])
             self.pair_user, self.pair_item, self.pair_target = (self.pair_user[keep].contiguous(), self.pair_item[keep].contiguous(),
                                                                 self.pair_target[keep].contiguous())
+            if self.pair_hist_lo is not None:
+                self.pair_hist_lo, self.pair_hist_hi = self.pair_hist_lo[keep].contiguous(), self.pair_hist_hi[keep].contiguous()
         self.pos_off, self.pos_items = i64(pos_off), i64(pos_items)
         if self.pos_items.numel() == 0:
             self.pos_items = torch.zeros(1, dtype=torch.int64, device=device)
@@ -313,6 +343,12 @@ class DeviceInteractionSampler:
                                             self.num_items, self.seed, int(step) * b, b, p, user.data_ptr(), item.data_ptr(),
                                             target.data_ptr(), None if pos is None else pos.data_ptr(), lib.stream_ptr()))
         ub = {"idx": user, "pos_idx": pos} if pos is not None else {"idx": user, "pos_csr": (user, self.pos_off, self.pos_items)}
+        if self.pair_hist_lo is not None:
+            h_start = torch.empty(b, dtype=torch.int64, device=dev)
+            h_end = torch.empty(b, dtype=torch.int64, device=dev)
+            lib.check(lib.lib().mf_sample_history(self.pair_hist_lo.data_ptr(), self.pair_hist_hi.data_ptr(), self.pair_user.numel(),
+                                                  self.seed, int(step) * b, b, h_start.data_ptr(), h_end.data_ptr(), lib.stream_ptr()))
+            ub["history"] = (h_start, h_end, self.hist_items)
         return {"target": target, "user": ub, "item": {"idx": item[:b]}, "neg_item": {"idx": item[b:]}}
 
     def __iter__(self) -> Iterator[InteractionBatchType]:

@@ -500,7 +500,11 @@ class ShardedTrainer:
     def __init__(self, mf, device, optimizer: str, num_negatives: int, *, num_users: int, num_items: int, dim: int,
                  logq: torch.Tensor | None = None, kind: str = "InfomationNoiseContrastiveEstimationLoss",
                  lr: float | None = None, ops=None, comm=None, seed: int = 0, num_hashes: int = 0, hash_seed: int = 0,
-                 user_mode: str = "routed", capacity_factor: float | None = None) -> None:
+                 user_mode: str = "routed", capacity_factor: float | None = None, user_tower: str = "table") -> None:
+        if user_tower != "table":
+            msg = (f"ShardedTrainer trains table user towers only: {user_tower = } (a history tower pools rows of the sharded "
+                   "item table; train it on one device with MatrixFactorizationLitModule)")
+            raise ValueError(msg)
         if user_mode not in USER_MODES:
             msg = f"user_mode must be one of {USER_MODES}: {user_mode = }"
             raise ValueError(msg)

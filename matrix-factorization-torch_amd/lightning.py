@@ -79,8 +79,32 @@ class MatrixFactorizationLitModule(_Base):
             raise ValueError(msg)
         exclude_item_ids = (exclude_item_ids or []) + list(self.history.get(int(user_idx), []))
         device = self.towers["user"].weight.device
-        embed = self(torch.tensor([int(user_idx)], device=device)).cpu().numpy()
+        if self.config.user_tower == "history":      # the user IS its history: pool it (xfmr_rec/lightning.py:89-90 excludes it)
+            embed = self._pool_item_ids(list(self.history.get(int(user_idx), []))).cpu().numpy()
+        else:
+            embed = self(torch.tensor([int(user_idx)], device=device)).cpu().numpy()
         return self.item_processor.search(embed, exclude_item_ids=exclude_item_ids, top_k=top_k)
+
+    def _pool_item_ids(self, item_ids: list[int]) -> torch.Tensor:
+        """``[1, d]`` history-tower query of a list of item ids (rows through the item index's id map when there is one)."""
+        proc = self.item_processor
+        rows = [proc.row_of(i) for i in item_ids] if (proc is not None and proc._row_of_id is not None) else [int(i) for i in item_ids]
+        device = self.towers["item"].weight.device
+        return self.towers["user"](torch.tensor([rows or [0]], dtype=torch.int64, device=device))
+
+    @torch.inference_mode()
+    def recommend_with_history(self, item_ids: list[int], *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
+        """Serve a user who is in no table from the items they consumed (history tower only): the query is the pooled
+        history and the history itself is excluded (xfmr_rec/lightning.py:89-90)."""
+        if self.config.user_tower != "history":
+            msg = "recommend_with_history needs user_tower='history' (a table user tower has no row for an unseen user)"
+            raise ValueError(msg)
+        if self.towers is None or self.item_processor is None or self.item_processor.index is None:
+            msg = "`user_processor` and `item_processor` must be initialised first"
+            raise ValueError(msg)
+        embed = self._pool_item_ids(list(item_ids)).cpu().numpy()
+        exclude = [*(exclude_item_ids or []), *map(int, item_ids)]
+        return self.item_processor.search(embed, exclude_item_ids=exclude, top_k=top_k)
 
     @torch.inference_mode()
     def recommend_with_item_id(self, item_id: int, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
@@ -112,7 +136,9 @@ class MatrixFactorizationLitModule(_Base):
             raise ValueError(msg)
         path = pathlib.Path(path)
         path.mkdir(parents=True, exist_ok=True)
-        save_file({f"{k}.weight": t.weight.detach().cpu().contiguous() for k, t in self.towers.items()}, str(path / TOWERS_PATH))
+        # (a history user tower has no table of its own: it shares the item table, which is written once)
+        save_file({f"{k}.weight": t.weight.detach().cpu().contiguous() for k, t in self.towers.items()
+                   if not isinstance(t, models.HistoryPoolingTower)}, str(path / TOWERS_PATH))
         proc = {"config": self.config.model_dump(), "history": {str(k): list(map(int, v)) for k, v in self.history.items()}}
         (path / PROCESSORS_JSON).write_text(json.dumps(proc, indent=2))
         if self.item_processor is not None and self.item_processor.index is not None:
@@ -135,7 +161,8 @@ class MatrixFactorizationLitModule(_Base):
         weights = load_file(str(path / TOWERS_PATH))
         with torch.no_grad():
             for k, t in module.towers.items():
-                t.weight.copy_(weights[f"{k}.weight"].to(device))
+                if not isinstance(t, models.HistoryPoolingTower):
+                    t.weight.copy_(weights[f"{k}.weight"].to(device))
         module.history = {int(k): v for k, v in proc.get("history", {}).items()}
         if (path / INDEX_PATH).exists():
             idx = load_file(str(path / INDEX_PATH))
@@ -151,7 +178,8 @@ class MatrixFactorizationLitModule(_Base):
         target = batch["target"]
         pos_idx = batch["user"].get("pos_idx")            # the reference's padded positives, or ...
         pos_csr = batch["user"].get("pos_csr")            # ... the producer's CSR lists (data.DeviceInteractionSampler)
-        user_embed = self(batch["user"]["idx"], tower="user")
+        # history tower: the user vector is the pooled history of the example (data.DeviceInteractionSampler(history=True))
+        user_embed = self(batch["user"]["history" if self.config.user_tower == "history" else "idx"], tower="user")
         # positives then sampled negatives, as xfmr_rec/lightning.py:133-134
         item_idx = torch.cat([batch["item"]["idx"], batch["neg_item"]["idx"]])
         item_embed = self(item_idx, tower="item")
@@ -184,12 +212,20 @@ class MatrixFactorizationLitModule(_Base):
         if self.item_processor is None or self.item_processor.index is None:
             msg = "`user_processor` and `item_processor` must be initialised first"
             raise ValueError(msg)
-        queries = self(batch["user"]["idx"], tower="user")
+        queries = self._queries(batch)
         _, rows = self.item_processor.index.search(queries, self.config.top_k, exclude_csr=batch.get("history"))
         off, ids, rating = batch["target"]
         metric = self.metrics[step_name]
         metric.update(rows, off, ids, rating)
         return metric.compute()
+
+    def _queries(self, batch) -> torch.Tensor:
+        """The users' query vectors: their table rows, or (history tower) their pooled history -- the same CSR
+        ``(offsets, item rows)`` that is excluded from retrieval (``InteractionTable.eval_sets``)."""
+        if self.config.user_tower != "history":
+            return self(batch["user"]["idx"], tower="user")
+        off, items = batch["history"]
+        return self((off[:-1], off[1:], items), tower="user")
 
     def validation_step(self, batch, _: int = 0) -> None:
         self.log_dict(self.update_metrics(batch, step_name="val"))
@@ -200,7 +236,7 @@ class MatrixFactorizationLitModule(_Base):
     @torch.no_grad()
     def predict_step(self, batch, _: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
         """``(scores, item rows)`` [Q, top_k] of the batch's users, histories excluded."""
-        queries = self(batch["user"]["idx"], tower="user")
+        queries = self._queries(batch)
         return self.item_processor.index.search(queries, self.config.top_k, exclude_csr=batch.get("history"))
 
     def training_step(self, batch, _: int = 0) -> torch.Tensor:

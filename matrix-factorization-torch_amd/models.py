@@ -14,6 +14,7 @@ spec is ``oracle/embed.py``.
 from __future__ import annotations
 
 import math
+from typing import Literal
 
 import pydantic
 import torch
@@ -32,6 +33,38 @@ class ModelConfig(pydantic.BaseModel):
     init_std: float | None = None  # default 1/sqrt(hidden_size)
     num_hashes: int = 0            # > 0: hash / bloom towers (config 5): num_users / num_items are BUCKET counts
     hash_seed: int = 0
+    # "history": the user vector is the pooled item rows of the user's history (HistoryPoolingTower), not a table row
+    user_tower: Literal["table", "history"] = "table"
+    pooling_mode: str = "mean"     # models.py:24 ("cls" / "pooler" need the transformer this repository does not have)
+    max_history: int | None = None
+
+    @pydantic.field_validator("pooling_mode")
+    @classmethod
+    def _check_pooling_mode(cls, v: str) -> str:
+        return check_pooling_mode(v)
+
+    @pydantic.field_validator("max_history")
+    @classmethod
+    def _check_max_history(cls, v: int | None) -> int | None:
+        if v is not None and v < 1:
+            msg = f"max_history must be None or >= 1: {v = }"
+            raise ValueError(msg)
+        return v
+
+
+POOLING_MODES = ("mean", "max")
+
+
+def check_pooling_mode(mode: str) -> str:
+    """The reference's ``pooling_mode`` (models.py:24) minus the two modes that read transformer outputs."""
+    if mode in ("cls", "pooler"):
+        msg = (f"pooling_mode {mode!r} pools a transformer's [CLS] / pooler output and there is no transformer here: "
+               f"the history tower pools item-table rows, use one of {POOLING_MODES}")
+        raise ValueError(msg)
+    if mode not in POOLING_MODES:
+        msg = f"pooling_mode must be one of {POOLING_MODES}: {mode = }"
+        raise ValueError(msg)
+    return mode
 
 
 class _GatherRows(torch.autograd.Function):
@@ -163,8 +196,159 @@ class HashEmbeddingTower(torch.nn.Module):
         return f"{self.weight.shape[0]} buckets, {self.weight.shape[1]}, num_hashes={self.num_hashes}, normalize={self.normalize}"
 
 
+class PooledHistoryGrad:
+    """The history tower's contribution to its item table's gradient, parked on the table by the backward and resolved by
+    the optimiser (``optim._pending``): there it is coalesced, in one pass, with the rows other towers parked on the same
+    table in the same step, so that the table receives ONE list of at most min(rows, entries) unique ids."""
+
+    def __init__(self, ctx, grad_p: torch.Tensor) -> None:
+        self.mode, self.normalize = ctx.mode, ctx.norm_item
+        self.items, self.lo, self.off, self.count = ctx.items, ctx.lo, ctx.off, ctx.count
+        self.arg, self.n_entries, self.grad_p = ctx.arg, ctx.n_entries, grad_p
+
+    def coalesce(self, table: torch.Tensor, ids: torch.Tensor | None, grad: torch.Tensor | None):
+        """``(unique ids [capacity] (then -1), summed rows [capacity, d])`` of this entry plus ``(ids, grad)``."""
+        lib = _lib.lib()
+        rows, d = table.shape
+        b = self.lo.numel()
+        n_extra = 0 if ids is None else ids.numel()
+        cap = min(rows, n_extra + self.n_entries)
+        out_ids = torch.empty(cap, dtype=torch.int64, device=table.device)
+        out_grad = torch.empty(cap, d, dtype=torch.float32, device=table.device)
+        if cap == 0:
+            return out_ids, out_grad
+        ws = _lib.workspace(lib.mf_pool_backward_ws_bytes(n_extra, self.n_entries, d), table.device)
+        _lib.check(lib.mf_pool_backward(rows, d, self.mode, self.items.data_ptr(), b, self.lo.data_ptr(), self.off.data_ptr(),
+                                        self.count.data_ptr(), _lib.ptr(self.arg), self.grad_p.data_ptr(), self.n_entries,
+                                        _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(), out_grad.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        return out_ids, out_grad
+
+
+class _PoolRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table: torch.Tensor, start: torch.Tensor, end: torch.Tensor, items: torch.Tensor, n_entries: int,
+                mode: int, max_history: int, norm_item: bool, norm_user: bool):
+        if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
+            raise _lib.MfHipError("embedding table must be a contiguous fp32 tensor on the GPU")
+        lib = _lib.lib()
+        rows, d = table.shape
+        b = start.numel()
+        dev = table.device
+        u = torch.empty(b, d, dtype=torch.float32, device=dev)
+        inv = torch.empty(b, dtype=torch.float32, device=dev)
+        count = torch.empty(b, dtype=torch.int32, device=dev)
+        lo = torch.empty(b, dtype=torch.int64, device=dev)
+        off = torch.empty(b + 1, dtype=torch.int64, device=dev)
+        arg = torch.empty(b, d, dtype=torch.int32, device=dev) if mode == 1 else None
+        ws = _lib.workspace(lib.mf_pool_ws_bytes(b, n_entries, d, mode), dev)
+        _lib.check(lib.mf_pool_forward(table.data_ptr(), rows, d, start.data_ptr(), end.data_ptr(), items.data_ptr(), items.numel(),
+                                       b, n_entries, max_history, mode, int(norm_item), int(norm_user), u.data_ptr(), inv.data_ptr(),
+                                       count.data_ptr(), lo.data_ptr(), off.data_ptr(), _lib.ptr(arg), ws.data_ptr(), ws.numel(),
+                                       _lib.stream_ptr()))
+        ctx.table, ctx.items, ctx.lo, ctx.off, ctx.count, ctx.arg = table, items, lo, off, count, arg
+        ctx.mode, ctx.n_entries, ctx.norm_item, ctx.norm_user = mode, n_entries, bool(norm_item), bool(norm_user)
+        ctx.save_for_backward(u, inv)
+        return u
+
+    @staticmethod
+    def backward(ctx, grad_u):
+        table = ctx.table
+        u, inv = ctx.saved_tensors
+        b, d = u.shape
+        g = grad_u.to(torch.float32).contiguous()
+        if ctx.norm_user:
+            gp = torch.empty_like(g)
+            _lib.check(_lib.lib().mf_normalize_backward(u.data_ptr(), inv.data_ptr(), g.data_ptr(), b, d, gp.data_ptr(),
+                                                        _lib.stream_ptr()))
+            g = gp
+        pending = getattr(table, "_mf_pending", None)
+        if pending is None:
+            pending = []
+            table._mf_pending = pending
+        pending.append(PooledHistoryGrad(ctx, g))
+        return (None,) * 9
+
+
+class HistoryPoolingTower(torch.nn.Module):
+    """``tower(history) -> [B, d]``: the L2-normalised mean (or channel-wise max) of the item-table rows of every user's
+    history -- the id-only counterpart of ``PoolingTransformer`` (xfmr_rec/models.py:66-84: pool the non-zero rows by
+    ``pooling_mode``, then Normalize).  It owns no parameter: it reads the item tower's table, and its backward lands on that
+    table's sparse update (coalesced with the item tower's own rows of the step, ``optim._pending``).  A user who is not
+    in any table, or whose history changed after training, is served by pooling the current history.
+
+    ``history``: ``(start [B], end [B], items)`` -- user b's list is ``items[start[b]:end[b]]`` (a CSR ``(off[:-1], off[1:],
+    items)``, or ``InteractionTable``'s rolling windows into ``sorted_item``) -- or a padded ``[B, L]`` int64 matrix (0 =
+    padding, the reference's ``pad_tensors`` layout).  Ids outside ``[1, num_items)`` are padding; ``max_history = L`` pools
+    the last L valid entries of each list.  HIP kernels ``mf_pool_forward`` / ``mf_pool_backward``."""
+
+    def __init__(self, item_tower: torch.nn.Module, *, pooling_mode: str = "mean", max_history: int | None = None,
+                 normalize: bool = True) -> None:
+        super().__init__()
+        if not isinstance(item_tower, EmbeddingTower):
+            msg = (f"HistoryPoolingTower pools the rows of a plain EmbeddingTower (one row per item); got {type(item_tower).__name__}"
+                   " (a hashed tower's rows are shared by many items)")
+            raise ValueError(msg)
+        if max_history is not None and max_history < 1:
+            msg = f"max_history must be None or >= 1: {max_history = }"
+            raise ValueError(msg)
+        object.__setattr__(self, "item_tower", item_tower)     # shared, not registered: the table is saved / optimised once
+        self.pooling_mode = check_pooling_mode(pooling_mode)
+        self.max_history = max_history
+        self.normalize = normalize
+
+    @property
+    def weight(self) -> torch.nn.Parameter:
+        return self.item_tower.weight
+
+    def segments(self, history):
+        """``(start, end, items, n_entries)`` of either input form (one host read of the entry count for segments)."""
+        dev = self.weight.device
+        if isinstance(history, (tuple, list)):
+            start, end, items = (_lib.dev_i64(t, name) for t, name in zip(history, ("start", "end", "items")))
+            start, end = start.reshape(-1), end.reshape(-1)
+            if start.numel() != end.numel():
+                msg = f"start and end must have the same length: {start.numel()} != {end.numel()}"
+                raise ValueError(msg)
+            items = items.reshape(-1)
+            n_entries = int((end - start).clamp_min(0).sum()) if start.numel() else 0
+        else:
+            pad = _lib.dev_i64(history, "history")
+            if pad.dim() != 2:  # noqa: PLR2004
+                msg = f"a padded history must be [B, L]: {tuple(pad.shape) = }"
+                raise ValueError(msg)
+            b, length = pad.shape
+            start = torch.arange(b, device=dev, dtype=torch.int64) * length
+            end = start + length
+            items = pad.reshape(-1)
+            n_entries = b * length
+        if items.numel() == 0:
+            items = torch.zeros(1, dtype=torch.int64, device=dev)
+        return start, end, items, n_entries
+
+    def forward(self, history) -> torch.Tensor:
+        start, end, items, n_entries = self.segments(history)
+        if start.numel() == 0:
+            return torch.zeros(0, self.weight.shape[1], device=self.weight.device)
+        return _PoolRows.apply(self.weight, start, end, items, n_entries, POOLING_MODES.index(self.pooling_mode),
+                               self.max_history or 0, self.item_tower.normalize, self.normalize)
+
+    def extra_repr(self) -> str:
+        return f"pooling_mode={self.pooling_mode}, max_history={self.max_history}, normalize={self.normalize}"
+
+
 def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
-    """Counterpart of ``init_bert`` + ``to_sentence_transformer`` (models.py:27-63)."""
+    """Counterpart of ``init_bert`` + ``to_sentence_transformer`` (models.py:27-63).  ``user_tower="history"``: the user
+    tower is a :class:`HistoryPoolingTower` over the item table (plain tables only)."""
+    if config.user_tower == "history":
+        if config.num_hashes > 0:
+            msg = "user_tower='history' pools plain item-table rows; hashed towers (num_hashes > 0) are not supported"
+            raise ValueError(msg)
+        item = EmbeddingTower(config.num_items, config.hidden_size, normalize=config.normalize, init_std=config.init_std,
+                              device=device)
+        user = HistoryPoolingTower(item, pooling_mode=config.pooling_mode, max_history=config.max_history,
+                                   normalize=config.normalize)
+        return torch.nn.ModuleDict({"user": user, "item": item})
     if config.num_hashes > 0:
         return torch.nn.ModuleDict(
             {

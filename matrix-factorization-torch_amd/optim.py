@@ -14,13 +14,36 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, models
+
+
+def _pending_pooled(p: torch.Tensor, items: list):
+    """A step in which a :class:`models.HistoryPoolingTower` parked its deferred gradient on ``p``: ONE coalesce over all
+    sources -- the rows the other towers parked (``(ids, grad, normalized)``), then each pooled entry -- gives the table
+    one list of at most min(rows, entries) unique ids (padded with -1), whatever order autograd ran the backwards in."""
+    rows = [x for x in items if not isinstance(x, models.PooledHistoryGrad)]
+    pooled = [x for x in items if isinstance(x, models.PooledHistoryGrad)]
+    norms = {n for _, _, n in rows} | {x.normalize for x in pooled}
+    if len(norms) != 1:
+        raise _lib.MfHipError("a table was gathered both with and without normalisation in one step")
+    ids = g = None
+    if rows:
+        ids = torch.cat([i for i, _, _ in rows]) if len(rows) > 1 else rows[0][0]
+        g = torch.cat([x for _, x, _ in rows]) if len(rows) > 1 else rows[0][1]
+    for x in pooled:
+        ids, g = x.coalesce(p, ids, g)
+    if ids.numel() == 0:
+        items.clear()
+        return None
+    return ids, g, norms.pop()
 
 
 def _pending(p: torch.Tensor):
     items = getattr(p, "_mf_pending", None)
     if not items:
         return None
+    if any(isinstance(x, models.PooledHistoryGrad) for x in items):
+        return _pending_pooled(p, items)
     if len(items) == 1:
         ids, g, norm = items[0]
     else:

@@ -383,6 +383,32 @@ int mf_pool_backward(int64_t n_rows, int d, int mode, const int64_t* items, int6
 int mf_sample_history(const int64_t* pair_hist_lo, const int64_t* pair_hist_hi, int64_t n_pairs, uint64_t seed, int64_t start,
                       int64_t B, int64_t* out_start, int64_t* out_end, mf_stream_t stream);
 
+/* ------------------------------------------------------------ hashed feature-bag towers ---
+ * The id-only counterpart of the reference's attribute encoder (xfmr_rec/lightning.py:60-74 over the JSON text of
+ * prepare.py:69-127): an EmbeddingBag over hashed attribute tokens.  Entity e's bag is tokens[seg_start[e], seg_end[e])
+ * (clamped to [0, n_tokens), at most max_len entries) with weights (null: 1); bag b is entity idx[b] (idx null: b); an
+ * entity outside [0, n_seg) is an empty bag; tokens outside [1, n_rows) are padding.  s_b = sum_e w_e F[t_e];
+ * combiner 0 / 1 / 2 = sum / mean / sqrtn: c_b = 1, 1 / sum w_e, 1 / sqrt(sum w_e^2), and 0 when sum w_e = 0; p_b = c_b s_b;
+ * u_b = normalize ? p_b / max(|p_b|, 1e-12) : p_b.  Outputs out_u [B, d], out_inv [B], out_scale [B] (= c_b).  max_len
+ * sizes the workspace and grids (no host read); the summation order depends on the bag lengths only.  MF_ENOTSUP above
+ * 2^20 table rows or B * max_len >= 2^31. */
+size_t mf_bag_ws_bytes(int64_t B, int64_t max_len, int d);
+int mf_bag_forward(const float* table, int64_t n_rows, int d, const int64_t* idx, int64_t B, const int64_t* seg_start,
+                   const int64_t* seg_end, int64_t n_seg, const int64_t* tokens, int64_t n_tokens, const float* weights,
+                   int64_t max_len, int combiner, int normalize, float* out_u, float* out_inv, float* out_scale, void* ws,
+                   size_t ws_bytes, mf_stream_t stream);
+/* Backward, coalesced with extra rows parked on the same table (extra_ids [n_extra], extra_grad [n_extra, d]; valid ids
+ * [0, n_rows)): grad_p [B, d] = dL/dp (after mf_normalize_backward); entry e of bag b gets w_e * scale[b] * grad_p[b]
+ * (entries with w_e = 0 or scale[b] = 0 are dropped).  A stable radix sort by id and a fixed tree of run sums, over the
+ * entry count the plan kernel leaves on the device: no float atomics, no host round trip.  out_ids [capacity] = the unique
+ * ids ascending, then -1; out_grad [capacity, d] their rows (-1 slots not written).  capacity must be
+ * min(n_rows, n_extra + B * max_len). */
+size_t mf_bag_backward_ws_bytes(int64_t n_extra, int64_t B, int64_t max_len, int d);
+int mf_bag_backward(int64_t n_rows, int d, const int64_t* idx, int64_t B, const int64_t* seg_start, const int64_t* seg_end,
+                    int64_t n_seg, const int64_t* tokens, int64_t n_tokens, const float* weights, int64_t max_len,
+                    const float* scale, const float* grad_p, const int64_t* extra_ids, const float* extra_grad, int64_t n_extra,
+                    int64_t capacity, int64_t* out_ids, float* out_grad, void* ws, size_t ws_bytes, mf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

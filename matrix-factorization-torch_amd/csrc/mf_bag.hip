@@ -1,0 +1,589 @@
+// mf_bag.hip -- hashed feature-bag towers: u_b = normalize(c_b * sum_e w_e F[t_e]) over the (token, weight) bag of entity
+// idx[b], and the backward as ONE coalesced (id, gradient row) list for the sparse updates.
+//
+// Reference interface replaced: the shared text encoder of xfmr_rec/lightning.py:60-74 over the JSON of an item's
+// {"title", "genres"} / a user's {"gender", "age", "occupation", "zipcode"} (xfmr_rec/data/prepare.py:69-127).  Here the
+// attributes are hashed into tokens on the host (data.FeatureHasher) and each token is a row of one bucket table F [R, d]:
+// the classic EmbeddingBag tower.  Spec: tests/test_feature_tower_cpu.py.
+//
+// Bags.  Entity e's bag is tokens[start[e], end[e]) (clamped to [0, n_tokens), cut to max_len) with weights[...] (or 1); a
+// registered CSR passes start = off, end = off + 1.  Bag b of a call is entity idx[b] (idx null: b itself); an entity id
+// outside [0, n_seg) is an empty bag.  Tokens outside [1, R) are padding: dropped from the sum, the weight sums and the counts.
+// s_b = sum w_e F[t_e]; c_b = 1 (sum), 1 / sum w_e (mean), 1 / sqrt(sum w_e^2) (sqrtn), 0 when sum w_e = 0; p_b = c_b s_b;
+// u_b = normalize ? p_b / max(|p_b|, 1e-12) : p_b.
+//
+// Nothing is read back on the host: max_len (fixed when the bags are registered) sizes every buffer and grid, the kernels
+// exit early past the real work, and the backward's entry count is left on the device by its plan kernel.
+//
+// Forward.  max_len <= BAG_SHORT: one lane group (d/4 lanes, 16-byte loads in the gather_rows layout) per bag sums the bag
+// in entry order -- no plan, no partials.  Longer bags: one wave per BAG_CHUNK entries of a bag (bag b's chunk j is work
+// item b * C + j, C = ceil(max_len / BAG_CHUNK)), lane groups in a fixed butterfly, then one group per bag adds its chunks
+// in order.  Either way the summation order depends on the bag lengths only.
+//
+// Backward.  Entry e of bag b carries w_e * c_b * g_p[b]; entries with w_e = 0 or c_b = 0 carry nothing and are dropped like
+// padding.  Keys (extras first, then the bags' entries), the stable LSD radix sort, the run heads and the fixed fan-out tree
+// of run sums are those of mf_pool.hip (mf_sort.h), over the device-side entry count; the weight is applied at the leaf.
+// The result is exactly `capacity` = min(R, n_extra + B * max_len) slots: unique ids ascending, then -1.  The only atomics
+// are the integer LDS histogram counts.
+#include "mf_sort.h"
+
+static constexpr int BAG_SHORT = 64;             // longest bag of the one-group-per-bag path
+static constexpr int BAG_CHUNK = 64;             // entries per wave on the chunked path
+static constexpr int BAG_MAX_ROWS = 1 << 20;     // feature-table rows the radix sort covers
+static constexpr int BAG_PLAN_THREADS = 1024;
+
+struct BagSrc {                                  // the bags of one call
+    const int64_t* idx;                          // [B] entity ids, or null (bag b = entity b)
+    const int64_t* start;                        // [n_seg]
+    const int64_t* end;                          // [n_seg]
+    int64_t n_seg;
+    const int64_t* tokens;
+    int64_t n_tokens;
+    const float* weights;                        // [n_tokens] or null (1)
+    int64_t max_len;
+    int64_t R;
+};
+
+// first position and length of bag b
+__device__ __forceinline__ void bag_span(const BagSrc& s, int64_t b, int64_t& lo, int64_t& len) {
+    const int64_t e = s.idx ? s.idx[b] : b;
+    lo = 0;
+    len = 0;
+    if (e < 0 || e >= s.n_seg) return;
+    lo = min(max(s.start[e], (int64_t)0), s.n_tokens);
+    const int64_t hi = min(max(s.end[e], lo), s.n_tokens);
+    len = min(hi - lo, s.max_len);
+}
+
+// weight of the entry at position pos (0 for padding tokens)
+__device__ __forceinline__ float bag_weight(const BagSrc& s, int64_t pos, long long tok) {
+    if (tok < 1 || tok >= s.R) return 0.f;
+    return s.weights ? s.weights[pos] : 1.f;
+}
+
+__device__ __forceinline__ float bag_scale(int combiner, float wsum, float w2sum) {
+    if (!(wsum > 0.f)) return 0.f;
+    return combiner == 0 ? 1.f : (combiner == 1 ? 1.f / wsum : 1.f / sqrtf(w2sum));
+}
+
+// p = scale * s, then the tower's normalisation (the arithmetic of pool_finish_kernel); every lane of the wave calls this
+template <int D>
+__device__ __forceinline__ void bag_finish(f32x4 acc, float wsum, float w2sum, int combiner, int normalize, bool valid, int64_t b,
+                                           int c, float* __restrict__ out_u, float* __restrict__ out_inv, float* __restrict__ out_scale) {
+    constexpr int LPR = D / 4;
+    const float scale = bag_scale(combiner, wsum, w2sum);
+    f32x4 p = acc * scale;
+    if (scale == 0.f) p = f32x4{0.f, 0.f, 0.f, 0.f};
+    float inv = 1.f;
+    if (normalize) {
+        const float ss = mf_group_sum(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3], LPR);
+        inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+        p = p * inv;
+    }
+    if (valid) {
+        reinterpret_cast<f32x4*>(out_u + b * D)[c] = p;
+        if (c == 0) {
+            out_inv[b] = inv;
+            out_scale[b] = scale;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- forward ----
+// short bags: lane group (D/4 lanes) = one bag, entries in order, four row loads in flight
+template <int D>
+__global__ __launch_bounds__(256) void bag_short_kernel(const float* __restrict__ table, BagSrc src, int64_t B, int combiner, int normalize,
+                                                        float* __restrict__ out_u, float* __restrict__ out_inv, float* __restrict__ out_scale) {
+    constexpr int LPR = D / 4, RPW = 64 / LPR, U = 4;
+    const int lane = mf_lane(), c = lane % LPR;
+    const int64_t b = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + lane / LPR;
+    const bool valid = b < B;
+    int64_t lo = 0, len = 0;
+    if (valid) bag_span(src, b, lo, len);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float wsum = 0.f, w2sum = 0.f;
+    for (int64_t j0 = 0; j0 < len; j0 += U) {
+        long long tok[U];
+        float w[U];
+#pragma unroll
+        for (int t = 0; t < U; ++t) {
+            const int64_t j = j0 + t;
+            tok[t] = j < len ? src.tokens[lo + j] : 0;
+            w[t] = j < len ? bag_weight(src, lo + j, tok[t]) : 0.f;
+        }
+        f32x4 x[U];
+#pragma unroll
+        for (int t = 0; t < U; ++t) x[t] = reinterpret_cast<const f32x4*>(table + (w[t] != 0.f ? tok[t] : 0) * D)[c];
+#pragma unroll
+        for (int t = 0; t < U; ++t) {
+            if (w[t] != 0.f) {
+                acc += x[t] * w[t];
+                wsum += w[t];
+                w2sum += w[t] * w[t];
+            }
+        }
+    }
+    bag_finish<D>(acc, wsum, w2sum, combiner, normalize, valid, b, c, out_u, out_inv, out_scale);
+}
+
+// long bags, first level: one wave per chunk of BAG_CHUNK entries (grid-stride over B * C work items)
+template <int D>
+__global__ __launch_bounds__(256) void bag_chunk_kernel(const float* __restrict__ table, BagSrc src, int64_t B, int64_t C,
+                                                        float* __restrict__ psum, float* __restrict__ pw) {
+    constexpr int LPR = D / 4, RPW = 64 / LPR, PER = BAG_CHUNK / RPW, U = PER < 4 ? PER : 4;
+    const int lane = mf_lane(), g = lane / LPR, c = lane % LPR;
+    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t k = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); k < B * C; k += nwaves) {
+        const int64_t b = k / C, j0 = (k % C) * BAG_CHUNK;
+        int64_t lo, len;
+        bag_span(src, b, lo, len);
+        if (j0 >= len) continue;                                       // (wave-uniform)
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        float wsum = 0.f, w2sum = 0.f;
+        for (int u0 = 0; u0 < PER; u0 += U) {
+            long long tok[U];
+            float w[U];
+#pragma unroll
+            for (int t = 0; t < U; ++t) {
+                const int64_t j = j0 + (int64_t)(u0 + t) * RPW + g;
+                tok[t] = j < len ? src.tokens[lo + j] : 0;
+                w[t] = j < len ? bag_weight(src, lo + j, tok[t]) : 0.f;
+            }
+            f32x4 x[U];
+#pragma unroll
+            for (int t = 0; t < U; ++t) x[t] = reinterpret_cast<const f32x4*>(table + (w[t] != 0.f ? tok[t] : 0) * D)[c];
+#pragma unroll
+            for (int t = 0; t < U; ++t) {
+                if (w[t] != 0.f) {
+                    acc += x[t] * w[t];
+                    wsum += w[t];
+                    w2sum += w[t] * w[t];
+                }
+            }
+        }
+        // groups in a fixed butterfly, the lower group's value first: every lane ends with the same sums
+#pragma unroll
+        for (int s = LPR; s < 64; s <<= 1) {
+            f32x4 o;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) o[t] = __shfl_xor(acc[t], s, 64);
+            const float ow = __shfl_xor(wsum, s, 64), ow2 = __shfl_xor(w2sum, s, 64);
+            const bool low = (lane & s) == 0;
+            acc = low ? acc + o : o + acc;
+            wsum = low ? wsum + ow : ow + wsum;
+            w2sum = low ? w2sum + ow2 : ow2 + w2sum;
+        }
+        if (g == 0) {
+            reinterpret_cast<f32x4*>(psum + k * D)[c] = acc;
+            if (c == 0) {
+                pw[2 * k] = wsum;
+                pw[2 * k + 1] = w2sum;
+            }
+        }
+    }
+}
+
+// long bags, second level: one lane group per bag adds its chunks in chunk order
+template <int D>
+__global__ __launch_bounds__(256) void bag_combine_kernel(BagSrc src, int64_t B, int64_t C, const float* __restrict__ psum,
+                                                          const float* __restrict__ pw, int combiner, int normalize,
+                                                          float* __restrict__ out_u, float* __restrict__ out_inv, float* __restrict__ out_scale) {
+    constexpr int LPR = D / 4, RPW = 64 / LPR;
+    const int lane = mf_lane(), c = lane % LPR;
+    const int64_t b = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + lane / LPR;
+    const bool valid = b < B;
+    int64_t lo = 0, len = 0;
+    if (valid) bag_span(src, b, lo, len);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float wsum = 0.f, w2sum = 0.f;
+    const int64_t nch = (len + BAG_CHUNK - 1) / BAG_CHUNK;
+    for (int64_t j = 0; j < nch; ++j) {
+        const int64_t k = b * C + j;
+        acc += reinterpret_cast<const f32x4*>(psum + k * D)[c];
+        wsum += pw[2 * k];
+        w2sum += pw[2 * k + 1];
+    }
+    bag_finish<D>(acc, wsum, w2sum, combiner, normalize, valid, b, c, out_u, out_inv, out_scale);
+}
+
+static int bag_grid(int64_t work_waves) {         // grid-stride kernels: enough waves to fill the chip, no more than the work
+    const int64_t blocks = (work_waves + 3) / 4;
+    return (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
+}
+
+static int64_t bag_chunks(int64_t max_len) { return max_len <= BAG_SHORT ? 0 : (max_len + BAG_CHUNK - 1) / BAG_CHUNK; }
+
+extern "C" size_t mf_bag_ws_bytes(int64_t B, int64_t max_len, int d) {
+    MfArena a(nullptr);
+    const int64_t C = bag_chunks(max_len);
+    a.take<float>((size_t)(B > 0 ? B : 0) * C * d);
+    a.take<float>((size_t)(B > 0 ? B : 0) * C * 2);
+    return a.used();
+}
+
+static int bag_check(const char* who, int64_t n_rows, int d, int64_t B, const int64_t* start, const int64_t* end, int64_t n_seg,
+                     const int64_t* tokens, int64_t n_tokens, int64_t max_len) {
+    if (!start || !end || !tokens || B <= 0 || n_rows <= 0 || n_seg < 0 || n_tokens <= 0 || max_len < 0)
+        return mf_set_error(MF_EINVAL, "%s: bad argument", who);
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "%s: embedding width %d not in {32,64,128,256}", who, d);
+    if (n_rows > BAG_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "%s: %lld feature-table rows > %d", who, (long long)n_rows, BAG_MAX_ROWS);
+    if (max_len > 0 && B >= ((1ll << 31) - 1) / max_len) return mf_set_error(MF_ENOTSUP, "%s: B * max_len >= 2^31", who);
+    return MF_OK;
+}
+
+extern "C" int mf_bag_forward(const float* table, int64_t n_rows, int d, const int64_t* idx, int64_t B, const int64_t* seg_start,
+                              const int64_t* seg_end, int64_t n_seg, const int64_t* tokens, int64_t n_tokens, const float* weights,
+                              int64_t max_len, int combiner, int normalize, float* out_u, float* out_inv, float* out_scale, void* ws,
+                              size_t ws_bytes, mf_stream_t stream) {
+    if (!table || !out_u || !out_inv || !out_scale || combiner < 0 || combiner > 2)
+        return mf_set_error(MF_EINVAL, "mf_bag_forward: bad argument");
+    if (int rc = bag_check("mf_bag_forward", n_rows, d, B, seg_start, seg_end, n_seg, tokens, n_tokens, max_len)) return rc;
+    const int64_t C = bag_chunks(max_len);
+    if (C > 0 && (!ws || ws_bytes < mf_bag_ws_bytes(B, max_len, d))) return mf_set_error(MF_ENOSPC, "mf_bag_forward: workspace too small");
+    const BagSrc src{idx, seg_start, seg_end, n_seg, tokens, n_tokens, weights, max_len, n_rows};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MF_DISPATCH_D(d, {
+        constexpr int RPB = (64 / (D / 4)) * 4;                     // bags per 256-thread block
+        const unsigned gb = (unsigned)((B + RPB - 1) / RPB);
+        MF_TIMED("bag_forward", s, {
+            if (C == 0) {
+                bag_short_kernel<D><<<gb, 256, 0, s>>>(table, src, B, combiner, normalize, out_u, out_inv, out_scale);
+            } else {
+                MfArena a(ws);
+                float* psum = a.take<float>((size_t)B * C * D);
+                float* pw = a.take<float>((size_t)B * C * 2);
+                bag_chunk_kernel<D><<<bag_grid(B * C), 256, 0, s>>>(table, src, B, C, psum, pw);
+                bag_combine_kernel<D><<<gb, 256, 0, s>>>(src, B, C, psum, pw, combiner, normalize, out_u, out_inv, out_scale);
+            }
+        });
+    });
+    return mf_check_launch("mf_bag_forward");
+}
+
+// =========================================================================================== backward ====
+// One workgroup: lo / len of every bag, the exclusive prefix of the lengths (the entry numbering) and the entry count
+// n = n_extra + sum len, left on the device for every later kernel.
+__global__ __launch_bounds__(BAG_PLAN_THREADS) void bag_plan_kernel(BagSrc src, int64_t B, int64_t n_extra, int64_t* __restrict__ lo_out,
+                                                                   int64_t* __restrict__ ent_off, int32_t* __restrict__ n_dev) {
+    __shared__ int64_t wsum[BAG_PLAN_THREADS / 64];
+    const int lane = mf_lane(), wave = threadIdx.x >> 6;
+    int64_t run = 0;
+    for (int64_t b0 = 0; b0 < B; b0 += BAG_PLAN_THREADS) {
+        const int64_t b = b0 + threadIdx.x;
+        int64_t lo = 0, len = 0;
+        if (b < B) bag_span(src, b, lo, len);
+        const int64_t inc = wave_incl_scan(len);
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int64_t before = 0, all = 0;
+        for (int w = 0; w < BAG_PLAN_THREADS / 64; ++w) {
+            if (w < wave) before += wsum[w];
+            all += wsum[w];
+        }
+        if (b < B) {
+            lo_out[b] = lo;
+            ent_off[b] = run + before + inc - len;
+        }
+        run += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ent_off[B] = run;
+        *n_dev = (int32_t)(n_extra + run);
+    }
+}
+
+// keys: entry q < n_extra is explicit row q (valid ids [0, R)), entry n_extra + h is bag entry h; padding tokens, zero
+// weights and bags with c_b = 0 get key R and sort last
+__global__ __launch_bounds__(256) void bag_keys_kernel(const int64_t* __restrict__ extra_ids, int64_t n_extra, BagSrc src, int64_t B,
+                                                       const int64_t* __restrict__ lo, const int64_t* __restrict__ ent_off,
+                                                       const float* __restrict__ scale, const int32_t* __restrict__ n_dev,
+                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, int32_t* __restrict__ euser) {
+    const int64_t n = *n_dev;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n; q += stride) {
+        uint32_t key = (uint32_t)src.R;
+        if (q < n_extra) {
+            const long long id = extra_ids[q];
+            if (id >= 0 && id < src.R) key = (uint32_t)id;
+        } else {
+            const int64_t h = q - n_extra;
+            const int64_t b = pool_owner(ent_off, B, h);
+            const int64_t pos = lo[b] + (h - ent_off[b]);
+            const long long tok = src.tokens[pos];
+            if (bag_weight(src, pos, tok) != 0.f && scale[b] != 0.f) key = (uint32_t)tok;
+            euser[h] = (int32_t)b;
+        }
+        keys[q] = key;
+        vals[q] = (uint32_t)q;
+    }
+}
+
+// one 8-bit digit of the LSD radix sort over the first *n_dev keys (radix_hist_kernel with the count on the device):
+// per-tile counts (zero past the end) ...
+__global__ __launch_bounds__(256) void bag_radix_hist_kernel(const uint32_t* __restrict__ keys, const int32_t* __restrict__ n_dev, int shift,
+                                                             int ntiles, int32_t* __restrict__ hist) {
+    __shared__ int cnt[256];
+    const int64_t n = *n_dev;
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
+    if (t0 < n) {
+        for (int i = threadIdx.x; i < RADIX_TILE; i += 256) {
+            const int64_t q = t0 + i;
+            if (q < n) atomicAdd(&cnt[(keys[q] >> shift) & 255], 1);       // integer counts: order-free
+        }
+    }
+    __syncthreads();
+    hist[(int64_t)threadIdx.x * ntiles + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// ... and the stable scatter (radix_scatter_kernel)
+__global__ __launch_bounds__(256) void bag_radix_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
+                                                                const int32_t* __restrict__ n_dev, int shift, int ntiles,
+                                                                const int32_t* __restrict__ hist, uint32_t* __restrict__ kout,
+                                                                uint32_t* __restrict__ vout) {
+    __shared__ int base[256];
+    __shared__ int wcnt[4][256];
+    const int64_t n = *n_dev;
+    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
+    if (t0 >= n) return;                                               // (block-uniform)
+    const int tid = threadIdx.x, lane = mf_lane(), wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    base[tid] = hist[(int64_t)tid * ntiles + blockIdx.x];
+    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0;
+    __syncthreads();
+    for (int r = 0; r < RADIX_TILE / 256; ++r) {
+        const int64_t q = t0 + r * 256 + tid;
+        const bool valid = q < n;
+        const uint32_t k = valid ? kin[q] : 0u;
+        const unsigned dg = (k >> shift) & 255u;
+        const unsigned long long peers = radix_peers(valid, dg);
+        if (valid && (peers & below) == 0) wcnt[wave][dg] = __popcll(peers);
+        __syncthreads();
+        if (valid) {
+            int pos = base[dg] + __popcll(peers & below);
+            for (int w = 0; w < wave; ++w) pos += wcnt[w][dg];
+            kout[pos] = k;
+            vout[pos] = vin[q];
+        }
+        __syncthreads();
+        base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+        for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0;
+        __syncthreads();
+    }
+}
+
+// heads of the runs of valid keys (pool_heads_kernel): per-tile counts, then the head position of every output slot
+template <bool SLOTS>
+__global__ __launch_bounds__(256) void bag_heads_kernel(const uint32_t* __restrict__ sk, const int32_t* __restrict__ n_dev, uint32_t R,
+                                                        int32_t* __restrict__ tcount, int32_t* __restrict__ head_pos) {
+    __shared__ int wcnt[4];
+    const int64_t n = *n_dev;
+    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
+    if (t0 >= n) {                                                     // (block-uniform) past the end: an empty tile
+        if (!SLOTS && threadIdx.x == 0) tcount[blockIdx.x] = 0;
+        return;
+    }
+    const int tid = threadIdx.x, lane = mf_lane(), wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int at = SLOTS ? tcount[blockIdx.x] : 0;
+    for (int r = 0; r < RADIX_TILE / 256; ++r) {
+        const int64_t q = t0 + r * 256 + tid;
+        const bool head = q < n && sk[q] < R && (q == 0 || sk[q - 1] != sk[q]);
+        const unsigned long long m = __ballot(head);
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0;
+        for (int w = 0; w < wave; ++w) before += wcnt[w];
+        if (SLOTS && head) head_pos[at + before + __popcll(m & below)] = (int32_t)q;
+        at += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+    if (!SLOTS && tid == 0) tcount[blockIdx.x] = at;
+}
+
+__global__ __launch_bounds__(256) void bag_fill_kernel(const int32_t* __restrict__ n_unique, int64_t capacity, int64_t* __restrict__ out_ids) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s < capacity && s >= *n_unique) out_ids[s] = -1;
+}
+
+struct BagGradSrc {
+    const float* extra_grad;
+    int64_t n_extra;
+    const int32_t* euser;
+    const int64_t* lo;
+    const int64_t* ent_off;
+    const float* scale;
+    const float* grad_p;
+    BagSrc bags;
+};
+
+// gradient row (lane c's 4 floats) of entry v: an extra row, or w_e * c_b * g_p[b]
+template <int D>
+__device__ __forceinline__ f32x4 bag_entry_grad(const BagGradSrc& src, uint32_t v, int c) {
+    if ((int64_t)v < src.n_extra) return reinterpret_cast<const f32x4*>(src.extra_grad + (int64_t)v * D)[c];
+    const int64_t h = (int64_t)v - src.n_extra;
+    const int64_t b = src.euser[h];
+    const float w = src.bags.weights ? src.bags.weights[src.lo[b] + (h - src.ent_off[b])] : 1.f;
+    return reinterpret_cast<const f32x4*>(src.grad_p + b * D)[c] * (w * src.scale[b]);
+}
+
+// The runs' sums in sorted order: pool_segsum_kernel's fixed tree of fan-out RUN_CHUNK (one launch per level), over the
+// device-side entry count, with the weight applied at the leaf.  A hot token (in 40 % of the bags) is summed by many lane
+// groups at level 1, their partials by fewer at the levels above.
+template <int D>
+__global__ __launch_bounds__(256) void bag_segsum_kernel(const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv,
+                                                         const int32_t* __restrict__ n_dev, uint32_t R, const int32_t* __restrict__ head_pos,
+                                                         const int32_t* __restrict__ n_unique, int64_t capacity, BagGradSrc src,
+                                                         int64_t unit, float* __restrict__ partial, int64_t* __restrict__ out_ids,
+                                                         float* __restrict__ out_grad) {
+    constexpr int LPR = D / 4, RPW = 64 / LPR;
+    const int lane = mf_lane(), c = lane % LPR;
+    const int64_t n = *n_dev;
+    const int64_t i = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + lane / LPR;
+    const int64_t block = unit * RUN_CHUNK;
+    int64_t p, sl = -1;
+    bool head;
+    if (i < capacity) {
+        if (i >= *n_unique) return;                      // (no cross-lane operation below)
+        sl = i;
+        p = head_pos[i];
+        head = true;
+    } else {
+        p = (i - capacity) * block;
+        if (p >= n || sk[p] >= R || p == 0 || sk[p - 1] != sk[p]) return;   // past the end, padding, or a run's head
+        head = false;
+    }
+    const uint32_t key = sk[p];
+    const int64_t sub = unit / RUN_CHUNK;
+    const int64_t sub_end = sub ? (p / unit + 1) * unit : p + 1;
+    if (sub && head && (sub_end >= n || sk[sub_end] != key)) return;   // finished at a lower level
+    const int64_t block_end = min((p / block + 1) * block, n);
+    constexpr int NB = 4;
+    const int64_t step = sub ? unit : 1;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    int64_t e = p;
+    if (sub) {
+        acc = reinterpret_cast<const f32x4*>(partial + p * D)[c];
+        e = sub_end;
+    }
+    for (;;) {
+        uint32_t k8[NB];
+#pragma unroll
+        for (int t = 0; t < NB; ++t) k8[t] = e + t * step < block_end ? sk[e + t * step] : 0xFFFFFFFFu;
+        int m = 0;
+#pragma unroll
+        for (int t = 0; t < NB; ++t) m += (m == t && k8[t] == key) ? 1 : 0;
+        f32x4 g[NB];
+        if (!sub) {
+            uint32_t v8[NB];
+#pragma unroll
+            for (int t = 0; t < NB; ++t) v8[t] = t < m ? sv[e + t] : 0u;
+#pragma unroll
+            for (int t = 0; t < NB; ++t)
+                if (t < m) g[t] = bag_entry_grad<D>(src, v8[t], c);
+        } else {
+#pragma unroll
+            for (int t = 0; t < NB; ++t)
+                if (t < m) g[t] = reinterpret_cast<const f32x4*>(partial + (e + t * step) * D)[c];
+        }
+#pragma unroll
+        for (int t = 0; t < NB; ++t)
+            if (t < m) acc += g[t];
+        e += m * step;
+        if (m < NB || e >= block_end) break;
+    }
+    e = min(e, block_end);
+    if (head && (e >= n || sk[e] != key)) {
+        reinterpret_cast<f32x4*>(out_grad + sl * D)[c] = acc;
+        if (c == 0) out_ids[sl] = key;
+    } else {
+        reinterpret_cast<f32x4*>(partial + p * D)[c] = acc;
+    }
+}
+
+struct BagBwdWs {
+    int64_t *lo, *ent_off;
+    uint32_t *k0, *v0, *k1, *v1;
+    int32_t *n_dev, *euser, *hist, *tcount, *head_pos;
+    float* partial;
+    int ntiles;
+    size_t total;
+};
+static BagBwdWs bag_bwd_ws(void* ws, int64_t n_cap, int64_t B, int64_t n_entries, int d) {
+    MfArena a(ws);
+    BagBwdWs w;
+    w.ntiles = (int)((n_cap + RADIX_TILE - 1) / RADIX_TILE);
+    w.lo = a.take<int64_t>((size_t)B);
+    w.ent_off = a.take<int64_t>((size_t)B + 1);
+    w.n_dev = a.take<int32_t>(1);
+    w.k0 = a.take<uint32_t>((size_t)n_cap);
+    w.v0 = a.take<uint32_t>((size_t)n_cap);
+    w.k1 = a.take<uint32_t>((size_t)n_cap);
+    w.v1 = a.take<uint32_t>((size_t)n_cap);
+    w.euser = a.take<int32_t>((size_t)n_entries);
+    w.hist = a.take<int32_t>((size_t)256 * w.ntiles + 1);
+    w.tcount = a.take<int32_t>((size_t)w.ntiles + 1);
+    w.head_pos = a.take<int32_t>((size_t)n_cap);
+    w.partial = a.take<float>((size_t)n_cap * d);
+    w.total = a.used();
+    return w;
+}
+
+extern "C" size_t mf_bag_backward_ws_bytes(int64_t n_extra, int64_t B, int64_t max_len, int d) {
+    B = B > 0 ? B : 1;
+    const int64_t n_entries = B * (max_len > 0 ? max_len : 0);
+    const int64_t n_cap = (n_extra > 0 ? n_extra : 0) + n_entries;
+    return bag_bwd_ws(nullptr, n_cap > 0 ? n_cap : 1, B, n_entries, d).total;
+}
+
+extern "C" int mf_bag_backward(int64_t n_rows, int d, const int64_t* idx, int64_t B, const int64_t* seg_start, const int64_t* seg_end,
+                               int64_t n_seg, const int64_t* tokens, int64_t n_tokens, const float* weights, int64_t max_len,
+                               const float* scale, const float* grad_p, const int64_t* extra_ids, const float* extra_grad, int64_t n_extra,
+                               int64_t capacity, int64_t* out_ids, float* out_grad, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    if (!scale || !grad_p || !out_ids || !out_grad || !ws || n_extra < 0 || (n_extra > 0 && (!extra_ids || !extra_grad)))
+        return mf_set_error(MF_EINVAL, "mf_bag_backward: bad argument");
+    if (int rc = bag_check("mf_bag_backward", n_rows, d, B, seg_start, seg_end, n_seg, tokens, n_tokens, max_len)) return rc;
+    const int64_t n_entries = B * max_len, n_cap = n_extra + n_entries;
+    if (n_cap >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_bag_backward: %lld entries >= 2^31", (long long)n_cap);
+    if (capacity != (n_cap < n_rows ? n_cap : n_rows))
+        return mf_set_error(MF_EINVAL, "mf_bag_backward: capacity must be min(n_rows, n_extra + B * max_len)");
+    if (ws_bytes < mf_bag_backward_ws_bytes(n_extra, B, max_len, d)) return mf_set_error(MF_ENOSPC, "mf_bag_backward: workspace too small");
+    if (n_cap == 0) return MF_OK;
+    BagBwdWs w = bag_bwd_ws(ws, n_cap, B, n_entries, d);
+    const BagSrc bags{idx, seg_start, seg_end, n_seg, tokens, n_tokens, weights, max_len, n_rows};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int bits = 1;
+    while ((1ll << bits) <= n_rows) ++bits;                  // keys 0 .. R
+    const int passes = (bits + 7) / 8;
+    const unsigned tiles = (unsigned)w.ntiles;
+    MF_TIMED("bag_backward", s, {
+        bag_plan_kernel<<<1, BAG_PLAN_THREADS, 0, s>>>(bags, B, n_extra, w.lo, w.ent_off, w.n_dev);
+        bag_keys_kernel<<<bag_grid((n_cap + 63) / 64), 256, 0, s>>>(extra_ids, n_extra, bags, B, w.lo, w.ent_off, scale, w.n_dev, w.k0,
+                                                                    w.v0, w.euser);
+        uint32_t *ki = w.k0, *vi = w.v0, *ko = w.k1, *vo = w.v1;
+        for (int ps = 0; ps < passes; ++ps) {
+            bag_radix_hist_kernel<<<tiles, 256, 0, s>>>(ki, w.n_dev, 8 * ps, w.ntiles, w.hist);
+            mf_scan_i32(w.hist, (int64_t)256 * w.ntiles, s);
+            bag_radix_scatter_kernel<<<tiles, 256, 0, s>>>(ki, vi, w.n_dev, 8 * ps, w.ntiles, w.hist, ko, vo);
+            uint32_t* t = ki; ki = ko; ko = t;
+            t = vi; vi = vo; vo = t;
+        }
+        bag_heads_kernel<false><<<tiles, 256, 0, s>>>(ki, w.n_dev, (uint32_t)n_rows, w.tcount, nullptr);
+        mf_scan_i32(w.tcount, w.ntiles, s);
+        bag_heads_kernel<true><<<tiles, 256, 0, s>>>(ki, w.n_dev, (uint32_t)n_rows, w.tcount, w.head_pos);
+        bag_fill_kernel<<<dim3((unsigned)((capacity + 255) / 256)), 256, 0, s>>>(w.tcount + w.ntiles, capacity, out_ids);
+        const BagGradSrc src{extra_grad, n_extra, w.euser, w.lo, w.ent_off, scale, grad_p, bags};
+        MF_DISPATCH_D(d, {
+            constexpr int RPB = (64 / (D / 4)) * 4;
+            for (int64_t unit = 1;; unit *= RUN_CHUNK) {          // levels until one block covers every possible position
+                const int64_t items = capacity + (n_cap + unit * RUN_CHUNK - 1) / (unit * RUN_CHUNK);
+                bag_segsum_kernel<D><<<dim3((unsigned)((items + RPB - 1) / RPB)), 256, 0, s>>>(
+                    ki, vi, w.n_dev, (uint32_t)n_rows, w.head_pos, w.tcount + w.ntiles, capacity, src, unit, w.partial, out_ids, out_grad);
+                if (unit * RUN_CHUNK >= n_cap) break;
+            }
+        });
+    });
+    return mf_check_launch("mf_bag_backward");
+}

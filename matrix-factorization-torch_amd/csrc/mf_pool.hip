@@ -20,26 +20,13 @@
 // host round trip), and the runs of equal ids are summed in sorted order (= entry order) by a fixed tree of RUN_CHUNK.  The
 // result is a list of exactly `capacity` = min(n_rows, entries) slots: the unique ids in ascending order with their summed
 // rows, then id -1 (skipped by every update kernel).  The run sums form a fixed tree of fan-out 32 (pool_segsum_kernel).
-#include "mf_update.h"
+#include "mf_sort.h"
 
 static constexpr int POOL_CHUNK = 64;            // entries per chunk (one wave)
 static constexpr int POOL_SUPER = 32;            // chunks per first-level combine
 static constexpr int POOL_MAX_ROWS = 1 << 20;    // item-table rows the radix sort covers (keys <= 2^20: three 8-bit digits)
-static constexpr int RADIX_TILE = 4096;          // sorted positions per workgroup (16 rounds of 256)
-static constexpr int SCAN_THREADS = 1024;
 
 __device__ __forceinline__ bool pool_valid(long long id, long long n_rows) { return id >= 1 && id < n_rows; }
-
-// last b in [0, B] with off[b] <= k  (off non-decreasing, off[0] = 0 <= k)
-__device__ __forceinline__ int64_t pool_owner(const int64_t* __restrict__ off, int64_t B, int64_t k) {
-    int64_t l = 0, r = B;
-    while (r - l > 1) {
-        const int64_t m = (l + r) >> 1;
-        if (off[m] <= k) l = m;
-        else r = m;
-    }
-    return l;
-}
 
 // ------------------------------------------------------------------------------------------- max_history ----
 // One wave per user: walk back from hi 64 entries at a time until the L-th valid entry.
@@ -70,16 +57,6 @@ __global__ __launch_bounds__(256) void pool_cut_kernel(const int64_t* __restrict
 
 // --------------------------------------------------------------------------------------------------- plan ----
 // One workgroup: lo / hi of every user, and the exclusive prefixes of its chunks, first-level groups and entries.
-__device__ __forceinline__ int64_t wave_incl_scan(int64_t x) {
-    const int lane = mf_lane();
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int64_t y = __shfl_up(x, s, 64);
-        if (lane >= s) x += y;
-    }
-    return x;
-}
-
 static constexpr int PLAN_THREADS = 256;
 // block-wide exclusive scan of three int64 per thread (PLAN_THREADS threads); returns the block totals in tot[3]
 __device__ __forceinline__ void block_scan3(int64_t v[3], int64_t tot[3]) {
@@ -473,16 +450,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i32_kernel(int32_t* __restr
     if (threadIdx.x == 0) x[n] = run;
 }
 
-// the lanes of this wave with my digit (8 ballots), among the `valid` lanes
-__device__ __forceinline__ unsigned long long radix_peers(bool valid, unsigned dg) {
-    unsigned long long m = __ballot(valid);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-        const unsigned long long on = __ballot(valid && ((dg >> bit) & 1u));
-        m &= ((dg >> bit) & 1u) ? on : ~on;
-    }
-    return m;
-}
+void mf_scan_i32(int32_t* x, int64_t n, hipStream_t s) { scan_i32_kernel<<<1, SCAN_THREADS, 0, s>>>(x, n); }
 
 // ... and a stable scatter: 16 rounds of 256 positions; inside a wave the rank among equal digits comes from the ballots,
 // across waves from a 4 x 256 count table

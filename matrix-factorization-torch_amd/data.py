@@ -456,3 +456,199 @@ def to_device(batch, device):
     if isinstance(batch, (tuple, list)):             # ``pos_csr`` / ``history`` triples
         return type(batch)(to_device(v, device) for v in batch)
     return batch.to(device) if isinstance(batch, torch.Tensor) else batch
+
+
+# ---------------------------------------------------------------------------------------- feature bags ----
+# The reference embeds each entity's ATTRIBUTES, not its id: an item is the JSON of {"title", "genres"}, a user the JSON of
+# {"gender", "age", "occupation", "zipcode"} (xfmr_rec/data/prepare.py:69-127), read by one shared text encoder
+# (xfmr_rec/lightning.py:60-74).  Here those attributes become hashed tokens, one row each of a bucket table
+# (models.FeatureBagTower): the classic EmbeddingBag tower of matrix-factorization recommenders.
+
+
+class FeatureBags:
+    """Bags of ``(token, weight)`` pairs as a CSR: entity e's bag is ``tokens[off[e]:off[e + 1]]`` with
+    ``weights[off[e]:off[e + 1]]`` (``None``: every weight is 1).  ``max_len`` (the longest bag) is fixed here, on the host,
+    so that the GPU kernels are sized without reading anything back.  Weights must be finite and >= 0."""
+
+    def __init__(self, off, tokens, weights=None) -> None:
+        self.off = torch.as_tensor(off, dtype=torch.int64)
+        self.tokens = torch.as_tensor(tokens, dtype=torch.int64)
+        self.weights = None if weights is None else torch.as_tensor(weights, dtype=torch.float32)
+        if self.off.dim() != 1 or self.off.numel() < 1 or self.tokens.dim() != 1:
+            msg = f"a bag CSR is off [n + 1] and tokens [nnz]: {tuple(self.off.shape) = }, {tuple(self.tokens.shape) = }"
+            raise ValueError(msg)
+        off_cpu = self.off.cpu()
+        if int(off_cpu[0]) != 0 or int(off_cpu[-1]) != self.tokens.numel() or bool((off_cpu[1:] < off_cpu[:-1]).any()):
+            msg = "bag offsets must start at 0, be non-decreasing and end at len(tokens)"
+            raise ValueError(msg)
+        if self.weights is not None:
+            if self.weights.shape != self.tokens.shape:
+                msg = f"one weight per token: {tuple(self.weights.shape)} != {tuple(self.tokens.shape)}"
+                raise ValueError(msg)
+            w = self.weights.cpu()
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                msg = "bag weights must be finite and >= 0"
+                raise ValueError(msg)
+        self.max_len = int((off_cpu[1:] - off_cpu[:-1]).max()) if off_cpu.numel() > 1 else 0
+
+    @classmethod
+    def from_lists(cls, lists, weights=None) -> "FeatureBags":
+        """From per-entity token lists (and optional per-entity weight lists of the same lengths)."""
+        lens = [len(x) for x in lists]
+        off = [0]
+        for n in lens:
+            off.append(off[-1] + n)
+        tokens = [int(t) for x in lists for t in x]
+        w = None
+        if weights is not None:
+            if [len(x) for x in weights] != lens:
+                msg = "one weight per token: weight lists must have the lengths of the token lists"
+                raise ValueError(msg)
+            w = [float(v) for x in weights for v in x]
+        return cls(off, tokens, w)
+
+    def __len__(self) -> int:
+        return self.off.numel() - 1
+
+    @property
+    def device(self) -> torch.device:
+        return self.tokens.device
+
+    def to(self, device) -> "FeatureBags":
+        out = object.__new__(FeatureBags)
+        out.off, out.tokens = self.off.to(device), self.tokens.to(device)
+        out.weights = None if self.weights is None else self.weights.to(device)
+        out.max_len = self.max_len
+        return out
+
+    def lists(self) -> list[list[int]]:
+        off, tok = self.off.tolist(), self.tokens.tolist()
+        return [tok[off[e]:off[e + 1]] for e in range(len(self))]
+
+
+class FeatureHasher:
+    """Attributes -> hashed bucket tokens.  An entity is the reference's JSON text (or the dict it encodes): a list value
+    gives one token per element (``genres=Comedy``), a field of ``text_fields`` one token per lowercase ``[a-z0-9]+`` word
+    (``title=toy``, ``title=story``, ``title=1995``), any other value one ``field=value`` token.  ``id_field``: the entity's
+    own id (passed to :meth:`bags`) is one more token.  Bucket = ``1 + blake2b(b"field=value", 8-byte digest, key = seed as
+    8 little-endian bytes) mod (num_buckets - 1)``: never 0 (padding), and the same in every process (``hash()`` is not)."""
+
+    def __init__(self, num_buckets: int, seed: int = 0, text_fields=("title",), id_field: str | None = None) -> None:
+        if num_buckets < 2:  # noqa: PLR2004
+            msg = f"num_buckets must be >= 2 (bucket 0 is padding): {num_buckets = }"
+            raise ValueError(msg)
+        if not 0 <= seed < 2**64:
+            msg = f"seed must fit in 8 bytes: {seed = }"
+            raise ValueError(msg)
+        self.num_buckets, self.seed = int(num_buckets), int(seed)
+        self.text_fields, self.id_field = tuple(text_fields), id_field
+        self._key = self.seed.to_bytes(8, "little")
+
+    def bucket(self, field: str, value) -> int:
+        import hashlib
+
+        h = hashlib.blake2b(f"{field}={value}".encode(), digest_size=8, key=self._key).digest()
+        return 1 + int.from_bytes(h, "little") % (self.num_buckets - 1)
+
+    def features(self, entity) -> list[str]:
+        """The ``field=value`` strings of one entity (JSON text, dict, or ``None`` / ``""`` for an empty bag)."""
+        import json
+        import re
+
+        if entity is None or entity == "":
+            return []
+        if isinstance(entity, str):
+            entity = json.loads(entity)
+        out = []
+        for field, value in entity.items():
+            if value is None:
+                continue
+            if isinstance(value, (list, tuple)):
+                out += [f"{field}={v}" for v in value if v is not None]
+            elif field in self.text_fields:
+                out += [f"{field}={w}" for w in re.findall(r"[a-z0-9]+", str(value).lower())]
+            else:
+                out.append(f"{field}={value}")
+        return out
+
+    def tokens(self, entity, entity_id=None) -> list[int]:
+        feats = self.features(entity)
+        toks = [self.bucket(*f.split("=", 1)) for f in feats]
+        if self.id_field is not None and entity_id is not None:
+            toks.append(self.bucket(self.id_field, entity_id))
+        return toks
+
+    def bags(self, texts, ids=None) -> FeatureBags:
+        """One bag per entity of ``texts``; ``ids`` (with ``id_field``) adds each entity's id token."""
+        texts = list(texts)
+        if self.id_field is not None and ids is not None and len(ids) != len(texts):
+            msg = f"one id per entity: {len(ids)} != {len(texts)}"
+            raise ValueError(msg)
+        return FeatureBags.from_lists([self.tokens(t, None if ids is None else int(ids[k])) for k, t in enumerate(texts)])
+
+    def config(self) -> dict:
+        return {"num_buckets": self.num_buckets, "seed": self.seed, "text_fields": list(self.text_fields), "id_field": self.id_field}
+
+
+def _json_text(obj: dict) -> str:
+    """polars' ``struct.json_encode`` layout (prepare.py:86-87, 118-121): compact, non-ASCII kept."""
+    import json
+
+    return json.dumps(obj, separators=(",", ":"), ensure_ascii=False)
+
+
+def read_movielens_features(ratings_path):
+    """``(item_texts, user_texts)``: the reference's JSON texts of every item (``{"title", "genres"}``, prepare.py:69-92)
+    and user (``{"gender", "age", "occupation", "zipcode"}``, :95-127), indexed by the rows :func:`movielens_interactions`
+    assigns (file order from 1; entry 0, the padding row, is ``None``: an empty bag).  Read from ``movies.dat`` /
+    ``movies.csv`` and ``users.dat`` next to the ratings file; a list is ``None`` when its file is absent (ML-25M has no
+    ``users.dat``)."""
+    import csv
+    import pathlib
+
+    root = pathlib.Path(ratings_path).parent
+    items = None
+    if (root / "movies.dat").is_file():
+        items = [None]
+        with open(root / "movies.dat", encoding="iso-8859-1") as f:
+            for line in f:
+                if line.strip():
+                    _, title, genres = line.rstrip("\r\n").split("::", 2)
+                    items.append(_json_text({"title": title, "genres": genres.split("|")}))
+    elif (root / "movies.csv").is_file():
+        items = [None]
+        with open(root / "movies.csv", encoding="utf-8", newline="") as f:
+            rows = csv.reader(f)
+            next(rows, None)
+            for row in rows:
+                if row:
+                    items.append(_json_text({"title": row[1], "genres": row[2].split("|")}))
+    users = None
+    if (root / "users.dat").is_file():
+        users = [None]
+        with open(root / "users.dat", encoding="iso-8859-1") as f:
+            for line in f:
+                if line.strip():
+                    _, gender, age, occupation, zipcode = line.rstrip("\r\n").split("::")[:5]
+                    users.append(_json_text({"gender": gender, "age": int(age), "occupation": int(occupation), "zipcode": zipcode}))
+    return items, users
+
+
+def synthetic_item_features(num_items: int, num_genres: int = 20, vocab: int = 5000, seed: int = 0):
+    """``(texts, genre)``: MovieLens-shaped item JSON texts for probes and tests (row 0 = ``None``, the padding row).
+    Item i has 1-3 genres from a skewed (Zipf-like) distribution -- ``genre[i]`` is its first -- and a title of 1-12 words
+    from a ``vocab``-word vocabulary plus a year, as ``"w12 w7 (1994)"``."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    p = 1.0 / np.arange(1, num_genres + 1) ** 1.1
+    p /= p.sum()
+    genre = np.zeros(num_items, dtype=np.int64)
+    texts = [None]
+    for i in range(1, num_items):
+        k = int(rng.integers(1, 4))
+        gs = list(dict.fromkeys(rng.choice(num_genres, size=k, p=p).tolist()))
+        genre[i] = gs[0]
+        words = " ".join(f"w{int(w)}" for w in rng.integers(0, vocab, int(rng.integers(1, 13))))
+        texts.append(_json_text({"title": f"{words} ({int(rng.integers(1920, 2020))})", "genres": [f"g{g}" for g in gs]}))
+    return texts, torch.from_numpy(genre)

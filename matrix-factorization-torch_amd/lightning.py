@@ -26,6 +26,8 @@ from . import fused, models, optim
 from .params import INDEX_PATH, PROCESSORS_JSON, TOP_K, TOWERS_PATH
 from .retrieval import RetrievalMetrics, ItemProcessor
 
+FEATURE_BAGS_PATH = "feature_bags.safetensors"     # the feature towers' registered bags (save / load)
+
 try:  # pragma: no cover - Lightning is absent from the build image
     from lightning import LightningModule as _Base
 except ImportError:  # noqa: SIM105
@@ -106,6 +108,71 @@ class MatrixFactorizationLitModule(_Base):
         exclude = [*(exclude_item_ids or []), *map(int, item_ids)]
         return self.item_processor.search(embed, exclude_item_ids=exclude, top_k=top_k)
 
+    # ------------------------------------------------------------ feature towers ---
+    def feature_hasher(self):
+        """The tokenizer of the feature towers (its settings are part of the config, so they are saved with it)."""
+        from .data import FeatureHasher
+
+        cfg = self.config
+        return FeatureHasher(cfg.feature_buckets, seed=cfg.feature_seed, text_fields=cfg.feature_text_fields)
+
+    def _feature_tower(self, name: str, what: str) -> models.FeatureBagTower:
+        if self.towers is None:
+            msg = "`model` must be initialised first"
+            raise ValueError(msg)
+        tower = self.towers[name]
+        if not isinstance(tower, models.FeatureBagTower):
+            msg = f"{what} needs {name}_tower='features' (a {type(tower).__name__} does not read attributes)"
+            raise ValueError(msg)
+        return tower
+
+    def _bags(self, x):
+        from .data import FeatureBags
+
+        return x if isinstance(x, FeatureBags) else self.feature_hasher().bags(x)
+
+    def set_features(self, *, item=None, user=None) -> None:
+        """Register every entity's attributes on the feature towers: ``data.FeatureBags``, or the reference's JSON texts
+        indexed by row (``data.read_movielens_features``; row 0 = ``None``, the padding row)."""
+        for name, x in (("item", item), ("user", user)):
+            if x is not None:
+                self._feature_tower(name, "set_features").set_bags(self._bags(x))
+
+    @torch.no_grad()
+    def add_items(self, item_ids, item_texts) -> None:
+        """Cold start: embed items that were not in the catalogue from their attributes (the reference's item JSON text)
+        and append their rows and ids to the item index -- and to the item tower's bags, so a rebuilt index keeps them."""
+        from .data import FeatureBags
+
+        tower = self._feature_tower("item", "add_items")
+        if self.item_processor is None or self.item_processor.index is None:
+            msg = "`user_processor` and `item_processor` must be initialised first"
+            raise ValueError(msg)
+        bags = self._bags(item_texts)
+        if len(bags) != len(item_ids):
+            msg = f"one text per item id: {len(item_ids)} != {len(bags)}"
+            raise ValueError(msg)
+        self.item_processor.append(item_ids, tower.embed(bags))
+        if tower.bags is not None:
+            old = tower.bags
+            w = None
+            if old.weights is not None or bags.weights is not None:
+                w = torch.cat([old.weights.cpu() if old.weights is not None else torch.ones(old.tokens.numel()),
+                               bags.weights.cpu() if bags.weights is not None else torch.ones(bags.tokens.numel())])
+            off = torch.cat([old.off.cpu(), bags.off.cpu()[1:] + int(old.off[-1])])
+            tower.set_bags(FeatureBags(off, torch.cat([old.tokens.cpu(), bags.tokens.cpu()]), w))
+
+    @torch.inference_mode()
+    def recommend_with_text(self, user_text, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
+        """Serve a user from their attributes alone (the reference's user JSON text, or a dict): the counterpart of
+        ``recommend(text, ...)`` (xfmr_rec/lightning.py:76-95)."""
+        tower = self._feature_tower("user", "recommend_with_text")
+        if self.item_processor is None or self.item_processor.index is None:
+            msg = "`user_processor` and `item_processor` must be initialised first"
+            raise ValueError(msg)
+        embed = tower.embed(self._bags([user_text])).cpu().numpy()
+        return self.item_processor.search(embed, exclude_item_ids=exclude_item_ids, top_k=top_k)
+
     @torch.inference_mode()
     def recommend_with_item_id(self, item_id: int, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
         """Items closest to item ``item_id`` -- the query is the item's own embedding and the item itself is
@@ -137,8 +204,20 @@ class MatrixFactorizationLitModule(_Base):
         path = pathlib.Path(path)
         path.mkdir(parents=True, exist_ok=True)
         # (a history user tower has no table of its own: it shares the item table, which is written once)
-        save_file({f"{k}.weight": t.weight.detach().cpu().contiguous() for k, t in self.towers.items()
-                   if not isinstance(t, models.HistoryPoolingTower)}, str(path / TOWERS_PATH))
+        # feature towers: their bucket table as "features.weight" (shared by both towers, written once), their bags apart
+        tables, bags = {}, {}
+        for k, t in self.towers.items():
+            if isinstance(t, models.FeatureBagTower):
+                tables["features.weight"] = t.weight.detach().cpu().contiguous()   # (init_towers: at most one feature table)
+                if t.bags is not None:
+                    bags[f"{k}.off"], bags[f"{k}.tokens"] = t.bags.off.cpu().contiguous(), t.bags.tokens.cpu().contiguous()
+                    if t.bags.weights is not None:
+                        bags[f"{k}.weights"] = t.bags.weights.cpu().contiguous()
+            elif not isinstance(t, models.HistoryPoolingTower):
+                tables[f"{k}.weight"] = t.weight.detach().cpu().contiguous()
+        save_file(tables, str(path / TOWERS_PATH))
+        if bags:
+            save_file(bags, str(path / FEATURE_BAGS_PATH))
         proc = {"config": self.config.model_dump(), "history": {str(k): list(map(int, v)) for k, v in self.history.items()}}
         (path / PROCESSORS_JSON).write_text(json.dumps(proc, indent=2))
         if self.item_processor is not None and self.item_processor.index is not None:
@@ -161,8 +240,17 @@ class MatrixFactorizationLitModule(_Base):
         weights = load_file(str(path / TOWERS_PATH))
         with torch.no_grad():
             for k, t in module.towers.items():
-                if not isinstance(t, models.HistoryPoolingTower):
+                if isinstance(t, models.FeatureBagTower):
+                    t.weight.copy_(weights["features.weight"].to(device))
+                elif not isinstance(t, models.HistoryPoolingTower):
                     t.weight.copy_(weights[f"{k}.weight"].to(device))
+        if (path / FEATURE_BAGS_PATH).exists():
+            from .data import FeatureBags
+
+            bags = load_file(str(path / FEATURE_BAGS_PATH))
+            for k, t in module.towers.items():
+                if f"{k}.off" in bags:
+                    t.set_bags(FeatureBags(bags[f"{k}.off"], bags[f"{k}.tokens"], bags.get(f"{k}.weights")))
         module.history = {int(k): v for k, v in proc.get("history", {}).items()}
         if (path / INDEX_PATH).exists():
             idx = load_file(str(path / INDEX_PATH))

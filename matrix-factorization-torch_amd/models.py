@@ -34,9 +34,16 @@ class ModelConfig(pydantic.BaseModel):
     num_hashes: int = 0            # > 0: hash / bloom towers (config 5): num_users / num_items are BUCKET counts
     hash_seed: int = 0
     # "history": the user vector is the pooled item rows of the user's history (HistoryPoolingTower), not a table row
-    user_tower: Literal["table", "history"] = "table"
+    user_tower: Literal["table", "history", "features"] = "table"
     pooling_mode: str = "mean"     # models.py:24 ("cls" / "pooler" need the transformer this repository does not have)
     max_history: int | None = None
+    # "features": the vector is the pooled hashed-attribute tokens of the entity (FeatureBagTower); when both towers are
+    # feature towers they share ONE bucket table, as the reference's towers share one encoder (lightning.py:60-74)
+    item_tower: Literal["table", "features"] = "table"
+    feature_buckets: int = 65535   # bucket rows of the feature table (keys 0..65535 sort in two 8-bit radix passes)
+    feature_combiner: Literal["sum", "mean", "sqrtn"] = "mean"    # mean: the reference mean-pools (models.py:24)
+    feature_seed: int = 0
+    feature_text_fields: tuple[str, ...] = ("title",)             # fields split into words (data.FeatureHasher)
 
     @pydantic.field_validator("pooling_mode")
     @classmethod
@@ -51,8 +58,29 @@ class ModelConfig(pydantic.BaseModel):
             raise ValueError(msg)
         return v
 
+    @pydantic.field_validator("feature_buckets")
+    @classmethod
+    def _check_feature_buckets(cls, v: int) -> int:
+        if not 2 <= v <= FEATURE_MAX_BUCKETS:
+            msg = f"feature_buckets must be in [2, 2^20] (the backward's radix sort covers 2^20 rows): {v = }"
+            raise ValueError(msg)
+        return v
+
+    @pydantic.model_validator(mode="after")
+    def _check_feature_towers(self):
+        if "features" in (self.user_tower, self.item_tower):
+            if self.num_hashes > 0:
+                msg = "feature towers hash attributes, not ids: num_hashes > 0 is not supported with a 'features' tower"
+                raise ValueError(msg)
+            if self.user_tower == "history":
+                msg = "user_tower='history' pools item-table rows and needs item_tower='table' (a feature item tower has no row per item)"
+                raise ValueError(msg)
+        return self
+
 
 POOLING_MODES = ("mean", "max")
+FEATURE_COMBINERS = ("sum", "mean", "sqrtn")
+FEATURE_MAX_BUCKETS = 1 << 20
 
 
 def check_pooling_mode(mode: str) -> str:
@@ -196,7 +224,18 @@ class HashEmbeddingTower(torch.nn.Module):
         return f"{self.weight.shape[0]} buckets, {self.weight.shape[1]}, num_hashes={self.num_hashes}, normalize={self.normalize}"
 
 
-class PooledHistoryGrad:
+class PooledGrad:
+    """A pooled tower's deferred contribution to a table's gradient (parked on the table by its backward, resolved by the
+    optimiser, ``optim._pending``): ``coalesce`` merges it, in one pass, with the rows other sources parked on the same
+    table in the same step.  ``normalize``: whether the table's rows were normalised when read."""
+
+    normalize: bool
+
+    def coalesce(self, table: torch.Tensor, ids: torch.Tensor | None, grad: torch.Tensor | None):
+        raise NotImplementedError
+
+
+class PooledHistoryGrad(PooledGrad):
     """The history tower's contribution to its item table's gradient, parked on the table by the backward and resolved by
     the optimiser (``optim._pending``): there it is coalesced, in one pass, with the rows other towers parked on the same
     table in the same step, so that the table receives ONE list of at most min(rows, entries) unique ids."""
@@ -337,9 +376,168 @@ class HistoryPoolingTower(torch.nn.Module):
         return f"pooling_mode={self.pooling_mode}, max_history={self.max_history}, normalize={self.normalize}"
 
 
+class FeatureBagGrad(PooledGrad):
+    """A feature tower's contribution to its bucket table's gradient: entry e of bag b carries w_e * c_b * g_p[b]
+    (``mf_bag_backward``), coalesced with the rows other sources parked on the table -- with both feature towers on one
+    table, the second tower's coalesce takes the first one's list as its extra rows."""
+
+    normalize = False
+
+    def __init__(self, ctx, grad_p: torch.Tensor) -> None:
+        self.idx, self.seg, self.max_len, self.scale, self.grad_p = ctx.idx, ctx.seg, ctx.max_len, ctx.scale, grad_p
+
+    def coalesce(self, table: torch.Tensor, ids: torch.Tensor | None, grad: torch.Tensor | None):
+        lib = _lib.lib()
+        rows, d = table.shape
+        b = self.scale.numel()
+        start, end, tokens, weights = self.seg
+        n_extra = 0 if ids is None else ids.numel()
+        cap = min(rows, n_extra + b * self.max_len)
+        out_ids = torch.empty(cap, dtype=torch.int64, device=table.device)
+        out_grad = torch.empty(cap, d, dtype=torch.float32, device=table.device)
+        if cap == 0:
+            return out_ids, out_grad
+        ws = _lib.workspace(lib.mf_bag_backward_ws_bytes(n_extra, b, self.max_len, d), table.device)
+        _lib.check(lib.mf_bag_backward(rows, d, _lib.ptr(self.idx), b, start.data_ptr(), end.data_ptr(), start.numel(),
+                                       tokens.data_ptr(), tokens.numel(), _lib.ptr(weights), self.max_len, self.scale.data_ptr(),
+                                       self.grad_p.data_ptr(), _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(),
+                                       out_grad.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        return out_ids, out_grad
+
+
+class _BagRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table: torch.Tensor, idx: torch.Tensor | None, b: int, seg: tuple, max_len: int, combiner: int,
+                normalize: bool):
+        if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
+            raise _lib.MfHipError("feature table must be a contiguous fp32 tensor on the GPU")
+        lib = _lib.lib()
+        rows, d = table.shape
+        dev = table.device
+        start, end, tokens, weights = seg
+        u = torch.empty(b, d, dtype=torch.float32, device=dev)
+        inv = torch.empty(b, dtype=torch.float32, device=dev)
+        scale = torch.empty(b, dtype=torch.float32, device=dev)
+        ws = _lib.workspace(lib.mf_bag_ws_bytes(b, max_len, d), dev)
+        _lib.check(lib.mf_bag_forward(table.data_ptr(), rows, d, _lib.ptr(idx), b, start.data_ptr(), end.data_ptr(), start.numel(),
+                                      tokens.data_ptr(), tokens.numel(), _lib.ptr(weights), max_len, combiner, int(normalize),
+                                      u.data_ptr(), inv.data_ptr(), scale.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        ctx.table, ctx.idx, ctx.seg, ctx.max_len, ctx.scale, ctx.normalize = table, idx, seg, max_len, scale, bool(normalize)
+        ctx.save_for_backward(u, inv)
+        return u
+
+    @staticmethod
+    def backward(ctx, grad_u):
+        table = ctx.table
+        u, inv = ctx.saved_tensors
+        b, d = u.shape
+        g = grad_u.to(torch.float32).contiguous()
+        if ctx.normalize:
+            gp = torch.empty_like(g)
+            _lib.check(_lib.lib().mf_normalize_backward(u.data_ptr(), inv.data_ptr(), g.data_ptr(), b, d, gp.data_ptr(),
+                                                        _lib.stream_ptr()))
+            g = gp
+        pending = getattr(table, "_mf_pending", None)
+        if pending is None:
+            pending = []
+            table._mf_pending = pending
+        pending.append(FeatureBagGrad(ctx, g))
+        return (None,) * 7
+
+
+class FeatureBagTower(torch.nn.Module):
+    """``tower(idx) -> [*, d]``: the pooled hashed-attribute tokens of entity ``idx`` -- an EmbeddingBag over one bucket
+    table, the id-only counterpart of the reference's text encoder over an entity's JSON attributes
+    (xfmr_rec/lightning.py:60-74, prepare.py:69-127).  ``set_bags`` registers every entity's bag (``data.FeatureBags``, from
+    ``data.FeatureHasher``) on the device; ``forward(idx)`` then reads entity ``idx[b]``'s bag (ids outside the registered
+    range give an empty bag, u = 0), so the loss path and the samplers are unchanged; ``embed(bags)`` embeds entities that
+    were never registered (cold start).  p = sum / mean / sqrtn of w_e F[t_e]; u = p / max(|p|, 1e-12) when ``normalize``.
+    ``num_embeddings`` is the number of registered entities; ``weight`` is the bucket table.  ``share_with``: use that
+    tower's table (not registered here: it is optimised and saved once).  HIP kernels ``mf_bag_forward`` /
+    ``mf_bag_backward``: no host read per call, so a step through this tower can be captured."""
+
+    def __init__(self, num_buckets: int, embedding_dim: int, *, combiner: str = "mean", normalize: bool = True,
+                 init_std: float | None = None, device=None, share_with: "FeatureBagTower | None" = None) -> None:
+        super().__init__()
+        if combiner not in FEATURE_COMBINERS:
+            msg = f"combiner must be one of {FEATURE_COMBINERS}: {combiner = }"
+            raise ValueError(msg)
+        if share_with is not None:
+            object.__setattr__(self, "weight", share_with.weight)       # shared, not registered
+        else:
+            if embedding_dim not in _lib.SUPPORTED_WIDTHS:
+                msg = f"embedding_dim must be one of {_lib.SUPPORTED_WIDTHS}: {embedding_dim = }"
+                raise ValueError(msg)
+            if not 2 <= num_buckets <= FEATURE_MAX_BUCKETS:  # noqa: PLR2004
+                msg = f"num_buckets must be in [2, 2^20]: {num_buckets = }"
+                raise ValueError(msg)
+            std = init_std if init_std is not None else 1.0 / math.sqrt(embedding_dim)
+            self.weight = torch.nn.Parameter(torch.randn(num_buckets, embedding_dim, device=device) * std)
+        self.combiner, self.normalize = combiner, normalize
+        self.bags = None
+
+    @staticmethod
+    def _segments(bags, device):
+        bags = bags.to(device)
+        tokens = bags.tokens if bags.tokens.numel() else torch.zeros(1, dtype=torch.int64, device=device)
+        return bags, (bags.off[:-1].contiguous(), bags.off[1:].contiguous(), tokens, bags.weights)
+
+    def set_bags(self, bags) -> None:
+        """Register every entity's bag (``data.FeatureBags``; entity e = row e, row 0 is usually the empty padding bag)."""
+        self.bags, self._seg = self._segments(bags, self.weight.device)
+
+    @property
+    def num_embeddings(self) -> int:
+        if self.bags is None:
+            msg = "no bags registered: call set_bags first"
+            raise ValueError(msg)
+        return len(self.bags)
+
+    @property
+    def embedding_dim(self) -> int:
+        return self.weight.shape[1]
+
+    def _apply_bags(self, idx, b: int, seg, max_len: int) -> torch.Tensor:
+        if b == 0:
+            return torch.zeros(0, self.weight.shape[1], device=self.weight.device)
+        return _BagRows.apply(self.weight, idx, b, seg, max_len, FEATURE_COMBINERS.index(self.combiner), self.normalize)
+
+    def forward(self, idx: torch.Tensor) -> torch.Tensor:
+        if self.bags is None:
+            msg = "FeatureBagTower.forward(idx) reads registered bags: call set_bags first (or embed(bags))"
+            raise ValueError(msg)
+        ids = _lib.dev_i64(idx, "idx").reshape(-1)
+        out = self._apply_bags(ids, ids.numel(), self._seg, self.bags.max_len)
+        return out.reshape(*idx.shape, self.weight.shape[1])
+
+    def embed(self, bags) -> torch.Tensor:
+        """``[len(bags), d]`` vectors of entities given by their bags (not registered)."""
+        bags, seg = self._segments(bags, self.weight.device)
+        return self._apply_bags(None, len(bags), seg, bags.max_len)
+
+    def extra_repr(self) -> str:
+        return f"{self.weight.shape[0]} buckets, {self.weight.shape[1]}, combiner={self.combiner}, normalize={self.normalize}"
+
+
 def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
     """Counterpart of ``init_bert`` + ``to_sentence_transformer`` (models.py:27-63).  ``user_tower="history"``: the user
-    tower is a :class:`HistoryPoolingTower` over the item table (plain tables only)."""
+    tower is a :class:`HistoryPoolingTower` over the item table (plain tables only).  ``"features"``: a
+    :class:`FeatureBagTower`; with both towers so, one shared bucket table."""
+    if "features" in (config.user_tower, config.item_tower):
+        def table(name):
+            return EmbeddingTower(getattr(config, f"num_{name}s"), config.hidden_size, normalize=config.normalize,
+                                  init_std=config.init_std, device=device)
+
+        kw = {"combiner": config.feature_combiner, "normalize": config.normalize}
+        item = (FeatureBagTower(config.feature_buckets, config.hidden_size, init_std=config.init_std, device=device, **kw)
+                if config.item_tower == "features" else table("item"))
+        if config.user_tower != "features":
+            user = table("user")
+        elif isinstance(item, FeatureBagTower):
+            user = FeatureBagTower(config.feature_buckets, config.hidden_size, share_with=item, **kw)
+        else:
+            user = FeatureBagTower(config.feature_buckets, config.hidden_size, init_std=config.init_std, device=device, **kw)
+        return torch.nn.ModuleDict({"user": user, "item": item})
     if config.user_tower == "history":
         if config.num_hashes > 0:
             msg = "user_tower='history' pools plain item-table rows; hashed towers (num_hashes > 0) are not supported"

@@ -18,11 +18,12 @@ from . import _lib, models
 
 
 def _pending_pooled(p: torch.Tensor, items: list):
-    """A step in which a :class:`models.HistoryPoolingTower` parked its deferred gradient on ``p``: ONE coalesce over all
+    """A step in which a pooled tower (:class:`models.HistoryPoolingTower`, :class:`models.FeatureBagTower`) parked its
+    deferred gradient on ``p`` (a :class:`models.PooledGrad`): ONE coalesce over all
     sources -- the rows the other towers parked (``(ids, grad, normalized)``), then each pooled entry -- gives the table
     one list of at most min(rows, entries) unique ids (padded with -1), whatever order autograd ran the backwards in."""
-    rows = [x for x in items if not isinstance(x, models.PooledHistoryGrad)]
-    pooled = [x for x in items if isinstance(x, models.PooledHistoryGrad)]
+    rows = [x for x in items if not isinstance(x, models.PooledGrad)]
+    pooled = [x for x in items if isinstance(x, models.PooledGrad)]
     norms = {n for _, _, n in rows} | {x.normalize for x in pooled}
     if len(norms) != 1:
         raise _lib.MfHipError("a table was gathered both with and without normalisation in one step")
@@ -42,7 +43,7 @@ def _pending(p: torch.Tensor):
     items = getattr(p, "_mf_pending", None)
     if not items:
         return None
-    if any(isinstance(x, models.PooledHistoryGrad) for x in items):
+    if any(isinstance(x, models.PooledGrad) for x in items):
         return _pending_pooled(p, items)
     if len(items) == 1:
         ids, g, norm = items[0]

@@ -200,6 +200,22 @@ class ItemProcessor:
         self._row_of_id = {int(i): r for r, i in enumerate(self.item_ids.tolist())}
         return self.index
 
+    def append(self, item_ids, embeddings: torch.Tensor) -> ItemIndex:
+        """Add items to a built index: their rows follow the existing ones (the index is rebuilt, the id map extended)."""
+        if self.index is None or self.item_ids is None:
+            msg = "`index` must be intialised first"
+            raise ValueError(msg)
+        ids = torch.as_tensor(item_ids, dtype=torch.int64).cpu().reshape(-1)
+        if ids.numel() != embeddings.shape[0]:
+            msg = f"one embedding per item id: {ids.numel()} != {embeddings.shape[0]}"
+            raise ValueError(msg)
+        if set(ids.tolist()) & set(self._row_of_id or {}) or len(set(ids.tolist())) != ids.numel():
+            msg = "item ids must be new and distinct"
+            raise ValueError(msg)
+        old = self.index.embeddings[:, : self.index.dim]
+        self.item_ids = torch.cat([self.item_ids, ids])
+        return self.set_index(torch.cat([old, embeddings.to(old.device, torch.float32)]))
+
     def row_of(self, item_id: int) -> int:
         if self._row_of_id is None or int(item_id) not in self._row_of_id:
             msg = f"unknown item id: {item_id = }"

@@ -13,7 +13,7 @@
 // u_b = normalize ? p_b / max(|p_b|, 1e-12) : p_b.
 //
 // Nothing is read back on the host: max_len (fixed when the bags are registered) sizes every buffer and grid, the kernels
-// exit early past the real work, and the backward's entry count is left on the device by its plan kernel.
+// exit early past the real work, and the backward's entry count stays on the device.
 //
 // Forward.  max_len <= BAG_SHORT: one lane group (d/4 lanes, 16-byte loads in the gather_rows layout) per bag sums the bag
 // in entry order -- no plan, no partials.  Longer bags: one wave per BAG_CHUNK entries of a bag (bag b's chunk j is work
@@ -21,15 +21,13 @@
 // in order.  Either way the summation order depends on the bag lengths only.
 //
 // Backward.  Entry e of bag b carries w_e * c_b * g_p[b]; entries with w_e = 0 or c_b = 0 carry nothing and are dropped like
-// padding.  Keys (extras first, then the bags' entries), the stable LSD radix sort, the run heads and the fixed fan-out tree
-// of run sums are those of mf_pool.hip (mf_sort.h), over the device-side entry count; the weight is applied at the leaf.
-// The result is exactly `capacity` = min(R, n_extra + B * max_len) slots: unique ids ascending, then -1.  The only atomics
-// are the integer LDS histogram counts.
-#include "mf_sort.h"
+// padding.  A plan kernel numbers the bags' entries; the engine of mf_coalesce.h coalesces them after the extras, applying
+// the weight at the leaf.  The result is exactly `capacity` = min(R, n_extra + B * max_len) slots: unique ids ascending,
+// then -1.  The only atomics are the integer LDS histogram counts.
+#include "mf_coalesce.h"
 
 static constexpr int BAG_SHORT = 64;             // longest bag of the one-group-per-bag path
 static constexpr int BAG_CHUNK = 64;             // entries per wave on the chunked path
-static constexpr int BAG_MAX_ROWS = 1 << 20;     // feature-table rows the radix sort covers
 static constexpr int BAG_PLAN_THREADS = 1024;
 
 struct BagSrc {                                  // the bags of one call
@@ -206,11 +204,6 @@ __global__ __launch_bounds__(256) void bag_combine_kernel(BagSrc src, int64_t B,
     bag_finish<D>(acc, wsum, w2sum, combiner, normalize, valid, b, c, out_u, out_inv, out_scale);
 }
 
-static int bag_grid(int64_t work_waves) {         // grid-stride kernels: enough waves to fill the chip, no more than the work
-    const int64_t blocks = (work_waves + 3) / 4;
-    return (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-}
-
 static int64_t bag_chunks(int64_t max_len) { return max_len <= BAG_SHORT ? 0 : (max_len + BAG_CHUNK - 1) / BAG_CHUNK; }
 
 extern "C" size_t mf_bag_ws_bytes(int64_t B, int64_t max_len, int d) {
@@ -226,7 +219,7 @@ static int bag_check(const char* who, int64_t n_rows, int d, int64_t B, const in
     if (!start || !end || !tokens || B <= 0 || n_rows <= 0 || n_seg < 0 || n_tokens <= 0 || max_len < 0)
         return mf_set_error(MF_EINVAL, "%s: bad argument", who);
     if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "%s: embedding width %d not in {32,64,128,256}", who, d);
-    if (n_rows > BAG_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "%s: %lld feature-table rows > %d", who, (long long)n_rows, BAG_MAX_ROWS);
+    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "%s: %lld feature-table rows > %d", who, (long long)n_rows, COALESCE_MAX_ROWS);
     if (max_len > 0 && B >= ((1ll << 31) - 1) / max_len) return mf_set_error(MF_ENOTSUP, "%s: B * max_len >= 2^31", who);
     return MF_OK;
 }
@@ -252,7 +245,7 @@ extern "C" int mf_bag_forward(const float* table, int64_t n_rows, int d, const i
                 MfArena a(ws);
                 float* psum = a.take<float>((size_t)B * C * D);
                 float* pw = a.take<float>((size_t)B * C * 2);
-                bag_chunk_kernel<D><<<bag_grid(B * C), 256, 0, s>>>(table, src, B, C, psum, pw);
+                bag_chunk_kernel<D><<<stride_grid(B * C), 256, 0, s>>>(table, src, B, C, psum, pw);
                 bag_combine_kernel<D><<<gb, 256, 0, s>>>(src, B, C, psum, pw, combiner, normalize, out_u, out_inv, out_scale);
             }
         });
@@ -261,10 +254,9 @@ extern "C" int mf_bag_forward(const float* table, int64_t n_rows, int d, const i
 }
 
 // =========================================================================================== backward ====
-// One workgroup: lo / len of every bag, the exclusive prefix of the lengths (the entry numbering) and the entry count
-// n = n_extra + sum len, left on the device for every later kernel.
-__global__ __launch_bounds__(BAG_PLAN_THREADS) void bag_plan_kernel(BagSrc src, int64_t B, int64_t n_extra, int64_t* __restrict__ lo_out,
-                                                                   int64_t* __restrict__ ent_off, int32_t* __restrict__ n_dev) {
+// One workgroup: lo of every bag and the exclusive prefix of the lengths (the entry numbering); ent_off[B] = the entry count.
+__global__ __launch_bounds__(BAG_PLAN_THREADS) void bag_plan_kernel(BagSrc src, int64_t B, int64_t* __restrict__ lo_out,
+                                                                   int64_t* __restrict__ ent_off) {
     __shared__ int64_t wsum[BAG_PLAN_THREADS / 64];
     const int lane = mf_lane(), wave = threadIdx.x >> 6;
     int64_t run = 0;
@@ -287,255 +279,44 @@ __global__ __launch_bounds__(BAG_PLAN_THREADS) void bag_plan_kernel(BagSrc src, 
         run += all;
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        ent_off[B] = run;
-        *n_dev = (int32_t)(n_extra + run);
-    }
+    if (threadIdx.x == 0) ent_off[B] = run;
 }
 
-// keys: entry q < n_extra is explicit row q (valid ids [0, R)), entry n_extra + h is bag entry h; padding tokens, zero
-// weights and bags with c_b = 0 get key R and sort last
-__global__ __launch_bounds__(256) void bag_keys_kernel(const int64_t* __restrict__ extra_ids, int64_t n_extra, BagSrc src, int64_t B,
-                                                       const int64_t* __restrict__ lo, const int64_t* __restrict__ ent_off,
-                                                       const float* __restrict__ scale, const int32_t* __restrict__ n_dev,
-                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, int32_t* __restrict__ euser) {
-    const int64_t n = *n_dev;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n; q += stride) {
-        uint32_t key = (uint32_t)src.R;
-        if (q < n_extra) {
-            const long long id = extra_ids[q];
-            if (id >= 0 && id < src.R) key = (uint32_t)id;
-        } else {
-            const int64_t h = q - n_extra;
-            const int64_t b = pool_owner(ent_off, B, h);
-            const int64_t pos = lo[b] + (h - ent_off[b]);
-            const long long tok = src.tokens[pos];
-            if (bag_weight(src, pos, tok) != 0.f && scale[b] != 0.f) key = (uint32_t)tok;
-            euser[h] = (int32_t)b;
-        }
-        keys[q] = key;
-        vals[q] = (uint32_t)q;
-    }
-}
-
-// one 8-bit digit of the LSD radix sort over the first *n_dev keys (radix_hist_kernel with the count on the device):
-// per-tile counts (zero past the end) ...
-__global__ __launch_bounds__(256) void bag_radix_hist_kernel(const uint32_t* __restrict__ keys, const int32_t* __restrict__ n_dev, int shift,
-                                                             int ntiles, int32_t* __restrict__ hist) {
-    __shared__ int cnt[256];
-    const int64_t n = *n_dev;
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
-    if (t0 < n) {
-        for (int i = threadIdx.x; i < RADIX_TILE; i += 256) {
-            const int64_t q = t0 + i;
-            if (q < n) atomicAdd(&cnt[(keys[q] >> shift) & 255], 1);       // integer counts: order-free
-        }
-    }
-    __syncthreads();
-    hist[(int64_t)threadIdx.x * ntiles + blockIdx.x] = cnt[threadIdx.x];
-}
-
-// ... and the stable scatter (radix_scatter_kernel)
-__global__ __launch_bounds__(256) void bag_radix_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
-                                                                const int32_t* __restrict__ n_dev, int shift, int ntiles,
-                                                                const int32_t* __restrict__ hist, uint32_t* __restrict__ kout,
-                                                                uint32_t* __restrict__ vout) {
-    __shared__ int base[256];
-    __shared__ int wcnt[4][256];
-    const int64_t n = *n_dev;
-    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
-    if (t0 >= n) return;                                               // (block-uniform)
-    const int tid = threadIdx.x, lane = mf_lane(), wave = tid >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    base[tid] = hist[(int64_t)tid * ntiles + blockIdx.x];
-    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0;
-    __syncthreads();
-    for (int r = 0; r < RADIX_TILE / 256; ++r) {
-        const int64_t q = t0 + r * 256 + tid;
-        const bool valid = q < n;
-        const uint32_t k = valid ? kin[q] : 0u;
-        const unsigned dg = (k >> shift) & 255u;
-        const unsigned long long peers = radix_peers(valid, dg);
-        if (valid && (peers & below) == 0) wcnt[wave][dg] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            int pos = base[dg] + __popcll(peers & below);
-            for (int w = 0; w < wave; ++w) pos += wcnt[w][dg];
-            kout[pos] = k;
-            vout[pos] = vin[q];
-        }
-        __syncthreads();
-        base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
-        for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0;
-        __syncthreads();
-    }
-}
-
-// heads of the runs of valid keys (pool_heads_kernel): per-tile counts, then the head position of every output slot
-template <bool SLOTS>
-__global__ __launch_bounds__(256) void bag_heads_kernel(const uint32_t* __restrict__ sk, const int32_t* __restrict__ n_dev, uint32_t R,
-                                                        int32_t* __restrict__ tcount, int32_t* __restrict__ head_pos) {
-    __shared__ int wcnt[4];
-    const int64_t n = *n_dev;
-    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
-    if (t0 >= n) {                                                     // (block-uniform) past the end: an empty tile
-        if (!SLOTS && threadIdx.x == 0) tcount[blockIdx.x] = 0;
-        return;
-    }
-    const int tid = threadIdx.x, lane = mf_lane(), wave = tid >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int at = SLOTS ? tcount[blockIdx.x] : 0;
-    for (int r = 0; r < RADIX_TILE / 256; ++r) {
-        const int64_t q = t0 + r * 256 + tid;
-        const bool head = q < n && sk[q] < R && (q == 0 || sk[q - 1] != sk[q]);
-        const unsigned long long m = __ballot(head);
-        if (lane == 0) wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wave; ++w) before += wcnt[w];
-        if (SLOTS && head) head_pos[at + before + __popcll(m & below)] = (int32_t)q;
-        at += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
-    }
-    if (!SLOTS && tid == 0) tcount[blockIdx.x] = at;
-}
-
-__global__ __launch_bounds__(256) void bag_fill_kernel(const int32_t* __restrict__ n_unique, int64_t capacity, int64_t* __restrict__ out_ids) {
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s < capacity && s >= *n_unique) out_ids[s] = -1;
-}
-
-struct BagGradSrc {
-    const float* extra_grad;
-    int64_t n_extra;
-    const int32_t* euser;
+// bag entries: padding tokens, zero weights and bags with c_b = 0 carry nothing; entry h of bag b carries w_e * c_b * g_p[b]
+struct BagEntries {
+    BagSrc bags;
     const int64_t* lo;
     const int64_t* ent_off;
     const float* scale;
     const float* grad_p;
-    BagSrc bags;
+    __device__ __forceinline__ uint32_t key(int64_t b, int64_t pos) const {
+        const long long tok = bags.tokens[pos];
+        return bag_weight(bags, pos, tok) != 0.f && scale[b] != 0.f ? (uint32_t)tok : (uint32_t)bags.R;
+    }
+    template <int D>
+    __device__ __forceinline__ f32x4 grad(int64_t b, int64_t h, int c) const {
+        const float w = bags.weights ? bags.weights[lo[b] + (h - ent_off[b])] : 1.f;
+        return reinterpret_cast<const f32x4*>(grad_p + b * D)[c] * (w * scale[b]);
+    }
 };
-
-// gradient row (lane c's 4 floats) of entry v: an extra row, or w_e * c_b * g_p[b]
-template <int D>
-__device__ __forceinline__ f32x4 bag_entry_grad(const BagGradSrc& src, uint32_t v, int c) {
-    if ((int64_t)v < src.n_extra) return reinterpret_cast<const f32x4*>(src.extra_grad + (int64_t)v * D)[c];
-    const int64_t h = (int64_t)v - src.n_extra;
-    const int64_t b = src.euser[h];
-    const float w = src.bags.weights ? src.bags.weights[src.lo[b] + (h - src.ent_off[b])] : 1.f;
-    return reinterpret_cast<const f32x4*>(src.grad_p + b * D)[c] * (w * src.scale[b]);
-}
-
-// The runs' sums in sorted order: pool_segsum_kernel's fixed tree of fan-out RUN_CHUNK (one launch per level), over the
-// device-side entry count, with the weight applied at the leaf.  A hot token (in 40 % of the bags) is summed by many lane
-// groups at level 1, their partials by fewer at the levels above.
-template <int D>
-__global__ __launch_bounds__(256) void bag_segsum_kernel(const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv,
-                                                         const int32_t* __restrict__ n_dev, uint32_t R, const int32_t* __restrict__ head_pos,
-                                                         const int32_t* __restrict__ n_unique, int64_t capacity, BagGradSrc src,
-                                                         int64_t unit, float* __restrict__ partial, int64_t* __restrict__ out_ids,
-                                                         float* __restrict__ out_grad) {
-    constexpr int LPR = D / 4, RPW = 64 / LPR;
-    const int lane = mf_lane(), c = lane % LPR;
-    const int64_t n = *n_dev;
-    const int64_t i = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + lane / LPR;
-    const int64_t block = unit * RUN_CHUNK;
-    int64_t p, sl = -1;
-    bool head;
-    if (i < capacity) {
-        if (i >= *n_unique) return;                      // (no cross-lane operation below)
-        sl = i;
-        p = head_pos[i];
-        head = true;
-    } else {
-        p = (i - capacity) * block;
-        if (p >= n || sk[p] >= R || p == 0 || sk[p - 1] != sk[p]) return;   // past the end, padding, or a run's head
-        head = false;
-    }
-    const uint32_t key = sk[p];
-    const int64_t sub = unit / RUN_CHUNK;
-    const int64_t sub_end = sub ? (p / unit + 1) * unit : p + 1;
-    if (sub && head && (sub_end >= n || sk[sub_end] != key)) return;   // finished at a lower level
-    const int64_t block_end = min((p / block + 1) * block, n);
-    constexpr int NB = 4;
-    const int64_t step = sub ? unit : 1;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int64_t e = p;
-    if (sub) {
-        acc = reinterpret_cast<const f32x4*>(partial + p * D)[c];
-        e = sub_end;
-    }
-    for (;;) {
-        uint32_t k8[NB];
-#pragma unroll
-        for (int t = 0; t < NB; ++t) k8[t] = e + t * step < block_end ? sk[e + t * step] : 0xFFFFFFFFu;
-        int m = 0;
-#pragma unroll
-        for (int t = 0; t < NB; ++t) m += (m == t && k8[t] == key) ? 1 : 0;
-        f32x4 g[NB];
-        if (!sub) {
-            uint32_t v8[NB];
-#pragma unroll
-            for (int t = 0; t < NB; ++t) v8[t] = t < m ? sv[e + t] : 0u;
-#pragma unroll
-            for (int t = 0; t < NB; ++t)
-                if (t < m) g[t] = bag_entry_grad<D>(src, v8[t], c);
-        } else {
-#pragma unroll
-            for (int t = 0; t < NB; ++t)
-                if (t < m) g[t] = reinterpret_cast<const f32x4*>(partial + (e + t * step) * D)[c];
-        }
-#pragma unroll
-        for (int t = 0; t < NB; ++t)
-            if (t < m) acc += g[t];
-        e += m * step;
-        if (m < NB || e >= block_end) break;
-    }
-    e = min(e, block_end);
-    if (head && (e >= n || sk[e] != key)) {
-        reinterpret_cast<f32x4*>(out_grad + sl * D)[c] = acc;
-        if (c == 0) out_ids[sl] = key;
-    } else {
-        reinterpret_cast<f32x4*>(partial + p * D)[c] = acc;
-    }
-}
 
 struct BagBwdWs {
     int64_t *lo, *ent_off;
-    uint32_t *k0, *v0, *k1, *v1;
-    int32_t *n_dev, *euser, *hist, *tcount, *head_pos;
-    float* partial;
-    int ntiles;
+    CoalesceWs co;
     size_t total;
 };
-static BagBwdWs bag_bwd_ws(void* ws, int64_t n_cap, int64_t B, int64_t n_entries, int d) {
+static BagBwdWs bag_bwd_ws(void* ws, int64_t n_extra, int64_t B, int64_t max_len, int d) {
     MfArena a(ws);
     BagBwdWs w;
-    w.ntiles = (int)((n_cap + RADIX_TILE - 1) / RADIX_TILE);
     w.lo = a.take<int64_t>((size_t)B);
     w.ent_off = a.take<int64_t>((size_t)B + 1);
-    w.n_dev = a.take<int32_t>(1);
-    w.k0 = a.take<uint32_t>((size_t)n_cap);
-    w.v0 = a.take<uint32_t>((size_t)n_cap);
-    w.k1 = a.take<uint32_t>((size_t)n_cap);
-    w.v1 = a.take<uint32_t>((size_t)n_cap);
-    w.euser = a.take<int32_t>((size_t)n_entries);
-    w.hist = a.take<int32_t>((size_t)256 * w.ntiles + 1);
-    w.tcount = a.take<int32_t>((size_t)w.ntiles + 1);
-    w.head_pos = a.take<int32_t>((size_t)n_cap);
-    w.partial = a.take<float>((size_t)n_cap * d);
+    w.co = coalesce_ws(a, n_extra, B * max_len, d);
     w.total = a.used();
     return w;
 }
 
 extern "C" size_t mf_bag_backward_ws_bytes(int64_t n_extra, int64_t B, int64_t max_len, int d) {
-    B = B > 0 ? B : 1;
-    const int64_t n_entries = B * (max_len > 0 ? max_len : 0);
-    const int64_t n_cap = (n_extra > 0 ? n_extra : 0) + n_entries;
-    return bag_bwd_ws(nullptr, n_cap > 0 ? n_cap : 1, B, n_entries, d).total;
+    return bag_bwd_ws(nullptr, n_extra > 0 ? n_extra : 0, B > 0 ? B : 1, max_len > 0 ? max_len : 0, d).total;
 }
 
 extern "C" int mf_bag_backward(int64_t n_rows, int d, const int64_t* idx, int64_t B, const int64_t* seg_start, const int64_t* seg_end,
@@ -551,39 +332,15 @@ extern "C" int mf_bag_backward(int64_t n_rows, int d, const int64_t* idx, int64_
         return mf_set_error(MF_EINVAL, "mf_bag_backward: capacity must be min(n_rows, n_extra + B * max_len)");
     if (ws_bytes < mf_bag_backward_ws_bytes(n_extra, B, max_len, d)) return mf_set_error(MF_ENOSPC, "mf_bag_backward: workspace too small");
     if (n_cap == 0) return MF_OK;
-    BagBwdWs w = bag_bwd_ws(ws, n_cap, B, n_entries, d);
+    const BagBwdWs w = bag_bwd_ws(ws, n_extra, B, max_len, d);
     const BagSrc bags{idx, seg_start, seg_end, n_seg, tokens, n_tokens, weights, max_len, n_rows};
+    const CoalesceSrc src{n_rows, extra_ids, extra_grad, n_extra, w.lo, w.ent_off, B, n_entries};
+    const BagEntries ent{bags, w.lo, w.ent_off, scale, grad_p};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int bits = 1;
-    while ((1ll << bits) <= n_rows) ++bits;                  // keys 0 .. R
-    const int passes = (bits + 7) / 8;
-    const unsigned tiles = (unsigned)w.ntiles;
+    int rc;
     MF_TIMED("bag_backward", s, {
-        bag_plan_kernel<<<1, BAG_PLAN_THREADS, 0, s>>>(bags, B, n_extra, w.lo, w.ent_off, w.n_dev);
-        bag_keys_kernel<<<bag_grid((n_cap + 63) / 64), 256, 0, s>>>(extra_ids, n_extra, bags, B, w.lo, w.ent_off, scale, w.n_dev, w.k0,
-                                                                    w.v0, w.euser);
-        uint32_t *ki = w.k0, *vi = w.v0, *ko = w.k1, *vo = w.v1;
-        for (int ps = 0; ps < passes; ++ps) {
-            bag_radix_hist_kernel<<<tiles, 256, 0, s>>>(ki, w.n_dev, 8 * ps, w.ntiles, w.hist);
-            mf_scan_i32(w.hist, (int64_t)256 * w.ntiles, s);
-            bag_radix_scatter_kernel<<<tiles, 256, 0, s>>>(ki, vi, w.n_dev, 8 * ps, w.ntiles, w.hist, ko, vo);
-            uint32_t* t = ki; ki = ko; ko = t;
-            t = vi; vi = vo; vo = t;
-        }
-        bag_heads_kernel<false><<<tiles, 256, 0, s>>>(ki, w.n_dev, (uint32_t)n_rows, w.tcount, nullptr);
-        mf_scan_i32(w.tcount, w.ntiles, s);
-        bag_heads_kernel<true><<<tiles, 256, 0, s>>>(ki, w.n_dev, (uint32_t)n_rows, w.tcount, w.head_pos);
-        bag_fill_kernel<<<dim3((unsigned)((capacity + 255) / 256)), 256, 0, s>>>(w.tcount + w.ntiles, capacity, out_ids);
-        const BagGradSrc src{extra_grad, n_extra, w.euser, w.lo, w.ent_off, scale, grad_p, bags};
-        MF_DISPATCH_D(d, {
-            constexpr int RPB = (64 / (D / 4)) * 4;
-            for (int64_t unit = 1;; unit *= RUN_CHUNK) {          // levels until one block covers every possible position
-                const int64_t items = capacity + (n_cap + unit * RUN_CHUNK - 1) / (unit * RUN_CHUNK);
-                bag_segsum_kernel<D><<<dim3((unsigned)((items + RPB - 1) / RPB)), 256, 0, s>>>(
-                    ki, vi, w.n_dev, (uint32_t)n_rows, w.head_pos, w.tcount + w.ntiles, capacity, src, unit, w.partial, out_ids, out_grad);
-                if (unit * RUN_CHUNK >= n_cap) break;
-            }
-        });
+        bag_plan_kernel<<<1, BAG_PLAN_THREADS, 0, s>>>(bags, B, w.lo, w.ent_off);
+        rc = coalesce(src, ent, w.co, d, capacity, out_ids, out_grad, nullptr, s);
     });
-    return mf_check_launch("mf_bag_backward");
+    return rc ? rc : mf_check_launch("mf_bag_backward");
 }

@@ -16,15 +16,12 @@
 //
 // Backward: every (entry, gradient row) of the batch -- the history entries, whose rows are w_b * g_p[b] (mean) or g_p[b]
 // routed by the max's winners, plus any explicit rows parked on the same table in the same step (the item tower's) -- is
-// sorted by item id with a stable LSD radix sort (8-bit digits, ballot multi-split inside a wave: linear, no atomics, no
-// host round trip), and the runs of equal ids are summed in sorted order (= entry order) by a fixed tree of RUN_CHUNK.  The
-// result is a list of exactly `capacity` = min(n_rows, entries) slots: the unique ids in ascending order with their summed
-// rows, then id -1 (skipped by every update kernel).  The run sums form a fixed tree of fan-out 32 (pool_segsum_kernel).
-#include "mf_sort.h"
+// coalesced into one list of exactly `capacity` = min(n_rows, entries) slots by the engine of mf_coalesce.h: the unique
+// ids in ascending order with their summed rows, then id -1 (skipped by every update kernel).
+#include "mf_coalesce.h"
 
 static constexpr int POOL_CHUNK = 64;            // entries per chunk (one wave)
 static constexpr int POOL_SUPER = 32;            // chunks per first-level combine
-static constexpr int POOL_MAX_ROWS = 1 << 20;    // item-table rows the radix sort covers (keys <= 2^20: three 8-bit digits)
 
 __device__ __forceinline__ bool pool_valid(long long id, long long n_rows) { return id >= 1 && id < n_rows; }
 
@@ -319,11 +316,6 @@ extern "C" size_t mf_pool_ws_bytes(int64_t B, int64_t n_entries, int d, int mode
     return pool_ws(nullptr, B > 0 ? B : 1, n_entries > 0 ? n_entries : 0, d, mode).total;
 }
 
-static int pool_grid(int64_t work_waves) {        // grid-stride kernels: enough waves to fill the chip, no more than the work
-    const int64_t blocks = (work_waves + 3) / 4;
-    return (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-}
-
 extern "C" int mf_pool_forward(const float* table, int64_t n_rows, int d, const int64_t* seg_start, const int64_t* seg_end,
                                const int64_t* items, int64_t n_items, int64_t B, int64_t n_entries, int max_history, int mode,
                                int norm_item, int norm_user, float* out_u, float* out_inv, int32_t* out_count, int64_t* out_lo,
@@ -331,7 +323,7 @@ extern "C" int mf_pool_forward(const float* table, int64_t n_rows, int d, const 
     if (!table || !seg_start || !seg_end || !items || !out_u || !out_inv || !out_count || !out_lo || !out_off || !ws || B <= 0 ||
         n_rows <= 0 || n_items <= 0 || n_entries < 0 || max_history < 0 || (mode != 0 && mode != 1) || (mode == 1 && !out_arg))
         return mf_set_error(MF_EINVAL, "mf_pool_forward: bad argument");
-    if (n_rows > POOL_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_pool_forward: %lld table rows > %d", (long long)n_rows, POOL_MAX_ROWS);
+    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_pool_forward: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
     if (n_entries >= (1ll << 31) || B >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_pool_forward: more than 2^31 entries or users");
     if (ws_bytes < mf_pool_ws_bytes(B, n_entries, d, mode)) return mf_set_error(MF_ENOSPC, "mf_pool_forward: workspace too small");
     PoolWs w = pool_ws(ws, B, n_entries, d, mode);
@@ -340,10 +332,10 @@ extern "C" int mf_pool_forward(const float* table, int64_t n_rows, int d, const 
         pool_cut_kernel<<<dim3((unsigned)((B + 3) / 4)), 256, 0, s>>>(seg_start, seg_end, items, n_items, B, n_rows, max_history, w.cut);
     pool_plan_kernel<<<dim3(1), PLAN_THREADS, 0, s>>>(seg_start, seg_end, max_history > 0 ? w.cut : nullptr, n_items, B, out_lo, out_off,
                                               w.chunk_off, w.super_off);
-    const int gc = pool_grid(w.cap_chunks);
+    const int gc = stride_grid(w.cap_chunks);
     MF_DISPATCH_D(d, {
         constexpr int RPB = (64 / (D / 4)) * 4;
-        const int gs = pool_grid((w.cap_supers + RPB / 4 - 1) / (RPB / 4));
+        const int gs = stride_grid((w.cap_supers + RPB / 4 - 1) / (RPB / 4));
         const unsigned gf = (unsigned)((B + RPB - 1) / RPB);
         MF_TIMED("pool_forward", s, {
             if (mode == 1) {
@@ -367,284 +359,34 @@ extern "C" int mf_pool_forward(const float* table, int64_t n_rows, int d, const 
 }
 
 // =========================================================================================== backward ====
-// keys: entry q < n_extra is explicit row q (valid ids [0, n_rows)), entry n_extra + h is history entry h (valid ids
-// [1, n_rows), h < ent_off[B]); invalid entries get key n_rows and sort last
-__global__ __launch_bounds__(256) void pool_keys_kernel(const int64_t* __restrict__ extra_ids, int64_t n_extra, const int64_t* __restrict__ items,
-                                                        const int64_t* __restrict__ lo, const int64_t* __restrict__ ent_off, int64_t B,
-                                                        int64_t n_entries, int64_t n_rows, uint32_t* __restrict__ keys,
-                                                        uint32_t* __restrict__ vals, int32_t* __restrict__ euser) {
-    const int64_t n = n_extra + n_entries;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    const int64_t total_h = min(ent_off[B], n_entries);
-    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n; q += stride) {
-        uint32_t key = (uint32_t)n_rows;
-        if (q < n_extra) {
-            const long long id = extra_ids[q];
-            if (id >= 0 && id < n_rows) key = (uint32_t)id;
-        } else {
-            const int64_t h = q - n_extra;
-            if (h < total_h) {
-                const int64_t b = pool_owner(ent_off, B, h);
-                const long long id = items[lo[b] + (h - ent_off[b])];
-                if (pool_valid(id, n_rows)) key = (uint32_t)id;
-                euser[h] = (int32_t)b;
-            }
-        }
-        keys[q] = key;
-        vals[q] = (uint32_t)q;
-    }
-}
-
-// one 8-bit digit of the LSD radix sort: per-tile counts ...
-__global__ __launch_bounds__(256) void radix_hist_kernel(const uint32_t* __restrict__ keys, int64_t n, int shift, int ntiles,
-                                                         int32_t* __restrict__ hist) {
-    __shared__ int cnt[256];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
-    for (int i = threadIdx.x; i < RADIX_TILE; i += 256) {
-        const int64_t q = t0 + i;
-        if (q < n) atomicAdd(&cnt[(keys[q] >> shift) & 255], 1);        // integer counts: order-free
-    }
-    __syncthreads();
-    hist[(int64_t)threadIdx.x * ntiles + blockIdx.x] = cnt[threadIdx.x];  // digit-major: the scan gives each (digit, tile) its base
-}
-
-// ... an exclusive scan (one workgroup; x[n] = total) ...
-__global__ __launch_bounds__(SCAN_THREADS) void scan_i32_kernel(int32_t* __restrict__ x, int64_t n) {
-    __shared__ int wsum[SCAN_THREADS / 64];
-    constexpr int PER = 16;
-    const int lane = mf_lane(), wave = threadIdx.x >> 6;
-    int run = 0;
-    for (int64_t base = 0; base < n; base += (int64_t)SCAN_THREADS * PER) {
-        const int64_t q0 = base + (int64_t)threadIdx.x * PER;
-        int v[PER];
-        int sum = 0;
-#pragma unroll
-        for (int t = 0; t < PER; ++t) {
-            v[t] = q0 + t < n ? x[q0 + t] : 0;
-            sum += v[t];
-        }
-        int inc = sum;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int y = __shfl_up(inc, s, 64);
-            if (lane >= s) inc += y;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < SCAN_THREADS / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
-        int at = run + before + inc - sum;
-#pragma unroll
-        for (int t = 0; t < PER; ++t) {
-            if (q0 + t < n) x[q0 + t] = at;
-            at += v[t];
-        }
-        run += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) x[n] = run;
-}
-
-void mf_scan_i32(int32_t* x, int64_t n, hipStream_t s) { scan_i32_kernel<<<1, SCAN_THREADS, 0, s>>>(x, n); }
-
-// ... and a stable scatter: 16 rounds of 256 positions; inside a wave the rank among equal digits comes from the ballots,
-// across waves from a 4 x 256 count table
-__global__ __launch_bounds__(256) void radix_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin, int64_t n,
-                                                            int shift, int ntiles, const int32_t* __restrict__ hist,
-                                                            uint32_t* __restrict__ kout, uint32_t* __restrict__ vout) {
-    __shared__ int base[256];
-    __shared__ int wcnt[4][256];
-    const int tid = threadIdx.x, lane = mf_lane(), wave = tid >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    base[tid] = hist[(int64_t)tid * ntiles + blockIdx.x];
-    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0;
-    __syncthreads();
-    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
-    for (int r = 0; r < RADIX_TILE / 256; ++r) {
-        const int64_t q = t0 + r * 256 + tid;
-        const bool valid = q < n;
-        const uint32_t k = valid ? kin[q] : 0u;
-        const unsigned dg = (k >> shift) & 255u;
-        const unsigned long long peers = radix_peers(valid, dg);
-        if (valid && (peers & below) == 0) wcnt[wave][dg] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            int pos = base[dg] + __popcll(peers & below);
-            for (int w = 0; w < wave; ++w) pos += wcnt[w][dg];
-            kout[pos] = k;
-            vout[pos] = vin[q];
-        }
-        __syncthreads();
-        base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
-        for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0;
-        __syncthreads();
-    }
-}
-
-// heads of the runs of valid keys: per-tile counts, then (after the scan) the head position of every output slot
-template <bool SLOTS>
-__global__ __launch_bounds__(256) void pool_heads_kernel(const uint32_t* __restrict__ sk, int64_t n, uint32_t n_rows,
-                                                         int32_t* __restrict__ tcount, int32_t* __restrict__ head_pos) {
-    __shared__ int wcnt[4];
-    const int tid = threadIdx.x, lane = mf_lane(), wave = tid >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int at = SLOTS ? tcount[blockIdx.x] : 0;
-    const int64_t t0 = (int64_t)blockIdx.x * RADIX_TILE;
-    for (int r = 0; r < RADIX_TILE / 256; ++r) {
-        const int64_t q = t0 + r * 256 + tid;
-        const bool head = q < n && sk[q] < n_rows && (q == 0 || sk[q - 1] != sk[q]);
-        const unsigned long long m = __ballot(head);
-        if (lane == 0) wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wave; ++w) before += wcnt[w];
-        if (SLOTS && head) head_pos[at + before + __popcll(m & below)] = (int32_t)q;
-        at += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
-    }
-    if (!SLOTS && tid == 0) tcount[blockIdx.x] = at;
-}
-
-__global__ __launch_bounds__(256) void pool_fill_kernel(const int32_t* __restrict__ n_unique, int64_t capacity, int64_t* __restrict__ out_ids) {
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s < capacity && s >= *n_unique) out_ids[s] = -1;
-}
-
-struct PoolGradSrc {
-    const float* extra_grad;
-    int64_t n_extra;
-    const int32_t* euser;
+// history entries: valid ids [1, n_rows); entry h of user b carries g_p[b] / count[b] (mean) or, on the channels it won,
+// g_p[b] (max)
+struct PoolEntries {
+    const int64_t* items;
+    int64_t n_rows;
     const int64_t* ent_off;
     const int32_t* count;
     const int32_t* arg;
     const float* grad_p;
     int mode;
+    __device__ __forceinline__ uint32_t key(int64_t, int64_t pos) const {
+        const long long id = items[pos];
+        return pool_valid(id, n_rows) ? (uint32_t)id : (uint32_t)n_rows;
+    }
+    template <int D>
+    __device__ __forceinline__ f32x4 grad(int64_t b, int64_t h, int c) const {
+        const f32x4 g = reinterpret_cast<const f32x4*>(grad_p + b * D)[c];
+        if (mode == 0) return g * (1.f / (float)count[b]);
+        const int j = (int)(h - ent_off[b]);
+        const int4 a = reinterpret_cast<const int4*>(arg + b * D)[c];
+        return f32x4{a.x == j ? g[0] : 0.f, a.y == j ? g[1] : 0.f, a.z == j ? g[2] : 0.f, a.w == j ? g[3] : 0.f};
+    }
 };
-
-// gradient row (lane c's 4 floats) of entry v
-template <int D>
-__device__ __forceinline__ f32x4 pool_entry_grad(const PoolGradSrc& src, uint32_t v, int c) {
-    if ((int64_t)v < src.n_extra) return reinterpret_cast<const f32x4*>(src.extra_grad + (int64_t)v * D)[c];
-    const int64_t h = (int64_t)v - src.n_extra;
-    const int64_t b = src.euser[h];
-    const f32x4 g = reinterpret_cast<const f32x4*>(src.grad_p + b * D)[c];
-    if (src.mode == 0) return g * (1.f / (float)src.count[b]);
-    const int j = (int)(h - src.ent_off[b]);
-    const int4 a = reinterpret_cast<const int4*>(src.arg + b * D)[c];
-    return f32x4{a.x == j ? g[0] : 0.f, a.y == j ? g[1] : 0.f, a.z == j ? g[2] : 0.f, a.w == j ? g[3] : 0.f};
-}
-
-// The runs' sums in sorted order, as a fixed tree of fan-out RUN_CHUNK over sorted positions, one launch per level, so that
-// an item in a hundred thousand histories is summed by thousands of lane groups, not by one (update_rows_kernel's two
-// levels would leave ~n / 32 partials to one group).  Level 1: the owner of every RUN_CHUNK-aligned unit of a run (its first
-// position: the run's head or the unit's start) sums the unit's gradient rows in order.  Level L >= 2 (unit = 32^(L-1)
-// positions, block = 32^L): the owner of the run's part of a block adds the level-(L-1) partials of its units, in order.
-// A run that ends inside an owner's unit is written to its slot at that level; otherwise the sum is parked at the owner's
-// position.  The tree depends on sorted positions only: deterministic.
-template <int D>
-__global__ __launch_bounds__(256) void pool_segsum_kernel(const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, int64_t n,
-                                                          uint32_t n_rows, const int32_t* __restrict__ head_pos,
-                                                          const int32_t* __restrict__ n_unique, int64_t capacity, PoolGradSrc src,
-                                                          int64_t unit, float* __restrict__ partial, int64_t* __restrict__ out_ids,
-                                                          float* __restrict__ out_grad) {
-    constexpr int LPR = D / 4, RPW = 64 / LPR;
-    const int lane = mf_lane(), c = lane % LPR;
-    // work items: the runs (by output slot), then the blocks of this level (a block start inside a run owns the run's part)
-    const int64_t i = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + lane / LPR;
-    const int64_t block = unit * RUN_CHUNK;
-    int64_t p, sl = -1;
-    bool head;
-    if (i < capacity) {
-        if (i >= *n_unique) return;                      // (no cross-lane operation below)
-        sl = i;
-        p = head_pos[i];
-        head = true;
-    } else {
-        p = (i - capacity) * block;
-        if (p >= n || sk[p] >= n_rows || p == 0 || sk[p - 1] != sk[p]) return;   // past the end, padding, or a run's head
-        head = false;
-    }
-    const uint32_t key = sk[p];
-    const int64_t sub = unit / RUN_CHUNK;                // the level below (0: entries)
-    const int64_t sub_end = sub ? (p / unit + 1) * unit : p + 1;
-    if (sub && head && (sub_end >= n || sk[sub_end] != key)) return;   // finished at a lower level
-    const int64_t block_end = min((p / block + 1) * block, n);
-    // four positions at a time: their keys, then their rows (or partials), each batch of loads in flight together
-    constexpr int NB = 4;
-    const int64_t step = sub ? unit : 1;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int64_t e = p;
-    if (sub) {
-        acc = reinterpret_cast<const f32x4*>(partial + p * D)[c];
-        e = sub_end;
-    }
-    for (;;) {
-        uint32_t k8[NB];
-#pragma unroll
-        for (int t = 0; t < NB; ++t) k8[t] = e + t * step < block_end ? sk[e + t * step] : 0xFFFFFFFFu;
-        int m = 0;
-#pragma unroll
-        for (int t = 0; t < NB; ++t) m += (m == t && k8[t] == key) ? 1 : 0;      // leading positions of the run
-        f32x4 g[NB];
-        if (!sub) {
-            uint32_t v8[NB];
-#pragma unroll
-            for (int t = 0; t < NB; ++t) v8[t] = t < m ? sv[e + t] : 0u;
-#pragma unroll
-            for (int t = 0; t < NB; ++t)
-                if (t < m) g[t] = pool_entry_grad<D>(src, v8[t], c);
-        } else {
-#pragma unroll
-            for (int t = 0; t < NB; ++t)
-                if (t < m) g[t] = reinterpret_cast<const f32x4*>(partial + (e + t * step) * D)[c];
-        }
-#pragma unroll
-        for (int t = 0; t < NB; ++t)
-            if (t < m) acc += g[t];
-        e += m * step;
-        if (m < NB || e >= block_end) break;
-    }
-    e = min(e, block_end);
-    if (head && (e >= n || sk[e] != key)) {              // the whole run
-        reinterpret_cast<f32x4*>(out_grad + sl * D)[c] = acc;
-        if (c == 0) out_ids[sl] = key;
-    } else {
-        reinterpret_cast<f32x4*>(partial + p * D)[c] = acc;
-    }
-}
-
-struct PoolBwdWs {
-    uint32_t *k0, *v0, *k1, *v1;
-    int32_t *euser, *hist, *tcount, *head_pos;
-    float* partial;
-    int ntiles;
-    size_t total;
-};
-static PoolBwdWs pool_bwd_ws(void* ws, int64_t n, int64_t n_entries, int d) {
-    MfArena a(ws);
-    PoolBwdWs w;
-    w.ntiles = (int)((n + RADIX_TILE - 1) / RADIX_TILE);
-    w.k0 = a.take<uint32_t>((size_t)n);
-    w.v0 = a.take<uint32_t>((size_t)n);
-    w.k1 = a.take<uint32_t>((size_t)n);
-    w.v1 = a.take<uint32_t>((size_t)n);
-    w.euser = a.take<int32_t>((size_t)n_entries);
-    w.hist = a.take<int32_t>((size_t)256 * w.ntiles + 1);
-    w.tcount = a.take<int32_t>((size_t)w.ntiles + 1);
-    w.head_pos = a.take<int32_t>((size_t)n);
-    w.partial = a.take<float>((size_t)n * d);
-    w.total = a.used();
-    return w;
-}
 
 extern "C" size_t mf_pool_backward_ws_bytes(int64_t n_extra, int64_t n_entries, int d) {
-    const int64_t n = (n_extra > 0 ? n_extra : 0) + (n_entries > 0 ? n_entries : 0);
-    return pool_bwd_ws(nullptr, n > 0 ? n : 1, n_entries > 0 ? n_entries : 0, d).total;
+    MfArena a(nullptr);
+    coalesce_ws(a, n_extra > 0 ? n_extra : 0, n_entries > 0 ? n_entries : 0, d);
+    return a.used();
 }
 
 extern "C" int mf_pool_backward(int64_t n_rows, int d, int mode, const int64_t* items, int64_t B, const int64_t* lo, const int64_t* ent_off,
@@ -654,46 +396,19 @@ extern "C" int mf_pool_backward(int64_t n_rows, int d, int mode, const int64_t* 
     if (!items || !lo || !ent_off || !count || !grad_p || !out_ids || !out_grad || !ws || B <= 0 || n_rows <= 0 || n_entries < 0 ||
         n_extra < 0 || (n_extra > 0 && (!extra_ids || !extra_grad)) || (mode != 0 && mode != 1) || (mode == 1 && !arg))
         return mf_set_error(MF_EINVAL, "mf_pool_backward: bad argument");
-    if (n_rows > POOL_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_pool_backward: %lld table rows > %d", (long long)n_rows, POOL_MAX_ROWS);
+    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_pool_backward: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
     const int64_t n = n_extra + n_entries;
     if (n >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_pool_backward: %lld entries >= 2^31", (long long)n);
     if (capacity != (n < n_rows ? n : n_rows)) return mf_set_error(MF_EINVAL, "mf_pool_backward: capacity must be min(n_rows, entries)");
     if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_pool_backward: embedding width %d not in {32,64,128,256}", d);
     if (ws_bytes < mf_pool_backward_ws_bytes(n_extra, n_entries, d)) return mf_set_error(MF_ENOSPC, "mf_pool_backward: workspace too small");
     if (n == 0) return MF_OK;
-    PoolBwdWs w = pool_bwd_ws(ws, n, n_entries, d);
+    MfArena a(ws);
+    const CoalesceWs w = coalesce_ws(a, n_extra, n_entries, d);
+    const CoalesceSrc src{n_rows, extra_ids, extra_grad, n_extra, lo, ent_off, B, n_entries};
+    const PoolEntries ent{items, n_rows, ent_off, count, arg, grad_p, mode};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int bits = 1;
-    while ((1ll << bits) <= n_rows) ++bits;                  // keys 0 .. n_rows
-    const int passes = (bits + 7) / 8;
-    const unsigned tiles = (unsigned)w.ntiles;
-    MF_TIMED("pool_backward", s, {
-        pool_keys_kernel<<<pool_grid((n + 63) / 64), 256, 0, s>>>(extra_ids, n_extra, items, lo, ent_off, B, n_entries, n_rows, w.k0, w.v0,
-                                                                  w.euser);
-        uint32_t *ki = w.k0, *vi = w.v0, *ko = w.k1, *vo = w.v1;
-        for (int ps = 0; ps < passes; ++ps) {
-            radix_hist_kernel<<<tiles, 256, 0, s>>>(ki, n, 8 * ps, w.ntiles, w.hist);
-            scan_i32_kernel<<<1, SCAN_THREADS, 0, s>>>(w.hist, (int64_t)256 * w.ntiles);
-            radix_scatter_kernel<<<tiles, 256, 0, s>>>(ki, vi, n, 8 * ps, w.ntiles, w.hist, ko, vo);
-            uint32_t* t = ki; ki = ko; ko = t;
-            t = vi; vi = vo; vo = t;
-        }
-        pool_heads_kernel<false><<<tiles, 256, 0, s>>>(ki, n, (uint32_t)n_rows, w.tcount, nullptr);
-        scan_i32_kernel<<<1, SCAN_THREADS, 0, s>>>(w.tcount, w.ntiles);
-        pool_heads_kernel<true><<<tiles, 256, 0, s>>>(ki, n, (uint32_t)n_rows, w.tcount, w.head_pos);
-        pool_fill_kernel<<<dim3((unsigned)((capacity + 255) / 256)), 256, 0, s>>>(w.tcount + w.ntiles, capacity, out_ids);
-        PoolGradSrc src{extra_grad, n_extra, w.euser, ent_off, count, arg, grad_p, mode};
-        MF_DISPATCH_D(d, {
-            constexpr int RPB = (64 / (D / 4)) * 4;
-            MF_TIMED("pool_segsum", s, {
-                for (int64_t unit = 1;; unit *= RUN_CHUNK) {          // levels until one block covers every position
-                    const int64_t items = capacity + (n + unit * RUN_CHUNK - 1) / (unit * RUN_CHUNK);
-                    pool_segsum_kernel<D><<<dim3((unsigned)((items + RPB - 1) / RPB)), 256, 0, s>>>(
-                        ki, vi, n, (uint32_t)n_rows, w.head_pos, w.tcount + w.ntiles, capacity, src, unit, w.partial, out_ids, out_grad);
-                    if (unit * RUN_CHUNK >= n) break;
-                }
-            });
-        });
-    });
-    return mf_check_launch("mf_pool_backward");
+    int rc;
+    MF_TIMED("pool_backward", s, rc = coalesce(src, ent, w, d, capacity, out_ids, out_grad, "pool_segsum", s));
+    return rc ? rc : mf_check_launch("mf_pool_backward");
 }

@@ -95,6 +95,15 @@ def check_pooling_mode(mode: str) -> str:
     return mode
 
 
+def _park(table: torch.Tensor, item) -> None:
+    """Park one gradient source on the table for the sparse optimisers of ``optim.py``, which read and clear the list."""
+    pending = getattr(table, "_mf_pending", None)
+    if pending is None:
+        pending = []
+        table._mf_pending = pending
+    pending.append(item)
+
+
 class _GatherRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table: torch.Tensor, idx: torch.Tensor, normalize: bool):
@@ -114,11 +123,7 @@ class _GatherRows(torch.autograd.Function):
     def backward(ctx, grad_out):
         table = ctx.table
         g = grad_out.reshape(-1, table.shape[1]).to(torch.float32).contiguous()
-        pending = getattr(table, "_mf_pending", None)
-        if pending is None:
-            pending = []
-            table._mf_pending = pending
-        pending.append((ctx.ids, g, ctx.normalize))
+        _park(table, (ctx.ids, g, ctx.normalize))
         return None, None, None
 
 
@@ -182,11 +187,7 @@ class _GatherHashed(torch.autograd.Function):
         buckets = torch.empty(n * num_hashes, dtype=torch.int64, device=table.device)
         _lib.check(lib.mf_hash_buckets(ids.data_ptr(), n, num_hashes, seed, table.shape[0], buckets.data_ptr(),
                                        _lib.stream_ptr()))
-        pending = getattr(table, "_mf_pending", None)
-        if pending is None:
-            pending = []
-            table._mf_pending = pending
-        pending.append((buckets, g.repeat_interleave(num_hashes, dim=0), False))
+        _park(table, (buckets, g.repeat_interleave(num_hashes, dim=0), False))
         return None, None, None, None, None
 
 
@@ -301,11 +302,7 @@ class _PoolRows(torch.autograd.Function):
             _lib.check(_lib.lib().mf_normalize_backward(u.data_ptr(), inv.data_ptr(), g.data_ptr(), b, d, gp.data_ptr(),
                                                         _lib.stream_ptr()))
             g = gp
-        pending = getattr(table, "_mf_pending", None)
-        if pending is None:
-            pending = []
-            table._mf_pending = pending
-        pending.append(PooledHistoryGrad(ctx, g))
+        _park(table, PooledHistoryGrad(ctx, g))
         return (None,) * 9
 
 
@@ -437,11 +434,7 @@ class _BagRows(torch.autograd.Function):
             _lib.check(_lib.lib().mf_normalize_backward(u.data_ptr(), inv.data_ptr(), g.data_ptr(), b, d, gp.data_ptr(),
                                                         _lib.stream_ptr()))
             g = gp
-        pending = getattr(table, "_mf_pending", None)
-        if pending is None:
-            pending = []
-            table._mf_pending = pending
-        pending.append(FeatureBagGrad(ctx, g))
+        _park(table, FeatureBagGrad(ctx, g))
         return (None,) * 7
 
 

@@ -247,13 +247,13 @@ def test_feature_towers_share_one_table(mf):
     assert isinstance(mixed["item"], mf.models.FeatureBagTower)
 
 
-def test_bag_kernels_do_not_spill(mf):
+def test_bag_and_coalesce_kernels_do_not_spill(mf):
     spec = importlib.util.spec_from_file_location("kernel_resources", ROOT / "tools" / "kernel_resources.py")
     kr = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(kr)
     res = kr.kernel_resources()
-    mine = {k: v for k, v in res.items() if "bag_" in k}
-    assert len(mine) >= 23, sorted(mine)  # noqa: PLR2004
+    mine = {k: v for k, v in res.items() if "bag_" in k or "coalesce_" in k}
+    assert len(mine) >= 29, sorted(mine)  # noqa: PLR2004
     for k, v in mine.items():
         assert v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0, k
         assert v["private_segment_fixed_size"] == 0, k

@@ -409,6 +409,39 @@ int mf_bag_backward(int64_t n_rows, int d, const int64_t* idx, int64_t B, const 
                     const float* scale, const float* grad_p, const int64_t* extra_ids, const float* extra_grad, int64_t n_extra,
                     int64_t capacity, int64_t* out_ids, float* out_grad, void* ws, size_t ws_bytes, mf_stream_t stream);
 
+/* ------------------------------------------------------------ transformer user tower ---
+ * The sequence form of the reference's tower, PoolingTransformer.forward(inputs_embeds) (xfmr_rec/models.py:66-84): a BERT
+ * encoder over the item rows of a user's history, pooling_mode mean / max / cls (mode 0 / 1 / 2), then Normalize -- the
+ * eval-mode function (no dropout), fp32.  Lists as for mf_pool_forward; the last max_history (<= 64) valid entries are kept,
+ * oldest first (position 0), and PACKED: user b owns tokens tok_off[b] .. tok_off[b + 1], T = sum_b n_b <= t_cap, where t_cap
+ * (a host bound, min(entries, B * max_history)) sizes every buffer and grid.  x_t = the item row (normalised iff norm_item),
+ * e_t = LN((x_t + tok[0]) + pos[t]); per layer Q / K / V dense, `heads` heads, scores / sqrt(h / heads), softmax over the valid
+ * keys, context, dense + residual + LN, dense + act (0 gelu, 1 relu, 2 silu, 3 gelu_new), dense + residual + LN; LN eps 1e-12.
+ * params: 4 + 16 * layers device pointers: pos [max_pos, h], tok [2, h], LN gamma, beta, then per layer Wq bq Wk bk Wv bv Wo bo
+ * g1 b1 Wi [I, h] bi Wo2 [h, I] bo2 g2 b2 (torch Linear layout [out, in]).  Outputs: out_u [B, h], out_inv [B], out_arg [B, h]
+ * (mode 1: the winning position, -1 for an empty list); `stash` (mf_xfmr_ws_bytes) keeps the plan and the activations for
+ * the backward.  h in {32, 64, 128}, head width in {8, 16, 32, 64}, I a multiple of 32 <= 4 h, 1..4 layers: MF_ENOTSUP
+ * otherwise, and above 2^20 table rows.  Deterministic: no atomics. */
+size_t mf_xfmr_ws_bytes(int64_t B, int64_t t_cap, int h, int layers, int intermediate);
+int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                    const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
+                    int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params, float* out_u,
+                    float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, mf_stream_t stream);
+/* Backward of the dense part: grads = one buffer per parameter (the parameters' order and shapes), every element written;
+ * grad_x [t_cap, h] = dL/dx_t of the packed tokens.  Weight gradients are split-K sums over a fixed number of token slices
+ * added in slice order: bit-reproducible, no float atomics. */
+size_t mf_xfmr_backward_ws_bytes(int64_t t_cap, int h, int intermediate);
+int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads, int intermediate,
+                     int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
+                     const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
+                     void* ws, size_t ws_bytes, mf_stream_t stream);
+/* grad_x lands on the item table through the coalesce engine of the pooled towers (one entry per token, key = its item id),
+ * together with the extra rows parked on the table: outputs as mf_pool_backward; capacity = min(n_rows, n_extra + t_cap). */
+size_t mf_xfmr_coalesce_ws_bytes(int64_t n_extra, int64_t t_cap, int d);
+int mf_xfmr_coalesce(int64_t n_rows, int d, int64_t B, int64_t t_cap, int layers, int intermediate, const void* stash,
+                     const float* grad_x, const int64_t* extra_ids, const float* extra_grad, int64_t n_extra, int64_t capacity,
+                     int64_t* out_ids, float* out_grad, void* ws, size_t ws_bytes, mf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,15 @@ SIGNATURES = {
     "mf_bag_backward_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_int]),
     "mf_bag_backward": (c_int, [c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64,
                                 c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mf_xfmr_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int, c_int]),
+    "mf_xfmr_forward": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mf_xfmr_backward_ws_bytes": (c_sz, [c_i64, c_int, c_int]),
+    "mf_xfmr_backward": (c_int, [c_int, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mf_xfmr_coalesce_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
+    "mf_xfmr_coalesce": (c_int, [c_i64, c_int, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
+                                 c_sz, c_vp]),
 }
 
 MF_OK, MF_EINVAL, MF_ENOSPC, MF_ELAUNCH, MF_ENOTSUP = 0, -1, -2, -3, -4       # return codes (include/mf_hip.h)

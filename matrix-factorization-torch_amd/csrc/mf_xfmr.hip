@@ -1,0 +1,996 @@
+// mf_xfmr.hip -- the transformer user tower: u_b = normalize(pool(BertEncoder(rows of user b's last L history items))),
+// forward and backward, fp32 throughout, no float atomics, bit-reproducible.
+//
+// Reference interface replaced: PoolingTransformer.forward(inputs_embeds) (xfmr_rec/models.py:66-84): a BERT encoder over
+// a [B, L, h] stack of embedding rows whose all-zero rows are padding, pooling_mode mean / max / cls, then Normalize.
+// Here the rows are the item tower's rows of the user's history; validity comes from the id (ids outside [1, n_rows) are
+// padding) and work is proportional to the valid tokens T = sum_b n_b: tokens are PACKED, user b owns tokens
+// tok_off[b] .. tok_off[b + 1], oldest kept entry first (position 0).  Spec: tests/test_xfmr_tower_cpu.py (the eval-mode
+// function: no dropout).
+//
+//   plan      xfmr_cut (last L valid entries, n_b), xfmr_scan (tok_off, T on the device), xfmr_pack (token -> item id, user)
+//   embed     z0 = (x + tok[0]) + pos[t], x0 = LN(z0)                                   (gather + LayerNorm, one launch)
+//   layer     q, k, v = X W^T + b (three GEMMs); ctx = attention per (user, head), one wave each, softmax over the n_b valid
+//             keys only; z1 = ctx Wo^T + bo + X; y1 = LN(z1); a = y1 Wi^T + bi, f = act(a) (one GEMM, two outputs);
+//             z2 = f Wo2^T + bo2 + y1; y2 = LN(z2)
+//   pool      mean / max (first position wins ties) / cls over the n_b rows of the last layer, then u = p / max(|p|, 1e-12)
+//
+// GEMM engine: xfmr_gemm_kernel, v_mfma_f32_32x32x2_f32 (exact fp32 products, one k-ordered chain per element) on 64 x 64
+// tiles staged through LDS, in three forms: Y = X W^T (+ bias, + residual, activation), dX = dY W (+ residual, * act'),
+// and dW = dY^T X as split-K over the tokens with a FIXED number of slices (XFMR_SLICES; the slice length is a function of
+// T alone) whose partials a second launch adds in slice order -- so the weight gradients do not depend on scheduling.  The
+// bias gradient (column sums of dY) rides with the dW tiles of the first column block.
+//
+// Stash (what the forward keeps for the backward, per token): z0, x0, and per layer q, k, v, ctx, z1, y1, z2, y2 (h floats
+// each), a, f (I floats each) and the two LayerNorm row statistics; the attention probabilities are recomputed.
+//
+// The gradient into the item table, dL/dx_t = dz0[t], leaves through the coalesce engine of mf_coalesce.h (XfmrEntries).
+#include "mf_coalesce.h"
+
+static constexpr int XFMR_MAX_L = 64;
+static constexpr int XFMR_MAX_LAYERS = 4;
+static constexpr int XFMR_SLICES = 256;          // split-K slices of a weight gradient
+static constexpr int XFMR_LN_SLICES = 1024;      // token slices of the LayerNorm parameter gradients
+static constexpr int XFMR_POS_SLICES = 64;       // user slices of the position-embedding gradient
+static constexpr int XFMR_GLOBALS = 4;           // pos, tok, emb LN gamma, emb LN beta
+static constexpr int XFMR_PER_LAYER = 16;        // Wq bq Wk bk Wv bv Wo bo g1 b1 Wi bi Wo2 bo2 g2 b2
+static constexpr float XFMR_LN_EPS = 1e-12f;
+
+__device__ __forceinline__ bool xfmr_valid(long long id, long long n_rows) { return id >= 1 && id < n_rows; }
+
+// ================================================================================================ plan ====
+// One wave per user: walk back from hi, 64 entries at a time, until the L-th valid entry; n_b = min(valid entries, L).
+__global__ __launch_bounds__(256) void xfmr_cut_kernel(const int64_t* __restrict__ seg_start, const int64_t* __restrict__ seg_end,
+                                                       const int64_t* __restrict__ items, int64_t n_items, int64_t B, int64_t n_rows,
+                                                       int L, int64_t* __restrict__ cut_out, int32_t* __restrict__ nb_out) {
+    const int lane = mf_lane();
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int64_t lo = min(max(seg_start[b], (int64_t)0), n_items);
+    const int64_t hi = min(max(seg_end[b], lo), n_items);
+    int64_t cut = lo;
+    int need = L;
+    for (int64_t top = hi; top > lo; top -= 64) {
+        const int64_t pos = top - 1 - lane;                  // lane 0 = the most recent entry of this block
+        const bool ok = pos >= lo && xfmr_valid(items[pos >= lo ? pos : lo], n_rows);
+        unsigned long long m = __ballot(ok);
+        const int c = __popcll(m);
+        if (c >= need) {
+            for (int i = 1; i < need; ++i) m &= m - 1;       // the need-th valid entry from the end
+            cut = top - 1 - __builtin_ctzll(m);
+            need = 0;
+            break;
+        }
+        need -= c;
+    }
+    if (lane == 0) {
+        cut_out[b] = cut;
+        nb_out[b] = L - need;
+    }
+}
+
+// One workgroup: tok_off = exclusive prefix of n_b (clamped to the host bound t_cap), tok_off[B] = T, also left in *T_dev.
+__global__ __launch_bounds__(256) void xfmr_scan_kernel(const int32_t* __restrict__ nb, int64_t B, int64_t t_cap,
+                                                        int64_t* __restrict__ tok_off, int32_t* __restrict__ T_dev) {
+    __shared__ int64_t wsum[4];
+    const int lane = mf_lane(), wave = threadIdx.x >> 6;
+    int64_t run = 0;
+    for (int64_t b0 = 0; b0 < B; b0 += 256) {
+        const int64_t b = b0 + threadIdx.x;
+        const int64_t v = b < B ? nb[b] : 0;
+        const int64_t inc = wave_incl_scan(v);
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int64_t before = 0, all = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += wsum[w];
+            all += wsum[w];
+        }
+        if (b < B) tok_off[b] = min(run + before + inc - v, t_cap);
+        run += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        tok_off[B] = min(run, t_cap);
+        *T_dev = (int32_t)min(run, t_cap);
+    }
+}
+
+// One wave per user: the valid entries of [cut, hi) in list order -> tokens tok_off[b] ..
+__global__ __launch_bounds__(256) void xfmr_pack_kernel(const int64_t* __restrict__ seg_end, const int64_t* __restrict__ cut,
+                                                        const int64_t* __restrict__ items, int64_t n_items, int64_t B, int64_t n_rows,
+                                                        const int64_t* __restrict__ tok_off, int64_t* __restrict__ tok_item,
+                                                        int32_t* __restrict__ tok_user) {
+    const int lane = mf_lane();
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int64_t lo = cut[b];
+    const int64_t hi = min(max(seg_end[b], lo), n_items);
+    const int64_t t0 = tok_off[b], t1 = tok_off[b + 1];
+    int64_t done = 0;
+    for (int64_t base = lo; base < hi && t0 + done < t1; base += 64) {
+        const int64_t pos = base + lane;
+        const long long id = pos < hi ? items[pos] : 0;
+        const bool ok = xfmr_valid(id, n_rows);
+        const unsigned long long m = __ballot(ok);
+        const int64_t t = t0 + done + __popcll(m & ((1ull << lane) - 1ull));
+        if (ok && t < t1) {
+            tok_item[t] = id;
+            tok_user[t] = (int32_t)b;
+        }
+        done += __popcll(m);
+    }
+}
+
+// ================================================================================== rows of 32 lanes ====
+// H floats of a row on 32 lanes: lane c holds columns c * E .. c * E + E - 1, E = H / 32.
+template <int E>
+struct XRow {
+    float v[E];
+};
+template <int E>
+__device__ __forceinline__ XRow<E> xrow_load(const float* __restrict__ p, int c) {
+    XRow<E> r;
+    if constexpr (E == 4) {
+        const f32x4 x = reinterpret_cast<const f32x4*>(p)[c];
+        r.v[0] = x[0]; r.v[1] = x[1]; r.v[2] = x[2]; r.v[3] = x[3];
+    } else {
+#pragma unroll
+        for (int e = 0; e < E; ++e) r.v[e] = p[c * E + e];
+    }
+    return r;
+}
+template <int E>
+__device__ __forceinline__ void xrow_store(float* __restrict__ p, int c, const XRow<E>& r) {
+    if constexpr (E == 4) {
+        reinterpret_cast<f32x4*>(p)[c] = f32x4{r.v[0], r.v[1], r.v[2], r.v[3]};
+    } else {
+#pragma unroll
+        for (int e = 0; e < E; ++e) p[c * E + e] = r.v[e];
+    }
+}
+template <int E>
+__device__ __forceinline__ float xrow_dot(const XRow<E>& a, const XRow<E>& b) {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) s += a.v[e] * b.v[e];
+    return mf_butterfly_sum<32>(s);
+}
+// LayerNorm of one row (biased variance, two passes): returns y, leaves mean and 1 / sqrt(var + eps)
+template <int E>
+__device__ __forceinline__ XRow<E> xrow_layernorm(const XRow<E>& z, const XRow<E>& gamma, const XRow<E>& beta, float& mean, float& rstd) {
+    constexpr float invh = 1.f / (float)(32 * E);
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) s += z.v[e];
+    mean = mf_butterfly_sum<32>(s) * invh;
+    float q = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) q += (z.v[e] - mean) * (z.v[e] - mean);
+    rstd = 1.f / sqrtf(mf_butterfly_sum<32>(q) * invh + XFMR_LN_EPS);
+    XRow<E> y;
+#pragma unroll
+    for (int e = 0; e < E; ++e) y.v[e] = (z.v[e] - mean) * rstd * gamma.v[e] + beta.v[e];
+    return y;
+}
+
+// ============================================================================================== embed ====
+// token t of user b: x = the item row (normalised iff norm_item, gather_rows_kernel's arithmetic), z0 = (x + tok[0]) + pos[t],
+// x0 = LN(z0).  Eight tokens per workgroup.
+template <int H>
+__global__ __launch_bounds__(256) void xfmr_embed_kernel(const float* __restrict__ table, const int64_t* __restrict__ tok_item,
+                                                         const int32_t* __restrict__ tok_user, const int64_t* __restrict__ tok_off,
+                                                         const int32_t* __restrict__ T_dev, int norm_item, const float* __restrict__ pos,
+                                                         const float* __restrict__ tok, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* __restrict__ z0, float* __restrict__ st0,
+                                                         float* __restrict__ x0) {
+    constexpr int E = H / 32;
+    const int c = threadIdx.x & 31;
+    const int64_t t = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int64_t T = *T_dev;
+    const bool valid = t < T;
+    const int64_t tt = valid ? t : 0;
+    const bool any = T > 0;
+    const int64_t id = any ? tok_item[tt] : 0;
+    const int64_t b = any ? tok_user[tt] : 0;
+    const int p = any ? (int)(tt - tok_off[b]) : 0;
+    XRow<E> x = xrow_load<E>(table + id * H, c);
+    if (norm_item) {
+        const float inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(x, x)), 1e-12f);
+#pragma unroll
+        for (int e = 0; e < E; ++e) x.v[e] = x.v[e] * inv;
+    }
+    const XRow<E> pe = xrow_load<E>(pos + (int64_t)p * H, c), te = xrow_load<E>(tok, c);
+    XRow<E> z;
+#pragma unroll
+    for (int e = 0; e < E; ++e) z.v[e] = (x.v[e] + te.v[e]) + pe.v[e];
+    float mean, rstd;
+    const XRow<E> y = xrow_layernorm<E>(z, xrow_load<E>(gamma, c), xrow_load<E>(beta, c), mean, rstd);
+    if (valid) {
+        xrow_store<E>(z0 + t * H, c, z);
+        xrow_store<E>(x0 + t * H, c, y);
+        if (c == 0) {
+            st0[2 * t] = mean;
+            st0[2 * t + 1] = rstd;
+        }
+    }
+}
+
+// ========================================================================================== LayerNorm ====
+template <int H>
+__global__ __launch_bounds__(256) void xfmr_ln_kernel(const float* __restrict__ z, const int32_t* __restrict__ T_dev,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      float* __restrict__ y, float* __restrict__ st) {
+    constexpr int E = H / 32;
+    const int c = threadIdx.x & 31;
+    const int64_t t = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int64_t T = *T_dev;
+    if ((int64_t)blockIdx.x * 8 >= T) return;                 // (whole workgroup)
+    const bool valid = t < T;
+    const XRow<E> zr = xrow_load<E>(z + (valid ? t : 0) * H, c);
+    float mean, rstd;
+    const XRow<E> yr = xrow_layernorm<E>(zr, xrow_load<E>(gamma, c), xrow_load<E>(beta, c), mean, rstd);
+    if (valid) {
+        xrow_store<E>(y + t * H, c, yr);
+        if (c == 0) {
+            st[2 * t] = mean;
+            st[2 * t + 1] = rstd;
+        }
+    }
+}
+
+// length of one of S token slices: a function of T alone
+__device__ __forceinline__ int64_t xfmr_slice_len(int64_t T, int S, int round) {
+    const int64_t per = (T + S - 1) / S;
+    return (per + round - 1) / round * round;
+}
+
+// dz = rstd * (dy gamma - mean(dy gamma) - xhat mean(dy gamma xhat)); slice s of the tokens also leaves its partial of
+// dgamma = sum dy xhat and dbeta = sum dy in part[s][2H] (eight row groups, added in group order).
+template <int H>
+__global__ __launch_bounds__(256) void xfmr_ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ z,
+                                                          const float* __restrict__ st, const int32_t* __restrict__ T_dev,
+                                                          const float* __restrict__ gamma, float* __restrict__ dz,
+                                                          float* __restrict__ part) {
+    constexpr int E = H / 32;
+    constexpr float invh = 1.f / (float)H;
+    __shared__ float sh[8][2 * H];
+    const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int64_t T = *T_dev;
+    const int64_t len = xfmr_slice_len(T, XFMR_LN_SLICES, 8);
+    const int64_t beg = (int64_t)blockIdx.x * len, end = min(beg + len, T);
+    const XRow<E> gm = xrow_load<E>(gamma, c);
+    XRow<E> ag, ab;
+#pragma unroll
+    for (int e = 0; e < E; ++e) ag.v[e] = ab.v[e] = 0.f;
+    for (int64_t t0 = beg; t0 < end; t0 += 8) {              // (uniform trip count: the row sums need whole waves)
+        const int64_t t = t0 + g;
+        const bool valid = t < end;
+        const int64_t tt = valid ? t : beg;
+        const XRow<E> d = xrow_load<E>(dy + tt * H, c), zr = xrow_load<E>(z + tt * H, c);
+        const float mean = st[2 * tt], rstd = st[2 * tt + 1];
+        XRow<E> xh, gd;
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            xh.v[e] = (zr.v[e] - mean) * rstd;
+            gd.v[e] = d.v[e] * gm.v[e];
+            s1 += gd.v[e];
+            s2 += gd.v[e] * xh.v[e];
+        }
+        const float m1 = mf_butterfly_sum<32>(s1) * invh, m2 = mf_butterfly_sum<32>(s2) * invh;
+        if (valid) {
+            XRow<E> o;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                o.v[e] = rstd * (gd.v[e] - m1 - xh.v[e] * m2);
+                ag.v[e] += d.v[e] * xh.v[e];
+                ab.v[e] += d.v[e];
+            }
+            xrow_store<E>(dz + t * H, c, o);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        sh[g][c * E + e] = ag.v[e];
+        sh[g][H + c * E + e] = ab.v[e];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * H; i += 256) {
+        float s = sh[0][i];
+#pragma unroll
+        for (int q = 1; q < 8; ++q) s += sh[q][i];
+        part[(int64_t)blockIdx.x * 2 * H + i] = s;
+    }
+}
+
+// out[i] = sum_s part[s][i] in slice order; element i goes to out_a (i < n_a) or out_b
+__global__ __launch_bounds__(256) void xfmr_reduce_kernel(const float* __restrict__ part, int S, int64_t size, int64_t n_a,
+                                                          float* __restrict__ out_a, float* __restrict__ out_b) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= size) return;
+    float s = part[i];
+    for (int q = 1; q < S; ++q) s += part[(int64_t)q * size + i];
+    if (i < n_a) out_a[i] = s;
+    else out_b[i - n_a] = s;
+}
+
+// ========================================================================================= activations ====
+enum { XACT_GELU = 0, XACT_RELU = 1, XACT_SILU = 2, XACT_GELU_NEW = 3 };
+__device__ __forceinline__ float xfmr_act(float x, int kind) {
+    switch (kind) {
+        case XACT_RELU: return x > 0.f ? x : 0.f;
+        case XACT_SILU: return x / (1.f + expf(-x));
+        case XACT_GELU_NEW: {
+            const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
+            return 0.5f * x * (1.f + tanhf(u));
+        }
+        default: return 0.5f * x * (1.f + erff(x * 0.7071067811865476f));
+    }
+}
+__device__ __forceinline__ float xfmr_dact(float x, int kind) {
+    switch (kind) {
+        case XACT_RELU: return x > 0.f ? 1.f : 0.f;
+        case XACT_SILU: {
+            const float s = 1.f / (1.f + expf(-x));
+            return s * (1.f + x * (1.f - s));
+        }
+        case XACT_GELU_NEW: {
+            const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
+            const float th = tanhf(u);
+            const float du = 0.7978845608028654f * (1.f + 3.f * 0.044715f * x * x);
+            return 0.5f * (1.f + th) + 0.5f * x * (1.f - th * th) * du;
+        }
+        default: return 0.5f * (1.f + erff(x * 0.7071067811865476f)) + x * 0.3989422804014327f * expf(-0.5f * x * x);
+    }
+}
+
+// ================================================================================================ GEMM ====
+// C[m][n] = sum_k A(m, k) B(n, k).  An operand is k-contiguous (elem(r, k) = p[r * ld + k]; ld a multiple of 4, 16-byte
+// aligned) or row-contiguous (elem(r, k) = p[k * ld + r]).  dyn = 0: M = *T_dev tokens (tiles past T exit), K static (a
+// multiple of 16); dyn = 1: K = *T_dev, cut into XFMR_SLICES slices (blockIdx.z), slice s writes its partial tile to
+// C + s * slice_stride and, for the first column block, the column sums of A to C + s * slice_stride + M * N.
+enum { XEPI_NONE = 0, XEPI_ACT = 1, XEPI_DACT = 2 };
+struct XGemm {
+    const float* A; int64_t lda; int a_kc;
+    const float* B; int64_t ldb; int b_kc;
+    float* C; int64_t ldc;
+    int M, N, K;                 // static extents (the dynamic one is ignored)
+    const int32_t* T_dev; int dyn;
+    const float* bias;           // [N] or null
+    const float* R;              // [*, ldc] added to the result, or null (may alias C)
+    int epi, act;
+    float* C2;                   // XEPI_ACT: act(result)
+    const float* P;              // XEPI_DACT: pre-activations, result *= act'(P)
+    int64_t slice_stride;
+};
+static constexpr int XG_LD = 68;        // LDS row stride of a 16 x 64 operand tile
+
+// stage: the thread's share of a 64 (rows) x 16 (k) operand tile, global -> registers -> LDS[k][row]
+__device__ __forceinline__ f32x4 xg_fetch(const float* __restrict__ p, int64_t ld, int kc, int64_t r0, int64_t r_lim, int64_t k0,
+                                          int64_t k_lim) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (kc) {                                               // row = t / 4, k = (t % 4) * 4 .. + 3 (K is a multiple of 16: no k tail)
+        const int64_t r = r0 + (threadIdx.x >> 2), k = k0 + (threadIdx.x & 3) * 4;
+        if (r < r_lim && k < k_lim) v = *reinterpret_cast<const f32x4*>(p + r * ld + k);
+    } else {                                                // row = t % 64, k = t / 64 + 4 i
+        const int64_t r = r0 + (threadIdx.x & 63);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t k = k0 + (threadIdx.x >> 6) + 4 * i;
+            if (r < r_lim && k < k_lim) v[i] = p[k * ld + r];
+        }
+    }
+    return v;
+}
+__device__ __forceinline__ void xg_stage(float (*tile)[XG_LD], int kc, const f32x4& v) {
+    if (kc) {
+        const int r = threadIdx.x >> 2, k = (threadIdx.x & 3) * 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) tile[k + i][r] = v[i];
+    } else {
+        const int r = threadIdx.x & 63, k = threadIdx.x >> 6;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) tile[k + 4 * i][r] = v[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void xfmr_gemm_kernel(XGemm g) {
+    __shared__ float As[16][XG_LD], Bs[16][XG_LD];
+    const int64_t T = *g.T_dev;
+    const int64_t M = g.dyn == 0 ? T : g.M;
+    const int64_t m0 = (int64_t)blockIdx.x * 64, n0 = (int64_t)blockIdx.y * 64;
+    if (m0 >= M) return;
+    int64_t kbeg = 0, kend = g.K;
+    float* C = g.C;
+    if (g.dyn == 1) {
+        const int64_t len = xfmr_slice_len(T, XFMR_SLICES, 16);
+        kbeg = min((int64_t)blockIdx.z * len, T);
+        kend = min(kbeg + len, T);
+        C += (int64_t)blockIdx.z * g.slice_stride;
+    }
+    const int lane = mf_lane(), wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hh = lane >> 5;
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    float colsum = 0.f;
+    const bool want_colsum = g.dyn == 1 && blockIdx.y == 0 && threadIdx.x < 64;
+    f32x4 ra = xg_fetch(g.A, g.lda, g.a_kc, m0, M, kbeg, kend);
+    f32x4 rb = xg_fetch(g.B, g.ldb, g.b_kc, n0, g.N, kbeg, kend);
+    for (int64_t k0 = kbeg; k0 < kend; k0 += 16) {
+        __syncthreads();
+        xg_stage(As, g.a_kc, ra);
+        xg_stage(Bs, g.b_kc, rb);
+        __syncthreads();
+        if (k0 + 16 < kend) {                                // the next tile's loads fly under this tile's MFMAs
+            ra = xg_fetch(g.A, g.lda, g.a_kc, m0, M, k0 + 16, kend);
+            rb = xg_fetch(g.B, g.ldb, g.b_kc, n0, g.N, k0 + 16, kend);
+        }
+#pragma unroll
+        for (int kk = 0; kk < 16; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + hh][wm * 32 + l31], Bs[kk + hh][wn * 32 + l31], acc, 0, 0, 0);
+        if (want_colsum) {
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) colsum += As[kk][threadIdx.x];
+        }
+    }
+    const int64_t n = n0 + wn * 32 + l31;
+    if (n < g.N) {
+        const float bias = g.bias ? g.bias[n] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int64_t m = m0 + wm * 32 + mf_acc_row(e, hh);
+            if (m < M) {
+                const int64_t o = m * g.ldc + n;
+                float v = acc[e] + bias;
+                if (g.R) v += g.R[o];
+                if (g.epi == XEPI_ACT) g.C2[o] = xfmr_act(v, g.act);
+                else if (g.epi == XEPI_DACT) v *= xfmr_dact(g.P[o], g.act);
+                C[o] = v;
+            }
+        }
+    }
+    if (want_colsum && m0 + threadIdx.x < M) C[(int64_t)g.M * g.N + m0 + threadIdx.x] = colsum;
+}
+
+// =========================================================================================== attention ====
+// One wave per (user, head): keys across lanes.  K and V of the head sit in LDS; per query the scores, the softmax over
+// the n valid keys and the context stay in registers / LDS: nothing [L, L] goes to memory.
+template <int DH>
+__device__ __forceinline__ void xattn_load(float (*dst)[DH + 1], const float* __restrict__ src, int64_t t0, int n, int h, int col0) {
+    for (int i = mf_lane(); i < n * DH; i += 64) {
+        const int j = i / DH, c = i % DH;
+        dst[j][c] = src[(t0 + j) * h + col0 + c];
+    }
+}
+__device__ __forceinline__ float xattn_bcast(float x, int src_lane) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), src_lane));
+}
+__device__ __forceinline__ float xattn_wave_max(float x) {
+    x = fmaxf(x, mf_xor_lane<32>(x)); x = fmaxf(x, mf_xor_lane<16>(x)); x = fmaxf(x, mf_xor_lane<8>(x));
+    x = fmaxf(x, mf_xor_lane<4>(x)); x = fmaxf(x, mf_xor_lane<2>(x)); x = fmaxf(x, mf_xor_lane<1>(x));
+    return x;
+}
+// softmax probability of this lane's key (LDS row `row`) for the query row qv (lane c holds q[c]); inactive lanes give 0
+template <int DH>
+__device__ __forceinline__ float xattn_prob(float qv, const float (*Ks)[DH + 1], int row, bool active) {
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < DH; ++c) s += xattn_bcast(qv, c) * Ks[row][c];
+    s = active ? s / sqrtf((float)DH) : -__builtin_huge_valf();
+    const float mx = xattn_wave_max(s);
+    const float e = active ? expf(s - mx) : 0.f;
+    return e / mf_wave_sum(e);
+}
+// out[c] = sum_j w[j] M[j][c] for c < DH: 64 / DH lane groups take every (64 / DH)-th key, then a fixed butterfly
+template <int DH>
+__device__ __forceinline__ float xattn_mix(const float* w, const float (*Ms)[DH + 1], int lane, int n) {
+    constexpr int G = 64 / DH;
+    const int c = lane % DH, jg = lane / DH;
+    float acc = 0.f;
+    for (int j = jg; j < n; j += G) acc += w[j] * Ms[j][c];
+    if constexpr (DH <= 32) acc += mf_xor_lane<32>(acc);
+    if constexpr (DH <= 16) acc += mf_xor_lane<16>(acc);
+    if constexpr (DH <= 8) acc += mf_xor_lane<8>(acc);
+    return acc;
+}
+
+template <int DH>
+__global__ __launch_bounds__(64) void xfmr_attn_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                       const int64_t* __restrict__ tok_off, int h, int heads, float* __restrict__ ctx) {
+    __shared__ float Ks[XFMR_MAX_L][DH + 1], Vs[XFMR_MAX_L][DH + 1], Ps[XFMR_MAX_L];
+    const int64_t b = blockIdx.x / heads;
+    const int col0 = (int)(blockIdx.x % heads) * DH;
+    const int64_t t0 = tok_off[b];
+    const int n = (int)min(tok_off[b + 1] - t0, (int64_t)XFMR_MAX_L);
+    if (n <= 0) return;
+    const int lane = mf_lane();
+    xattn_load<DH>(Ks, k, t0, n, h, col0);
+    xattn_load<DH>(Vs, v, t0, n, h, col0);
+    __syncthreads();
+    for (int i = 0; i < n; ++i) {
+        const float qv = lane < DH ? q[(t0 + i) * h + col0 + lane] : 0.f;
+        const float p = xattn_prob<DH>(qv, Ks, lane < n ? lane : 0, lane < n);
+        __syncthreads();
+        Ps[lane] = p;
+        __syncthreads();
+        const float o = xattn_mix<DH>(Ps, Vs, lane, n);
+        if (lane < DH) ctx[(t0 + i) * h + col0 + lane] = o;
+    }
+}
+
+// backward: the probabilities are recomputed; lane j accumulates dK[j], dV[j] over the queries, dQ[i] is a mix over keys
+template <int DH>
+__global__ __launch_bounds__(64) void xfmr_attn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                           const float* __restrict__ v, const float* __restrict__ dctx,
+                                                           const int64_t* __restrict__ tok_off, int h, int heads, float* __restrict__ dq,
+                                                           float* __restrict__ dk, float* __restrict__ dv) {
+    __shared__ float Ks[XFMR_MAX_L][DH + 1], Vs[XFMR_MAX_L][DH + 1], Ps[XFMR_MAX_L], Qs[64], Ds[64];
+    const int64_t b = blockIdx.x / heads;
+    const int col0 = (int)(blockIdx.x % heads) * DH;
+    const int64_t t0 = tok_off[b];
+    const int n = (int)min(tok_off[b + 1] - t0, (int64_t)XFMR_MAX_L);
+    if (n <= 0) return;
+    const int lane = mf_lane(), row = lane < n ? lane : 0;
+    xattn_load<DH>(Ks, k, t0, n, h, col0);
+    xattn_load<DH>(Vs, v, t0, n, h, col0);
+    __syncthreads();
+    float dK[DH], dV[DH];
+#pragma unroll
+    for (int c = 0; c < DH; ++c) dK[c] = dV[c] = 0.f;
+    const float inv_scale = 1.f / sqrtf((float)DH);
+    for (int i = 0; i < n; ++i) {
+        const float qv = lane < DH ? q[(t0 + i) * h + col0 + lane] : 0.f;
+        const float dc = lane < DH ? dctx[(t0 + i) * h + col0 + lane] : 0.f;
+        const float p = xattn_prob<DH>(qv, Ks, row, lane < n);
+        float dp = 0.f;
+#pragma unroll
+        for (int c = 0; c < DH; ++c) dp += xattn_bcast(dc, c) * Vs[row][c];
+        const float pd = lane < n ? p * dp : 0.f;
+        const float pdsum = mf_wave_sum(pd);                 // (whole wave: not inside the select below)
+        const float ds = lane < n ? (p * (dp - pdsum)) * inv_scale : 0.f;
+        __syncthreads();
+        Ps[lane] = ds;
+        Qs[lane] = qv;                                       // (from LDS below: 2 DH more lane reads would not fit the SGPRs)
+        Ds[lane] = dc;
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < DH; ++c) {
+            dK[c] += ds * Qs[c];
+            dV[c] += p * Ds[c];
+        }
+        const float o = xattn_mix<DH>(Ps, Ks, lane, n);
+        if (lane < DH) dq[(t0 + i) * h + col0 + lane] = o;
+    }
+    __syncthreads();
+    if (lane < n) {
+#pragma unroll
+        for (int c = 0; c < DH; ++c) {
+            Ks[lane][c] = dK[c];
+            Vs[lane][c] = dV[c];
+        }
+    }
+    __syncthreads();
+    for (int i = lane; i < n * DH; i += 64) {
+        const int j = i / DH, c = i % DH;
+        dk[(t0 + j) * h + col0 + c] = Ks[j][c];
+        dv[(t0 + j) * h + col0 + c] = Vs[j][c];
+    }
+}
+
+// ================================================================================================ pool ====
+enum { XPOOL_MEAN = 0, XPOOL_MAX = 1, XPOOL_CLS = 2 };
+// 32 lanes per user: p = mean / max (first position wins ties) / position 0 of the n_b rows, u = p / max(|p|, 1e-12)
+template <int H>
+__global__ __launch_bounds__(256) void xfmr_pool_kernel(const float* __restrict__ y, const int64_t* __restrict__ tok_off, int64_t B, int mode,
+                                                        int norm_user, float* __restrict__ out_u, float* __restrict__ out_inv,
+                                                        int32_t* __restrict__ out_arg) {
+    constexpr int E = H / 32;
+    const int c = threadIdx.x & 31;
+    const int64_t b = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+    const bool valid = b < B;
+    const int64_t t0 = valid ? tok_off[b] : 0;
+    const int n = valid ? (int)(tok_off[b + 1] - t0) : 0;
+    XRow<E> p;
+    int arg[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        p.v[e] = 0.f;
+        arg[e] = -1;
+    }
+    if (n > 0) {
+        p = xrow_load<E>(y + t0 * H, c);
+#pragma unroll
+        for (int e = 0; e < E; ++e) arg[e] = 0;
+        if (mode != XPOOL_CLS) {
+            for (int j = 1; j < n; ++j) {
+                const XRow<E> r = xrow_load<E>(y + (t0 + j) * H, c);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    if (mode == XPOOL_MEAN) p.v[e] += r.v[e];
+                    else if (r.v[e] > p.v[e]) { p.v[e] = r.v[e]; arg[e] = j; }
+                }
+            }
+            if (mode == XPOOL_MEAN) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) p.v[e] = p.v[e] / (float)n;
+            }
+        }
+    }
+    float inv = 1.f;
+    if (norm_user) {
+        inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(p, p)), 1e-12f);
+#pragma unroll
+        for (int e = 0; e < E; ++e) p.v[e] = p.v[e] * inv;
+    }
+    if (valid) {
+        xrow_store<E>(out_u + b * H, c, p);
+        if (c == 0) out_inv[b] = inv;
+        if (mode == XPOOL_MAX) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) out_arg[b * H + c * E + e] = arg[e];
+        }
+    }
+}
+
+// 32 lanes per token: dL/dy of the last layer's row from dL/du (through the normalisation and the pool)
+template <int H>
+__global__ __launch_bounds__(256) void xfmr_pool_bwd_kernel(const float* __restrict__ grad_u, const float* __restrict__ u,
+                                                            const float* __restrict__ inv, const int32_t* __restrict__ arg,
+                                                            const int64_t* __restrict__ tok_off, const int32_t* __restrict__ tok_user,
+                                                            const int32_t* __restrict__ T_dev, int mode, int norm_user,
+                                                            float* __restrict__ dy) {
+    constexpr int E = H / 32;
+    const int c = threadIdx.x & 31;
+    const int64_t t = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int64_t T = *T_dev;
+    if ((int64_t)blockIdx.x * 8 >= T) return;
+    const bool valid = t < T;
+    const int64_t b = tok_user[valid ? t : 0];
+    const int64_t t0 = tok_off[b];
+    const int j = (int)((valid ? t : 0) - t0), n = (int)(tok_off[b + 1] - t0);
+    XRow<E> g = xrow_load<E>(grad_u + b * H, c);
+    if (norm_user) {
+        const XRow<E> ur = xrow_load<E>(u + b * H, c);
+        const float pr = xrow_dot<E>(g, ur), iv = inv[b];
+#pragma unroll
+        for (int e = 0; e < E; ++e) g.v[e] = (g.v[e] - ur.v[e] * pr) * iv;
+    }
+    XRow<E> o;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (mode == XPOOL_MEAN) o.v[e] = g.v[e] / (float)n;
+        else if (mode == XPOOL_CLS) o.v[e] = j == 0 ? g.v[e] : 0.f;
+        else o.v[e] = arg[b * H + c * E + e] == j ? g.v[e] : 0.f;
+    }
+    if (valid) xrow_store<E>(dy + t * H, c, o);
+}
+
+// position-embedding gradient: slice s of the users, position t: part[s][t][c] = sum_b dz0[tok_off[b] + t][c] (b in order)
+__global__ __launch_bounds__(128) void xfmr_pos_bwd_kernel(const float* __restrict__ dz0, const int64_t* __restrict__ tok_off, int64_t B,
+                                                           int H, int L, float* __restrict__ part) {
+    const int t = blockIdx.x, s = blockIdx.y, c = threadIdx.x;
+    if (c >= H) return;
+    const int64_t per = (B + XFMR_POS_SLICES - 1) / XFMR_POS_SLICES;
+    const int64_t b1 = min((int64_t)(s + 1) * per, B);
+    float acc = 0.f;
+    for (int64_t b = (int64_t)s * per; b < b1; ++b) {
+        const int64_t t0 = tok_off[b];
+        if (t0 + t < tok_off[b + 1]) acc += dz0[(t0 + t) * H + c];
+    }
+    part[((int64_t)s * L + t) * H + c] = acc;
+}
+// token-type row 0 receives every token's gradient = the column sums of dpos (rows >= L are zero); row 1 none
+__global__ __launch_bounds__(128) void xfmr_tok_bwd_kernel(const float* __restrict__ dpos, int H, int L, float* __restrict__ dtok) {
+    const int c = threadIdx.x;
+    if (c >= H) return;
+    float acc = 0.f;
+    for (int t = 0; t < L; ++t) acc += dpos[(int64_t)t * H + c];
+    dtok[c] = acc;
+    dtok[H + c] = 0.f;
+}
+
+// ======================================================================================== host: layout ====
+struct XfmrLayerStash {
+    float *q, *k, *v, *ctx, *z1, *st1, *y1, *a, *f, *z2, *st2, *y2;
+};
+struct XfmrStash {
+    int64_t *cut, *tok_off, *tok_item;
+    int32_t *nb, *T_dev, *tok_user;
+    float *z0, *st0, *x0;
+    XfmrLayerStash layer[XFMR_MAX_LAYERS];
+    size_t total;
+};
+static XfmrStash xfmr_stash(void* p, int64_t B, int64_t t_cap, int h, int layers, int I) {
+    MfArena a(p);
+    XfmrStash s;
+    const size_t T = (size_t)(t_cap > 0 ? t_cap : 1);
+    s.cut = a.take<int64_t>((size_t)B);
+    s.nb = a.take<int32_t>((size_t)B);
+    s.tok_off = a.take<int64_t>((size_t)B + 1);
+    s.T_dev = a.take<int32_t>(1);
+    s.tok_item = a.take<int64_t>(T);
+    s.tok_user = a.take<int32_t>(T);
+    s.z0 = a.take<float>(T * h);
+    s.st0 = a.take<float>(T * 2);
+    s.x0 = a.take<float>(T * h);
+    for (int l = 0; l < layers; ++l) {
+        XfmrLayerStash& y = s.layer[l];
+        y.q = a.take<float>(T * h); y.k = a.take<float>(T * h); y.v = a.take<float>(T * h); y.ctx = a.take<float>(T * h);
+        y.z1 = a.take<float>(T * h); y.st1 = a.take<float>(T * 2); y.y1 = a.take<float>(T * h);
+        y.a = a.take<float>(T * I); y.f = a.take<float>(T * I);
+        y.z2 = a.take<float>(T * h); y.st2 = a.take<float>(T * 2); y.y2 = a.take<float>(T * h);
+    }
+    s.total = a.used();
+    return s;
+}
+
+static const char* xfmr_check_shape(int h, int layers, int heads, int I, int L) {
+    if (h != 32 && h != 64 && h != 128) return "hidden size not in {32, 64, 128}";
+    if (layers < 1 || layers > XFMR_MAX_LAYERS) return "num_hidden_layers not in 1..4";
+    if (heads < 1 || h % heads) return "hidden size not a multiple of the heads";
+    const int dh = h / heads;
+    if (dh != 8 && dh != 16 && dh != 32 && dh != 64) return "head width not in {8, 16, 32, 64}";
+    if (I < 32 || I % 32 || I > 4 * h) return "intermediate size not a multiple of 32 in [32, 4 h]";
+    if (L < 1 || L > XFMR_MAX_L) return "max_history not in 1..64";
+    return nullptr;
+}
+
+extern "C" size_t mf_xfmr_ws_bytes(int64_t B, int64_t t_cap, int h, int layers, int I) {
+    if (layers < 1 || layers > XFMR_MAX_LAYERS) return 0;
+    return xfmr_stash(nullptr, B > 0 ? B : 1, t_cap, h, layers, I).total;
+}
+
+static void xfmr_gemm(hipStream_t s, int64_t t_cap, XGemm g) {
+    if (g.dyn == 0) {
+        const dim3 grid((unsigned)((t_cap + 63) / 64), (unsigned)((g.N + 63) / 64));
+        xfmr_gemm_kernel<<<grid, 256, 0, s>>>(g);
+    } else {
+        const dim3 grid((unsigned)((g.M + 63) / 64), (unsigned)((g.N + 63) / 64), XFMR_SLICES);
+        xfmr_gemm_kernel<<<grid, 256, 0, s>>>(g);
+    }
+}
+// Y [T, N] = X [T, K] W[N, K]^T + bias (+ R)
+static XGemm xg_linear(const float* X, int K, const float* W, const float* bias, int N, float* Y, const float* R, const int32_t* T_dev) {
+    XGemm g{};
+    g.A = X; g.lda = K; g.a_kc = 1;
+    g.B = W; g.ldb = K; g.b_kc = 1;
+    g.C = Y; g.ldc = N; g.N = N; g.K = K; g.T_dev = T_dev; g.dyn = 0; g.bias = bias; g.R = R;
+    return g;
+}
+// dX [T, K] = dY [T, N] W[N, K] (+ R)
+static XGemm xg_dinput(const float* dY, int N, const float* W, int K, float* dX, const float* R, const int32_t* T_dev) {
+    XGemm g{};
+    g.A = dY; g.lda = N; g.a_kc = 1;
+    g.B = W; g.ldb = K; g.b_kc = 0;
+    g.C = dX; g.ldc = K; g.N = K; g.K = N; g.T_dev = T_dev; g.dyn = 0; g.R = R;
+    return g;
+}
+// dW [N, K] = dY [T, N]^T X [T, K], db [N] = column sums of dY: XFMR_SLICES partials in `part`, then the ordered sum
+static void xfmr_dweight(hipStream_t s, const float* dY, int N, const float* X, int K, float* dW, float* db, float* part,
+                         const int32_t* T_dev) {
+    XGemm g{};
+    g.A = dY; g.lda = N; g.a_kc = 0;
+    g.B = X; g.ldb = K; g.b_kc = 0;
+    g.C = part; g.ldc = K; g.M = N; g.N = K; g.T_dev = T_dev; g.dyn = 1;
+    g.slice_stride = (int64_t)N * K + N;
+    xfmr_gemm(s, 0, g);
+    const int64_t size = g.slice_stride;
+    xfmr_reduce_kernel<<<dim3((unsigned)((size + 255) / 256)), 256, 0, s>>>(part, XFMR_SLICES, size, (int64_t)N * K, dW, db);
+}
+
+#define XFMR_DISPATCH_H(h, ...)                                  \
+    switch (h) {                                                 \
+        case 32: { constexpr int H = 32; __VA_ARGS__; } break;   \
+        case 64: { constexpr int H = 64; __VA_ARGS__; } break;   \
+        default: { constexpr int H = 128; __VA_ARGS__; } break;  \
+    }
+#define XFMR_DISPATCH_DH(dh, ...)                                \
+    switch (dh) {                                                \
+        case 8: { constexpr int DH = 8; __VA_ARGS__; } break;    \
+        case 16: { constexpr int DH = 16; __VA_ARGS__; } break;  \
+        case 32: { constexpr int DH = 32; __VA_ARGS__; } break;  \
+        default: { constexpr int DH = 64; __VA_ARGS__; } break;  \
+    }
+
+// ============================================================================================= forward ====
+extern "C" int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                               const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
+                               int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
+                               float* out_u, float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, mf_stream_t stream) {
+    if (!table || !seg_start || !seg_end || !items || !params || !out_u || !out_inv || !stash || B <= 0 || n_rows <= 0 ||
+        n_items <= 0 || t_cap < 0 || act < 0 || act > 3 || mode < 0 || mode > 2 || (mode == XPOOL_MAX && !out_arg))
+        return mf_set_error(MF_EINVAL, "mf_xfmr_forward: bad argument");
+    if (const char* why = xfmr_check_shape(h, layers, heads, intermediate, max_history))
+        return mf_set_error(MF_ENOTSUP, "mf_xfmr_forward: %s", why);
+    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_xfmr_forward: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
+    if (t_cap >= (1ll << 31) || B >= (1ll << 31) / 64)
+        return mf_set_error(MF_ENOTSUP, "mf_xfmr_forward: too many tokens or users");
+    if (stash_bytes < mf_xfmr_ws_bytes(B, t_cap, h, layers, intermediate)) return mf_set_error(MF_ENOSPC, "mf_xfmr_forward: stash too small");
+    for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i)
+        if (!params[i]) return mf_set_error(MF_EINVAL, "mf_xfmr_forward: parameter %d is null", i);
+    const XfmrStash st = xfmr_stash(stash, B, t_cap, h, layers, intermediate);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int I = intermediate, dh = h / heads;
+    const unsigned gu = (unsigned)((B + 3) / 4), gt = (unsigned)((t_cap + 7) / 8);
+    MF_TIMED("xfmr_forward", s, {
+        xfmr_cut_kernel<<<gu, 256, 0, s>>>(seg_start, seg_end, items, n_items, B, n_rows, max_history, st.cut, st.nb);
+        xfmr_scan_kernel<<<1, 256, 0, s>>>(st.nb, B, t_cap, st.tok_off, st.T_dev);
+        xfmr_pack_kernel<<<gu, 256, 0, s>>>(seg_end, st.cut, items, n_items, B, n_rows, st.tok_off, st.tok_item, st.tok_user);
+        if (t_cap > 0) {
+            XFMR_DISPATCH_H(h, xfmr_embed_kernel<H><<<gt, 256, 0, s>>>(table, st.tok_item, st.tok_user, st.tok_off, st.T_dev, norm_item,
+                                                                      params[0], params[1], params[2], params[3], st.z0, st.st0, st.x0));
+            const float* x = st.x0;
+            for (int l = 0; l < layers; ++l) {
+                const float* const* w = params + XFMR_GLOBALS + XFMR_PER_LAYER * l;
+                const XfmrLayerStash& y = st.layer[l];
+                MF_TIMED("xfmr_gemm_fwd", s, {
+                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[0], w[1], h, y.q, nullptr, st.T_dev));
+                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[2], w[3], h, y.k, nullptr, st.T_dev));
+                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[4], w[5], h, y.v, nullptr, st.T_dev));
+                });
+                MF_TIMED("xfmr_attn_fwd", s, XFMR_DISPATCH_DH(dh, xfmr_attn_kernel<DH><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
+                                                                      y.q, y.k, y.v, st.tok_off, h, heads, y.ctx)));
+                MF_TIMED("xfmr_gemm_fwd", s, xfmr_gemm(s, t_cap, xg_linear(y.ctx, h, w[6], w[7], h, y.z1, x, st.T_dev)));
+                XFMR_DISPATCH_H(h, xfmr_ln_kernel<H><<<gt, 256, 0, s>>>(y.z1, st.T_dev, w[8], w[9], y.y1, y.st1));
+                MF_TIMED("xfmr_gemm_fwd", s, {
+                    XGemm g = xg_linear(y.y1, h, w[10], w[11], I, y.a, nullptr, st.T_dev);
+                    g.epi = XEPI_ACT; g.act = act; g.C2 = y.f;
+                    xfmr_gemm(s, t_cap, g);
+                    xfmr_gemm(s, t_cap, xg_linear(y.f, I, w[12], w[13], h, y.z2, y.y1, st.T_dev));
+                });
+                XFMR_DISPATCH_H(h, xfmr_ln_kernel<H><<<gt, 256, 0, s>>>(y.z2, st.T_dev, w[14], w[15], y.y2, y.st2));
+                x = y.y2;
+            }
+        }
+        const float* last = t_cap > 0 ? st.layer[layers - 1].y2 : st.x0;
+        XFMR_DISPATCH_H(h, xfmr_pool_kernel<H><<<dim3((unsigned)((B + 7) / 8)), 256, 0, s>>>(last, st.tok_off, B, mode, norm_user, out_u,
+                                                                                            out_inv, out_arg));
+    });
+    return mf_check_launch("mf_xfmr_forward");
+}
+
+// ============================================================================================ backward ====
+struct XfmrBwdWs {
+    float *dy, *dz, *dt, *dctx, *dq, *dk, *dv, *di, *part;
+    size_t total;
+};
+static size_t xfmr_part_floats(int h, int I) {
+    size_t m = (size_t)XFMR_SLICES * ((size_t)I * h + (size_t)(I > h ? I : h));
+    const size_t ln = (size_t)XFMR_LN_SLICES * 2 * h, ps = (size_t)XFMR_POS_SLICES * XFMR_MAX_L * h;
+    if (ln > m) m = ln;
+    if (ps > m) m = ps;
+    return m;
+}
+static XfmrBwdWs xfmr_bwd_ws(void* p, int64_t t_cap, int h, int I) {
+    MfArena a(p);
+    XfmrBwdWs w;
+    const size_t T = (size_t)(t_cap > 0 ? t_cap : 1);
+    w.dy = a.take<float>(T * h); w.dz = a.take<float>(T * h); w.dt = a.take<float>(T * h); w.dctx = a.take<float>(T * h);
+    w.dq = a.take<float>(T * h); w.dk = a.take<float>(T * h); w.dv = a.take<float>(T * h);
+    w.di = a.take<float>(T * I);
+    w.part = a.take<float>(xfmr_part_floats(h, I));
+    w.total = a.used();
+    return w;
+}
+extern "C" size_t mf_xfmr_backward_ws_bytes(int64_t t_cap, int h, int I) { return xfmr_bwd_ws(nullptr, t_cap, h, I).total; }
+
+template <int H>
+static void xfmr_ln_bwd(hipStream_t s, const float* dy, const float* z, const float* st, const int32_t* T_dev, const float* gamma,
+                        float* dz, float* part, float* dgamma, float* dbeta) {
+    xfmr_ln_bwd_kernel<H><<<XFMR_LN_SLICES, 256, 0, s>>>(dy, z, st, T_dev, gamma, dz, part);
+    xfmr_reduce_kernel<<<dim3((2 * H + 255) / 256), 256, 0, s>>>(part, XFMR_LN_SLICES, 2 * H, H, dgamma, dbeta);
+}
+
+// grads: one buffer per parameter, in the parameters' order and shapes; every element is written (no accumulation).
+// grad_x [t_cap, h] receives dL/dx_t of the packed tokens (the rows mf_xfmr_coalesce lands on the item table).
+extern "C" int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads, int intermediate,
+                                int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
+                                const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
+                                void* ws, size_t ws_bytes, mf_stream_t stream) {
+    if (!params || !grads || !stash || !grad_u || !out_u || !out_inv || !grad_x || !ws || B <= 0 || t_cap <= 0 || act < 0 || act > 3 ||
+        mode < 0 || mode > 2 || (mode == XPOOL_MAX && !out_arg) || max_pos < max_history)
+        return mf_set_error(MF_EINVAL, "mf_xfmr_backward: bad argument");
+    if (const char* why = xfmr_check_shape(h, layers, heads, intermediate, max_history))
+        return mf_set_error(MF_ENOTSUP, "mf_xfmr_backward: %s", why);
+    if (ws_bytes < mf_xfmr_backward_ws_bytes(t_cap, h, intermediate)) return mf_set_error(MF_ENOSPC, "mf_xfmr_backward: workspace too small");
+    for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i)
+        if (!params[i] || !grads[i]) return mf_set_error(MF_EINVAL, "mf_xfmr_backward: parameter or gradient %d is null", i);
+    const XfmrStash st = xfmr_stash(const_cast<void*>(stash), B, t_cap, h, layers, intermediate);
+    const XfmrBwdWs w = xfmr_bwd_ws(ws, t_cap, h, intermediate);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int I = intermediate, dh = h / heads, L = max_history;
+    const unsigned gt = (unsigned)((t_cap + 7) / 8);
+    const int32_t* Td = st.T_dev;
+    MF_TIMED("xfmr_backward", s, {
+        XFMR_DISPATCH_H(h, xfmr_pool_bwd_kernel<H><<<gt, 256, 0, s>>>(grad_u, out_u, out_inv, out_arg, st.tok_off, st.tok_user, Td, mode,
+                                                                     norm_user, w.dy));
+        for (int l = layers - 1; l >= 0; --l) {
+            const float* const* p = params + XFMR_GLOBALS + XFMR_PER_LAYER * l;
+            float* const* g = grads + XFMR_GLOBALS + XFMR_PER_LAYER * l;
+            const XfmrLayerStash& y = st.layer[l];
+            const float* x = l == 0 ? st.x0 : st.layer[l - 1].y2;
+            // output block: y2 = LN(z2), z2 = f Wo2^T + bo2 + y1
+            XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dy, y.z2, y.st2, Td, p[14], w.dz, w.part, g[14], g[15]));
+            MF_TIMED("xfmr_gemm_bwd", s, {
+                xfmr_dweight(s, w.dz, h, y.f, I, g[12], g[13], w.part, Td);
+                XGemm d = xg_dinput(w.dz, h, p[12], I, w.di, nullptr, Td);        // da = (dz2 Wo2) * act'(a)
+                d.epi = XEPI_DACT; d.act = act; d.P = y.a;
+                xfmr_gemm(s, t_cap, d);
+                xfmr_dweight(s, w.di, I, y.y1, h, g[10], g[11], w.part, Td);
+                xfmr_gemm(s, t_cap, xg_dinput(w.di, I, p[10], h, w.dt, w.dz, Td));  // dy1 = da Wi + dz2
+            });
+            // attention block: y1 = LN(z1), z1 = ctx Wo^T + bo + x
+            XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dt, y.z1, y.st1, Td, p[8], w.dz, w.part, g[8], g[9]));
+            MF_TIMED("xfmr_gemm_bwd", s, {
+                xfmr_dweight(s, w.dz, h, y.ctx, h, g[6], g[7], w.part, Td);
+                xfmr_gemm(s, t_cap, xg_dinput(w.dz, h, p[6], h, w.dctx, nullptr, Td));
+            });
+            MF_TIMED("xfmr_attn_bwd", s, XFMR_DISPATCH_DH(dh, xfmr_attn_bwd_kernel<DH><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
+                                                                  y.q, y.k, y.v, w.dctx, st.tok_off, h, heads, w.dq, w.dk, w.dv)));
+            MF_TIMED("xfmr_gemm_bwd", s, {
+                xfmr_dweight(s, w.dq, h, x, h, g[0], g[1], w.part, Td);
+                xfmr_dweight(s, w.dk, h, x, h, g[2], g[3], w.part, Td);
+                xfmr_dweight(s, w.dv, h, x, h, g[4], g[5], w.part, Td);
+                xfmr_gemm(s, t_cap, xg_dinput(w.dq, h, p[0], h, w.dy, w.dz, Td));   // dx = dz1 + dq Wq + dk Wk + dv Wv
+                xfmr_gemm(s, t_cap, xg_dinput(w.dk, h, p[2], h, w.dy, w.dy, Td));
+                xfmr_gemm(s, t_cap, xg_dinput(w.dv, h, p[4], h, w.dy, w.dy, Td));
+            });
+        }
+        // embeddings: x0 = LN(z0), z0 = (x + tok[0]) + pos[t]
+        XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dy, st.z0, st.st0, Td, params[2], grad_x, w.part, grads[2], grads[3]));
+        mf_zero_async(grads[0], (size_t)max_pos * h * sizeof(float), s);
+        xfmr_pos_bwd_kernel<<<dim3((unsigned)L, XFMR_POS_SLICES), 128, 0, s>>>(grad_x, st.tok_off, B, h, L, w.part);
+        xfmr_reduce_kernel<<<dim3((unsigned)(((int64_t)L * h + 255) / 256)), 256, 0, s>>>(w.part, XFMR_POS_SLICES, (int64_t)L * h,
+                                                                                         (int64_t)L * h, grads[0], grads[0]);
+        xfmr_tok_bwd_kernel<<<1, 128, 0, s>>>(grads[0], h, L, grads[1]);
+    });
+    return mf_check_launch("mf_xfmr_backward");
+}
+
+// ============================================================================================ coalesce ====
+// every packed token is an entry: its key is its item id, its row dL/dx_t
+struct XfmrEntries {
+    const int64_t* tok_item;
+    int64_t n_rows;
+    const float* grad_x;
+    __device__ __forceinline__ uint32_t key(int64_t, int64_t pos) const {
+        const long long id = tok_item[pos];
+        return xfmr_valid(id, n_rows) ? (uint32_t)id : (uint32_t)n_rows;
+    }
+    template <int D>
+    __device__ __forceinline__ f32x4 grad(int64_t, int64_t t, int c) const {
+        return reinterpret_cast<const f32x4*>(grad_x + t * D)[c];
+    }
+};
+
+extern "C" size_t mf_xfmr_coalesce_ws_bytes(int64_t n_extra, int64_t t_cap, int d) {
+    MfArena a(nullptr);
+    coalesce_ws(a, n_extra > 0 ? n_extra : 0, t_cap > 0 ? t_cap : 0, d);
+    return a.used();
+}
+
+extern "C" int mf_xfmr_coalesce(int64_t n_rows, int d, int64_t B, int64_t t_cap, int layers, int intermediate, const void* stash,
+                                const float* grad_x, const int64_t* extra_ids, const float* extra_grad, int64_t n_extra,
+                                int64_t capacity, int64_t* out_ids, float* out_grad, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    if (!stash || !grad_x || !out_ids || !out_grad || !ws || B <= 0 || n_rows <= 0 || t_cap < 0 || n_extra < 0 ||
+        (n_extra > 0 && (!extra_ids || !extra_grad)) || layers < 1 || layers > XFMR_MAX_LAYERS)
+        return mf_set_error(MF_EINVAL, "mf_xfmr_coalesce: bad argument");
+    if (d != 32 && d != 64 && d != 128) return mf_set_error(MF_EINVAL, "mf_xfmr_coalesce: width %d not in {32,64,128}", d);
+    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_xfmr_coalesce: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
+    const int64_t n = n_extra + t_cap;
+    if (n >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_xfmr_coalesce: %lld entries >= 2^31", (long long)n);
+    if (capacity != (n < n_rows ? n : n_rows)) return mf_set_error(MF_EINVAL, "mf_xfmr_coalesce: capacity must be min(n_rows, entries)");
+    if (ws_bytes < mf_xfmr_coalesce_ws_bytes(n_extra, t_cap, d)) return mf_set_error(MF_ENOSPC, "mf_xfmr_coalesce: workspace too small");
+    if (n == 0) return MF_OK;
+    const XfmrStash st = xfmr_stash(const_cast<void*>(stash), B, t_cap, d, layers, intermediate);
+    MfArena a(ws);
+    const CoalesceWs w = coalesce_ws(a, n_extra, t_cap, d);
+    const CoalesceSrc src{n_rows, extra_ids, extra_grad, n_extra, st.tok_off, st.tok_off, B, t_cap};
+    const XfmrEntries ent{st.tok_item, n_rows, grad_x};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc;
+    MF_TIMED("xfmr_coalesce", s, rc = coalesce(src, ent, w, d, capacity, out_ids, out_grad, nullptr, s));
+    return rc ? rc : mf_check_launch("mf_xfmr_coalesce");
+}

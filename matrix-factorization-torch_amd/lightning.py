@@ -55,6 +55,9 @@ class MatrixFactorizationLitConfig(models.ModelConfig):
     use_logq: bool = False         # logQ correction (absent upstream)
 
 
+HISTORY_TOWERS = ("history", "transformer")      # user towers whose input is the user's history, not its id
+
+
 class MatrixFactorizationLitModule(_Base):
     def __init__(self, config: MatrixFactorizationLitConfig | dict) -> None:
         super().__init__()
@@ -81,7 +84,7 @@ class MatrixFactorizationLitModule(_Base):
             raise ValueError(msg)
         exclude_item_ids = (exclude_item_ids or []) + list(self.history.get(int(user_idx), []))
         device = self.towers["user"].weight.device
-        if self.config.user_tower == "history":      # the user IS its history: pool it (xfmr_rec/lightning.py:89-90 excludes it)
+        if self.config.user_tower in HISTORY_TOWERS:      # the user IS its history: pool it (xfmr_rec/lightning.py:89-90 excludes it)
             embed = self._pool_item_ids(list(self.history.get(int(user_idx), []))).cpu().numpy()
         else:
             embed = self(torch.tensor([int(user_idx)], device=device)).cpu().numpy()
@@ -98,8 +101,9 @@ class MatrixFactorizationLitModule(_Base):
     def recommend_with_history(self, item_ids: list[int], *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
         """Serve a user who is in no table from the items they consumed (history tower only): the query is the pooled
         history and the history itself is excluded (xfmr_rec/lightning.py:89-90)."""
-        if self.config.user_tower != "history":
-            msg = "recommend_with_history needs user_tower='history' (a table user tower has no row for an unseen user)"
+        if self.config.user_tower not in HISTORY_TOWERS:
+            msg = ("recommend_with_history needs user_tower='history' or 'transformer' (a table user tower has no row for an "
+                   "unseen user)")
             raise ValueError(msg)
         if self.towers is None or self.item_processor is None or self.item_processor.index is None:
             msg = "`user_processor` and `item_processor` must be initialised first"
@@ -213,6 +217,8 @@ class MatrixFactorizationLitModule(_Base):
                     bags[f"{k}.off"], bags[f"{k}.tokens"] = t.bags.off.cpu().contiguous(), t.bags.tokens.cpu().contiguous()
                     if t.bags.weights is not None:
                         bags[f"{k}.weights"] = t.bags.weights.cpu().contiguous()
+            elif isinstance(t, models.HistoryTransformerTower):      # the encoder's weights, next to the shared table
+                tables.update({f"{k}.{name}": v.detach().cpu().contiguous() for name, v in t.state_dict().items()})
             elif not isinstance(t, models.HistoryPoolingTower):
                 tables[f"{k}.weight"] = t.weight.detach().cpu().contiguous()
         save_file(tables, str(path / TOWERS_PATH))
@@ -242,6 +248,8 @@ class MatrixFactorizationLitModule(_Base):
             for k, t in module.towers.items():
                 if isinstance(t, models.FeatureBagTower):
                     t.weight.copy_(weights["features.weight"].to(device))
+                elif isinstance(t, models.HistoryTransformerTower):
+                    t.load_state_dict({name: weights[f"{k}.{name}"].to(device) for name in t.state_dict()})
                 elif not isinstance(t, models.HistoryPoolingTower):
                     t.weight.copy_(weights[f"{k}.weight"].to(device))
         if (path / FEATURE_BAGS_PATH).exists():
@@ -267,7 +275,7 @@ class MatrixFactorizationLitModule(_Base):
         pos_idx = batch["user"].get("pos_idx")            # the reference's padded positives, or ...
         pos_csr = batch["user"].get("pos_csr")            # ... the producer's CSR lists (data.DeviceInteractionSampler)
         # history tower: the user vector is the pooled history of the example (data.DeviceInteractionSampler(history=True))
-        user_embed = self(batch["user"]["history" if self.config.user_tower == "history" else "idx"], tower="user")
+        user_embed = self(batch["user"]["history" if self.config.user_tower in HISTORY_TOWERS else "idx"], tower="user")
         # positives then sampled negatives, as xfmr_rec/lightning.py:133-134
         item_idx = torch.cat([batch["item"]["idx"], batch["neg_item"]["idx"]])
         item_embed = self(item_idx, tower="item")
@@ -310,7 +318,7 @@ class MatrixFactorizationLitModule(_Base):
     def _queries(self, batch) -> torch.Tensor:
         """The users' query vectors: their table rows, or (history tower) their pooled history -- the same CSR
         ``(offsets, item rows)`` that is excluded from retrieval (``InteractionTable.eval_sets``)."""
-        if self.config.user_tower != "history":
+        if self.config.user_tower not in HISTORY_TOWERS:
             return self(batch["user"]["idx"], tower="user")
         off, items = batch["history"]
         return self((off[:-1], off[1:], items), tower="user")
@@ -370,6 +378,8 @@ class MatrixFactorizationLitModule(_Base):
 
     # ------------------------------------------------------------------- setup ---
     def configure_optimizers(self) -> torch.optim.Optimizer:
+        if self.config.user_tower == "transformer":     # tables + the encoder's dense weights: one object steps both
+            return optim.tower_optimizer(self.towers, "sgd" if self.config.optimizer == "sgd" else "adam", self.config.learning_rate)
         params = list(self.towers.parameters())
         if self.config.optimizer == "sgd":
             return optim.SparseSGD(params, lr=self.config.learning_rate)

@@ -34,9 +34,16 @@ class ModelConfig(pydantic.BaseModel):
     num_hashes: int = 0            # > 0: hash / bloom towers (config 5): num_users / num_items are BUCKET counts
     hash_seed: int = 0
     # "history": the user vector is the pooled item rows of the user's history (HistoryPoolingTower), not a table row
-    user_tower: Literal["table", "history", "features"] = "table"
-    pooling_mode: str = "mean"     # models.py:24 ("cls" / "pooler" need the transformer this repository does not have)
+    # "transformer": a BERT encoder over those rows, then the pool (HistoryTransformerTower)
+    user_tower: Literal["table", "history", "features", "transformer"] = "table"
+    pooling_mode: str = "mean"     # models.py:24 ("cls" needs user_tower="transformer"; "pooler" is refused everywhere)
     max_history: int | None = None
+    # the encoder of user_tower="transformer" (the reference's field names, models.py:14-24; BertConfig's meanings)
+    num_hidden_layers: int = 1
+    num_attention_heads: int = 4
+    intermediate_size: int | None = None       # None: hidden_size, as the reference's module config
+    hidden_act: str = "gelu"
+    max_position_embeddings: int = 64
     # "features": the vector is the pooled hashed-attribute tokens of the entity (FeatureBagTower); when both towers are
     # feature towers they share ONE bucket table, as the reference's towers share one encoder (lightning.py:60-74)
     item_tower: Literal["table", "features"] = "table"
@@ -45,10 +52,19 @@ class ModelConfig(pydantic.BaseModel):
     feature_seed: int = 0
     feature_text_fields: tuple[str, ...] = ("title",)             # fields split into words (data.FeatureHasher)
 
-    @pydantic.field_validator("pooling_mode")
-    @classmethod
-    def _check_pooling_mode(cls, v: str) -> str:
-        return check_pooling_mode(v)
+    @pydantic.model_validator(mode="after")
+    def _check_pooling_mode(self):
+        # (a model validator: which modes exist depends on user_tower)
+        if self.user_tower == "transformer":
+            check_transformer_shape(self.hidden_size, self.num_hidden_layers, self.num_attention_heads, self.intermediate_size,
+                                    self.hidden_act, self.max_position_embeddings, self.max_history, self.pooling_mode)
+            if self.num_hashes > 0 or self.item_tower != "table":
+                msg = ("user_tower='transformer' encodes the rows of a plain item table: hashed towers (num_hashes > 0) and "
+                       "item_tower='features' are not supported")
+                raise ValueError(msg)
+        else:
+            check_pooling_mode(self.pooling_mode)
+        return self
 
     @pydantic.field_validator("max_history")
     @classmethod
@@ -93,6 +109,46 @@ def check_pooling_mode(mode: str) -> str:
         msg = f"pooling_mode must be one of {POOLING_MODES}: {mode = }"
         raise ValueError(msg)
     return mode
+
+
+TRANSFORMER_POOLING_MODES = ("mean", "max", "cls")
+HIDDEN_ACTS = ("gelu", "relu", "silu", "gelu_new")      # the kernels' activation codes, in this order
+XFMR_MAX_POSITIONS = 64
+
+
+def check_transformer_shape(hidden_size: int, num_hidden_layers: int, num_attention_heads: int, intermediate_size: int | None,
+                            hidden_act: str, max_position_embeddings: int, max_history: int | None, pooling_mode: str) -> None:
+    """The limits of ``csrc/mf_xfmr.hip``, as explicit errors."""
+    if pooling_mode == "pooler":
+        msg = ("pooling_mode 'pooler' is not supported: what sentence-transformers' Pooling does with it could not be checked; "
+               f"use one of {TRANSFORMER_POOLING_MODES}")
+        raise ValueError(msg)
+    if pooling_mode not in TRANSFORMER_POOLING_MODES:
+        msg = f"pooling_mode must be one of {TRANSFORMER_POOLING_MODES}: {pooling_mode = }"
+        raise ValueError(msg)
+    if hidden_size not in (32, 64, 128):
+        msg = f"the transformer tower supports hidden_size in (32, 64, 128): {hidden_size = }"
+        raise ValueError(msg)
+    if not 1 <= num_hidden_layers <= 4:  # noqa: PLR2004
+        msg = f"num_hidden_layers must be in 1..4: {num_hidden_layers = }"
+        raise ValueError(msg)
+    if num_attention_heads < 1 or hidden_size % num_attention_heads or hidden_size // num_attention_heads not in (8, 16, 32, 64):
+        msg = (f"hidden_size / num_attention_heads must be a whole head width in (8, 16, 32, 64): {hidden_size = }, "
+               f"{num_attention_heads = }")
+        raise ValueError(msg)
+    inter = hidden_size if intermediate_size is None else intermediate_size
+    if inter < 32 or inter % 32 or inter > 4 * hidden_size:  # noqa: PLR2004
+        msg = f"intermediate_size must be a multiple of 32 in [32, 4 * hidden_size]: {intermediate_size = }"
+        raise ValueError(msg)
+    if hidden_act not in HIDDEN_ACTS:
+        msg = f"hidden_act must be one of {HIDDEN_ACTS}: {hidden_act = }"
+        raise ValueError(msg)
+    if not 1 <= max_position_embeddings <= XFMR_MAX_POSITIONS:
+        msg = f"max_position_embeddings must be in 1..{XFMR_MAX_POSITIONS}: {max_position_embeddings = }"
+        raise ValueError(msg)
+    if max_history is not None and not 1 <= max_history <= max_position_embeddings:
+        msg = f"max_history must be None or in 1..max_position_embeddings = {max_position_embeddings}: {max_history = }"
+        raise ValueError(msg)
 
 
 def _park(table: torch.Tensor, item) -> None:
@@ -373,6 +429,185 @@ class HistoryPoolingTower(torch.nn.Module):
         return f"pooling_mode={self.pooling_mode}, max_history={self.max_history}, normalize={self.normalize}"
 
 
+class TransformerHistoryGrad(PooledGrad):
+    """The transformer tower's contribution to its item table's gradient: one entry per packed token, key = the token's
+    item id, row = dL/dx_t (``mf_xfmr_backward``'s ``grad_x``), coalesced with the rows other towers parked on the table."""
+
+    def __init__(self, ctx, grad_x: torch.Tensor) -> None:
+        self.normalize, self.stash, self.grad_x = ctx.norm_item, ctx.stash, grad_x
+        self.b, self.t_cap, self.layers, self.inter = ctx.b, ctx.t_cap, ctx.shape[0], ctx.shape[2]
+
+    def coalesce(self, table: torch.Tensor, ids: torch.Tensor | None, grad: torch.Tensor | None):
+        lib = _lib.lib()
+        rows, d = table.shape
+        n_extra = 0 if ids is None else ids.numel()
+        cap = min(rows, n_extra + self.t_cap)
+        out_ids = torch.empty(cap, dtype=torch.int64, device=table.device)
+        out_grad = torch.empty(cap, d, dtype=torch.float32, device=table.device)
+        if cap == 0:
+            return out_ids, out_grad
+        ws = _lib.workspace(lib.mf_xfmr_coalesce_ws_bytes(n_extra, self.t_cap, d), table.device)
+        _lib.check(lib.mf_xfmr_coalesce(rows, d, self.b, self.t_cap, self.layers, self.inter, self.stash.data_ptr(),
+                                        self.grad_x.data_ptr(), _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(),
+                                        out_grad.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        return out_ids, out_grad
+
+
+def _pointer_array(tensors):
+    import ctypes
+
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _EncodeHistory(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table: torch.Tensor, start: torch.Tensor, end: torch.Tensor, items: torch.Tensor, n_entries: int, cfg: tuple,
+                *params: torch.Tensor):
+        layers, heads, inter, act, mode, max_history, norm_item, norm_user = cfg
+        if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
+            raise _lib.MfHipError("embedding table must be a contiguous fp32 tensor on the GPU")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.MfHipError("the transformer tower does not support hipGraph capture")
+        for p in params:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.MfHipError("encoder parameters must be contiguous fp32 tensors on the GPU")
+        lib = _lib.lib()
+        rows, d = table.shape
+        b = start.numel()
+        dev = table.device
+        t_cap = min(n_entries, b * max_history)
+        u = torch.empty(b, d, dtype=torch.float32, device=dev)
+        inv = torch.empty(b, dtype=torch.float32, device=dev)
+        arg = torch.empty(b, d, dtype=torch.int32, device=dev) if mode == 1 else None
+        stash = _lib.workspace(lib.mf_xfmr_ws_bytes(b, t_cap, d, layers, inter), dev)
+        params = tuple(p.detach() for p in params)
+        _lib.check(lib.mf_xfmr_forward(table.data_ptr(), rows, d, start.data_ptr(), end.data_ptr(), items.data_ptr(), items.numel(),
+                                       b, t_cap, max_history, layers, heads, inter, act, mode, int(norm_item), int(norm_user),
+                                       _pointer_array(params), u.data_ptr(), inv.data_ptr(), _lib.ptr(arg), stash.data_ptr(),
+                                       stash.numel(), _lib.stream_ptr()))
+        ctx.table, ctx.stash, ctx.arg, ctx.params = table, stash, arg, params
+        ctx.b, ctx.t_cap, ctx.shape, ctx.mode = b, t_cap, (layers, heads, inter, act), mode
+        ctx.max_history, ctx.norm_item, ctx.norm_user = max_history, bool(norm_item), bool(norm_user)
+        ctx.save_for_backward(u, inv)
+        return u
+
+    @staticmethod
+    def backward(ctx, grad_u):
+        table, params = ctx.table, ctx.params
+        u, inv = ctx.saved_tensors
+        d = u.shape[1]
+        layers, heads, inter, act = ctx.shape
+        grads = [torch.empty_like(p) for p in params]
+        if ctx.t_cap == 0:                           # no valid token in the batch: no gradient anywhere
+            return (None,) * 6 + tuple(g.zero_() for g in grads)
+        lib = _lib.lib()
+        g = grad_u.to(torch.float32).contiguous()
+        grad_x = torch.empty(ctx.t_cap, d, dtype=torch.float32, device=u.device)
+        ws = _lib.workspace(lib.mf_xfmr_backward_ws_bytes(ctx.t_cap, d, inter), u.device)
+        _lib.check(lib.mf_xfmr_backward(d, ctx.b, ctx.t_cap, ctx.max_history, params[0].shape[0], layers, heads, inter, act, ctx.mode,
+                                        int(ctx.norm_user), _pointer_array(params), _pointer_array(grads), ctx.stash.data_ptr(),
+                                        g.data_ptr(), u.data_ptr(), inv.data_ptr(), _lib.ptr(ctx.arg), grad_x.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        _park(table, TransformerHistoryGrad(ctx, grad_x))
+        return (None,) * 6 + tuple(grads)
+
+
+class _Names(torch.nn.Module):
+    """A parameter container: only there so that ``state_dict`` carries BertModel's names."""
+
+
+class HistoryTransformerTower(torch.nn.Module):
+    """``tower(history) -> [B, d]``: ``Normalize(Pool(BertEncoder(rows of the user's last L history items)))`` -- the
+    sequence form of the reference's tower, ``PoolingTransformer.forward(inputs_embeds)`` (xfmr_rec/models.py:66-84), so the
+    user vector depends on the ORDER of the history.  ``history`` as for :class:`HistoryPoolingTower`; the last
+    ``max_history`` (default ``max_position_embeddings``, at most 64) valid entries are kept, the oldest at position 0.
+    ``pooling_mode``: "mean" / "max" over the valid positions, or "cls" = position 0.  The tower shares the item tower's
+    table (its backward lands on that table's sparse update) and owns the encoder's dense parameters, named as
+    ``transformers.BertModel``'s ``state_dict`` names them (no word-embedding table, no pooler dense); those receive ordinary
+    ``.grad`` tensors.  **No dropout**: BertConfig defaults to 0.1 on hidden states and attention probabilities and the
+    reference does not override it; this tower computes the eval-mode function in training too.  fp32 throughout, LayerNorm
+    eps 1e-12.  HIP kernels ``mf_xfmr_forward`` / ``mf_xfmr_backward`` / ``mf_xfmr_coalesce``; no hipGraph capture."""
+
+    def __init__(self, item_tower: torch.nn.Module, *, num_hidden_layers: int = 1, num_attention_heads: int = 4,
+                 intermediate_size: int | None = None, hidden_act: str = "gelu", max_position_embeddings: int = 64,
+                 pooling_mode: str = "mean", max_history: int | None = None, normalize: bool = True,
+                 initializer_range: float = 0.02, device=None) -> None:
+        super().__init__()
+        if not isinstance(item_tower, EmbeddingTower):
+            msg = (f"HistoryTransformerTower encodes the rows of a plain EmbeddingTower (one row per item); got "
+                   f"{type(item_tower).__name__} (a hashed tower's rows are shared by many items)")
+            raise ValueError(msg)
+        h = item_tower.embedding_dim
+        check_transformer_shape(h, num_hidden_layers, num_attention_heads, intermediate_size, hidden_act, max_position_embeddings,
+                                max_history, pooling_mode)
+        if item_tower.num_embeddings > FEATURE_MAX_BUCKETS:
+            msg = f"the item table must have at most 2^20 rows (the backward's radix sort): {item_tower.num_embeddings = }"
+            raise ValueError(msg)
+        object.__setattr__(self, "item_tower", item_tower)     # shared, not registered: the table is saved / optimised once
+        inter = h if intermediate_size is None else intermediate_size
+        self.num_hidden_layers, self.num_attention_heads, self.intermediate_size = num_hidden_layers, num_attention_heads, inter
+        self.hidden_act, self.max_position_embeddings = hidden_act, max_position_embeddings
+        self.pooling_mode, self.normalize = pooling_mode, normalize
+        self.max_history = max_position_embeddings if max_history is None else max_history
+        dev = device if device is not None else item_tower.weight.device
+
+        def linear(n_out, n_in):
+            m = torch.nn.Linear(n_in, n_out, device=dev)
+            torch.nn.init.normal_(m.weight, std=initializer_range)       # BertPreTrainedModel._init_weights
+            torch.nn.init.zeros_(m.bias)
+            return m
+
+        def names(**children):
+            m = _Names()
+            for k, v in children.items():
+                m.add_module(k, v)
+            return m
+
+        def norm():
+            return torch.nn.LayerNorm(h, eps=1e-12, device=dev)
+
+        emb = names(position_embeddings=torch.nn.Embedding(max_position_embeddings, h, device=dev),
+                    token_type_embeddings=torch.nn.Embedding(2, h, device=dev), LayerNorm=norm())
+        torch.nn.init.normal_(emb.position_embeddings.weight, std=initializer_range)
+        torch.nn.init.normal_(emb.token_type_embeddings.weight, std=initializer_range)
+        self.embeddings = emb
+        layers = [names(attention=names(self=names(query=linear(h, h), key=linear(h, h), value=linear(h, h)),
+                                        output=names(dense=linear(h, h), LayerNorm=norm())),
+                        intermediate=names(dense=linear(inter, h)),
+                        output=names(dense=linear(h, inter), LayerNorm=norm()))
+                  for _ in range(num_hidden_layers)]
+        self.encoder = names(layer=torch.nn.ModuleList(layers))
+
+    @property
+    def weight(self) -> torch.nn.Parameter:
+        return self.item_tower.weight
+
+    def encoder_parameters(self) -> list[torch.nn.Parameter]:
+        """The dense parameters in the kernels' order (``include/mf_hip.h``): 4 + 16 per layer."""
+        e = self.embeddings
+        out = [e.position_embeddings.weight, e.token_type_embeddings.weight, e.LayerNorm.weight, e.LayerNorm.bias]
+        for layer in self.encoder.layer:
+            a = layer.attention
+            for m in (a.self.query, a.self.key, a.self.value, a.output.dense, a.output.LayerNorm, layer.intermediate.dense,
+                      layer.output.dense, layer.output.LayerNorm):
+                out += [m.weight, m.bias]
+        return out
+
+    segments = HistoryPoolingTower.segments
+
+    def forward(self, history) -> torch.Tensor:
+        start, end, items, n_entries = self.segments(history)
+        if start.numel() == 0:
+            return torch.zeros(0, self.weight.shape[1], device=self.weight.device)
+        cfg = (self.num_hidden_layers, self.num_attention_heads, self.intermediate_size, HIDDEN_ACTS.index(self.hidden_act),
+               TRANSFORMER_POOLING_MODES.index(self.pooling_mode), self.max_history, self.item_tower.normalize, self.normalize)
+        return _EncodeHistory.apply(self.weight, start, end, items, n_entries, cfg, *self.encoder_parameters())
+
+    def extra_repr(self) -> str:
+        return (f"layers={self.num_hidden_layers}, heads={self.num_attention_heads}, intermediate={self.intermediate_size}, "
+                f"act={self.hidden_act}, pooling_mode={self.pooling_mode}, max_history={self.max_history}, normalize={self.normalize}")
+
+
 class FeatureBagGrad(PooledGrad):
     """A feature tower's contribution to its bucket table's gradient: entry e of bag b carries w_e * c_b * g_p[b]
     (``mf_bag_backward``), coalesced with the rows other sources parked on the table -- with both feature towers on one
@@ -514,7 +749,8 @@ class FeatureBagTower(torch.nn.Module):
 
 def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
     """Counterpart of ``init_bert`` + ``to_sentence_transformer`` (models.py:27-63).  ``user_tower="history"``: the user
-    tower is a :class:`HistoryPoolingTower` over the item table (plain tables only).  ``"features"``: a
+    tower is a :class:`HistoryPoolingTower` over the item table (plain tables only); ``"transformer"``: a
+    :class:`HistoryTransformerTower` over it.  ``"features"``: a
     :class:`FeatureBagTower`; with both towers so, one shared bucket table."""
     if "features" in (config.user_tower, config.item_tower):
         def table(name):
@@ -530,6 +766,15 @@ def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
             user = FeatureBagTower(config.feature_buckets, config.hidden_size, share_with=item, **kw)
         else:
             user = FeatureBagTower(config.feature_buckets, config.hidden_size, init_std=config.init_std, device=device, **kw)
+        return torch.nn.ModuleDict({"user": user, "item": item})
+    if config.user_tower == "transformer":
+        item = EmbeddingTower(config.num_items, config.hidden_size, normalize=config.normalize, init_std=config.init_std,
+                              device=device)
+        user = HistoryTransformerTower(item, num_hidden_layers=config.num_hidden_layers,
+                                       num_attention_heads=config.num_attention_heads, intermediate_size=config.intermediate_size,
+                                       hidden_act=config.hidden_act, max_position_embeddings=config.max_position_embeddings,
+                                       pooling_mode=config.pooling_mode, max_history=config.max_history,
+                                       normalize=config.normalize, device=device)
         return torch.nn.ModuleDict({"user": user, "item": item})
     if config.user_tower == "history":
         if config.num_hashes > 0:

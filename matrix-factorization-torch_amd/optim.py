@@ -250,3 +250,49 @@ class RowAdam(_SparseRowOptimizer):
         for p in done:
             p._mf_pending.clear()
         return loss
+
+
+class TowerOptimizer(torch.optim.Optimizer):
+    """ONE optimiser for towers that own both embedding tables and dense parameters (:class:`models.HistoryTransformerTower`):
+    ``sparse`` (:class:`SparseSGD` / :class:`RowAdam`) steps the tables from the rows their backwards parked, ``dense``
+    (``torch.optim.AdamW``, the reference's own optimiser, xfmr_rec/lightning.py:238-239) steps the parameters that received
+    ordinary ``.grad`` tensors.  ``step`` / ``zero_grad`` / ``state_dict`` / ``load_state_dict`` drive both; ``param_groups`` are
+    the two optimisers' own group dicts, so a scheduler that edits them reaches both."""
+
+    def __init__(self, sparse: _SparseRowOptimizer, dense: torch.optim.Optimizer) -> None:
+        self.sparse, self.dense = sparse, dense
+        super().__init__(sparse.param_groups + dense.param_groups, {})
+        self.param_groups = sparse.param_groups + dense.param_groups      # (the same dicts, not copies)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.sparse.step()
+        self.dense.step()
+        return loss
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        self.sparse.zero_grad(set_to_none=set_to_none)
+        self.dense.zero_grad(set_to_none=set_to_none)
+
+    def state_dict(self) -> dict:
+        return {"sparse": self.sparse.state_dict(), "dense": self.dense.state_dict()}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        self.sparse.load_state_dict(state_dict["sparse"])
+        self.dense.load_state_dict(state_dict["dense"])
+
+
+def tower_optimizer(towers: torch.nn.ModuleDict, kind: str, lr: float) -> torch.optim.Optimizer:
+    """The optimiser of a tower dict: ``kind`` "adam" -> :class:`RowAdam`, "sgd" -> :class:`SparseSGD` over the tables; when a
+    tower owns dense parameters (``encoder_parameters``), a :class:`TowerOptimizer` that also steps those with AdamW."""
+    if kind not in ("adam", "sgd"):
+        msg = f"the towers' optimiser must be 'adam' or 'sgd': {kind = }"
+        raise ValueError(msg)
+    dense = [p for t in towers.values() if hasattr(t, "encoder_parameters") for p in t.encoder_parameters()]
+    tables = [p for p in towers.parameters() if not any(p is q for q in dense)]
+    sparse = SparseSGD(tables, lr=lr) if kind == "sgd" else RowAdam(tables, lr=lr)
+    return TowerOptimizer(sparse, torch.optim.AdamW(dense, lr=lr)) if dense else sparse

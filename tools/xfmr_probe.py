@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Times the transformer user tower (models.HistoryTransformerTower) at the history probe's world: the ML-25M-shaped
+synthetic InteractionTable of tools/history_probe.py, batches of B = 8192 history windows.
+
+    python tools/xfmr_probe.py [--out profiles/xfmr_probe.json] [--ratings 25000000]
+    MF_HIP_LIB=path/to/parent/libmf_hip.so python tools/xfmr_probe.py --baseline-only --out profiles/xfmr_probe_parent.json
+
+For (d, L, I) in (64, 32, 64), (128, 32, 128), (128, 64, 512), one layer, 4 heads, mean pooling: the step time (InfoNCE over
+the batch's items, CSR positives, RowAdam on the table + AdamW on the encoder, through optim.TowerOptimizer), medians of
+three timed regions after warm-up, and the mf_timing spans of the forward, the backward, the coalesce, the GEMM launches and
+the attention.  For the GEMM spans: achieved fp32 matrix rate from the algorithmic flops 2 T (4 h^2 + 2 h I) per layer
+forward, twice that backward, against 157.3 TFLOP/s.  Next to it the same step with user_tower="history" (mean);
+``--baseline-only`` measures only that one, so that it can run against another build of the library (MF_HIP_LIB), whose
+missing mf_xfmr_* exports are then left unbound.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import importlib
+import importlib.util
+import json
+import pathlib
+import statistics
+import sys
+
+import torch
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+_spec = importlib.util.spec_from_file_location("history_probe", ROOT / "tools" / "history_probe.py")
+hp = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(hp)
+
+SHAPES = ((64, 32, 64), (128, 32, 128), (128, 64, 512))
+PEAK_TFLOPS = 157.3
+SPANS = ("xfmr_forward", "xfmr_backward", "xfmr_coalesce", "xfmr_gemm_fwd", "xfmr_gemm_bwd", "xfmr_attn_fwd", "xfmr_attn_bwd",
+         "pool_forward", "pool_backward", "update_rows")
+
+
+def median_ms(fn, regions: int = 3, warmup: int = 10, iters: int = 10) -> float:
+    hp.time_ms(fn, warmup=warmup, iters=2)
+    return statistics.median(hp.time_ms(fn, warmup=0, iters=iters) for _ in range(regions))
+
+
+def spans(mf, lib, step, steps: int = 6) -> dict:
+    lib.mf_timing_reset()
+    lib.mf_timing_enable(1)
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    lib.mf_timing_enable(0)
+    out = {}
+    for name in SPANS:
+        tot = ctypes.c_double(0.0)
+        n = lib.mf_timing_get(name.encode(), ctypes.byref(tot))
+        if n:
+            out[name] = {"spans_per_step": n / steps, "ms_per_step": tot.value / steps}
+    return out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "xfmr_probe.json"))
+    ap.add_argument("--ratings", type=int, default=25_000_000)
+    ap.add_argument("--baseline-only", action="store_true")
+    args = ap.parse_args()
+    mf = importlib.import_module("matrix-factorization-torch_amd")
+    if args.baseline_only:                      # another build of the library may not have the new exports
+        have = ctypes.CDLL(str(mf._lib.LIB_PATH))
+        for name in [n for n in mf._lib.SIGNATURES if n.startswith("mf_xfmr_") and not hasattr(have, n)]:
+            del mf._lib.SIGNATURES[name]
+    lib = mf._lib.lib()
+    torch.manual_seed(0)
+    table = hp.synthetic_table(mf, args.ratings)
+    sampler = table.sampler(num_items=hp.ITEMS, batch_size=hp.B, seed=0, device="cuda", history=True)
+    batches = [sampler.batch(i) for i in range(8)]
+    res = {"library": str(mf._lib.LIB_PATH), "shape": {"items": hp.ITEMS, "batch": hp.B, "ratings": int(table.sorted_user.numel())},
+           "cases": []}
+    loss_fn = mf.losses.InfomationNoiseContrastiveEstimationLoss(num_negatives=0)
+    for d, L, inter in SHAPES:
+        for user_tower in (("history",) if args.baseline_only else ("history", "transformer")):
+            cfg = mf.models.ModelConfig(num_items=hp.ITEMS, hidden_size=d, user_tower=user_tower, max_history=L, intermediate_size=inter,
+                                        num_hidden_layers=1, num_attention_heads=4)
+            towers = mf.models.init_towers(cfg, device="cuda")
+            if user_tower == "transformer":
+                opt = mf.optim.tower_optimizer(towers, "adam", 1e-3)
+                opt.sparse.init_state()
+            else:
+                opt = mf.optim.RowAdam(towers.parameters(), lr=1e-3)
+                opt.init_state()
+            k = [0]
+
+            def step():
+                bt = batches[k[0] % len(batches)]
+                k[0] += 1
+                u = towers["user"](bt["user"]["history"])
+                idx = torch.cat([bt["item"]["idx"], bt["neg_item"]["idx"]])
+                loss = loss_fn(u, towers["item"](idx), bt["target"], item_idx=idx, pos_csr=bt["user"]["pos_csr"])
+                loss.backward()
+                opt.step()
+                opt.zero_grad()
+
+            case = {"user_tower": user_tower, "d": d, "L": L, "I": inter, "ms_per_step": median_ms(step), "spans": spans(mf, lib, step)}
+            if user_tower == "transformer":
+                st, en, items = batches[0]["user"]["history"]
+                valid = (items >= 1) & (items < hp.ITEMS)
+                csum = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), valid.cumsum(0)])
+                tokens = float(torch.stack([(csum[en] - csum[st]).clamp(max=L) for _ in (0,)]).sum())
+                flops = 2.0 * tokens * (4 * d * d + 2 * d * inter)
+                case["tokens_batch0"] = tokens
+                for name, mult in (("xfmr_gemm_fwd", 1.0), ("xfmr_gemm_bwd", 2.0)):
+                    if name in case["spans"]:
+                        tf = mult * flops / (case["spans"][name]["ms_per_step"] * 1e-3) / 1e12
+                        case["spans"][name]["achieved_TFLOPs"] = tf
+                        case["spans"][name]["fraction_of_fp32_matrix_peak"] = tf / PEAK_TFLOPS
+            res["cases"].append(case)
+            print(json.dumps(case))
+    out = pathlib.Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(res, indent=2))
+    print(f"wrote {out}")
+
+
+if __name__ == "__main__":
+    main()

@@ -526,7 +526,9 @@ class HistoryTransformerTower(torch.nn.Module):
     ``transformers.BertModel``'s ``state_dict`` names them (no word-embedding table, no pooler dense); those receive ordinary
     ``.grad`` tensors.  **No dropout**: BertConfig defaults to 0.1 on hidden states and attention probabilities and the
     reference does not override it; this tower computes the eval-mode function in training too.  fp32 throughout, LayerNorm
-    eps 1e-12.  HIP kernels ``mf_xfmr_forward`` / ``mf_xfmr_backward`` / ``mf_xfmr_coalesce``; no hipGraph capture."""
+    eps 1e-12.  HIP kernels ``mf_xfmr_forward`` / ``mf_xfmr_backward`` / ``mf_xfmr_coalesce``.  The tower may be
+    applied more than once before a step (each call parks its own table gradient; the optimiser chains the coalesces, the
+    dense gradients accumulate).  No hipGraph capture: ``forward`` raises ``MfHipError`` when the stream is capturing."""
 
     def __init__(self, item_tower: torch.nn.Module, *, num_hidden_layers: int = 1, num_attention_heads: int = 4,
                  intermediate_size: int | None = None, hidden_act: str = "gelu", max_position_embeddings: int = 64,
@@ -596,6 +598,8 @@ class HistoryTransformerTower(torch.nn.Module):
     segments = HistoryPoolingTower.segments
 
     def forward(self, history) -> torch.Tensor:
+        if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():    # (before ``segments``: its host read would fail first)
+            raise _lib.MfHipError("the transformer tower does not support hipGraph capture")
         start, end, items, n_entries = self.segments(history)
         if start.numel() == 0:
             return torch.zeros(0, self.weight.shape[1], device=self.weight.device)

@@ -11,7 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.test_xfmr_tower_cpu import load_fixture, random_state, spec_tower
+from tests.test_xfmr_tower_cpu import HARD_CASES, HARD_ROWS, hard_case, load_fixture, random_state, spec_step, spec_tower, tie_world
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -20,6 +20,8 @@ FACTOR = 8.0
 
 def _check(name: str, got: torch.Tensor, spec32: torch.Tensor, ref64: torch.Tensor) -> float:
     """The rule of the module docstring; returns kernel error / fp32-spec error."""
+    kernel_value_is_finite = bool(torch.isfinite(got).all())
+    assert kernel_value_is_finite, name                                      # (nan <= x is False below; this says so by name)
     ref = ref64.double().cpu()
     scale = max(float(ref.abs().max()), 1e-30) if ref.numel() else 1.0
     e_k = float((got.double().cpu() - ref).abs().max()) / scale if ref.numel() else 0.0
@@ -107,19 +109,7 @@ def test_forward_matches_spec(mf, d, heads, L, mode, layers, act, inter):
         _check(f"u d={d} heads={heads} L={L} {mode} layers={layers} {act} n_i={n_i} n_u={n_u} padded={padded}", got, s32, ref)
 
 
-def _spec_step(w, sd, lists, c, kw, extra, lr, dtype):
-    """(u, table delta of one SGD step, dense gradients) of sum(u . c) [+ sum(v . c2)] through the spec, in ``dtype``."""
-    wl = w.to(dtype).clone().requires_grad_(True)
-    leaf = {k: v.to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
-    u = spec_tower(wl, lists, leaf, **kw)
-    loss = (u * c.to(dtype)).sum()
-    if extra is not None:
-        ids, c2 = extra
-        v = wl[ids]
-        loss = loss + ((F.normalize(v, dim=1, eps=1e-12) if kw["n_i"] else v) * c2.to(dtype)).sum()
-    loss.backward()
-    delta = (wl.detach() - lr * wl.grad) - wl.detach()
-    return u.detach(), delta, {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaf.items()}
+_spec_step = spec_step          # (u, table delta of one SGD step, dense gradients) through the spec: tests/test_xfmr_tower_cpu.py
 
 
 def _kernel_step(mf, w, sd, hist, c, kw, extra, lr):
@@ -379,3 +369,248 @@ def test_refusals(mf):
     towers["user"].encoder_parameters()[0].grad = None
     with pytest.raises(mf._lib.MfHipError, match="on the GPU"):
         towers["user"](torch.zeros(2, 4, dtype=torch.int64))
+
+
+# ------------------------------------------------------------------------------------------- second round ----
+# The tower at its limits: hard worlds (conditions proven on the CPU: test_xfmr_tower_cpu.test_hard_world_conditions), depth
+# 3 and 4, every accepted (hidden, heads) pair, token counts at the engine's boundaries, T = 0, two encodes in one step.
+def _step_against_spec(mf, label, w, sd, lists, c, kw, extra, lr, forms=(False, True), ref=None):
+    """One SGD step of the kernels (each input form) against the spec under the module's rule; returns the worst ratio."""
+    u64, d64, g64 = ref[0] if ref else spec_step(w, sd, lists, c, kw, extra, lr, torch.float64)
+    u32, d32, g32 = ref[1] if ref else spec_step(w, sd, lists, c, kw, extra, lr, torch.float32)
+    worst = 0.0
+    for padded in forms:
+        u, delta, grads = _kernel_step(mf, w, sd, _padded(lists) if padded else _segments(lists), c, kw, extra, lr)
+        print(f"{label} padded={padded}")
+        worst = max(worst, _check("u", u, u32, u64), _check("table step", delta, d32, d64))
+        for k in g64:
+            assert grads[k] is not None, k
+            worst = max(worst, _check(k, grads[k], g32[k], g64[k]))
+    return worst
+
+
+@pytest.mark.parametrize("case", HARD_CASES, ids=lambda case: "-".join(str(x) for x in case))
+def test_hard_world_one_sgd_step(mf, case):
+    """u, the table step and every encoder gradient on a world whose conditions the CPU file asserts; on ``sharp`` every
+    output is finite and every user vector has norm 1 before anything is compared."""
+    world = case[0]
+    w, sd, lists, c, kw = hard_case(*case)
+    assert w.shape[0] == HARD_ROWS
+    lr = 0.5
+    ref = (spec_step(w, sd, lists, c, kw, None, lr, torch.float64), spec_step(w, sd, lists, c, kw, None, lr, torch.float32))
+    if world == "sharp":
+        some = torch.tensor([any(1 <= i < HARD_ROWS for i in lst) for lst in lists])
+        for padded in (False, True):
+            u, delta, grads = _kernel_step(mf, w, sd, _padded(lists) if padded else _segments(lists), c, kw, None, lr)
+            for name, t in [("u", u), ("table step", delta), *grads.items()]:
+                assert bool(torch.isfinite(t).all()), (name, padded)
+            norm = u.double().norm(dim=1).cpu()
+            assert float((norm[some] - 1).abs().max()) <= 1e-5 and float(norm[~some].abs().max()) == 0.0, norm  # noqa: PLR2004
+    worst = _step_against_spec(mf, " ".join(str(x) for x in case), w, sd, lists, c, kw, None, lr, ref=ref)
+    print(f"worst ratio on {world}: {worst:.2f}")
+
+
+# depth 3 and 4; the (hidden, heads) pairs without a backward case above: (32, 1), (32, 2), (64, 2), (64, 4), (128, 2), (128, 8);
+# intermediate sizes 96 and 160 (the GEMM's N tail), 4 h at h = 32 and h = 64, 32 at h = 128
+SHAPE_CASES = [(32, 1, 16, "max", 1, "relu", 128), (32, 2, 32, "mean", 2, "silu", 96), (64, 2, 16, "cls", 1, "gelu_new", 256),
+               (64, 4, 64, "max", 3, "silu", 160), (128, 2, 64, "mean", 1, "gelu", 32), (128, 8, 16, "max", 4, "relu", 128)]
+
+
+@pytest.mark.parametrize(("d", "heads", "L", "mode", "layers", "act", "inter"), SHAPE_CASES)
+def test_backward_depth_and_shapes(mf, d, heads, L, mode, layers, act, inter):
+    rng = np.random.default_rng(d * 5 + heads)
+    rows = 200
+    w, sd = _world(100 + d + heads, rows, d, layers, inter, 64)
+    lists = _lists(rng, rows, [1, 5, 17, 64, 70, 3, 9, 30])
+    g = torch.Generator().manual_seed(d + heads)
+    c = torch.randn(len(lists), d, generator=g, dtype=torch.float64)
+    extra = (torch.randint(0, rows, (40,), generator=g), torch.randn(40, d, generator=g, dtype=torch.float64))
+    kw = {"heads": heads, "act": act, "mode": mode, "n_i": True, "n_u": True, "max_history": L}
+    _step_against_spec(mf, f"d={d} heads={heads} L={L} {mode} layers={layers} {act} I={inter}", w, sd, lists, c, kw, extra, 0.5)
+
+
+def _valid_tokens(lists, rows, L):
+    return sum(min(L, sum(1 <= i < rows for i in lst)) for lst in lists)
+
+
+TOKEN_COUNTS = [1, 15, 16, 17, 63, 64, 65, 127, 129, 4095, 4096, 4097, 8193]
+
+
+@pytest.mark.parametrize("T", TOKEN_COUNTS)
+def test_token_count_boundaries(mf, T):
+    """Exactly T valid tokens (asserted from the lists): 64-token GEMM tiles, 16-token k-steps, the weight gradient's 256
+    slices (their length steps at T = 4096 n; only T = 4095 and 4096 fill the last slice), LayerNorm's 1,024 slices.
+    B = 1 for T <= 64, otherwise full lists plus a remainder, with an empty user appended when B would be a multiple of 8."""
+    rows, d, L = 300, 32, 64
+    rng = np.random.default_rng(T)
+    sizes = [L] * (T // L) + ([T % L] if T % L else [])
+    lists = [rng.integers(1, rows, n).tolist() for n in sizes]
+    if T > L:
+        lists[0] = lists[0][:10] + [0, rows, -2] + lists[0][10:]             # padding inside a list does not count
+        if len(lists) % 8 == 0:
+            lists.append([])
+        assert len(lists) % 8
+    else:
+        assert len(lists) == 1
+    assert _valid_tokens(lists, rows, L) == T
+    w, sd = _world(T, rows, d, 1, 32, 64)
+    g = torch.Generator().manual_seed(T)
+    c = torch.randn(len(lists), d, generator=g, dtype=torch.float64) / len(lists) ** 0.5
+    kw = {"heads": 2, "act": "gelu", "mode": "max" if T % 2 else "mean", "n_i": True, "n_u": True, "max_history": L}
+    _step_against_spec(mf, f"T={T} B={len(lists)}", w, sd, lists, c, kw, None, 0.5, forms=(T <= L,))
+
+
+def test_full_lists_behind_invalid_entries(mf):
+    """Every user keeps exactly L = 64 valid entries that sit behind more than 64 invalid ones: the cut walks back over
+    several 64-entry blocks, some of them without a valid entry."""
+    rows, d, L = 300, 64, 64
+    rng = np.random.default_rng(21)
+    bad = lambda n: rng.choice([0, -1, -7, rows, rows + 9], n).tolist()  # noqa: E731
+    ids = lambda n: rng.integers(1, rows, n).tolist()  # noqa: E731
+    spread = [x for i in ids(L) for x in (i, *bad(2))]                       # 64 valid entries in 192
+    lists = [bad(70) + spread + bad(80), ids(100) + bad(130), ids(L) + bad(65), bad(3) + ids(40) + bad(64) + ids(24) + bad(129),
+             bad(200) + ids(L) + bad(65)]
+    assert _valid_tokens(lists, rows, L) == len(lists) * L
+    assert all(sum(1 <= i < rows for i in lst) >= L and len(lst) - max(k for k, i in enumerate(lst) if 1 <= i < rows) > L for lst in lists)
+    w, sd = _world(21, rows, d, 1, 64, 64)
+    c = torch.randn(len(lists), d, generator=torch.Generator().manual_seed(21), dtype=torch.float64)
+    kw = {"heads": 4, "act": "gelu", "mode": "mean", "n_i": True, "n_u": True, "max_history": L}
+    _step_against_spec(mf, "full lists behind invalid entries", w, sd, lists, c, kw, None, 0.5)
+
+
+def test_one_user_holds_every_token(mf):
+    rows, d, L = 300, 64, 64
+    rng = np.random.default_rng(22)
+    lists = [[] if b != 20 else rng.integers(1, rows, L).tolist() for b in range(37)]  # noqa: PLR2004
+    lists[3], lists[30] = [0, 0], [rows, -1, 0]
+    assert _valid_tokens(lists, rows, L) == L
+    w, sd = _world(22, rows, d, 2, 128, 64)
+    c = torch.randn(len(lists), d, generator=torch.Generator().manual_seed(22), dtype=torch.float64)
+    kw = {"heads": 8, "act": "silu", "mode": "max", "n_i": True, "n_u": True, "max_history": L}
+    _step_against_spec(mf, "one user of 37 holds all 64 tokens", w, sd, lists, c, kw, None, 0.5)
+
+
+@pytest.mark.parametrize("kind", ["sgd", "adam"])
+def test_no_valid_token_in_the_batch(mf, kind):
+    """T = 0 with t_cap > 0 (a cold batch: every id is 0, negative or >= rows): u is exactly 0, every encoder gradient is
+    exactly 0 -- the gradient buffers are uninitialised memory that the kernels must write, so the allocator's free blocks
+    are filled with NaN first -- and the optimiser step leaves the table's rows bit-identical."""
+    rows, d = 50, 32
+    w, sd = _world(3, rows, d, 2, 64, 64)
+    lists = [[0, 0, -1], [rows, rows + 7, 0, -5], [0], []]
+    c = torch.randn(len(lists), d, generator=torch.Generator().manual_seed(3)).to(DEV)
+    for padded, mode in ((False, "max"), (True, "mean")):
+        item, user = _towers(mf, w, sd, heads=4, act="gelu", mode=mode, L=16)
+        opt = mf.optim.tower_optimizer(torch.nn.ModuleDict({"user": user, "item": item}), kind, 0.05)
+        assert isinstance(opt, mf.optim.TowerOptimizer)
+        junk = [torch.full_like(p, float("nan")) for p in user.parameters()] + [torch.full((1 << 20,), float("nan"), device=DEV)]
+        del junk
+        u = user(_padded(lists) if padded else _segments(lists))
+        assert torch.equal(u, torch.zeros(len(lists), d, device=DEV))
+        (u * c).sum().backward()
+        for k, p in user.named_parameters():
+            assert p.grad is not None and torch.equal(p.grad, torch.zeros_like(p)), k
+        before = item.weight.detach().clone()
+        opt.step()
+        torch.cuda.synchronize()
+        assert torch.equal(item.weight.detach(), before)
+        # the step after a cold batch is an ordinary one
+        opt.zero_grad()
+        (user(_segments([[4, 9, 4], [7]])) * c[:2]).sum().backward()
+        opt.step()
+        moved = (item.weight.detach() != before).any(1).nonzero().flatten().tolist()
+        assert moved == [4, 7, 9]
+
+
+def _two_encode_spec(w, sd, la, lb, ca, cb, ids, c3, kw, dtype):
+    wl = w.to(dtype).clone().requires_grad_(True)
+    leaf = {k: v.to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
+    loss = (spec_tower(wl, la, leaf, **kw) * ca.to(dtype)).sum() + (spec_tower(wl, lb, leaf, **kw) * cb.to(dtype)).sum()
+    loss = loss + (F.normalize(wl[ids], dim=1, eps=1e-12) * c3.to(dtype)).sum()
+    loss.backward()
+    return wl.grad, {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaf.items()}
+
+
+@pytest.mark.parametrize("kind", ["sgd", "adam"])
+def test_two_encodes_in_one_step(mf, kind):
+    """One tower applied to two history batches (different B; segments and padded) and the item tower on ids that overlap
+    both, one backward, one step: two TransformerHistoryGrad entries on the table, the second coalesce taking the first
+    one's -1-padded list as its extra rows; the encoder's gradients are the sums over both encodes.  The table gradient
+    is read from the SGD step (lr = 1) or from RowAdam's first moment ((1 - beta1) g after one step); twice, bit for bit."""
+    rows, d, L = 120, 64, 16
+    rng = np.random.default_rng(31)
+    w, sd = _world(31, rows, d, 2, 96, 64)
+    la = _lists(rng, rows, [1, 5, 17, 20, 3, 9])
+    lb = _lists(rng, rows, [16, 2, 40])
+    g = torch.Generator().manual_seed(31)
+    ca, cb = (torch.randn(len(x), d, generator=g, dtype=torch.float64) for x in (la, lb))
+    seen = [[i for i in lst if 1 <= i < rows] for lst in (la[2], lb[0])]
+    ids = torch.cat([torch.tensor(seen[0][:6] + seen[1][-6:]), torch.randint(1, rows, (20,), generator=g)])
+    c3 = torch.randn(ids.numel(), d, generator=g, dtype=torch.float64)
+    kw = {"heads": 4, "act": "gelu", "mode": "mean", "n_i": True, "n_u": True, "max_history": L}
+    dw64, g64 = _two_encode_spec(w, sd, la, lb, ca, cb, ids, c3, kw, torch.float64)
+    dw32, g32 = _two_encode_spec(w, sd, la, lb, ca, cb, ids, c3, kw, torch.float32)
+    runs = []
+    for _ in range(2):
+        item, user = _towers(mf, w, sd, heads=4, act="gelu", mode="mean", L=L)
+        opt = mf.optim.tower_optimizer(torch.nn.ModuleDict({"user": user, "item": item}), kind, 1.0 if kind == "sgd" else 0.01)
+        loss = (user(_segments(la)) * ca.float().to(DEV)).sum() + (user(_padded(lb)) * cb.float().to(DEV)).sum()
+        loss = loss + (item(ids.to(DEV)) * c3.float().to(DEV)).sum()
+        loss.backward()
+        pending = list(item.weight._mf_pending)
+        assert sum(isinstance(x, mf.models.TransformerHistoryGrad) for x in pending) == 2 and len(pending) == 3  # noqa: PLR2004
+        grads = {k: p.grad.detach().clone() for k, p in user.named_parameters()}
+        before = item.weight.detach().clone()
+        opt.step()
+        if kind == "sgd":
+            dw = before - item.weight.detach()
+        else:
+            state = opt.sparse.state[item.weight]
+            dw = state["exp_avg"] / (1.0 - opt.sparse.param_groups[0]["betas"][0])
+            touched = (dw64 != 0).any(1)
+            assert torch.equal((item.weight.detach() != before).any(1).cpu(), touched)
+        runs.append((item.weight.detach().clone(), dw.clone(), grads))
+    print(f"two encodes in one step, {kind}")
+    _check("table gradient", runs[0][1], dw32, dw64)
+    for k in g64:
+        _check(k, runs[0][2][k], g32[k], g64[k])
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+    for k in g64:
+        assert torch.equal(runs[0][2][k], runs[1][2][k]), k
+
+
+def test_capture_is_refused_and_the_stream_stays_usable(mf):
+    rows, d = 60, 32
+    w, sd = _world(41, rows, d, 1, 32, 64)
+    _, user = _towers(mf, w, sd, heads=4, act="gelu", mode="mean", L=16)
+    with torch.no_grad():
+        for hist in (_segments([[3, 4, 5], [9]]), _padded([[3, 4, 5], [9]])):   # (segments: before the entry count's host read)
+            want = user(hist).clone()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with pytest.raises(mf._lib.MfHipError, match="capture"):            # raised before any kernel is launched
+                with torch.cuda.graph(graph):
+                    user(hist)
+            del graph
+            torch.cuda.synchronize()
+            assert not torch.cuda.is_current_stream_capturing()
+            assert torch.equal(user(hist), want)
+
+
+def test_max_pool_ties_go_to_the_first_position(mf):
+    """A history that repeats one item under equal position rows: every channel of the max pool is an n-way tie (the CPU
+    file shows the rows bit-identical in fp64 and fp32).  The first position wins, in the forward's ``arg`` and in where
+    the gradient goes: the step matches the spec (whose max takes the first of equal values), and it is bit-identical to
+    the step with cls pooling, which routes the tied user's gradient through position 0 by construction."""
+    w, sd, lists = tie_world()
+    kw = {"heads": 4, "act": "gelu", "mode": "max", "n_i": True, "n_u": True, "max_history": 16}
+    c = torch.randn(len(lists), w.shape[1], generator=torch.Generator().manual_seed(8), dtype=torch.float64)
+    _step_against_spec(mf, "max-pool ties", w, sd, lists, c, kw, None, 0.5)
+    # the same step with cls pooling routes the gradient through position 0 alone: with ties, max must agree with it for the tied user
+    c1 = c.clone()
+    c1[1] = 0
+    u_max, d_max, g_max = _kernel_step(mf, w, sd, _segments(lists), c1, kw, None, 0.5)
+    u_cls, d_cls, g_cls = _kernel_step(mf, w, sd, _segments(lists), c1, {**kw, "mode": "cls"}, None, 0.5)
+    assert torch.equal(u_max[0], u_cls[0]) and torch.equal(d_max, d_cls)
+    for k in g_max:
+        assert torch.equal(g_max[k], g_cls[k]), k

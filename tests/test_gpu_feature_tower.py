@@ -75,11 +75,8 @@ def _dense_grad(w, parts):
     return wt.grad
 
 
-@pytest.mark.parametrize("combiner", COMBINERS)
-@pytest.mark.parametrize("shared", [False, True])
-def test_backward_one_sgd_step(mf, combiner, shared):
+def _one_sgd_step(mf, combiner, shared, R, d):
     rng = np.random.default_rng(11)
-    R, d = 400, 64
     lists, weights = _lists(rng, R, [1, 9, 33, 0, 130, 6, 2], True)
     lists2, _ = _lists(rng, R, [4, 4, 20, 1], False)
     for normalize in (True, False):
@@ -105,6 +102,20 @@ def test_backward_one_sgd_step(mf, combiner, shared):
         seen = {t for p in parts for x in p[0] for t in x if 1 <= t < R}
         others = torch.tensor(sorted(set(range(R)) - seen))
         assert torch.equal(item.weight.detach().cpu()[others], before.cpu()[others])   # bit-identical
+
+
+@pytest.mark.parametrize("combiner", COMBINERS)
+@pytest.mark.parametrize("shared", [False, True])
+def test_backward_one_sgd_step(mf, combiner, shared):
+    _one_sgd_step(mf, combiner, shared, 400, 64)
+
+
+@pytest.mark.parametrize(("R", "d", "combiner"), [(200, 32, "sum"), (200, 256, "mean"), (70000, 32, "sqrtn"), (70000, 256, "sum"),
+                                                  (1 << 20, 32, "mean"), (1 << 20, 256, "sqrtn")])
+def test_backward_one_sgd_step_one_and_three_pass_tables(mf, R, d, combiner):
+    """The same step (both towers on one table) on tables whose coalesce sorts in one and in three radix passes (400
+    buckets: two), up to the documented maximum of 2^20 buckets, at d = 32 and d = 256."""
+    _one_sgd_step(mf, combiner, True, R, d)
 
 
 def _catalog(rng, n_ent, R, hot_frac=0.4):

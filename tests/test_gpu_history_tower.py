@@ -107,11 +107,8 @@ def _dense_grad(w, lists, mode, n_i, n_u, c, extra=None):
     return wt.grad
 
 
-@pytest.mark.parametrize("mode", ["mean", "max"])
-@pytest.mark.parametrize("with_items", [False, True])
-def test_backward_one_sgd_step(mf, mode, with_items):
+def _one_sgd_step(mf, mode, with_items, n_rows, d):
     rng = np.random.default_rng(11)
-    n_rows, d = 400, 64
     lists = _lists(rng, n_rows, [1, 9, 33, 130, 300, 6])
     for n_i, n_u in ((True, True), (False, False), (True, False)):
         item, tower = _tower(mf, n_rows, d, mode, n_i, n_u, seed=5)
@@ -121,7 +118,7 @@ def test_backward_one_sgd_step(mf, mode, with_items):
         loss = (u * c.to(DEV)).sum()
         extra = None
         if with_items:
-            ids = torch.tensor(rng.integers(0, 250, 200), device=DEV)     # overlaps the lists' ids; includes row 0
+            ids = torch.tensor(rng.integers(0, min(250, n_rows), 200), device=DEV)     # overlaps the lists' ids; includes row 0
             c2 = torch.randn(200, d)
             loss = loss + (item(ids) * c2.to(DEV)).sum()
             extra = (ids, c2)
@@ -136,6 +133,21 @@ def test_backward_one_sgd_step(mf, mode, with_items):
         ids_seen = {i for x in lists for i in x if 1 <= i < n_rows} | (set(extra[0].tolist()) if extra else set())
         others = torch.tensor(sorted(set(range(n_rows)) - ids_seen))
         assert torch.equal(item.weight.detach().cpu()[others], before.cpu()[others])        # bit-identical
+
+
+@pytest.mark.parametrize("mode", ["mean", "max"])
+@pytest.mark.parametrize("with_items", [False, True])
+def test_backward_one_sgd_step(mf, mode, with_items):
+    _one_sgd_step(mf, mode, with_items, 400, 64)
+
+
+@pytest.mark.parametrize("mode", ["mean", "max"])
+@pytest.mark.parametrize("d", [32, 256])
+@pytest.mark.parametrize("n_rows", [200, 70000])
+def test_backward_one_sgd_step_one_and_three_pass_tables(mf, mode, d, n_rows):
+    """The same step on tables whose coalesce sorts in one and in three radix passes (400 rows: two), at the widths the
+    run sums lay out differently (d = 32: eight rows per wave, d = 256: one)."""
+    _one_sgd_step(mf, mode, True, n_rows, d)
 
 
 def _zipf_windows(rng, n_rows, batch, mean_len):

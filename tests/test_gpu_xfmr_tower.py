@@ -129,11 +129,8 @@ BACKWARD_CASES = [(32, 4, 16, "mean", 1, "gelu", 32), (64, 8, 7, "max", 2, "relu
                   (64, 1, 64, "mean", 2, "gelu_new", 64), (128, 16, 1, "max", 1, "gelu", 512)]
 
 
-@pytest.mark.parametrize("with_items", [False, True])
-@pytest.mark.parametrize(("d", "heads", "L", "mode", "layers", "act", "inter"), BACKWARD_CASES)
-def test_backward_one_sgd_step(mf, d, heads, L, mode, layers, act, inter, with_items):
+def _one_sgd_step(mf, d, heads, L, mode, layers, act, inter, with_items, rows):
     rng = np.random.default_rng(d * 3 + L)
-    rows = 200
     w, sd = _world(d + L, rows, d, layers, inter, 64)
     lists = _lists(rng, rows, [1, 5, 17, 64, 70, 3, 9, 30])
     g = torch.Generator().manual_seed(d)
@@ -151,6 +148,19 @@ def test_backward_one_sgd_step(mf, d, heads, L, mode, layers, act, inter, with_i
         for k in g64:
             assert grads[k] is not None, k
             _check(k, grads[k], g32[k], g64[k])
+
+
+@pytest.mark.parametrize("with_items", [False, True])
+@pytest.mark.parametrize(("d", "heads", "L", "mode", "layers", "act", "inter"), BACKWARD_CASES)
+def test_backward_one_sgd_step(mf, d, heads, L, mode, layers, act, inter, with_items):
+    _one_sgd_step(mf, d, heads, L, mode, layers, act, inter, with_items, 200)
+
+
+@pytest.mark.parametrize(("d", "heads", "L", "mode", "layers", "act", "inter"), [BACKWARD_CASES[0], BACKWARD_CASES[2], BACKWARD_CASES[4]])
+def test_backward_one_sgd_step_three_pass_table(mf, d, heads, L, mode, layers, act, inter):
+    """The same step on a 70,000-row table: the coalesce sorts in three radix passes (200 rows: one), at the tower's
+    narrowest and widest hidden size (32 and 128: it has no d = 256)."""
+    _one_sgd_step(mf, d, heads, L, mode, layers, act, inter, True, 70000)
 
 
 def test_fixture_outputs_and_gradients(mf):

@@ -48,14 +48,14 @@ __device__ __forceinline__ void bag_span(const BagSrc& s, int64_t b, int64_t& lo
     lo = 0;
     len = 0;
     if (e < 0 || e >= s.n_seg) return;
-    lo = min(max(s.start[e], (int64_t)0), s.n_tokens);
-    const int64_t hi = min(max(s.end[e], lo), s.n_tokens);
+    int64_t hi;
+    list_clamp(s.start[e], s.end[e], s.n_tokens, lo, hi);
     len = min(hi - lo, s.max_len);
 }
 
 // weight of the entry at position pos (0 for padding tokens)
 __device__ __forceinline__ float bag_weight(const BagSrc& s, int64_t pos, long long tok) {
-    if (tok < 1 || tok >= s.R) return 0.f;
+    if (!list_valid(tok, s.R)) return 0.f;
     return s.weights ? s.weights[pos] : 1.f;
 }
 
@@ -64,20 +64,15 @@ __device__ __forceinline__ float bag_scale(int combiner, float wsum, float w2sum
     return combiner == 0 ? 1.f : (combiner == 1 ? 1.f / wsum : 1.f / sqrtf(w2sum));
 }
 
-// p = scale * s, then the tower's normalisation (the arithmetic of pool_finish_kernel); every lane of the wave calls this
+// p = scale * s, then the tower's normalisation; every lane of the wave calls this
 template <int D>
 __device__ __forceinline__ void bag_finish(f32x4 acc, float wsum, float w2sum, int combiner, int normalize, bool valid, int64_t b,
                                            int c, float* __restrict__ out_u, float* __restrict__ out_inv, float* __restrict__ out_scale) {
-    constexpr int LPR = D / 4;
     const float scale = bag_scale(combiner, wsum, w2sum);
     f32x4 p = acc * scale;
     if (scale == 0.f) p = f32x4{0.f, 0.f, 0.f, 0.f};
-    float inv = 1.f;
-    if (normalize) {
-        const float ss = mf_group_sum(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3], LPR);
-        inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-        p = p * inv;
-    }
+    float inv;
+    p = row_normalize<D>(p, normalize, inv);
     if (valid) {
         reinterpret_cast<f32x4*>(out_u + b * D)[c] = p;
         if (c == 0) {
@@ -160,17 +155,9 @@ __global__ __launch_bounds__(256) void bag_chunk_kernel(const float* __restrict_
             }
         }
         // groups in a fixed butterfly, the lower group's value first: every lane ends with the same sums
-#pragma unroll
-        for (int s = LPR; s < 64; s <<= 1) {
-            f32x4 o;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) o[t] = __shfl_xor(acc[t], s, 64);
-            const float ow = __shfl_xor(wsum, s, 64), ow2 = __shfl_xor(w2sum, s, 64);
-            const bool low = (lane & s) == 0;
-            acc = low ? acc + o : o + acc;
-            wsum = low ? wsum + ow : ow + wsum;
-            w2sum = low ? w2sum + ow2 : ow2 + w2sum;
-        }
+        acc = group_butterfly_sum<D>(acc);
+        wsum = group_butterfly_sum<D>(wsum);
+        w2sum = group_butterfly_sum<D>(w2sum);
         if (g == 0) {
             reinterpret_cast<f32x4*>(psum + k * D)[c] = acc;
             if (c == 0) {
@@ -257,27 +244,17 @@ extern "C" int mf_bag_forward(const float* table, int64_t n_rows, int d, const i
 // One workgroup: lo of every bag and the exclusive prefix of the lengths (the entry numbering); ent_off[B] = the entry count.
 __global__ __launch_bounds__(BAG_PLAN_THREADS) void bag_plan_kernel(BagSrc src, int64_t B, int64_t* __restrict__ lo_out,
                                                                    int64_t* __restrict__ ent_off) {
-    __shared__ int64_t wsum[BAG_PLAN_THREADS / 64];
-    const int lane = mf_lane(), wave = threadIdx.x >> 6;
     int64_t run = 0;
     for (int64_t b0 = 0; b0 < B; b0 += BAG_PLAN_THREADS) {
         const int64_t b = b0 + threadIdx.x;
-        int64_t lo = 0, len = 0;
-        if (b < B) bag_span(src, b, lo, len);
-        const int64_t inc = wave_incl_scan(len);
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int64_t before = 0, all = 0;
-        for (int w = 0; w < BAG_PLAN_THREADS / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
+        int64_t lo = 0, v[1] = {0}, tot[1];
+        if (b < B) bag_span(src, b, lo, v[0]);
+        block_excl_scan<BAG_PLAN_THREADS>(v, tot);
         if (b < B) {
             lo_out[b] = lo;
-            ent_off[b] = run + before + inc - len;
+            ent_off[b] = run + v[0];
         }
-        run += all;
-        __syncthreads();
+        run += tot[0];
     }
     if (threadIdx.x == 0) ent_off[B] = run;
 }
@@ -323,15 +300,13 @@ extern "C" int mf_bag_backward(int64_t n_rows, int d, const int64_t* idx, int64_
                                int64_t n_seg, const int64_t* tokens, int64_t n_tokens, const float* weights, int64_t max_len,
                                const float* scale, const float* grad_p, const int64_t* extra_ids, const float* extra_grad, int64_t n_extra,
                                int64_t capacity, int64_t* out_ids, float* out_grad, void* ws, size_t ws_bytes, mf_stream_t stream) {
-    if (!scale || !grad_p || !out_ids || !out_grad || !ws || n_extra < 0 || (n_extra > 0 && (!extra_ids || !extra_grad)))
-        return mf_set_error(MF_EINVAL, "mf_bag_backward: bad argument");
+    if (!scale || !grad_p || !out_ids || !out_grad) return mf_set_error(MF_EINVAL, "mf_bag_backward: bad argument");
     if (int rc = bag_check("mf_bag_backward", n_rows, d, B, seg_start, seg_end, n_seg, tokens, n_tokens, max_len)) return rc;
-    const int64_t n_entries = B * max_len, n_cap = n_extra + n_entries;
-    if (n_cap >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_bag_backward: %lld entries >= 2^31", (long long)n_cap);
-    if (capacity != (n_cap < n_rows ? n_cap : n_rows))
-        return mf_set_error(MF_EINVAL, "mf_bag_backward: capacity must be min(n_rows, n_extra + B * max_len)");
-    if (ws_bytes < mf_bag_backward_ws_bytes(n_extra, B, max_len, d)) return mf_set_error(MF_ENOSPC, "mf_bag_backward: workspace too small");
-    if (n_cap == 0) return MF_OK;
+    const int64_t n_entries = B * max_len;
+    if (int rc = coalesce_check("mf_bag_backward", "feature-table", n_rows, n_extra, extra_ids, extra_grad, n_entries, capacity, ws, ws_bytes,
+                                mf_bag_backward_ws_bytes(n_extra, B, max_len, d)))
+        return rc;
+    if (n_extra + n_entries == 0) return MF_OK;
     const BagBwdWs w = bag_bwd_ws(ws, n_extra, B, max_len, d);
     const BagSrc bags{idx, seg_start, seg_end, n_seg, tokens, n_tokens, weights, max_len, n_rows};
     const CoalesceSrc src{n_rows, extra_ids, extra_grad, n_extra, w.lo, w.ent_off, B, n_entries};

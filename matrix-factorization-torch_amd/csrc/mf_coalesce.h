@@ -1,5 +1,7 @@
-// mf_coalesce.h -- the pooled towers' backward (mf_pool.hip: history tower, mf_bag.hip: feature-bag towers): every
-// (entry, gradient row) a step parks on one table, coalesced into ONE list of (id, summed row) for the sparse updates.
+// mf_coalesce.h -- the list towers' backward (mf_pool.hip: history tower, mf_bag.hip: feature-bag towers, mf_xfmr.hip:
+// transformer tower): every (entry, gradient row) a step parks on one table, coalesced into ONE list of (id, summed row)
+// for the sparse updates.  What the towers share beyond this engine -- id validity, the list clamp and cut, the owner
+// search, the block scan, stride_grid -- is in mf_lists.h, included here.
 //
 // Entries are numbered q = 0 .. n: the explicit (ids, grad) rows first (valid ids [0, n_rows)), then pooled entry h = q -
 // n_extra, whose owner b is the last with ent_off[b] <= h and whose list position is lo[b] + h - ent_off[b].  The entry
@@ -21,36 +23,10 @@
 //                                                                    lane c's four floats of entry h's gradient row (only
 //                                                                    called for entries with a valid key).
 #pragma once
+#include "mf_lists.h"
 #include "mf_update.h"
 
 static constexpr int COALESCE_MAX_ROWS = 1 << 20;   // table rows the sort covers (keys <= 2^20: three 8-bit digits)
-
-// grid-stride kernels: enough waves to fill the chip, no more than the work
-static inline int stride_grid(int64_t work_waves) {
-    const int64_t blocks = (work_waves + 3) / 4;
-    return (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-}
-
-// last b in [0, B] with off[b] <= k  (off non-decreasing, off[0] = 0 <= k)
-__device__ __forceinline__ int64_t pool_owner(const int64_t* __restrict__ off, int64_t B, int64_t k) {
-    int64_t l = 0, r = B;
-    while (r - l > 1) {
-        const int64_t m = (l + r) >> 1;
-        if (off[m] <= k) l = m;
-        else r = m;
-    }
-    return l;
-}
-
-__device__ __forceinline__ int64_t wave_incl_scan(int64_t x) {
-    const int lane = mf_lane();
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int64_t y = __shfl_up(x, s, 64);
-        if (lane >= s) x += y;
-    }
-    return x;
-}
 
 struct CoalesceSrc {                 // what one call coalesces
     int64_t n_rows;                  // (first: see coalesce_segsum_kernel)
@@ -71,6 +47,12 @@ struct CoalesceWs {
 };
 // carves the workspace of a call with n_extra + n_entries entries of width d from `a`
 CoalesceWs coalesce_ws(MfArena& a, int64_t n_extra, int64_t n_entries, int d);
+// its size: what stands behind the towers' *_backward_ws_bytes / *_coalesce_ws_bytes exports
+size_t coalesce_ws_bytes(int64_t n_extra, int64_t n_entries, int d);
+// The entry checks every backward shares, with the codes and texts they always had: the explicit rows, the table's size
+// (`rows`: how `who` calls the table's rows), the entry count, capacity = min(n_rows, n_extra + n_entries), the workspace.
+int coalesce_check(const char* who, const char* rows, int64_t n_rows, int64_t n_extra, const int64_t* extra_ids, const float* extra_grad,
+                   int64_t n_entries, int64_t capacity, const void* ws, size_t ws_bytes, size_t need_bytes);
 // the radix sort of the keys left by coalesce_keys_kernel, the run heads and the -1 fill of out_ids; returns the sorted
 // keys and values
 void coalesce_sort(const CoalesceWs& w, int64_t n_rows, int64_t capacity, int64_t* out_ids, hipStream_t s,
@@ -89,7 +71,7 @@ __global__ __launch_bounds__(256) void coalesce_keys_kernel(CoalesceSrc src, E e
             if (id >= 0 && id < src.n_rows) key = (uint32_t)id;
         } else {
             const int64_t h = q - src.n_extra;
-            const int64_t b = pool_owner(src.ent_off, src.B, h);
+            const int64_t b = list_owner(src.ent_off, src.B, h);
             key = ent.key(b, src.lo[b] + (h - src.ent_off[b]));
             w.euser[h] = (int32_t)b;
         }

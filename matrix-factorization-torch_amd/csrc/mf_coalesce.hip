@@ -1,5 +1,5 @@
-// mf_coalesce.hip -- the parts of the pooled towers' coalesce (mf_coalesce.h) that do not depend on the tower: the LSD
-// radix sort over the device-side entry count, the run heads and their output slots, and the -1 fill.
+// mf_coalesce.hip -- the parts of the list towers' coalesce (mf_coalesce.h) that do not depend on the tower: the entry
+// checks, the LSD radix sort over the device-side entry count, the run heads and their output slots, and the -1 fill.
 #include "mf_coalesce.h"
 
 static constexpr int RADIX_TILE = 4096;          // sorted positions per workgroup (16 rounds of 256)
@@ -49,12 +49,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void coalesce_scan_kernel(int32_t* __
             v[t] = q0 + t < n ? x[q0 + t] : 0;
             sum += v[t];
         }
-        int inc = sum;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int y = __shfl_up(inc, s, 64);
-            if (lane >= s) inc += y;
-        }
+        const int inc = wave_incl_scan(sum);
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
         int before = 0, all = 0;
@@ -160,6 +155,24 @@ CoalesceWs coalesce_ws(MfArena& a, int64_t n_extra, int64_t n_entries, int d) {
     w.head_pos = a.take<int32_t>((size_t)n_cap);
     w.partial = a.take<float>((size_t)n_cap * d);
     return w;
+}
+
+size_t coalesce_ws_bytes(int64_t n_extra, int64_t n_entries, int d) {
+    MfArena a(nullptr);
+    coalesce_ws(a, n_extra > 0 ? n_extra : 0, n_entries > 0 ? n_entries : 0, d);
+    return a.used();
+}
+
+int coalesce_check(const char* who, const char* rows, int64_t n_rows, int64_t n_extra, const int64_t* extra_ids, const float* extra_grad,
+                   int64_t n_entries, int64_t capacity, const void* ws, size_t ws_bytes, size_t need_bytes) {
+    if (!ws || n_rows <= 0 || n_entries < 0 || n_extra < 0 || (n_extra > 0 && (!extra_ids || !extra_grad)))
+        return mf_set_error(MF_EINVAL, "%s: bad argument", who);
+    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "%s: %lld %s rows > %d", who, (long long)n_rows, rows, COALESCE_MAX_ROWS);
+    const int64_t n = n_extra + n_entries;
+    if (n >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "%s: %lld entries >= 2^31", who, (long long)n);
+    if (capacity != (n < n_rows ? n : n_rows)) return mf_set_error(MF_EINVAL, "%s: capacity must be min(n_rows, entries)", who);
+    if (ws_bytes < need_bytes) return mf_set_error(MF_ENOSPC, "%s: workspace too small", who);
+    return MF_OK;
 }
 
 void coalesce_sort(const CoalesceWs& w, int64_t n_rows, int64_t capacity, int64_t* out_ids, hipStream_t s,

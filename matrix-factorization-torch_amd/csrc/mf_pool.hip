@@ -7,7 +7,7 @@
 //
 // Lists.  User b's list is items[lo_b, hi_b), lo_b = clamp(start[b]), hi_b = clamp(end[b]) (a CSR, the rolling windows
 // of InteractionTable or a padded [B, L] matrix all have this form).  Ids outside [1, n_rows) are padding.  max_history = L
-// moves lo_b up to the first of the last L valid entries (pool_cut_kernel).
+// moves lo_b up to the first of the last L valid entries (list_cut_kernel, mf_lists.h).
 //
 // Forward, deterministic and without atomics: the lists are cut into chunks of POOL_CHUNK entries (a 30,000-entry list is
 // 469 chunks on as many waves); each wave sums (or maxes) its chunk in a fixed order; chunks are combined in chunk order,
@@ -23,62 +23,9 @@
 static constexpr int POOL_CHUNK = 64;            // entries per chunk (one wave)
 static constexpr int POOL_SUPER = 32;            // chunks per first-level combine
 
-__device__ __forceinline__ bool pool_valid(long long id, long long n_rows) { return id >= 1 && id < n_rows; }
-
-// ------------------------------------------------------------------------------------------- max_history ----
-// One wave per user: walk back from hi 64 entries at a time until the L-th valid entry.
-__global__ __launch_bounds__(256) void pool_cut_kernel(const int64_t* __restrict__ seg_start, const int64_t* __restrict__ seg_end,
-                                                       const int64_t* __restrict__ items, int64_t n_items, int64_t B, int64_t n_rows,
-                                                       int max_history, int64_t* __restrict__ lo_out) {
-    const int lane = mf_lane();
-    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const int64_t lo = min(max(seg_start[b], (int64_t)0), n_items);
-    const int64_t hi = min(max(seg_end[b], lo), n_items);
-    int64_t cut = lo;
-    int need = max_history;
-    for (int64_t top = hi; top > lo; top -= 64) {
-        const int64_t pos = top - 1 - lane;                  // lane 0 = the most recent entry of this block
-        const bool ok = pos >= lo && pool_valid(items[pos >= lo ? pos : lo], n_rows);
-        unsigned long long m = __ballot(ok);
-        const int c = __popcll(m);
-        if (c >= need) {
-            for (int i = 1; i < need; ++i) m &= m - 1;       // the need-th valid entry from the end
-            cut = top - 1 - __builtin_ctzll(m);
-            break;
-        }
-        need -= c;
-    }
-    if (lane == 0) lo_out[b] = cut;
-}
-
 // --------------------------------------------------------------------------------------------------- plan ----
 // One workgroup: lo / hi of every user, and the exclusive prefixes of its chunks, first-level groups and entries.
 static constexpr int PLAN_THREADS = 256;
-// block-wide exclusive scan of three int64 per thread (PLAN_THREADS threads); returns the block totals in tot[3]
-__device__ __forceinline__ void block_scan3(int64_t v[3], int64_t tot[3]) {
-    __shared__ int64_t wsum[PLAN_THREADS / 64][3];
-    const int lane = mf_lane(), wave = threadIdx.x >> 6;
-    int64_t inc[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        inc[q] = wave_incl_scan(v[q]);
-        if (lane == 63) wsum[wave][q] = inc[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        int64_t before = 0, all = 0;
-        for (int w = 0; w < PLAN_THREADS / 64; ++w) {
-            if (w < wave) before += wsum[w][q];
-            all += wsum[w][q];
-        }
-        v[q] = before + inc[q] - v[q];
-        tot[q] = all;
-    }
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(PLAN_THREADS) void pool_plan_kernel(const int64_t* __restrict__ seg_start, const int64_t* __restrict__ seg_end,
                                                          const int64_t* __restrict__ cut, int64_t n_items, int64_t B,
                                                          int64_t* __restrict__ lo_out, int64_t* __restrict__ ent_off,
@@ -88,8 +35,8 @@ __global__ __launch_bounds__(PLAN_THREADS) void pool_plan_kernel(const int64_t* 
         const int64_t b = b0 + threadIdx.x;
         int64_t v[3] = {0, 0, 0};
         if (b < B) {
-            const int64_t lo0 = min(max(seg_start[b], (int64_t)0), n_items);
-            const int64_t hi = min(max(seg_end[b], lo0), n_items);
+            int64_t lo0, hi;
+            list_clamp(seg_start[b], seg_end[b], n_items, lo0, hi);
             const int64_t lo = cut ? min(max(cut[b], lo0), hi) : lo0;
             lo_out[b] = lo;
             const int64_t len = hi - lo, nch = (len + POOL_CHUNK - 1) / POOL_CHUNK;
@@ -98,7 +45,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void pool_plan_kernel(const int64_t* 
             v[2] = (nch + POOL_SUPER - 1) / POOL_SUPER;
         }
         int64_t tot[3];
-        block_scan3(v, tot);
+        block_excl_scan<PLAN_THREADS>(v, tot);
         if (b < B) {
             ent_off[b] = run[0] + v[0];
             chunk_off[b] = run[1] + v[1];
@@ -153,7 +100,7 @@ __global__ __launch_bounds__(256) void pool_chunk_kernel(const float* __restrict
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
     const int64_t total = min(chunk_off[B], cap_chunks);
     for (int64_t k = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); k < total; k += nwaves) {
-        const int64_t b = pool_owner(chunk_off, B, k);
+        const int64_t b = list_owner(chunk_off, B, k);
         const int64_t j0 = (k - chunk_off[b]) * POOL_CHUNK;            // offset of the chunk in the user's list
         const int64_t len = ent_off[b + 1] - ent_off[b];
         const int64_t base = lo[b];
@@ -166,7 +113,7 @@ __global__ __launch_bounds__(256) void pool_chunk_kernel(const float* __restrict
             for (int t = 0; t < U; ++t) {
                 const int64_t j = j0 + (int64_t)(u0 + t) * RPW + g;
                 id[t] = j < len ? items[base + j] : 0;
-                ok[t] = pool_valid(id[t], n_rows);
+                ok[t] = list_valid(id[t], n_rows);
             }
             f32x4 x[U];
 #pragma unroll
@@ -185,24 +132,22 @@ __global__ __launch_bounds__(256) void pool_chunk_kernel(const float* __restrict
             }
         }
         // groups in a fixed butterfly: group 0 ends up with all of them (a later group's ties lose: its offsets are larger)
+        if (MAX) {
 #pragma unroll
-        for (int s = LPR; s < 64; s <<= 1) {
-            f32x4 o;
-            int oa[4];
+            for (int s = LPR; s < 64; s <<= 1) {
+                f32x4 o;
+                int oa[4];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                o[t] = __shfl_xor(acc.v[t], s, 64);
-                oa[t] = __shfl_xor(acc.a[t], s, 64);
-            }
-            const int on = __shfl_xor(acc.n, s, 64);
-            if (MAX) {
+                for (int t = 0; t < 4; ++t) {
+                    o[t] = __shfl_xor(acc.v[t], s, 64);
+                    oa[t] = __shfl_xor(acc.a[t], s, 64);
+                }
+                const int on = __shfl_xor(acc.n, s, 64);
                 acc.add(o, oa, on);
-            } else {                                                    // the lower group's value first: the same sum in both
-                const bool low = (lane & s) == 0;
-                f32x4 lo4 = low ? acc.v : o, hi4 = low ? o : acc.v;
-                acc.v = lo4 + hi4;
-                acc.n += on;
             }
+        } else {
+            acc.v = group_butterfly_sum<D>(acc.v);
+            acc.n = group_butterfly_sum<D>(acc.n);
         }
         if (g == 0) {
             reinterpret_cast<f32x4*>(psum + k * D)[c] = acc.v;
@@ -223,7 +168,7 @@ __global__ __launch_bounds__(256) void pool_super_kernel(const int64_t* __restri
     const int64_t ngroups = (int64_t)gridDim.x * (blockDim.x >> 6) * RPW;
     const int64_t total = min(super_off[B], cap_supers);
     for (int64_t s = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + lane / LPR; s < total; s += ngroups) {
-        const int64_t b = pool_owner(super_off, B, s);
+        const int64_t b = list_owner(super_off, B, s);
         const int64_t k0 = chunk_off[b] + (s - super_off[b]) * POOL_SUPER;
         const int64_t k1 = min(min(k0 + POOL_SUPER, chunk_off[b + 1]), cap_chunks);
         PoolAcc<D, MAX> acc;
@@ -270,12 +215,8 @@ __global__ __launch_bounds__(256) void pool_finish_kernel(const int64_t* __restr
     }
     f32x4 p = {0.f, 0.f, 0.f, 0.f};
     if (acc.n > 0) p = MAX ? acc.v : acc.v * (1.f / (float)acc.n);
-    float inv = 1.f;
-    if (norm_user) {
-        const float ss = mf_group_sum(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3], LPR);
-        inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-        p = p * inv;
-    }
+    float inv;
+    p = row_normalize<D>(p, norm_user, inv);
     if (valid) {
         reinterpret_cast<f32x4*>(out_u + b * D)[c] = p;
         if (MAX) reinterpret_cast<int4*>(out_arg + b * D)[c] = acc.n > 0 ? int4{acc.a[0], acc.a[1], acc.a[2], acc.a[3]} : int4{-1, -1, -1, -1};
@@ -329,7 +270,7 @@ extern "C" int mf_pool_forward(const float* table, int64_t n_rows, int d, const 
     PoolWs w = pool_ws(ws, B, n_entries, d, mode);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (max_history > 0)
-        pool_cut_kernel<<<dim3((unsigned)((B + 3) / 4)), 256, 0, s>>>(seg_start, seg_end, items, n_items, B, n_rows, max_history, w.cut);
+        list_cut_kernel<false><<<dim3((unsigned)((B + 3) / 4)), 256, 0, s>>>(seg_start, seg_end, items, n_items, B, n_rows, max_history, w.cut, nullptr);
     pool_plan_kernel<<<dim3(1), PLAN_THREADS, 0, s>>>(seg_start, seg_end, max_history > 0 ? w.cut : nullptr, n_items, B, out_lo, out_off,
                                               w.chunk_off, w.super_off);
     const int gc = stride_grid(w.cap_chunks);
@@ -371,7 +312,7 @@ struct PoolEntries {
     int mode;
     __device__ __forceinline__ uint32_t key(int64_t, int64_t pos) const {
         const long long id = items[pos];
-        return pool_valid(id, n_rows) ? (uint32_t)id : (uint32_t)n_rows;
+        return list_valid(id, n_rows) ? (uint32_t)id : (uint32_t)n_rows;
     }
     template <int D>
     __device__ __forceinline__ f32x4 grad(int64_t b, int64_t h, int c) const {
@@ -384,25 +325,20 @@ struct PoolEntries {
 };
 
 extern "C" size_t mf_pool_backward_ws_bytes(int64_t n_extra, int64_t n_entries, int d) {
-    MfArena a(nullptr);
-    coalesce_ws(a, n_extra > 0 ? n_extra : 0, n_entries > 0 ? n_entries : 0, d);
-    return a.used();
+    return coalesce_ws_bytes(n_extra, n_entries, d);
 }
 
 extern "C" int mf_pool_backward(int64_t n_rows, int d, int mode, const int64_t* items, int64_t B, const int64_t* lo, const int64_t* ent_off,
                                 const int32_t* count, const int32_t* arg, const float* grad_p, int64_t n_entries, const int64_t* extra_ids,
                                 const float* extra_grad, int64_t n_extra, int64_t capacity, int64_t* out_ids, float* out_grad, void* ws,
                                 size_t ws_bytes, mf_stream_t stream) {
-    if (!items || !lo || !ent_off || !count || !grad_p || !out_ids || !out_grad || !ws || B <= 0 || n_rows <= 0 || n_entries < 0 ||
-        n_extra < 0 || (n_extra > 0 && (!extra_ids || !extra_grad)) || (mode != 0 && mode != 1) || (mode == 1 && !arg))
+    if (!items || !lo || !ent_off || !count || !grad_p || !out_ids || !out_grad || B <= 0 || (mode != 0 && mode != 1) || (mode == 1 && !arg))
         return mf_set_error(MF_EINVAL, "mf_pool_backward: bad argument");
-    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_pool_backward: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
-    const int64_t n = n_extra + n_entries;
-    if (n >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_pool_backward: %lld entries >= 2^31", (long long)n);
-    if (capacity != (n < n_rows ? n : n_rows)) return mf_set_error(MF_EINVAL, "mf_pool_backward: capacity must be min(n_rows, entries)");
     if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_pool_backward: embedding width %d not in {32,64,128,256}", d);
-    if (ws_bytes < mf_pool_backward_ws_bytes(n_extra, n_entries, d)) return mf_set_error(MF_ENOSPC, "mf_pool_backward: workspace too small");
-    if (n == 0) return MF_OK;
+    if (int rc = coalesce_check("mf_pool_backward", "table", n_rows, n_extra, extra_ids, extra_grad, n_entries, capacity, ws, ws_bytes,
+                                coalesce_ws_bytes(n_extra, n_entries, d)))
+        return rc;
+    if (n_extra + n_entries == 0) return MF_OK;
     MfArena a(ws);
     const CoalesceWs w = coalesce_ws(a, n_extra, n_entries, d);
     const CoalesceSrc src{n_rows, extra_ids, extra_grad, n_extra, lo, ent_off, B, n_entries};

@@ -8,7 +8,7 @@
 // tok_off[b] .. tok_off[b + 1], oldest kept entry first (position 0).  Spec: tests/test_xfmr_tower_cpu.py (the eval-mode
 // function: no dropout).
 //
-//   plan      xfmr_cut (last L valid entries, n_b), xfmr_scan (tok_off, T on the device), xfmr_pack (token -> item id, user)
+//   plan      list_cut (last L valid entries, n_b), xfmr_scan (tok_off, T on the device), xfmr_pack (token -> item id, user)
 //   embed     z0 = (x + tok[0]) + pos[t], x0 = LN(z0)                                   (gather + LayerNorm, one launch)
 //   layer     q, k, v = X W^T + b (three GEMMs); ctx = attention per (user, head), one wave each, softmax over the n_b valid
 //             keys only; z1 = ctx Wo^T + bo + X; y1 = LN(z1); a = y1 Wi^T + bi, f = act(a) (one GEMM, two outputs);
@@ -37,59 +37,17 @@ static constexpr int XFMR_PER_LAYER = 16;        // Wq bq Wk bk Wv bv Wo bo g1 b
 static constexpr float XFMR_LN_EPS = 1e-12f;
 static_assert(XFMR_SLICES % 64 == 0 && XFMR_LN_SLICES % 64 == 0 && XFMR_POS_SLICES % 64 == 0, "xfmr_reduce_kernel adds 64 slices at a time");
 
-__device__ __forceinline__ bool xfmr_valid(long long id, long long n_rows) { return id >= 1 && id < n_rows; }
-
 // ================================================================================================ plan ====
-// One wave per user: walk back from hi, 64 entries at a time, until the L-th valid entry; n_b = min(valid entries, L).
-__global__ __launch_bounds__(256) void xfmr_cut_kernel(const int64_t* __restrict__ seg_start, const int64_t* __restrict__ seg_end,
-                                                       const int64_t* __restrict__ items, int64_t n_items, int64_t B, int64_t n_rows,
-                                                       int L, int64_t* __restrict__ cut_out, int32_t* __restrict__ nb_out) {
-    const int lane = mf_lane();
-    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const int64_t lo = min(max(seg_start[b], (int64_t)0), n_items);
-    const int64_t hi = min(max(seg_end[b], lo), n_items);
-    int64_t cut = lo;
-    int need = L;
-    for (int64_t top = hi; top > lo; top -= 64) {
-        const int64_t pos = top - 1 - lane;                  // lane 0 = the most recent entry of this block
-        const bool ok = pos >= lo && xfmr_valid(items[pos >= lo ? pos : lo], n_rows);
-        unsigned long long m = __ballot(ok);
-        const int c = __popcll(m);
-        if (c >= need) {
-            for (int i = 1; i < need; ++i) m &= m - 1;       // the need-th valid entry from the end
-            cut = top - 1 - __builtin_ctzll(m);
-            need = 0;
-            break;
-        }
-        need -= c;
-    }
-    if (lane == 0) {
-        cut_out[b] = cut;
-        nb_out[b] = L - need;
-    }
-}
-
 // One workgroup: tok_off = exclusive prefix of n_b (clamped to the host bound t_cap), tok_off[B] = T, also left in *T_dev.
 __global__ __launch_bounds__(256) void xfmr_scan_kernel(const int32_t* __restrict__ nb, int64_t B, int64_t t_cap,
                                                         int64_t* __restrict__ tok_off, int32_t* __restrict__ T_dev) {
-    __shared__ int64_t wsum[4];
-    const int lane = mf_lane(), wave = threadIdx.x >> 6;
     int64_t run = 0;
     for (int64_t b0 = 0; b0 < B; b0 += 256) {
         const int64_t b = b0 + threadIdx.x;
-        const int64_t v = b < B ? nb[b] : 0;
-        const int64_t inc = wave_incl_scan(v);
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int64_t before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
-        if (b < B) tok_off[b] = min(run + before + inc - v, t_cap);
-        run += all;
-        __syncthreads();
+        int64_t v[1] = {b < B ? nb[b] : 0}, tot[1];
+        block_excl_scan<256>(v, tot);
+        if (b < B) tok_off[b] = min(run + v[0], t_cap);
+        run += tot[0];
     }
     if (threadIdx.x == 0) {
         tok_off[B] = min(run, t_cap);
@@ -105,14 +63,14 @@ __global__ __launch_bounds__(256) void xfmr_pack_kernel(const int64_t* __restric
     const int lane = mf_lane();
     const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
-    const int64_t lo = cut[b];
-    const int64_t hi = min(max(seg_end[b], lo), n_items);
+    int64_t lo, hi;
+    list_clamp(cut[b], seg_end[b], n_items, lo, hi);            // (cut[b] lies in the list: lo = cut[b])
     const int64_t t0 = tok_off[b], t1 = tok_off[b + 1];
     int64_t done = 0;
     for (int64_t base = lo; base < hi && t0 + done < t1; base += 64) {
         const int64_t pos = base + lane;
         const long long id = pos < hi ? items[pos] : 0;
-        const bool ok = xfmr_valid(id, n_rows);
+        const bool ok = list_valid(id, n_rows);
         const unsigned long long m = __ballot(ok);
         const int64_t t = t0 + done + __popcll(m & ((1ull << lane) - 1ull));
         if (ok && t < t1) {
@@ -828,7 +786,7 @@ extern "C" int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const 
     const int I = intermediate, dh = h / heads;
     const unsigned gu = (unsigned)((B + 3) / 4), gt = (unsigned)((t_cap + 7) / 8);
     MF_TIMED("xfmr_forward", s, {
-        xfmr_cut_kernel<<<gu, 256, 0, s>>>(seg_start, seg_end, items, n_items, B, n_rows, max_history, st.cut, st.nb);
+        list_cut_kernel<true><<<gu, 256, 0, s>>>(seg_start, seg_end, items, n_items, B, n_rows, max_history, st.cut, st.nb);
         xfmr_scan_kernel<<<1, 256, 0, s>>>(st.nb, B, t_cap, st.tok_off, st.T_dev);
         xfmr_pack_kernel<<<gu, 256, 0, s>>>(seg_end, st.cut, items, n_items, B, n_rows, st.tok_off, st.tok_item, st.tok_user);
         if (t_cap > 0) {
@@ -970,7 +928,7 @@ struct XfmrEntries {
     const float* grad_x;
     __device__ __forceinline__ uint32_t key(int64_t, int64_t pos) const {
         const long long id = tok_item[pos];
-        return xfmr_valid(id, n_rows) ? (uint32_t)id : (uint32_t)n_rows;
+        return list_valid(id, n_rows) ? (uint32_t)id : (uint32_t)n_rows;
     }
     template <int D>
     __device__ __forceinline__ f32x4 grad(int64_t, int64_t t, int c) const {
@@ -979,24 +937,19 @@ struct XfmrEntries {
 };
 
 extern "C" size_t mf_xfmr_coalesce_ws_bytes(int64_t n_extra, int64_t t_cap, int d) {
-    MfArena a(nullptr);
-    coalesce_ws(a, n_extra > 0 ? n_extra : 0, t_cap > 0 ? t_cap : 0, d);
-    return a.used();
+    return coalesce_ws_bytes(n_extra, t_cap, d);
 }
 
 extern "C" int mf_xfmr_coalesce(int64_t n_rows, int d, int64_t B, int64_t t_cap, int layers, int intermediate, const void* stash,
                                 const float* grad_x, const int64_t* extra_ids, const float* extra_grad, int64_t n_extra,
                                 int64_t capacity, int64_t* out_ids, float* out_grad, void* ws, size_t ws_bytes, mf_stream_t stream) {
-    if (!stash || !grad_x || !out_ids || !out_grad || !ws || B <= 0 || n_rows <= 0 || t_cap < 0 || n_extra < 0 ||
-        (n_extra > 0 && (!extra_ids || !extra_grad)) || layers < 1 || layers > XFMR_MAX_LAYERS)
+    if (!stash || !grad_x || !out_ids || !out_grad || B <= 0 || layers < 1 || layers > XFMR_MAX_LAYERS)
         return mf_set_error(MF_EINVAL, "mf_xfmr_coalesce: bad argument");
     if (d != 32 && d != 64 && d != 128) return mf_set_error(MF_EINVAL, "mf_xfmr_coalesce: width %d not in {32,64,128}", d);
-    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_xfmr_coalesce: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
-    const int64_t n = n_extra + t_cap;
-    if (n >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_xfmr_coalesce: %lld entries >= 2^31", (long long)n);
-    if (capacity != (n < n_rows ? n : n_rows)) return mf_set_error(MF_EINVAL, "mf_xfmr_coalesce: capacity must be min(n_rows, entries)");
-    if (ws_bytes < mf_xfmr_coalesce_ws_bytes(n_extra, t_cap, d)) return mf_set_error(MF_ENOSPC, "mf_xfmr_coalesce: workspace too small");
-    if (n == 0) return MF_OK;
+    if (int rc = coalesce_check("mf_xfmr_coalesce", "table", n_rows, n_extra, extra_ids, extra_grad, t_cap, capacity, ws, ws_bytes,
+                                coalesce_ws_bytes(n_extra, t_cap, d)))
+        return rc;
+    if (n_extra + t_cap == 0) return MF_OK;
     const XfmrStash st = xfmr_stash(const_cast<void*>(stash), B, t_cap, d, layers, intermediate);
     MfArena a(ws);
     const CoalesceWs w = coalesce_ws(a, n_extra, t_cap, d);

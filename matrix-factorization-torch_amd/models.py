@@ -160,11 +160,23 @@ def _park(table: torch.Tensor, item) -> None:
     pending.append(item)
 
 
+def _check_table(table: torch.Tensor, what: str) -> None:
+    if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
+        raise _lib.MfHipError(f"{what} table must be a contiguous fp32 tensor on the GPU")
+
+
+def _normalize_backward(u: torch.Tensor, inv: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """The gradient w.r.t. p of u = p * inv, inv = 1 / max(|p|, 1e-12), from the gradient ``g`` w.r.t. u (rows of ``[n, d]``)."""
+    n, d = u.shape
+    gp = torch.empty_like(g)
+    _lib.check(_lib.lib().mf_normalize_backward(u.data_ptr(), inv.data_ptr(), g.data_ptr(), n, d, gp.data_ptr(), _lib.stream_ptr()))
+    return gp
+
+
 class _GatherRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table: torch.Tensor, idx: torch.Tensor, normalize: bool):
-        if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
-            raise _lib.MfHipError("embedding table must be a contiguous fp32 tensor on the GPU")
+        _check_table(table, "embedding")
         ids = _lib.dev_i64(idx, "idx").reshape(-1)
         n, d = ids.numel(), table.shape[1]
         out = torch.empty(n, d, dtype=torch.float32, device=table.device)
@@ -215,8 +227,7 @@ class EmbeddingTower(torch.nn.Module):
 class _GatherHashed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table: torch.Tensor, idx: torch.Tensor, num_hashes: int, seed: int, normalize: bool):
-        if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
-            raise _lib.MfHipError("embedding table must be a contiguous fp32 tensor on the GPU")
+        _check_table(table, "embedding")
         ids = _lib.dev_i64(idx, "idx").reshape(-1)
         n, d = ids.numel(), table.shape[1]
         out = torch.empty(n, d, dtype=torch.float32, device=table.device)
@@ -236,10 +247,7 @@ class _GatherHashed(torch.autograd.Function):
         lib = _lib.lib()
         g = grad_out.reshape(-1, d).to(torch.float32).contiguous()
         if normalize:      # gradient w.r.t. the summed rows: the same for each of the id's bucket rows
-            graw = torch.empty_like(g)
-            _lib.check(lib.mf_normalize_backward(out.data_ptr(), inv.data_ptr(), g.data_ptr(), n, d, graw.data_ptr(),
-                                                 _lib.stream_ptr()))
-            g = graw
+            g = _normalize_backward(out, inv, g)
         buckets = torch.empty(n * num_hashes, dtype=torch.int64, device=table.device)
         _lib.check(lib.mf_hash_buckets(ids.data_ptr(), n, num_hashes, seed, table.shape[0], buckets.data_ptr(),
                                        _lib.stream_ptr()))
@@ -287,8 +295,21 @@ class PooledGrad:
     table in the same step.  ``normalize``: whether the table's rows were normalised when read."""
 
     normalize: bool
+    n_bound: int           # host bound of this source's entries
 
     def coalesce(self, table: torch.Tensor, ids: torch.Tensor | None, grad: torch.Tensor | None):
+        """``(unique ids [capacity] (then -1), summed rows [capacity, d])`` of this source plus ``(ids, grad)``; capacity =
+        min(rows, entries)."""
+        n_extra = 0 if ids is None else ids.numel()
+        cap = min(table.shape[0], n_extra + self.n_bound)
+        out_ids = torch.empty(cap, dtype=torch.int64, device=table.device)
+        out_grad = torch.empty(cap, table.shape[1], dtype=torch.float32, device=table.device)
+        if cap:
+            _lib.check(self._launch(_lib.lib(), table, ids, grad, n_extra, cap, out_ids, out_grad))
+        return out_ids, out_grad
+
+    def _launch(self, lib, table, ids, grad, n_extra: int, cap: int, out_ids, out_grad) -> int:
+        """Ask for the workspace and make the tower's C call; returns its code."""
         raise NotImplementedError
 
 
@@ -300,33 +321,47 @@ class PooledHistoryGrad(PooledGrad):
     def __init__(self, ctx, grad_p: torch.Tensor) -> None:
         self.mode, self.normalize = ctx.mode, ctx.norm_item
         self.items, self.lo, self.off, self.count = ctx.items, ctx.lo, ctx.off, ctx.count
-        self.arg, self.n_entries, self.grad_p = ctx.arg, ctx.n_entries, grad_p
+        self.arg, self.n_bound, self.grad_p = ctx.arg, ctx.n_entries, grad_p
 
-    def coalesce(self, table: torch.Tensor, ids: torch.Tensor | None, grad: torch.Tensor | None):
-        """``(unique ids [capacity] (then -1), summed rows [capacity, d])`` of this entry plus ``(ids, grad)``."""
-        lib = _lib.lib()
+    def _launch(self, lib, table, ids, grad, n_extra, cap, out_ids, out_grad):
         rows, d = table.shape
-        b = self.lo.numel()
-        n_extra = 0 if ids is None else ids.numel()
-        cap = min(rows, n_extra + self.n_entries)
-        out_ids = torch.empty(cap, dtype=torch.int64, device=table.device)
-        out_grad = torch.empty(cap, d, dtype=torch.float32, device=table.device)
-        if cap == 0:
-            return out_ids, out_grad
-        ws = _lib.workspace(lib.mf_pool_backward_ws_bytes(n_extra, self.n_entries, d), table.device)
-        _lib.check(lib.mf_pool_backward(rows, d, self.mode, self.items.data_ptr(), b, self.lo.data_ptr(), self.off.data_ptr(),
-                                        self.count.data_ptr(), _lib.ptr(self.arg), self.grad_p.data_ptr(), self.n_entries,
-                                        _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(), out_grad.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-        return out_ids, out_grad
+        ws = _lib.workspace(lib.mf_pool_backward_ws_bytes(n_extra, self.n_bound, d), table.device)
+        return lib.mf_pool_backward(rows, d, self.mode, self.items.data_ptr(), self.lo.numel(), self.lo.data_ptr(), self.off.data_ptr(),
+                                    self.count.data_ptr(), _lib.ptr(self.arg), self.grad_p.data_ptr(), self.n_bound,
+                                    _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(), out_grad.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+
+
+def _history_segments(dev, history):
+    """``(start, end, items, n_entries)`` of either input form (one host read of the entry count for segments)."""
+    if isinstance(history, (tuple, list)):
+        start, end, items = (_lib.dev_i64(t, name) for t, name in zip(history, ("start", "end", "items")))
+        start, end = start.reshape(-1), end.reshape(-1)
+        if start.numel() != end.numel():
+            msg = f"start and end must have the same length: {start.numel()} != {end.numel()}"
+            raise ValueError(msg)
+        items = items.reshape(-1)
+        n_entries = int((end - start).clamp_min(0).sum()) if start.numel() else 0
+    else:
+        pad = _lib.dev_i64(history, "history")
+        if pad.dim() != 2:  # noqa: PLR2004
+            msg = f"a padded history must be [B, L]: {tuple(pad.shape) = }"
+            raise ValueError(msg)
+        b, length = pad.shape
+        start = torch.arange(b, device=dev, dtype=torch.int64) * length
+        end = start + length
+        items = pad.reshape(-1)
+        n_entries = b * length
+    if items.numel() == 0:
+        items = torch.zeros(1, dtype=torch.int64, device=dev)
+    return start, end, items, n_entries
 
 
 class _PoolRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table: torch.Tensor, start: torch.Tensor, end: torch.Tensor, items: torch.Tensor, n_entries: int,
                 mode: int, max_history: int, norm_item: bool, norm_user: bool):
-        if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
-            raise _lib.MfHipError("embedding table must be a contiguous fp32 tensor on the GPU")
+        _check_table(table, "embedding")
         lib = _lib.lib()
         rows, d = table.shape
         b = start.numel()
@@ -351,13 +386,9 @@ class _PoolRows(torch.autograd.Function):
     def backward(ctx, grad_u):
         table = ctx.table
         u, inv = ctx.saved_tensors
-        b, d = u.shape
         g = grad_u.to(torch.float32).contiguous()
         if ctx.norm_user:
-            gp = torch.empty_like(g)
-            _lib.check(_lib.lib().mf_normalize_backward(u.data_ptr(), inv.data_ptr(), g.data_ptr(), b, d, gp.data_ptr(),
-                                                        _lib.stream_ptr()))
-            g = gp
+            g = _normalize_backward(u, inv, g)
         _park(table, PooledHistoryGrad(ctx, g))
         return (None,) * 9
 
@@ -395,28 +426,7 @@ class HistoryPoolingTower(torch.nn.Module):
 
     def segments(self, history):
         """``(start, end, items, n_entries)`` of either input form (one host read of the entry count for segments)."""
-        dev = self.weight.device
-        if isinstance(history, (tuple, list)):
-            start, end, items = (_lib.dev_i64(t, name) for t, name in zip(history, ("start", "end", "items")))
-            start, end = start.reshape(-1), end.reshape(-1)
-            if start.numel() != end.numel():
-                msg = f"start and end must have the same length: {start.numel()} != {end.numel()}"
-                raise ValueError(msg)
-            items = items.reshape(-1)
-            n_entries = int((end - start).clamp_min(0).sum()) if start.numel() else 0
-        else:
-            pad = _lib.dev_i64(history, "history")
-            if pad.dim() != 2:  # noqa: PLR2004
-                msg = f"a padded history must be [B, L]: {tuple(pad.shape) = }"
-                raise ValueError(msg)
-            b, length = pad.shape
-            start = torch.arange(b, device=dev, dtype=torch.int64) * length
-            end = start + length
-            items = pad.reshape(-1)
-            n_entries = b * length
-        if items.numel() == 0:
-            items = torch.zeros(1, dtype=torch.int64, device=dev)
-        return start, end, items, n_entries
+        return _history_segments(self.weight.device, history)
 
     def forward(self, history) -> torch.Tensor:
         start, end, items, n_entries = self.segments(history)
@@ -435,22 +445,14 @@ class TransformerHistoryGrad(PooledGrad):
 
     def __init__(self, ctx, grad_x: torch.Tensor) -> None:
         self.normalize, self.stash, self.grad_x = ctx.norm_item, ctx.stash, grad_x
-        self.b, self.t_cap, self.layers, self.inter = ctx.b, ctx.t_cap, ctx.shape[0], ctx.shape[2]
+        self.b, self.n_bound, self.layers, self.inter = ctx.b, ctx.t_cap, ctx.shape[0], ctx.shape[2]
 
-    def coalesce(self, table: torch.Tensor, ids: torch.Tensor | None, grad: torch.Tensor | None):
-        lib = _lib.lib()
+    def _launch(self, lib, table, ids, grad, n_extra, cap, out_ids, out_grad):
         rows, d = table.shape
-        n_extra = 0 if ids is None else ids.numel()
-        cap = min(rows, n_extra + self.t_cap)
-        out_ids = torch.empty(cap, dtype=torch.int64, device=table.device)
-        out_grad = torch.empty(cap, d, dtype=torch.float32, device=table.device)
-        if cap == 0:
-            return out_ids, out_grad
-        ws = _lib.workspace(lib.mf_xfmr_coalesce_ws_bytes(n_extra, self.t_cap, d), table.device)
-        _lib.check(lib.mf_xfmr_coalesce(rows, d, self.b, self.t_cap, self.layers, self.inter, self.stash.data_ptr(),
-                                        self.grad_x.data_ptr(), _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(),
-                                        out_grad.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-        return out_ids, out_grad
+        ws = _lib.workspace(lib.mf_xfmr_coalesce_ws_bytes(n_extra, self.n_bound, d), table.device)
+        return lib.mf_xfmr_coalesce(rows, d, self.b, self.n_bound, self.layers, self.inter, self.stash.data_ptr(),
+                                    self.grad_x.data_ptr(), _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(),
+                                    out_grad.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
 
 
 def _pointer_array(tensors):
@@ -464,8 +466,7 @@ class _EncodeHistory(torch.autograd.Function):
     def forward(ctx, table: torch.Tensor, start: torch.Tensor, end: torch.Tensor, items: torch.Tensor, n_entries: int, cfg: tuple,
                 *params: torch.Tensor):
         layers, heads, inter, act, mode, max_history, norm_item, norm_user = cfg
-        if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
-            raise _lib.MfHipError("embedding table must be a contiguous fp32 tensor on the GPU")
+        _check_table(table, "embedding")
         if torch.cuda.is_current_stream_capturing():
             raise _lib.MfHipError("the transformer tower does not support hipGraph capture")
         for p in params:
@@ -595,7 +596,9 @@ class HistoryTransformerTower(torch.nn.Module):
                 out += [m.weight, m.bias]
         return out
 
-    segments = HistoryPoolingTower.segments
+    def segments(self, history):
+        """As :meth:`HistoryPoolingTower.segments`."""
+        return _history_segments(self.weight.device, history)
 
     def forward(self, history) -> torch.Tensor:
         if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():    # (before ``segments``: its host read would fail first)
@@ -621,32 +624,24 @@ class FeatureBagGrad(PooledGrad):
 
     def __init__(self, ctx, grad_p: torch.Tensor) -> None:
         self.idx, self.seg, self.max_len, self.scale, self.grad_p = ctx.idx, ctx.seg, ctx.max_len, ctx.scale, grad_p
+        self.n_bound = self.scale.numel() * self.max_len
 
-    def coalesce(self, table: torch.Tensor, ids: torch.Tensor | None, grad: torch.Tensor | None):
-        lib = _lib.lib()
+    def _launch(self, lib, table, ids, grad, n_extra, cap, out_ids, out_grad):
         rows, d = table.shape
         b = self.scale.numel()
         start, end, tokens, weights = self.seg
-        n_extra = 0 if ids is None else ids.numel()
-        cap = min(rows, n_extra + b * self.max_len)
-        out_ids = torch.empty(cap, dtype=torch.int64, device=table.device)
-        out_grad = torch.empty(cap, d, dtype=torch.float32, device=table.device)
-        if cap == 0:
-            return out_ids, out_grad
         ws = _lib.workspace(lib.mf_bag_backward_ws_bytes(n_extra, b, self.max_len, d), table.device)
-        _lib.check(lib.mf_bag_backward(rows, d, _lib.ptr(self.idx), b, start.data_ptr(), end.data_ptr(), start.numel(),
-                                       tokens.data_ptr(), tokens.numel(), _lib.ptr(weights), self.max_len, self.scale.data_ptr(),
-                                       self.grad_p.data_ptr(), _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(),
-                                       out_grad.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-        return out_ids, out_grad
+        return lib.mf_bag_backward(rows, d, _lib.ptr(self.idx), b, start.data_ptr(), end.data_ptr(), start.numel(),
+                                   tokens.data_ptr(), tokens.numel(), _lib.ptr(weights), self.max_len, self.scale.data_ptr(),
+                                   self.grad_p.data_ptr(), _lib.ptr(ids), _lib.ptr(grad), n_extra, cap, out_ids.data_ptr(),
+                                   out_grad.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
 
 
 class _BagRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table: torch.Tensor, idx: torch.Tensor | None, b: int, seg: tuple, max_len: int, combiner: int,
                 normalize: bool):
-        if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous():
-            raise _lib.MfHipError("feature table must be a contiguous fp32 tensor on the GPU")
+        _check_table(table, "feature")
         lib = _lib.lib()
         rows, d = table.shape
         dev = table.device
@@ -666,13 +661,9 @@ class _BagRows(torch.autograd.Function):
     def backward(ctx, grad_u):
         table = ctx.table
         u, inv = ctx.saved_tensors
-        b, d = u.shape
         g = grad_u.to(torch.float32).contiguous()
         if ctx.normalize:
-            gp = torch.empty_like(g)
-            _lib.check(_lib.lib().mf_normalize_backward(u.data_ptr(), inv.data_ptr(), g.data_ptr(), b, d, gp.data_ptr(),
-                                                        _lib.stream_ptr()))
-            g = gp
+            g = _normalize_backward(u, inv, g)
         _park(table, FeatureBagGrad(ctx, g))
         return (None,) * 7
 
@@ -756,11 +747,11 @@ def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
     tower is a :class:`HistoryPoolingTower` over the item table (plain tables only); ``"transformer"``: a
     :class:`HistoryTransformerTower` over it.  ``"features"``: a
     :class:`FeatureBagTower`; with both towers so, one shared bucket table."""
-    if "features" in (config.user_tower, config.item_tower):
-        def table(name):
-            return EmbeddingTower(getattr(config, f"num_{name}s"), config.hidden_size, normalize=config.normalize,
-                                  init_std=config.init_std, device=device)
+    def table(name):
+        return EmbeddingTower(getattr(config, f"num_{name}s"), config.hidden_size, normalize=config.normalize,
+                              init_std=config.init_std, device=device)
 
+    if "features" in (config.user_tower, config.item_tower):
         kw = {"combiner": config.feature_combiner, "normalize": config.normalize}
         item = (FeatureBagTower(config.feature_buckets, config.hidden_size, init_std=config.init_std, device=device, **kw)
                 if config.item_tower == "features" else table("item"))
@@ -772,8 +763,7 @@ def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
             user = FeatureBagTower(config.feature_buckets, config.hidden_size, init_std=config.init_std, device=device, **kw)
         return torch.nn.ModuleDict({"user": user, "item": item})
     if config.user_tower == "transformer":
-        item = EmbeddingTower(config.num_items, config.hidden_size, normalize=config.normalize, init_std=config.init_std,
-                              device=device)
+        item = table("item")
         user = HistoryTransformerTower(item, num_hidden_layers=config.num_hidden_layers,
                                        num_attention_heads=config.num_attention_heads, intermediate_size=config.intermediate_size,
                                        hidden_act=config.hidden_act, max_position_embeddings=config.max_position_embeddings,
@@ -784,8 +774,7 @@ def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
         if config.num_hashes > 0:
             msg = "user_tower='history' pools plain item-table rows; hashed towers (num_hashes > 0) are not supported"
             raise ValueError(msg)
-        item = EmbeddingTower(config.num_items, config.hidden_size, normalize=config.normalize, init_std=config.init_std,
-                              device=device)
+        item = table("item")
         user = HistoryPoolingTower(item, pooling_mode=config.pooling_mode, max_history=config.max_history,
                                    normalize=config.normalize)
         return torch.nn.ModuleDict({"user": user, "item": item})
@@ -798,11 +787,4 @@ def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
                 for salt, (name, rows) in enumerate((("user", config.num_users), ("item", config.num_items)))
             }
         )
-    return torch.nn.ModuleDict(
-        {
-            "user": EmbeddingTower(config.num_users, config.hidden_size, normalize=config.normalize,
-                                   init_std=config.init_std, device=device),
-            "item": EmbeddingTower(config.num_items, config.hidden_size, normalize=config.normalize,
-                                   init_std=config.init_std, device=device),
-        }
-    )
+    return torch.nn.ModuleDict({"user": table("user"), "item": table("item")})

@@ -593,7 +593,7 @@ def test_xfmr_kernels_do_not_spill(mf):
     kr = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(kr)
     res = kr.kernel_resources()
-    mine = {k: v for k, v in res.items() if "xfmr_" in k or "XfmrEntries" in k}
+    mine = {k: v for k, v in res.items() if "xfmr_" in k or "XfmrEntries" in k or "list_cut_kernel" in k}   # (the cut is shared: mf_lists.h)
     assert len(mine) >= 35, sorted(mine)  # noqa: PLR2004
     for k, v in mine.items():
         assert v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0, k

@@ -435,6 +435,28 @@ int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int max_p
                      int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
                      const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
                      void* ws, size_t ws_bytes, mf_stream_t stream);
+/* Training dropout (BertModel's four sites; mf_xfmr_forward / mf_xfmr_backward are the case p_hidden = p_attn = 0 of the same
+ * implementation): p_hidden drops the embeddings after their LayerNorm and the attention-output and FFN-output dense results
+ * before their residual adds, p_attn the attention probabilities.  A probability counts as thr / 65536, thr = round(p * 65536)
+ * (halves up, at most 65535); thr = 0 switches the site off; p outside [0, 1) is MF_EINVAL.  The masks are the counter-based
+ * words of include/mf_numerics.h, keyed by (seed, call, site) and indexed by (user, position, column) or (user, query, head,
+ * key) -- not by the packed token number, so they do not depend on the packing or the input form.  They are generated
+ * inside the kernels: no mask tensor, nothing added to the stash (mf_xfmr_ws_bytes, mf_xfmr_coalesce unchanged); the backward,
+ * called with the forward's (p_hidden, p_attn, seed, call), regenerates the same bits.  Its workspace holds one more [t_cap, h]
+ * buffer than the plain backward's.  Still no float atomics: a step with dropout is bit-reproducible. */
+int mf_xfmr_forward_dropout(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                            const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
+                            int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
+                            float* out_u, float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, double p_hidden,
+                            double p_attn, uint64_t seed, uint64_t call, mf_stream_t stream);
+size_t mf_xfmr_backward_dropout_ws_bytes(int64_t t_cap, int h, int intermediate);
+int mf_xfmr_backward_dropout(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads, int intermediate,
+                             int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
+                             const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
+                             void* ws, size_t ws_bytes, double p_hidden, double p_attn, uint64_t seed, uint64_t call,
+                             mf_stream_t stream);
+/* Host only (no GPU call): out[i] = the mask word idx0 + i of (seed, call, stream), i < n -- what the kernels compute, for tests. */
+int mf_dropout_words(uint64_t seed, uint64_t call, uint64_t stream, uint64_t idx0, int64_t n, uint64_t* out);
 /* grad_x lands on the item table through the coalesce engine of the pooled towers (one entry per token, key = its item id),
  * together with the extra rows parked on the table: outputs as mf_pool_backward; capacity = min(n_rows, n_extra + t_cap). */
 size_t mf_xfmr_coalesce_ws_bytes(int64_t n_extra, int64_t t_cap, int d);

@@ -142,4 +142,29 @@ MF_HD long long mf_hash_bucket(long long id, int j, unsigned long long seed, lon
     return (long long)(mf_splitmix64(z) % (unsigned long long)num_buckets);
 }
 
+/*
+ * Counter-based dropout masks (the transformer user tower; our spec: BertModel draws its masks from torch's generator).
+ * A mask bit is a pure function of (seed, call, stream, element), so the backward regenerates the forward's bits and no
+ * mask is ever stored.  With G the golden gamma and wrapping 64-bit arithmetic:
+ *     key(seed, call, stream) = splitmix64(splitmix64(seed + G (call + 1)) + G (stream + 1))      (on the host)
+ *     word(key, idx)          = splitmix64(key + idx G)                                          (four elements)
+ *     field f = 0..3 of a word = (word >> 16 f) & 0xFFFF;   keep iff field >= thr,   thr = round(p * 65536)
+ *     kept elements are scaled by 1 / (1 - thr / 65536) (fp32 in the kernels)
+ * so the probability that counts is thr / 65536, and thr = 0 switches a site off.  Known answers (tests/test_xfmr_dropout_cpu.py):
+ * key(0, 0, 0) = 0xA706DD2F4D197E6F, word(that, 0) = 0xB49AB477BB8685E2.  Streams and element indices: DESIGN.md.
+ */
+#define MF_GOLDEN_GAMMA 0x9E3779B97F4A7C15ull
+MF_HD unsigned long long mf_dropout_key(unsigned long long seed, unsigned long long call, unsigned long long stream) {
+    return mf_splitmix64(mf_splitmix64(seed + MF_GOLDEN_GAMMA * (call + 1ull)) + MF_GOLDEN_GAMMA * (stream + 1ull));
+}
+MF_HD unsigned long long mf_dropout_word(unsigned long long key, unsigned long long idx) {
+    return mf_splitmix64(key + idx * MF_GOLDEN_GAMMA);
+}
+MF_HD unsigned mf_dropout_field(unsigned long long word, int f) { return (unsigned)(word >> (16 * f)) & 0xFFFFu; }
+/* the multiplier of an element: 0 (dropped) or scale (kept) */
+MF_HD float mf_dropout_mul(unsigned long long word, int f, unsigned thr, float scale) {
+    return mf_dropout_field(word, f) >= thr ? scale : 0.0f;
+}
+MF_HD float mf_dropout_scale(unsigned thr) { return 1.0f / (1.0f - (float)thr / 65536.0f); }
+
 #endif /* MF_NUMERICS_H */

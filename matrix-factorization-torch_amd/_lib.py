@@ -16,6 +16,7 @@ _PKG = pathlib.Path(__file__).resolve().parent
 LIB_PATH = pathlib.Path(os.environ.get("MF_HIP_LIB", _PKG / "lib" / "libmf_hip.so"))   # override: A/B builds
 
 c_i64, c_int, c_f32, c_vp, c_sz = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+c_f64, c_u64 = ctypes.c_double, ctypes.c_uint64
 
 # name -> (restype, argtypes); must list every symbol include/mf_hip.h declares
 SIGNATURES = {
@@ -101,6 +102,12 @@ SIGNATURES = {
     "mf_xfmr_backward_ws_bytes": (c_sz, [c_i64, c_int, c_int]),
     "mf_xfmr_backward": (c_int, [c_int, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mf_xfmr_forward_dropout": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_f64, c_f64, c_u64, c_u64, c_vp]),
+    "mf_xfmr_backward_dropout_ws_bytes": (c_sz, [c_i64, c_int, c_int]),
+    "mf_xfmr_backward_dropout": (c_int, [c_int, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_f64, c_f64, c_u64, c_u64, c_vp]),
+    "mf_dropout_words": (c_int, [c_u64, c_u64, c_u64, c_u64, c_i64, c_vp]),
     "mf_xfmr_coalesce_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_xfmr_coalesce": (c_int, [c_i64, c_int, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
                                  c_sz, c_vp]),

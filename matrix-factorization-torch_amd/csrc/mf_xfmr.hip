@@ -6,7 +6,7 @@
 // Here the rows are the item tower's rows of the user's history; validity comes from the id (ids outside [1, n_rows) are
 // padding) and work is proportional to the valid tokens T = sum_b n_b: tokens are PACKED, user b owns tokens
 // tok_off[b] .. tok_off[b + 1], oldest kept entry first (position 0).  Spec: tests/test_xfmr_tower_cpu.py (the eval-mode
-// function: no dropout).
+// function) and tests/test_xfmr_dropout_cpu.py (training dropout).
 //
 //   plan      list_cut (last L valid entries, n_b), xfmr_scan (tok_off, T on the device), xfmr_pack (token -> item id, user)
 //   embed     z0 = (x + tok[0]) + pos[t], x0 = LN(z0)                                   (gather + LayerNorm, one launch)
@@ -25,6 +25,12 @@
 // each), a, f (I floats each) and the two LayerNorm row statistics; the attention probabilities are recomputed.
 //
 // The gradient into the item table, dL/dx_t = dz0[t], leaves through the coalesce engine of mf_coalesce.h (XfmrEntries).
+//
+// Training dropout (mf_xfmr_forward_dropout / mf_xfmr_backward_dropout): BertModel's four sites -- the embeddings after
+// their LayerNorm, the attention probabilities, the attention-output dense and the FFN-output dense before their residual
+// adds.  The masks are counter-based (include/mf_numerics.h): a function of (seed, call, site, user, position, column),
+// generated where they are applied; nothing is stored and the backward regenerates the same bits.  Every kernel that can
+// drop is a template on that (DROP = false is the code the plain exports always ran), chosen per site on the host.
 #include "mf_coalesce.h"
 
 static constexpr int XFMR_MAX_L = 64;
@@ -36,6 +42,22 @@ static constexpr int XFMR_GLOBALS = 4;           // pos, tok, emb LN gamma, emb 
 static constexpr int XFMR_PER_LAYER = 16;        // Wq bq Wk bk Wv bv Wo bo g1 b1 Wi bi Wo2 bo2 g2 b2
 static constexpr float XFMR_LN_EPS = 1e-12f;
 static_assert(XFMR_SLICES % 64 == 0 && XFMR_LN_SLICES % 64 == 0 && XFMR_POS_SLICES % 64 == 0, "xfmr_reduce_kernel adds 64 slices at a time");
+
+// ============================================================================================= dropout ====
+// One site of one call: the host-made key, the threshold (an element is kept iff its 16-bit field >= thr) and the scale of
+// the kept elements.  Hidden-state sites: element (user b, position t, column c) is field c & 3 of word ((b 64 + t) 32 + c / 4);
+// attention probabilities: (b, query i, head, key j) is field j & 3 of word (((b 64 + i) 16 + head) 16 + j / 4).
+struct XDrop {
+    unsigned long long key;
+    unsigned thr;
+    float scale;
+};
+__device__ __forceinline__ unsigned long long xdrop_hidden_word(const XDrop& d, int64_t b, int t, int col) {
+    return mf_dropout_word(d.key, (unsigned long long)((b * 64 + t) * 32 + (col >> 2)));
+}
+__device__ __forceinline__ unsigned long long xdrop_attn_word(const XDrop& d, int64_t b, int i, int head, int j) {
+    return mf_dropout_word(d.key, (unsigned long long)(((b * 64 + i) * 16 + head) * 16 + (j >> 2)));
+}
 
 // ================================================================================================ plan ====
 // One workgroup: tok_off = exclusive prefix of n_b (clamped to the host bound t_cap), tok_off[B] = T, also left in *T_dev.
@@ -135,14 +157,14 @@ __device__ __forceinline__ XRow<E> xrow_layernorm(const XRow<E>& z, const XRow<E
 
 // ============================================================================================== embed ====
 // token t of user b: x = the item row (normalised iff norm_item, gather_rows_kernel's arithmetic), z0 = (x + tok[0]) + pos[t],
-// x0 = LN(z0).  Eight tokens per workgroup.
-template <int H>
+// x0 = LN(z0) [DROP: times the embeddings mask].  Eight tokens per workgroup.
+template <int H, bool DROP>
 __global__ __launch_bounds__(256) void xfmr_embed_kernel(const float* __restrict__ table, const int64_t* __restrict__ tok_item,
                                                          const int32_t* __restrict__ tok_user, const int64_t* __restrict__ tok_off,
                                                          const int32_t* __restrict__ T_dev, int norm_item, const float* __restrict__ pos,
                                                          const float* __restrict__ tok, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ z0, float* __restrict__ st0,
-                                                         float* __restrict__ x0) {
+                                                         float* __restrict__ x0, XDrop dr) {
     constexpr int E = H / 32;
     const int c = threadIdx.x & 31;
     const int64_t t = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
@@ -164,7 +186,12 @@ __global__ __launch_bounds__(256) void xfmr_embed_kernel(const float* __restrict
 #pragma unroll
     for (int e = 0; e < E; ++e) z.v[e] = (x.v[e] + te.v[e]) + pe.v[e];
     float mean, rstd;
-    const XRow<E> y = xrow_layernorm<E>(z, xrow_load<E>(gamma, c), xrow_load<E>(beta, c), mean, rstd);
+    XRow<E> y = xrow_layernorm<E>(z, xrow_load<E>(gamma, c), xrow_load<E>(beta, c), mean, rstd);
+    if constexpr (DROP) {                                      // (the lane's E <= 4 columns share one word)
+        const unsigned long long wd = xdrop_hidden_word(dr, b, p, c * E);
+#pragma unroll
+        for (int e = 0; e < E; ++e) y.v[e] = y.v[e] * mf_dropout_mul(wd, (c * E + e) & 3, dr.thr, dr.scale);
+    }
     if (valid) {
         xrow_store<E>(z0 + t * H, c, z);
         xrow_store<E>(x0 + t * H, c, y);
@@ -206,11 +233,15 @@ __device__ __forceinline__ int64_t xfmr_slice_len(int64_t T, int S, int round) {
 
 // dz = rstd * (dy gamma - mean(dy gamma) - xhat mean(dy gamma xhat)); slice s of the tokens also leaves its partial of
 // dgamma = sum dy xhat and dbeta = sum dy in part[s][2H] (eight row groups, added in group order).
-template <int H>
+// DROP = XLN_DROP_IN: this LayerNorm's output was dropped (the embeddings): dy is read as mask * dy.  DROP = XLN_DROP_OUT: its
+// input is dropped(dense) + residual: dz goes to the residual path as it is and dzm = mask * dz to the dense's backward.
+enum { XLN_DROP_NONE = 0, XLN_DROP_IN = 1, XLN_DROP_OUT = 2 };
+template <int H, int DROP>
 __global__ __launch_bounds__(256) void xfmr_ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ z,
                                                           const float* __restrict__ st, const int32_t* __restrict__ T_dev,
                                                           const float* __restrict__ gamma, float* __restrict__ dz,
-                                                          float* __restrict__ part) {
+                                                          float* __restrict__ part, const int32_t* __restrict__ tok_user,
+                                                          const int64_t* __restrict__ tok_off, XDrop dr, float* __restrict__ dzm) {
     constexpr int E = H / 32;
     constexpr float invh = 1.f / (float)H;
     __shared__ float sh[8][2 * H];
@@ -226,8 +257,20 @@ __global__ __launch_bounds__(256) void xfmr_ln_bwd_kernel(const float* __restric
         const int64_t t = t0 + g;
         const bool valid = t < end;
         const int64_t tt = valid ? t : beg;
-        const XRow<E> d = xrow_load<E>(dy + tt * H, c), zr = xrow_load<E>(z + tt * H, c);
+        XRow<E> d = xrow_load<E>(dy + tt * H, c);
+        const XRow<E> zr = xrow_load<E>(z + tt * H, c);
         const float mean = st[2 * tt], rstd = st[2 * tt + 1];
+        float mul[E];
+        if constexpr (DROP != XLN_DROP_NONE) {
+            const int64_t b = tok_user[tt];
+            const unsigned long long wd = xdrop_hidden_word(dr, b, (int)(tt - tok_off[b]), c * E);
+#pragma unroll
+            for (int e = 0; e < E; ++e) mul[e] = mf_dropout_mul(wd, (c * E + e) & 3, dr.thr, dr.scale);
+        }
+        if constexpr (DROP == XLN_DROP_IN) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) d.v[e] = d.v[e] * mul[e];
+        }
         XRow<E> xh, gd;
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -247,6 +290,11 @@ __global__ __launch_bounds__(256) void xfmr_ln_bwd_kernel(const float* __restric
                 ab.v[e] += d.v[e];
             }
             xrow_store<E>(dz + t * H, c, o);
+            if constexpr (DROP == XLN_DROP_OUT) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) o.v[e] = o.v[e] * mul[e];
+                xrow_store<E>(dzm + t * H, c, o);
+            }
         }
     }
 #pragma unroll
@@ -366,7 +414,14 @@ __device__ __forceinline__ void xg_stage(float (*tile)[XG_LD], int kc, const f32
     }
 }
 
-__global__ __launch_bounds__(256) void xfmr_gemm_kernel(XGemm g) {
+// DROP (a linear with a residual, dyn = 0): C = (acc + bias) * mask + R, the mask of row m = token (b, t) at column n
+struct XDropRows {
+    XDrop d;
+    const int32_t* tok_user;
+    const int64_t* tok_off;
+};
+template <bool DROP>
+__global__ __launch_bounds__(256) void xfmr_gemm_kernel(XGemm g, XDropRows dr) {
     __shared__ float As[16][XG_LD], Bs[16][XG_LD];
     const int64_t T = *g.T_dev;
     const int64_t M = g.dyn == 0 ? T : g.M;
@@ -415,6 +470,10 @@ __global__ __launch_bounds__(256) void xfmr_gemm_kernel(XGemm g) {
             if (m < M) {
                 const int64_t o = m * g.ldc + n;
                 float v = acc[e] + bias;
+                if constexpr (DROP) {
+                    const int64_t b = dr.tok_user[m];
+                    v = v * mf_dropout_mul(xdrop_hidden_word(dr.d, b, (int)(m - dr.tok_off[b]), (int)n), (int)n & 3, dr.d.thr, dr.d.scale);
+                }
                 if (g.R) v += g.R[o];
                 if (g.epi == XEPI_ACT) g.C2[o] = xfmr_act(v, g.act);
                 else if (g.epi == XEPI_DACT) v *= xfmr_dact(g.P[o], g.act);
@@ -467,9 +526,10 @@ __device__ __forceinline__ float xattn_mix(const float* w, const float (*Ms)[DH 
     return acc;
 }
 
-template <int DH>
+template <int DH, bool DROP>
 __global__ __launch_bounds__(64) void xfmr_attn_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                       const int64_t* __restrict__ tok_off, int h, int heads, float* __restrict__ ctx) {
+                                                       const int64_t* __restrict__ tok_off, int h, int heads, float* __restrict__ ctx,
+                                                       XDrop dr) {
     __shared__ float Ks[XFMR_MAX_L][DH + 1], Vs[XFMR_MAX_L][DH + 1], Ps[XFMR_MAX_L];
     const int64_t b = blockIdx.x / heads;
     const int col0 = (int)(blockIdx.x % heads) * DH;
@@ -482,7 +542,11 @@ __global__ __launch_bounds__(64) void xfmr_attn_kernel(const float* __restrict__
     __syncthreads();
     for (int i = 0; i < n; ++i) {
         const float qv = lane < DH ? q[(t0 + i) * h + col0 + lane] : 0.f;
-        const float p = xattn_prob<DH>(qv, Ks, lane < n ? lane : 0, lane < n);
+        float p = xattn_prob<DH>(qv, Ks, lane < n ? lane : 0, lane < n);
+        if constexpr (DROP) {                                    // lane j's probability of query i: one word per lane per query
+            const unsigned long long wd = xdrop_attn_word(dr, b, i, (int)(blockIdx.x % heads), lane);
+            p = p * mf_dropout_mul(wd, lane & 3, dr.thr, dr.scale);
+        }
         __syncthreads();
         Ps[lane] = p;
         __syncthreads();
@@ -491,12 +555,13 @@ __global__ __launch_bounds__(64) void xfmr_attn_kernel(const float* __restrict__
     }
 }
 
-// backward: the probabilities are recomputed; lane j accumulates dK[j], dV[j] over the queries, dQ[i] is a mix over keys
-template <int DH>
+// backward: the probabilities are recomputed; lane j accumulates dK[j], dV[j] over the queries, dQ[i] is a mix over keys.
+// DROP: the mask is recomputed too (one word per lane per query): dV[j] += (p mask) dc, dp = mask (dc . V[j]).
+template <int DH, bool DROP>
 __global__ __launch_bounds__(64) void xfmr_attn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                            const float* __restrict__ v, const float* __restrict__ dctx,
                                                            const int64_t* __restrict__ tok_off, int h, int heads, float* __restrict__ dq,
-                                                           float* __restrict__ dk, float* __restrict__ dv) {
+                                                           float* __restrict__ dk, float* __restrict__ dv, XDrop dr) {
     __shared__ float Ks[XFMR_MAX_L][DH + 1], Vs[XFMR_MAX_L][DH + 1], Ps[XFMR_MAX_L], Qs[64], Ds[64];
     const int64_t b = blockIdx.x / heads;
     const int col0 = (int)(blockIdx.x % heads) * DH;
@@ -518,6 +583,12 @@ __global__ __launch_bounds__(64) void xfmr_attn_bwd_kernel(const float* __restri
         float dp = 0.f;
 #pragma unroll
         for (int c = 0; c < DH; ++c) dp += xattn_bcast(dc, c) * Vs[row][c];
+        float pm = p;                                        // the probability that met V in the forward
+        if constexpr (DROP) {
+            const float mul = mf_dropout_mul(xdrop_attn_word(dr, b, i, (int)(blockIdx.x % heads), lane), lane & 3, dr.thr, dr.scale);
+            pm = p * mul;
+            dp = dp * mul;
+        }
         const float pd = lane < n ? p * dp : 0.f;
         const float pdsum = mf_wave_sum(pd);                 // (whole wave: not inside the select below)
         const float ds = lane < n ? (p * (dp - pdsum)) * inv_scale : 0.f;
@@ -529,7 +600,7 @@ __global__ __launch_bounds__(64) void xfmr_attn_bwd_kernel(const float* __restri
 #pragma unroll
         for (int c = 0; c < DH; ++c) {
             dK[c] += ds * Qs[c];
-            dV[c] += p * Ds[c];
+            dV[c] += pm * Ds[c];
         }
         const float o = xattn_mix<DH>(Ps, Ks, lane, n);
         if (lane < DH) dq[(t0 + i) * h + col0 + lane] = o;
@@ -716,11 +787,47 @@ extern "C" size_t mf_xfmr_ws_bytes(int64_t B, int64_t t_cap, int h, int layers, 
 static void xfmr_gemm(hipStream_t s, int64_t t_cap, XGemm g) {
     if (g.dyn == 0) {
         const dim3 grid((unsigned)((t_cap + 63) / 64), (unsigned)((g.N + 63) / 64));
-        xfmr_gemm_kernel<<<grid, 256, 0, s>>>(g);
+        xfmr_gemm_kernel<false><<<grid, 256, 0, s>>>(g, XDropRows{});
     } else {
         const dim3 grid((unsigned)((g.M + 63) / 64), (unsigned)((g.N + 63) / 64), XFMR_SLICES);
-        xfmr_gemm_kernel<<<grid, 256, 0, s>>>(g);
+        xfmr_gemm_kernel<false><<<grid, 256, 0, s>>>(g, XDropRows{});
     }
+}
+// a linear whose result is dropped before its residual add (site d; d.thr = 0: the plain kernel)
+static void xfmr_gemm_dropped(hipStream_t s, int64_t t_cap, XGemm g, const XDrop& d, const int32_t* tok_user, const int64_t* tok_off) {
+    if (d.thr == 0) return xfmr_gemm(s, t_cap, g);
+    const dim3 grid((unsigned)((t_cap + 63) / 64), (unsigned)((g.N + 63) / 64));
+    xfmr_gemm_kernel<true><<<grid, 256, 0, s>>>(g, XDropRows{d, tok_user, tok_off});
+}
+
+// The dropout of one call: thresholds of the two probabilities (0 = off) and what the keys are made of.
+struct XfmrDropout {
+    unsigned thr_hidden, thr_attn;
+    unsigned long long seed, call;
+    XDrop site(unsigned thr, int stream) const { return XDrop{mf_dropout_key(seed, call, (unsigned long long)stream), thr, mf_dropout_scale(thr)}; }
+    XDrop attn(int layer) const { return site(thr_attn, 4 * layer + 0); }
+    XDrop attn_out(int layer) const { return site(thr_hidden, 4 * layer + 1); }
+    XDrop ffn_out(int layer) const { return site(thr_hidden, 4 * layer + 2); }
+    XDrop embeddings() const { return site(thr_hidden, 4 * XFMR_MAX_LAYERS); }
+};
+// thr = round(p * 65536) (halves up; at most 65535, so that the scale stays finite); false: p outside [0, 1)
+static bool xfmr_drop_thr(double p, unsigned* thr) {
+    if (!(p >= 0.0 && p < 1.0)) return false;
+    const double t = floor(p * 65536.0 + 0.5);
+    *thr = t > 65535.0 ? 65535u : (unsigned)t;
+    return true;
+}
+static bool xfmr_dropout(double p_hidden, double p_attn, uint64_t seed, uint64_t call, XfmrDropout* d) {
+    d->seed = seed;
+    d->call = call;
+    return xfmr_drop_thr(p_hidden, &d->thr_hidden) && xfmr_drop_thr(p_attn, &d->thr_attn);
+}
+
+extern "C" int mf_dropout_words(uint64_t seed, uint64_t call, uint64_t stream, uint64_t idx0, int64_t n, uint64_t* out) {
+    if (!out || n < 0) return mf_set_error(MF_EINVAL, "mf_dropout_words: bad argument");
+    const unsigned long long key = mf_dropout_key(seed, call, stream);
+    for (int64_t i = 0; i < n; ++i) out[i] = mf_dropout_word(key, idx0 + (uint64_t)i);
+    return MF_OK;
 }
 // Y [T, N] = X [T, K] W[N, K]^T + bias (+ R)
 static XGemm xg_linear(const float* X, int K, const float* W, const float* bias, int N, float* Y, const float* R, const int32_t* T_dev) {
@@ -766,10 +873,11 @@ static void xfmr_dweight(hipStream_t s, const float* dY, int N, const float* X, 
     }
 
 // ============================================================================================= forward ====
-extern "C" int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
-                               const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
-                               int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
-                               float* out_u, float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, mf_stream_t stream) {
+static int xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                        const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
+                        int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
+                        float* out_u, float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, const XfmrDropout& drop,
+                        mf_stream_t stream) {
     if (!table || !seg_start || !seg_end || !items || !params || !out_u || !out_inv || !stash || B <= 0 || n_rows <= 0 ||
         n_items <= 0 || t_cap < 0 || act < 0 || act > 3 || mode < 0 || mode > 2 || (mode == XPOOL_MAX && !out_arg))
         return mf_set_error(MF_EINVAL, "mf_xfmr_forward: bad argument");
@@ -790,8 +898,15 @@ extern "C" int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const 
         xfmr_scan_kernel<<<1, 256, 0, s>>>(st.nb, B, t_cap, st.tok_off, st.T_dev);
         xfmr_pack_kernel<<<gu, 256, 0, s>>>(seg_end, st.cut, items, n_items, B, n_rows, st.tok_off, st.tok_item, st.tok_user);
         if (t_cap > 0) {
-            XFMR_DISPATCH_H(h, xfmr_embed_kernel<H><<<gt, 256, 0, s>>>(table, st.tok_item, st.tok_user, st.tok_off, st.T_dev, norm_item,
-                                                                      params[0], params[1], params[2], params[3], st.z0, st.st0, st.x0));
+            if (drop.thr_hidden) {
+                XFMR_DISPATCH_H(h, xfmr_embed_kernel<H, true><<<gt, 256, 0, s>>>(table, st.tok_item, st.tok_user, st.tok_off, st.T_dev,
+                                                                                norm_item, params[0], params[1], params[2], params[3],
+                                                                                st.z0, st.st0, st.x0, drop.embeddings()));
+            } else {
+                XFMR_DISPATCH_H(h, xfmr_embed_kernel<H, false><<<gt, 256, 0, s>>>(table, st.tok_item, st.tok_user, st.tok_off, st.T_dev,
+                                                                                 norm_item, params[0], params[1], params[2], params[3],
+                                                                                 st.z0, st.st0, st.x0, XDrop{}));
+            }
             const float* x = st.x0;
             for (int l = 0; l < layers; ++l) {
                 const float* const* w = params + XFMR_GLOBALS + XFMR_PER_LAYER * l;
@@ -801,15 +916,24 @@ extern "C" int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const 
                     xfmr_gemm(s, t_cap, xg_linear(x, h, w[2], w[3], h, y.k, nullptr, st.T_dev));
                     xfmr_gemm(s, t_cap, xg_linear(x, h, w[4], w[5], h, y.v, nullptr, st.T_dev));
                 });
-                MF_TIMED("xfmr_attn_fwd", s, XFMR_DISPATCH_DH(dh, xfmr_attn_kernel<DH><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
-                                                                      y.q, y.k, y.v, st.tok_off, h, heads, y.ctx)));
-                MF_TIMED("xfmr_gemm_fwd", s, xfmr_gemm(s, t_cap, xg_linear(y.ctx, h, w[6], w[7], h, y.z1, x, st.T_dev)));
+                MF_TIMED("xfmr_attn_fwd", s, {
+                    if (drop.thr_attn) {
+                        XFMR_DISPATCH_DH(dh, xfmr_attn_kernel<DH, true><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
+                                                 y.q, y.k, y.v, st.tok_off, h, heads, y.ctx, drop.attn(l)));
+                    } else {
+                        XFMR_DISPATCH_DH(dh, xfmr_attn_kernel<DH, false><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
+                                                 y.q, y.k, y.v, st.tok_off, h, heads, y.ctx, XDrop{}));
+                    }
+                });
+                MF_TIMED("xfmr_gemm_fwd", s, xfmr_gemm_dropped(s, t_cap, xg_linear(y.ctx, h, w[6], w[7], h, y.z1, x, st.T_dev),
+                                                               drop.attn_out(l), st.tok_user, st.tok_off));
                 XFMR_DISPATCH_H(h, xfmr_ln_kernel<H><<<gt, 256, 0, s>>>(y.z1, st.T_dev, w[8], w[9], y.y1, y.st1));
                 MF_TIMED("xfmr_gemm_fwd", s, {
                     XGemm g = xg_linear(y.y1, h, w[10], w[11], I, y.a, nullptr, st.T_dev);
                     g.epi = XEPI_ACT; g.act = act; g.C2 = y.f;
                     xfmr_gemm(s, t_cap, g);
-                    xfmr_gemm(s, t_cap, xg_linear(y.f, I, w[12], w[13], h, y.z2, y.y1, st.T_dev));
+                    xfmr_gemm_dropped(s, t_cap, xg_linear(y.f, I, w[12], w[13], h, y.z2, y.y1, st.T_dev), drop.ffn_out(l), st.tok_user,
+                                      st.tok_off);
                 });
                 XFMR_DISPATCH_H(h, xfmr_ln_kernel<H><<<gt, 256, 0, s>>>(y.z2, st.T_dev, w[14], w[15], y.y2, y.st2));
                 x = y.y2;
@@ -822,19 +946,43 @@ extern "C" int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const 
     return mf_check_launch("mf_xfmr_forward");
 }
 
+extern "C" int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                               const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
+                               int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
+                               float* out_u, float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, mf_stream_t stream) {
+    return xfmr_forward(table, n_rows, h, seg_start, seg_end, items, n_items, B, t_cap, max_history, layers, heads, intermediate, act, mode,
+                        norm_item, norm_user, params, out_u, out_inv, out_arg, stash, stash_bytes, XfmrDropout{}, stream);
+}
+extern "C" int mf_xfmr_forward_dropout(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                                       const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers,
+                                       int heads, int intermediate, int act, int mode, int norm_item, int norm_user,
+                                       const float* const* params, float* out_u, float* out_inv, int32_t* out_arg, void* stash,
+                                       size_t stash_bytes, double p_hidden, double p_attn, uint64_t seed, uint64_t call,
+                                       mf_stream_t stream) {
+    XfmrDropout drop;
+    if (!xfmr_dropout(p_hidden, p_attn, seed, call, &drop))
+        return mf_set_error(MF_EINVAL, "mf_xfmr_forward_dropout: dropout probabilities must be in [0, 1): %g, %g", p_hidden, p_attn);
+    return xfmr_forward(table, n_rows, h, seg_start, seg_end, items, n_items, B, t_cap, max_history, layers, heads, intermediate, act, mode,
+                        norm_item, norm_user, params, out_u, out_inv, out_arg, stash, stash_bytes, drop, stream);
+}
+
 // ============================================================================================ backward ====
 struct XfmrBwdWs {
     float *dy, *dz, *dt, *dctx, *dq, *dk, *dv, *di, *part;
+    float* dzm;                 // hidden dropout only: mask * dz, the operand of a dropped dense's backward
     size_t total;
 };
+// the largest set of partials: XFMR_SLICES slices of a weight gradient with its bias gradient -- [I, h] + I, [h, I] + h, and the
+// attention's [h, h] + h, which is the largest one when I < h
 static size_t xfmr_part_floats(int h, int I) {
-    size_t m = (size_t)XFMR_SLICES * ((size_t)I * h + (size_t)(I > h ? I : h));
+    const size_t widest = (size_t)(I > h ? I : h);
+    size_t m = (size_t)XFMR_SLICES * (widest * h + widest);
     const size_t ln = (size_t)XFMR_LN_SLICES * 2 * h, ps = (size_t)XFMR_POS_SLICES * XFMR_MAX_L * h;
     if (ln > m) m = ln;
     if (ps > m) m = ps;
     return m;
 }
-static XfmrBwdWs xfmr_bwd_ws(void* p, int64_t t_cap, int h, int I) {
+static XfmrBwdWs xfmr_bwd_ws(void* p, int64_t t_cap, int h, int I, bool dropout = false) {
     MfArena a(p);
     XfmrBwdWs w;
     const size_t T = (size_t)(t_cap > 0 ? t_cap : 1);
@@ -842,36 +990,47 @@ static XfmrBwdWs xfmr_bwd_ws(void* p, int64_t t_cap, int h, int I) {
     w.dq = a.take<float>(T * h); w.dk = a.take<float>(T * h); w.dv = a.take<float>(T * h);
     w.di = a.take<float>(T * I);
     w.part = a.take<float>(xfmr_part_floats(h, I));
+    w.dzm = dropout ? a.take<float>(T * h) : w.dz;
     w.total = a.used();
     return w;
 }
 extern "C" size_t mf_xfmr_backward_ws_bytes(int64_t t_cap, int h, int I) { return xfmr_bwd_ws(nullptr, t_cap, h, I).total; }
+extern "C" size_t mf_xfmr_backward_dropout_ws_bytes(int64_t t_cap, int h, int I) { return xfmr_bwd_ws(nullptr, t_cap, h, I, true).total; }
 
+// kind: XLN_DROP_*; d.thr = 0 runs the plain kernel whatever the kind (then the caller's dzm is dz)
 template <int H>
 static void xfmr_ln_bwd(hipStream_t s, const float* dy, const float* z, const float* st, const int32_t* T_dev, const float* gamma,
-                        float* dz, float* part, float* dgamma, float* dbeta) {
-    xfmr_ln_bwd_kernel<H><<<XFMR_LN_SLICES, 256, 0, s>>>(dy, z, st, T_dev, gamma, dz, part);
+                        float* dz, float* part, float* dgamma, float* dbeta, int kind = XLN_DROP_NONE, const XDrop& d = XDrop{},
+                        const int32_t* tok_user = nullptr, const int64_t* tok_off = nullptr, float* dzm = nullptr) {
+    if (d.thr == 0 || kind == XLN_DROP_NONE)
+        xfmr_ln_bwd_kernel<H, XLN_DROP_NONE><<<XFMR_LN_SLICES, 256, 0, s>>>(dy, z, st, T_dev, gamma, dz, part, nullptr, nullptr, XDrop{}, nullptr);
+    else if (kind == XLN_DROP_IN)
+        xfmr_ln_bwd_kernel<H, XLN_DROP_IN><<<XFMR_LN_SLICES, 256, 0, s>>>(dy, z, st, T_dev, gamma, dz, part, tok_user, tok_off, d, nullptr);
+    else
+        xfmr_ln_bwd_kernel<H, XLN_DROP_OUT><<<XFMR_LN_SLICES, 256, 0, s>>>(dy, z, st, T_dev, gamma, dz, part, tok_user, tok_off, d, dzm);
     xfmr_reduce_kernel<<<dim3((2 * H + 255) / 256), 256, 0, s>>>(part, XFMR_LN_SLICES, 2 * H, H, dgamma, dbeta);
 }
 
 // grads: one buffer per parameter, in the parameters' order and shapes; every element is written (no accumulation).
 // grad_x [t_cap, h] receives dL/dx_t of the packed tokens (the rows mf_xfmr_coalesce lands on the item table).
-extern "C" int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads, int intermediate,
-                                int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
-                                const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
-                                void* ws, size_t ws_bytes, mf_stream_t stream) {
+static int xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads, int intermediate,
+                         int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
+                         const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
+                         void* ws, size_t ws_bytes, const XfmrDropout& drop, bool dropout_ws, mf_stream_t stream) {
     if (!params || !grads || !stash || !grad_u || !out_u || !out_inv || !grad_x || !ws || B <= 0 || t_cap <= 0 || act < 0 || act > 3 ||
         mode < 0 || mode > 2 || (mode == XPOOL_MAX && !out_arg) || max_pos < max_history)
         return mf_set_error(MF_EINVAL, "mf_xfmr_backward: bad argument");
     if (const char* why = xfmr_check_shape(h, layers, heads, intermediate, max_history))
         return mf_set_error(MF_ENOTSUP, "mf_xfmr_backward: %s", why);
-    if (ws_bytes < mf_xfmr_backward_ws_bytes(t_cap, h, intermediate)) return mf_set_error(MF_ENOSPC, "mf_xfmr_backward: workspace too small");
+    if (ws_bytes < xfmr_bwd_ws(nullptr, t_cap, h, intermediate, dropout_ws).total)
+        return mf_set_error(MF_ENOSPC, "mf_xfmr_backward: workspace too small");
     for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i)
         if (!params[i] || !grads[i]) return mf_set_error(MF_EINVAL, "mf_xfmr_backward: parameter or gradient %d is null", i);
     const XfmrStash st = xfmr_stash(const_cast<void*>(stash), B, t_cap, h, layers, intermediate);
-    const XfmrBwdWs w = xfmr_bwd_ws(ws, t_cap, h, intermediate);
+    const XfmrBwdWs w = xfmr_bwd_ws(ws, t_cap, h, intermediate, dropout_ws);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int I = intermediate, dh = h / heads, L = max_history;
+    float* const dzm = drop.thr_hidden ? w.dzm : w.dz;      // what a dropped dense's backward reads (the residual path reads dz)
     const unsigned gt = (unsigned)((t_cap + 7) / 8);
     const int32_t* Td = st.T_dev;
     MF_TIMED("xfmr_backward", s, {
@@ -882,24 +1041,33 @@ extern "C" int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history
             float* const* g = grads + XFMR_GLOBALS + XFMR_PER_LAYER * l;
             const XfmrLayerStash& y = st.layer[l];
             const float* x = l == 0 ? st.x0 : st.layer[l - 1].y2;
-            // output block: y2 = LN(z2), z2 = f Wo2^T + bo2 + y1
-            XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dy, y.z2, y.st2, Td, p[14], w.dz, w.part, g[14], g[15]));
+            // output block: y2 = LN(z2), z2 = drop(f Wo2^T + bo2) + y1
+            XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dy, y.z2, y.st2, Td, p[14], w.dz, w.part, g[14], g[15], XLN_DROP_OUT, drop.ffn_out(l),
+                                              st.tok_user, st.tok_off, dzm));
             MF_TIMED("xfmr_gemm_bwd", s, {
-                xfmr_dweight(s, w.dz, h, y.f, I, g[12], g[13], w.part, Td);
-                XGemm d = xg_dinput(w.dz, h, p[12], I, w.di, nullptr, Td);        // da = (dz2 Wo2) * act'(a)
+                xfmr_dweight(s, dzm, h, y.f, I, g[12], g[13], w.part, Td);
+                XGemm d = xg_dinput(dzm, h, p[12], I, w.di, nullptr, Td);         // da = (mask dz2 Wo2) * act'(a)
                 d.epi = XEPI_DACT; d.act = act; d.P = y.a;
                 xfmr_gemm(s, t_cap, d);
                 xfmr_dweight(s, w.di, I, y.y1, h, g[10], g[11], w.part, Td);
                 xfmr_gemm(s, t_cap, xg_dinput(w.di, I, p[10], h, w.dt, w.dz, Td));  // dy1 = da Wi + dz2
             });
-            // attention block: y1 = LN(z1), z1 = ctx Wo^T + bo + x
-            XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dt, y.z1, y.st1, Td, p[8], w.dz, w.part, g[8], g[9]));
+            // attention block: y1 = LN(z1), z1 = drop(ctx Wo^T + bo) + x
+            XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dt, y.z1, y.st1, Td, p[8], w.dz, w.part, g[8], g[9], XLN_DROP_OUT, drop.attn_out(l),
+                                              st.tok_user, st.tok_off, dzm));
             MF_TIMED("xfmr_gemm_bwd", s, {
-                xfmr_dweight(s, w.dz, h, y.ctx, h, g[6], g[7], w.part, Td);
-                xfmr_gemm(s, t_cap, xg_dinput(w.dz, h, p[6], h, w.dctx, nullptr, Td));
+                xfmr_dweight(s, dzm, h, y.ctx, h, g[6], g[7], w.part, Td);
+                xfmr_gemm(s, t_cap, xg_dinput(dzm, h, p[6], h, w.dctx, nullptr, Td));
             });
-            MF_TIMED("xfmr_attn_bwd", s, XFMR_DISPATCH_DH(dh, xfmr_attn_bwd_kernel<DH><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
-                                                                  y.q, y.k, y.v, w.dctx, st.tok_off, h, heads, w.dq, w.dk, w.dv)));
+            MF_TIMED("xfmr_attn_bwd", s, {
+                if (drop.thr_attn) {
+                    XFMR_DISPATCH_DH(dh, xfmr_attn_bwd_kernel<DH, true><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
+                                             y.q, y.k, y.v, w.dctx, st.tok_off, h, heads, w.dq, w.dk, w.dv, drop.attn(l)));
+                } else {
+                    XFMR_DISPATCH_DH(dh, xfmr_attn_bwd_kernel<DH, false><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
+                                             y.q, y.k, y.v, w.dctx, st.tok_off, h, heads, w.dq, w.dk, w.dv, XDrop{}));
+                }
+            });
             MF_TIMED("xfmr_gemm_bwd", s, {
                 xfmr_dweight(s, w.dq, h, x, h, g[0], g[1], w.part, Td);
                 xfmr_dweight(s, w.dk, h, x, h, g[2], g[3], w.part, Td);
@@ -909,8 +1077,9 @@ extern "C" int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history
                 xfmr_gemm(s, t_cap, xg_dinput(w.dv, h, p[4], h, w.dy, w.dy, Td));
             });
         }
-        // embeddings: x0 = LN(z0), z0 = (x + tok[0]) + pos[t]
-        XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dy, st.z0, st.st0, Td, params[2], grad_x, w.part, grads[2], grads[3]));
+        // embeddings: x0 = drop(LN(z0)), z0 = (x + tok[0]) + pos[t]
+        XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dy, st.z0, st.st0, Td, params[2], grad_x, w.part, grads[2], grads[3], XLN_DROP_IN,
+                                          drop.embeddings(), st.tok_user, st.tok_off));
         mf_zero_async(grads[0], (size_t)max_pos * h * sizeof(float), s);
         xfmr_pos_bwd_kernel<<<dim3((unsigned)L, XFMR_POS_SLICES), 128, 0, s>>>(grad_x, st.tok_off, B, h, L, w.part);
         xfmr_reduce_kernel<<<dim3((unsigned)(((int64_t)L * h + 255) / 256)), 256, 0, s>>>(w.part, XFMR_POS_SLICES, (int64_t)L * h,
@@ -918,6 +1087,25 @@ extern "C" int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history
         xfmr_tok_bwd_kernel<<<1, 128, 0, s>>>(grads[0], h, L, grads[1]);
     });
     return mf_check_launch("mf_xfmr_backward");
+}
+
+extern "C" int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads, int intermediate,
+                                int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
+                                const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
+                                void* ws, size_t ws_bytes, mf_stream_t stream) {
+    return xfmr_backward(h, B, t_cap, max_history, max_pos, layers, heads, intermediate, act, mode, norm_user, params, grads, stash, grad_u,
+                         out_u, out_inv, out_arg, grad_x, ws, ws_bytes, XfmrDropout{}, false, stream);
+}
+extern "C" int mf_xfmr_backward_dropout(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads,
+                                        int intermediate, int act, int mode, int norm_user, const float* const* params,
+                                        float* const* grads, const void* stash, const float* grad_u, const float* out_u,
+                                        const float* out_inv, const int32_t* out_arg, float* grad_x, void* ws, size_t ws_bytes,
+                                        double p_hidden, double p_attn, uint64_t seed, uint64_t call, mf_stream_t stream) {
+    XfmrDropout drop;
+    if (!xfmr_dropout(p_hidden, p_attn, seed, call, &drop))
+        return mf_set_error(MF_EINVAL, "mf_xfmr_backward_dropout: dropout probabilities must be in [0, 1): %g, %g", p_hidden, p_attn);
+    return xfmr_backward(h, B, t_cap, max_history, max_pos, layers, heads, intermediate, act, mode, norm_user, params, grads, stash, grad_u,
+                         out_u, out_inv, out_arg, grad_x, ws, ws_bytes, drop, true, stream);
 }
 
 // ============================================================================================ coalesce ====

@@ -19,6 +19,8 @@ plane and stay out of scope.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import losses as mf_losses
@@ -87,15 +89,29 @@ class MatrixFactorizationLitModule(_Base):
         if self.config.user_tower in HISTORY_TOWERS:      # the user IS its history: pool it (xfmr_rec/lightning.py:89-90 excludes it)
             embed = self._pool_item_ids(list(self.history.get(int(user_idx), []))).cpu().numpy()
         else:
-            embed = self(torch.tensor([int(user_idx)], device=device)).cpu().numpy()
+            with self._user_tower_eval():
+                embed = self(torch.tensor([int(user_idx)], device=device)).cpu().numpy()
         return self.item_processor.search(embed, exclude_item_ids=exclude_item_ids, top_k=top_k)
+
+    @contextlib.contextmanager
+    def _user_tower_eval(self):
+        """The user tower in eval mode for one serving / metric call (a transformer tower with dropout never drops there),
+        its mode restored afterwards; training steps run the tower in whatever mode the module is in."""
+        tower = self.towers["user"]
+        was = tower.training
+        tower.eval()
+        try:
+            yield tower
+        finally:
+            tower.train(was)
 
     def _pool_item_ids(self, item_ids: list[int]) -> torch.Tensor:
         """``[1, d]`` history-tower query of a list of item ids (rows through the item index's id map when there is one)."""
         proc = self.item_processor
         rows = [proc.row_of(i) for i in item_ids] if (proc is not None and proc._row_of_id is not None) else [int(i) for i in item_ids]
         device = self.towers["item"].weight.device
-        return self.towers["user"](torch.tensor([rows or [0]], dtype=torch.int64, device=device))
+        with self._user_tower_eval() as tower:
+            return tower(torch.tensor([rows or [0]], dtype=torch.int64, device=device))
 
     @torch.inference_mode()
     def recommend_with_history(self, item_ids: list[int], *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
@@ -318,10 +334,11 @@ class MatrixFactorizationLitModule(_Base):
     def _queries(self, batch) -> torch.Tensor:
         """The users' query vectors: their table rows, or (history tower) their pooled history -- the same CSR
         ``(offsets, item rows)`` that is excluded from retrieval (``InteractionTable.eval_sets``)."""
-        if self.config.user_tower not in HISTORY_TOWERS:
-            return self(batch["user"]["idx"], tower="user")
-        off, items = batch["history"]
-        return self((off[:-1], off[1:], items), tower="user")
+        with self._user_tower_eval():
+            if self.config.user_tower not in HISTORY_TOWERS:
+                return self(batch["user"]["idx"], tower="user")
+            off, items = batch["history"]
+            return self((off[:-1], off[1:], items), tower="user")
 
     def validation_step(self, batch, _: int = 0) -> None:
         self.log_dict(self.update_metrics(batch, step_name="val"))

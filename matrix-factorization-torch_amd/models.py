@@ -44,6 +44,11 @@ class ModelConfig(pydantic.BaseModel):
     intermediate_size: int | None = None       # None: hidden_size, as the reference's module config
     hidden_act: str = "gelu"
     max_position_embeddings: int = 64
+    # training dropout of that encoder (BertConfig's names; the reference trains with BertConfig's defaults, 0.1 / 0.1).
+    # 0.0 here: the tower then computes the eval-mode function in training too, as it always did
+    hidden_dropout_prob: float = 0.0
+    attention_probs_dropout_prob: float = 0.0
+    dropout_seed: int = 0
     # "features": the vector is the pooled hashed-attribute tokens of the entity (FeatureBagTower); when both towers are
     # feature towers they share ONE bucket table, as the reference's towers share one encoder (lightning.py:60-74)
     item_tower: Literal["table", "features"] = "table"
@@ -64,6 +69,16 @@ class ModelConfig(pydantic.BaseModel):
                 raise ValueError(msg)
         else:
             check_pooling_mode(self.pooling_mode)
+        return self
+
+    @pydantic.model_validator(mode="after")
+    def _check_dropout(self):
+        for name in ("hidden_dropout_prob", "attention_probs_dropout_prob"):
+            p = check_dropout_prob(getattr(self, name), name)
+            if p > 0.0 and self.user_tower != "transformer":
+                msg = f"{name} is the dropout of user_tower='transformer' (no other tower has dropout): {name} = {p}, {self.user_tower = }"
+                raise ValueError(msg)
+        check_dropout_seed(self.dropout_seed)
         return self
 
     @pydantic.field_validator("max_history")
@@ -149,6 +164,29 @@ def check_transformer_shape(hidden_size: int, num_hidden_layers: int, num_attent
     if max_history is not None and not 1 <= max_history <= max_position_embeddings:
         msg = f"max_history must be None or in 1..max_position_embeddings = {max_position_embeddings}: {max_history = }"
         raise ValueError(msg)
+
+
+def check_dropout_prob(p: float, name: str = "p") -> float:
+    """A dropout probability is in [0, 1) (torch.nn.Dropout's p = 1 would need a scale of 1 / 0)."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:          # (nan fails both)
+        msg = f"{name} must be in [0, 1): {p}"
+        raise ValueError(msg)
+    return p
+
+
+def check_dropout_seed(seed: int) -> int:
+    if not 0 <= int(seed) < 1 << 64:
+        msg = f"dropout_seed must fit an unsigned 64-bit word: {seed = }"
+        raise ValueError(msg)
+    return int(seed)
+
+
+def dropout_threshold(p: float) -> int:
+    """``thr = round(p * 65536)`` (halves up, at most 65535) of ``include/mf_numerics.h``: an element is kept iff its
+    16-bit field is >= thr, so the probability that counts is ``thr / 65536`` and the scale ``1 / (1 - thr / 65536)``;
+    thr = 0 means the site is off."""
+    return min(int(math.floor(check_dropout_prob(p) * 65536.0 + 0.5)), 65535)
 
 
 def _park(table: torch.Tensor, item) -> None:
@@ -465,7 +503,8 @@ class _EncodeHistory(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table: torch.Tensor, start: torch.Tensor, end: torch.Tensor, items: torch.Tensor, n_entries: int, cfg: tuple,
                 *params: torch.Tensor):
-        layers, heads, inter, act, mode, max_history, norm_item, norm_user = cfg
+        layers, heads, inter, act, mode, max_history, norm_item, norm_user = cfg[:8]
+        drop = cfg[8] if len(cfg) > 8 else None      # (p_hidden, p_attn, seed, call): the *_dropout exports; None: the plain ones
         _check_table(table, "embedding")
         if torch.cuda.is_current_stream_capturing():
             raise _lib.MfHipError("the transformer tower does not support hipGraph capture")
@@ -482,11 +521,14 @@ class _EncodeHistory(torch.autograd.Function):
         arg = torch.empty(b, d, dtype=torch.int32, device=dev) if mode == 1 else None
         stash = _lib.workspace(lib.mf_xfmr_ws_bytes(b, t_cap, d, layers, inter), dev)
         params = tuple(p.detach() for p in params)
-        _lib.check(lib.mf_xfmr_forward(table.data_ptr(), rows, d, start.data_ptr(), end.data_ptr(), items.data_ptr(), items.numel(),
-                                       b, t_cap, max_history, layers, heads, inter, act, mode, int(norm_item), int(norm_user),
-                                       _pointer_array(params), u.data_ptr(), inv.data_ptr(), _lib.ptr(arg), stash.data_ptr(),
-                                       stash.numel(), _lib.stream_ptr()))
-        ctx.table, ctx.stash, ctx.arg, ctx.params = table, stash, arg, params
+        args = (table.data_ptr(), rows, d, start.data_ptr(), end.data_ptr(), items.data_ptr(), items.numel(), b, t_cap, max_history,
+                layers, heads, inter, act, mode, int(norm_item), int(norm_user), _pointer_array(params), u.data_ptr(), inv.data_ptr(),
+                _lib.ptr(arg), stash.data_ptr(), stash.numel())
+        if drop is None:
+            _lib.check(lib.mf_xfmr_forward(*args, _lib.stream_ptr()))
+        else:
+            _lib.check(lib.mf_xfmr_forward_dropout(*args, *drop, _lib.stream_ptr()))
+        ctx.table, ctx.stash, ctx.arg, ctx.params, ctx.drop = table, stash, arg, params, drop
         ctx.b, ctx.t_cap, ctx.shape, ctx.mode = b, t_cap, (layers, heads, inter, act), mode
         ctx.max_history, ctx.norm_item, ctx.norm_user = max_history, bool(norm_item), bool(norm_user)
         ctx.save_for_backward(u, inv)
@@ -504,11 +546,16 @@ class _EncodeHistory(torch.autograd.Function):
         lib = _lib.lib()
         g = grad_u.to(torch.float32).contiguous()
         grad_x = torch.empty(ctx.t_cap, d, dtype=torch.float32, device=u.device)
-        ws = _lib.workspace(lib.mf_xfmr_backward_ws_bytes(ctx.t_cap, d, inter), u.device)
-        _lib.check(lib.mf_xfmr_backward(d, ctx.b, ctx.t_cap, ctx.max_history, params[0].shape[0], layers, heads, inter, act, ctx.mode,
-                                        int(ctx.norm_user), _pointer_array(params), _pointer_array(grads), ctx.stash.data_ptr(),
-                                        g.data_ptr(), u.data_ptr(), inv.data_ptr(), _lib.ptr(ctx.arg), grad_x.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        drop = ctx.drop
+        ws_bytes = lib.mf_xfmr_backward_ws_bytes if drop is None else lib.mf_xfmr_backward_dropout_ws_bytes
+        ws = _lib.workspace(ws_bytes(ctx.t_cap, d, inter), u.device)
+        args = (d, ctx.b, ctx.t_cap, ctx.max_history, params[0].shape[0], layers, heads, inter, act, ctx.mode, int(ctx.norm_user),
+                _pointer_array(params), _pointer_array(grads), ctx.stash.data_ptr(), g.data_ptr(), u.data_ptr(), inv.data_ptr(),
+                _lib.ptr(ctx.arg), grad_x.data_ptr(), ws.data_ptr(), ws.numel())
+        if drop is None:
+            _lib.check(lib.mf_xfmr_backward(*args, _lib.stream_ptr()))
+        else:                                        # the same (seed, call): the kernels regenerate the forward's masks
+            _lib.check(lib.mf_xfmr_backward_dropout(*args, *drop, _lib.stream_ptr()))
         _park(table, TransformerHistoryGrad(ctx, grad_x))
         return (None,) * 6 + tuple(grads)
 
@@ -525,17 +572,32 @@ class HistoryTransformerTower(torch.nn.Module):
     ``pooling_mode``: "mean" / "max" over the valid positions, or "cls" = position 0.  The tower shares the item tower's
     table (its backward lands on that table's sparse update) and owns the encoder's dense parameters, named as
     ``transformers.BertModel``'s ``state_dict`` names them (no word-embedding table, no pooler dense); those receive ordinary
-    ``.grad`` tensors.  **No dropout**: BertConfig defaults to 0.1 on hidden states and attention probabilities and the
-    reference does not override it; this tower computes the eval-mode function in training too.  fp32 throughout, LayerNorm
-    eps 1e-12.  HIP kernels ``mf_xfmr_forward`` / ``mf_xfmr_backward`` / ``mf_xfmr_coalesce``.  The tower may be
-    applied more than once before a step (each call parks its own table gradient; the optimiser chains the coalesces, the
-    dense gradients accumulate).  No hipGraph capture: ``forward`` raises ``MfHipError`` when the stream is capturing."""
+    ``.grad`` tensors.  fp32 throughout, LayerNorm eps 1e-12.  HIP kernels ``mf_xfmr_forward`` / ``mf_xfmr_backward`` /
+    ``mf_xfmr_coalesce``.  The tower may be applied more than once before a step (each call parks its own table gradient;
+    the optimiser chains the coalesces, the dense gradients accumulate).  No hipGraph capture: ``forward`` raises
+    ``MfHipError`` when the stream is capturing.
+
+    **Dropout** (BertConfig's names): ``hidden_dropout_prob`` on the embeddings, the attention output and the FFN output,
+    ``attention_probs_dropout_prob`` on the softmax, where ``BertModel`` has them.  Both default to 0.0, not BertConfig's
+    0.1: the reference builds its BERT with BertConfig's defaults and trains it in train mode, so **0.1 / 0.1 is what the
+    reference trains with**; pass them to train that model.  Dropout applies iff ``tower.training`` and a probability is
+    non-zero (torch's rule); ``eval()`` computes the function without it.  The masks are counter-based
+    (``include/mf_numerics.h``: a function of ``dropout_seed``, the number of the training forward, the site and the
+    element's (user, position, column)), generated inside the kernels ``mf_xfmr_forward_dropout`` /
+    ``mf_xfmr_backward_dropout`` -- no mask tensor exists and the backward regenerates the same bits, so a step is
+    bit-reproducible.  Each training forward uses the next ``call`` number (``self.dropout_call``, a Python int);
+    :meth:`manual_seed` sets the seed and resets the counter.  Seed and counter are NOT part of ``state_dict`` (its names
+    keep mirroring ``BertModel``): a resumed run that wants the same masks calls ``manual_seed`` itself."""
 
     def __init__(self, item_tower: torch.nn.Module, *, num_hidden_layers: int = 1, num_attention_heads: int = 4,
                  intermediate_size: int | None = None, hidden_act: str = "gelu", max_position_embeddings: int = 64,
                  pooling_mode: str = "mean", max_history: int | None = None, normalize: bool = True,
-                 initializer_range: float = 0.02, device=None) -> None:
+                 initializer_range: float = 0.02, device=None, hidden_dropout_prob: float = 0.0,
+                 attention_probs_dropout_prob: float = 0.0, dropout_seed: int = 0) -> None:
         super().__init__()
+        self.hidden_dropout_prob = check_dropout_prob(hidden_dropout_prob, "hidden_dropout_prob")
+        self.attention_probs_dropout_prob = check_dropout_prob(attention_probs_dropout_prob, "attention_probs_dropout_prob")
+        self.manual_seed(dropout_seed)
         if not isinstance(item_tower, EmbeddingTower):
             msg = (f"HistoryTransformerTower encodes the rows of a plain EmbeddingTower (one row per item); got "
                    f"{type(item_tower).__name__} (a hashed tower's rows are shared by many items)")
@@ -596,6 +658,12 @@ class HistoryTransformerTower(torch.nn.Module):
                 out += [m.weight, m.bias]
         return out
 
+    def manual_seed(self, seed: int) -> "HistoryTransformerTower":
+        """Set the dropout seed and restart the count of training forwards: the masks of the forwards that follow are those
+        of a fresh tower built with ``dropout_seed=seed``."""
+        self.dropout_seed, self.dropout_call = check_dropout_seed(seed), 0
+        return self
+
     def segments(self, history):
         """As :meth:`HistoryPoolingTower.segments`."""
         return _history_segments(self.weight.device, history)
@@ -608,11 +676,15 @@ class HistoryTransformerTower(torch.nn.Module):
             return torch.zeros(0, self.weight.shape[1], device=self.weight.device)
         cfg = (self.num_hidden_layers, self.num_attention_heads, self.intermediate_size, HIDDEN_ACTS.index(self.hidden_act),
                TRANSFORMER_POOLING_MODES.index(self.pooling_mode), self.max_history, self.item_tower.normalize, self.normalize)
+        if self.training and (self.hidden_dropout_prob > 0.0 or self.attention_probs_dropout_prob > 0.0):
+            cfg += ((self.hidden_dropout_prob, self.attention_probs_dropout_prob, self.dropout_seed, self.dropout_call),)
+            self.dropout_call += 1
         return _EncodeHistory.apply(self.weight, start, end, items, n_entries, cfg, *self.encoder_parameters())
 
     def extra_repr(self) -> str:
         return (f"layers={self.num_hidden_layers}, heads={self.num_attention_heads}, intermediate={self.intermediate_size}, "
-                f"act={self.hidden_act}, pooling_mode={self.pooling_mode}, max_history={self.max_history}, normalize={self.normalize}")
+                f"act={self.hidden_act}, pooling_mode={self.pooling_mode}, max_history={self.max_history}, normalize={self.normalize}, "
+                f"hidden_dropout_prob={self.hidden_dropout_prob}, attention_probs_dropout_prob={self.attention_probs_dropout_prob}")
 
 
 class FeatureBagGrad(PooledGrad):
@@ -768,7 +840,9 @@ def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
                                        num_attention_heads=config.num_attention_heads, intermediate_size=config.intermediate_size,
                                        hidden_act=config.hidden_act, max_position_embeddings=config.max_position_embeddings,
                                        pooling_mode=config.pooling_mode, max_history=config.max_history,
-                                       normalize=config.normalize, device=device)
+                                       normalize=config.normalize, device=device, hidden_dropout_prob=config.hidden_dropout_prob,
+                                       attention_probs_dropout_prob=config.attention_probs_dropout_prob,
+                                       dropout_seed=config.dropout_seed)
         return torch.nn.ModuleDict({"user": user, "item": item})
     if config.user_tower == "history":
         if config.num_hashes > 0:

@@ -12,6 +12,15 @@ the attention.  For the GEMM spans: achieved fp32 matrix rate from the algorithm
 forward, twice that backward, against 157.3 TFLOP/s.  Next to it the same step with user_tower="history" (mean);
 ``--baseline-only`` measures only that one, so that it can run against another build of the library (MF_HIP_LIB), whose
 missing mf_xfmr_* exports are then left unbound.
+
+    python tools/xfmr_probe.py --transformer-only --repeat 3 --dropout 0.1 0.1 --out profiles/xfmr_dropout_probe.json
+    MF_HIP_LIB=path/to/parent/libmf_hip.so python tools/xfmr_probe.py --transformer-only --repeat 3 --out parent.json
+
+``--dropout P_HIDDEN P_ATTN`` adds, per shape, the same step with the tower's training dropout (its spans, and the share of
+the step that dropout adds: mask generation, the masked multiplies and the backward's masked copy); ``--repeat N`` repeats
+every step measurement N times (``ms_per_step_runs``: the spread that a comparison between two libraries has to respect);
+``--transformer-only`` skips the history-tower steps.  A library without the dropout exports (the parent commit's) still runs
+the p = 0 step: the exports it lacks are left unbound.
 """
 from __future__ import annotations
 
@@ -64,12 +73,18 @@ def main() -> None:
     ap.add_argument("--out", default=str(ROOT / "profiles" / "xfmr_probe.json"))
     ap.add_argument("--ratings", type=int, default=25_000_000)
     ap.add_argument("--baseline-only", action="store_true")
+    ap.add_argument("--transformer-only", action="store_true")
+    ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--dropout", type=float, nargs=2, metavar=("P_HIDDEN", "P_ATTN"))
     args = ap.parse_args()
     mf = importlib.import_module("matrix-factorization-torch_amd")
-    if args.baseline_only:                      # another build of the library may not have the new exports
-        have = ctypes.CDLL(str(mf._lib.LIB_PATH))
-        for name in [n for n in mf._lib.SIGNATURES if n.startswith("mf_xfmr_") and not hasattr(have, n)]:
-            del mf._lib.SIGNATURES[name]
+    have = ctypes.CDLL(str(mf._lib.LIB_PATH))   # another build of the library may not have the newest exports
+    new = lambda n: "dropout" in n or (args.baseline_only and n.startswith("mf_xfmr_"))  # noqa: E731
+    missing = [n for n in mf._lib.SIGNATURES if new(n) and not hasattr(have, n)]
+    for name in missing:
+        del mf._lib.SIGNATURES[name]
+    if args.dropout and missing:
+        raise SystemExit(f"--dropout needs the dropout exports, which {mf._lib.LIB_PATH} lacks")
     lib = mf._lib.lib()
     torch.manual_seed(0)
     table = hp.synthetic_table(mf, args.ratings)
@@ -78,10 +93,15 @@ def main() -> None:
     res = {"library": str(mf._lib.LIB_PATH), "shape": {"items": hp.ITEMS, "batch": hp.B, "ratings": int(table.sorted_user.numel())},
            "cases": []}
     loss_fn = mf.losses.InfomationNoiseContrastiveEstimationLoss(num_negatives=0)
+    variants = [("history", None)] * (not args.transformer_only) + [("transformer", None)] * (not args.baseline_only)
+    if args.dropout and not args.baseline_only:
+        variants.append(("transformer", tuple(args.dropout)))
     for d, L, inter in SHAPES:
-        for user_tower in (("history",) if args.baseline_only else ("history", "transformer")):
+        plain = None
+        for user_tower, dropout in variants:
+            kw = {"hidden_dropout_prob": dropout[0], "attention_probs_dropout_prob": dropout[1]} if dropout else {}
             cfg = mf.models.ModelConfig(num_items=hp.ITEMS, hidden_size=d, user_tower=user_tower, max_history=L, intermediate_size=inter,
-                                        num_hidden_layers=1, num_attention_heads=4)
+                                        num_hidden_layers=1, num_attention_heads=4, **kw)
             towers = mf.models.init_towers(cfg, device="cuda")
             if user_tower == "transformer":
                 opt = mf.optim.tower_optimizer(towers, "adam", 1e-3)
@@ -101,7 +121,17 @@ def main() -> None:
                 opt.step()
                 opt.zero_grad()
 
-            case = {"user_tower": user_tower, "d": d, "L": L, "I": inter, "ms_per_step": median_ms(step), "spans": spans(mf, lib, step)}
+            runs = [median_ms(step) for _ in range(max(1, args.repeat))]
+            case = {"user_tower": user_tower, "d": d, "L": L, "I": inter, "ms_per_step": statistics.median(runs), "ms_per_step_runs": runs,
+                    "spans": spans(mf, lib, step)}
+            if user_tower == "transformer" and dropout is None:
+                plain = case
+            if dropout:
+                case["dropout"] = {"hidden_dropout_prob": dropout[0], "attention_probs_dropout_prob": dropout[1]}
+                if plain:
+                    case["dropout"]["share_of_step_added_by_dropout"] = 1.0 - plain["ms_per_step"] / case["ms_per_step"]
+                    for name in ("xfmr_forward", "xfmr_backward"):
+                        case["dropout"][f"{name}_ms_added"] = case["spans"][name]["ms_per_step"] - plain["spans"][name]["ms_per_step"]
             if user_tower == "transformer":
                 st, en, items = batches[0]["user"]["history"]
                 valid = (items >= 1) & (items < hp.ITEMS)

@@ -139,6 +139,11 @@ int mf_group_keys(const int64_t* keys, int64_t n, int nkeys, int32_t* perm, int6
  * and the forward is then called with item_idx = NULL on the SAME workspace, after the caller has
  * ordered the two streams (event); with item_idx != NULL mf_loss_fwd builds them itself. */
 size_t mf_loss_ws_bytes(int64_t B, int64_t N, int d, int P, int num_negatives);
+/* Host-only view of how the dense sweeps split a shape (nothing is launched, no GPU needed): out[8] = {mined (no dense sweep
+ * runs), forward splits, tiles per forward split, dU splits, tiles per dU split, dV splits, tiles per dV split, tiles in the
+ * LAST split of the three: forward | dU << 20 | dV << 40}.  A tile is 32 columns of the streamed axis (items for the forward
+ * and dU, users for dV).  MF_EINVAL for the shapes mf_loss_ws_bytes answers with 0, and for a width outside {32,64,128,256}. */
+int mf_loss_plan(int64_t B, int64_t N, int d, int num_negatives, int64_t* out);
 int mf_loss_masks(int64_t B, int64_t N, int d, int P, int num_negatives, const int64_t* item_idx,
                   const int64_t* pos_idx, void* ws, size_t ws_bytes, mf_stream_t stream);
 /* CSR form of the positives (the batch producer's own lists, mf_sample_batch's pos_off / pos_items): the positives of batch

@@ -35,6 +35,7 @@ SIGNATURES = {
     "mf_sort_keys": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mf_group_keys": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "mf_loss_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int, c_int]),
+    "mf_loss_plan": (c_int, [c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64)]),
     "mf_loss_masks": (c_int, [c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mf_loss_fwd": (c_int, [c_i64, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_int, c_vp, c_vp, c_vp, c_vp,
                             c_vp, c_vp, c_i64, c_int, c_vp, c_sz, c_vp, c_vp, c_vp]),

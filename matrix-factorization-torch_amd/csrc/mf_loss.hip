@@ -175,6 +175,20 @@ extern "C" size_t mf_loss_ws_bytes(int64_t B, int64_t N, int d, int P, int num_n
     return loss_ws(nullptr, B, N, d, P, num_negatives).total;
 }
 
+// host-only: the split geometry of the three dense sweeps for a shape, as the launches would use it (nothing is launched)
+extern "C" int mf_loss_plan(int64_t B, int64_t N, int d, int num_negatives, int64_t* out8) {
+    if (!out8) return mf_set_error(MF_EINVAL, "mf_loss_plan: out is NULL");
+    if (B <= 0 || N < B) return mf_set_error(MF_EINVAL, "mf_loss_plan: need 0 < B <= N (B=%lld N=%lld)", (long long)B, (long long)N);
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_loss_plan: embedding width %d not in {32,64,128,256}", d);
+    const LossWs w = loss_ws(nullptr, B, N, d, 0, num_negatives);
+    const int64_t last_f = w.NT - (int64_t)(w.nsplit_f - 1) * w.tps_f, last_u = w.NT - (int64_t)(w.nsplit_u - 1) * w.tps_u,
+                  last_v = w.BT - (int64_t)(w.nsplit_v - 1) * w.tps_v;
+    const int64_t o[8] = {w.mined ? 1 : 0, w.nsplit_f, w.tps_f, w.nsplit_u, w.tps_u, w.nsplit_v, w.tps_v,
+                          last_f | (last_u << 20) | (last_v << 40)};     // (a split holds < 2^19 tiles: N < 2^24)
+    for (int i = 0; i < 8; ++i) out8[i] = o[i];
+    return MF_OK;
+}
+
 // ------------------------------------------------------------- per-call setup ---
 // ONE launch for everything the sweeps need that is O(B + N): chain norms of both operands, the
 // diagonal (L_ii, D_ii, sign), the zero-padded logQ copy, and the clearing of the hash table, the

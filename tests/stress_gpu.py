@@ -112,8 +112,9 @@ def update_case():
 
 
 def loss_case():
-    """random tile-ragged shapes through every loss class, dense and mined, against the oracle (the forward's loop is
-    unrolled by two tiles: odd / even tile counts, every split length)"""
+    """random tile-ragged shapes through every loss class, dense and mined, against the oracle.  At these sizes
+    (Bp * Np <= 2^21) every workgroup of the dense sweeps streams exactly ONE tile: the pipelined loops, their rings and
+    short last splits are reached by tests/test_gpu_dense_sweeps.py, not here."""
     import numpy as np
 
     from oracle import chain, losses as ol

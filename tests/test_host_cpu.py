@@ -93,6 +93,38 @@ def test_mining_prefilter_plan_holds_what_its_kernels_write(mf):
     assert lib.mf_mining_prefilter_plan(8192, 16384, 32, 4, out) == 0 and out[0] == 0     # d = 32: never served
 
 
+def test_loss_plan_tells_how_many_tiles_a_workgroup_streams(mf):
+    """mf_loss_plan is host arithmetic on the launch geometry of the dense sweeps (split_geometry, csrc/mf_loss.hip).
+    What a workgroup does depends on its tile count, so the tests that are about the multi-tile paths
+    (tests/test_gpu_dense_sweeps.py) assert through it that they reach them -- and this one, that the dense cases of
+    the older tests never did: one tile per workgroup up to Bp * Np = 2^21."""
+    import ctypes
+
+    from tests import _dense_cases as dc
+
+    lib = mf._lib.lib()
+    for d in dc.WIDTHS:
+        for (b, n), (fu, dv, _) in dc.SHAPES.items():
+            p = dc.plan(lib, b, n, d)
+            nt, bt = -(-n // 128) * 4, -(-b // 128) * 4
+            assert p["mined"] == 0 and (p["tps_f"], p["last_f"]) == (p["tps_u"], p["last_u"]) == fu, (b, n, d, p)
+            assert (p["tps_v"], p["last_v"]) == dv, (b, n, d, p)
+            assert p["nsplit_f"] == p["nsplit_u"] == -(-nt // fu[0]) and p["nsplit_v"] == -(-bt // dv[0]), (b, n, d, p)
+        for b, n in dc.OLD_SHAPES + ((64, 64), (4, 8), (33, 95), (100, 260)):
+            p = dc.plan(lib, b, n, d)
+            assert p["tps_f"] == p["tps_u"] == p["tps_v"] == p["last_f"] == p["last_u"] == p["last_v"] == 1, (b, n, d, p)
+        assert dc.plan(lib, 1024, 2048 + 1, d)["tps_f"] == 2                  # the first shape past the threshold
+        p = dc.plan(lib, 8192, 16384, d)                                      # the full-size training step
+        assert (p["nsplit_f"], p["tps_f"], p["nsplit_v"], p["tps_v"], p["last_f"], p["last_v"]) == (8, 64, 4, 64, 64, 64)
+        assert dc.plan(lib, 8192, 16384, d, num_negatives=4)["mined"] == 1    # mining: no dense sweep runs
+        assert dc.plan(lib, 8192, 16384, d, num_negatives=16384)["mined"] == 0
+    out = (ctypes.c_int64 * 8)()
+    for b, n, d in ((4, 2, 128), (0, 8, 64), (-1, 8, 64), (8, 16, 48)):      # what mf_loss_ws_bytes answers with 0; a bad width
+        assert lib.mf_loss_plan(b, n, d, 0, out) == mf._lib.MF_EINVAL and b"mf_loss_plan" in lib.mf_last_error(), (b, n, d)
+    assert lib.mf_loss_ws_bytes(4, 2, 128, 0, 0) == 0 and lib.mf_loss_ws_bytes(0, 8, 64, 0, 0) == 0
+    assert lib.mf_loss_plan(8, 16, 64, 0, None) == mf._lib.MF_EINVAL
+
+
 def test_no_product_kernel_spills():
     """vgpr_spill_count == 0 and no scratch for every kernel of the training step, its set-up and the retrieval paths
     (read from the code objects' notes: tools/kernel_resources.py).  Spills in update_fused_kernel<*, Adam> and

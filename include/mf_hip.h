@@ -460,6 +460,36 @@ int mf_xfmr_backward_dropout(int h, int64_t B, int64_t t_cap, int max_history, i
                              const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
                              void* ws, size_t ws_bytes, double p_hidden, double p_attn, uint64_t seed, uint64_t call,
                              mf_stream_t stream);
+/* Mixed precision of the six dense layers of every encoder layer (Q, K, V, attention output, FFN in, FFN out).  precision =
+ * MF_XFMR_FP32: the calls above (the four of them are this case of the same implementation).  MF_XFMR_BF16_MIXED: BOTH operands
+ * of every GEMM of those layers -- Y = X W^T, dX = dY W, dW = dY^T X -- are rounded to bf16 (round-to-nearest-even) where they
+ * are staged; the products are exact and accumulate in fp32 (v_mfma_f32_32x32x16_bf16); bias, residual, activation, its
+ * derivative and the dropout multiply stay fp32, db stays the fp32 column sum of the unrounded dY, and outputs, stash,
+ * parameters and every gradient stay fp32, as does everything that is not one of those GEMMs (LayerNorms, attention, pooling,
+ * the position / token-type / table gradients).  Same stash and workspaces (mf_xfmr_ws_bytes, mf_xfmr_backward_dropout_ws_bytes),
+ * same fixed split of dW over the tokens, no float atomics: bit-reproducible.  The backward takes the forward's precision.
+ * Any other precision: MF_EINVAL. */
+#define MF_XFMR_FP32 0
+#define MF_XFMR_BF16_MIXED 1
+int mf_xfmr_forward_mixed(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                          const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
+                          int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
+                          float* out_u, float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, double p_hidden,
+                          double p_attn, uint64_t seed, uint64_t call, int precision, mf_stream_t stream);
+int mf_xfmr_backward_mixed(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads, int intermediate,
+                           int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
+                           const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
+                           void* ws, size_t ws_bytes, double p_hidden, double p_attn, uint64_t seed, uint64_t call, int precision,
+                           mf_stream_t stream);
+/* ONE dense operation of that engine on the caller's row-major fp32 buffers, through the tower's own launches (for tests of
+ * the arithmetic contract).  M tokens in [1, 2^31), N and K multiples of 32 in [32, 512] (MF_ENOTSUP otherwise).
+ *   form 0: out [M, N] = a [M, K] b[N, K]^T + bias [N] (bias may be null)
+ *   form 1: out [M, K] = a [M, N] b[N, K]
+ *   form 2: out [N, K] = a [M, N]^T b[M, K], out_bias [N] = the column sums of a
+ * form outside 0..2 or an unknown precision: MF_EINVAL, decided before any GPU call. */
+size_t mf_xfmr_dense_ws_bytes(int form, int N, int K);
+int mf_xfmr_dense(int form, int precision, int64_t M, int N, int K, const float* a, const float* b, const float* bias, float* out,
+                  float* out_bias, void* ws, size_t ws_bytes, mf_stream_t stream);
 /* Host only (no GPU call): out[i] = the mask word idx0 + i of (seed, call, stream), i < n -- what the kernels compute, for tests. */
 int mf_dropout_words(uint64_t seed, uint64_t call, uint64_t stream, uint64_t idx0, int64_t n, uint64_t* out);
 /* grad_x lands on the item table through the coalesce engine of the pooled towers (one entry per token, key = its item id),

@@ -108,6 +108,12 @@ SIGNATURES = {
     "mf_xfmr_backward_dropout_ws_bytes": (c_sz, [c_i64, c_int, c_int]),
     "mf_xfmr_backward_dropout": (c_int, [c_int, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_f64, c_f64, c_u64, c_u64, c_vp]),
+    "mf_xfmr_forward_mixed": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_f64, c_f64, c_u64, c_u64, c_int, c_vp]),
+    "mf_xfmr_backward_mixed": (c_int, [c_int, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_f64, c_f64, c_u64, c_u64, c_int, c_vp]),
+    "mf_xfmr_dense_ws_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mf_xfmr_dense": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mf_dropout_words": (c_int, [c_u64, c_u64, c_u64, c_u64, c_i64, c_vp]),
     "mf_xfmr_coalesce_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_xfmr_coalesce": (c_int, [c_i64, c_int, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
@@ -115,6 +121,7 @@ SIGNATURES = {
 }
 
 MF_OK, MF_EINVAL, MF_ENOSPC, MF_ELAUNCH, MF_ENOTSUP = 0, -1, -2, -3, -4       # return codes (include/mf_hip.h)
+XFMR_FP32, XFMR_BF16_MIXED = 0, 1                         # precision of the transformer tower's dense layers (include/mf_hip.h)
 LOSS_TARGET_I64, LOSS_ROWC, LOSS_MASKS_READY = 1, 2, 4     # flags of mf_loss_fwd / mf_loss_bwd (include/mf_hip.h)
 
 _lib: ctypes.CDLL | None = None

@@ -1,5 +1,5 @@
 // mf_xfmr.hip -- the transformer user tower: u_b = normalize(pool(BertEncoder(rows of user b's last L history items))),
-// forward and backward, fp32 throughout, no float atomics, bit-reproducible.
+// forward and backward, fp32 throughout (bf16-mixed dense layers on request), no float atomics, bit-reproducible.
 //
 // Reference interface replaced: PoolingTransformer.forward(inputs_embeds) (xfmr_rec/models.py:66-84): a BERT encoder over
 // a [B, L, h] stack of embedding rows whose all-zero rows are padding, pooling_mode mean / max / cls, then Normalize.
@@ -31,6 +31,11 @@
 // adds.  The masks are counter-based (include/mf_numerics.h): a function of (seed, call, site, user, position, column),
 // generated where they are applied; nothing is stored and the backward regenerates the same bits.  Every kernel that can
 // drop is a template on that (DROP = false is the code the plain exports always ran), chosen per site on the host.
+//
+// Mixed precision (mf_xfmr_forward_mixed / mf_xfmr_backward_mixed, precision MF_XFMR_BF16_MIXED): the GEMMs of the six dense
+// layers per encoder layer, in all three forms, run on xfmr_gemm_bf16_kernel -- both operands rounded to bf16 (nearest even)
+// where they are staged, exact products, fp32 accumulation (v_mfma_f32_32x32x16_bf16), the same fp32 epilogue; db, outputs,
+// stash, parameters, gradients and every other kernel stay fp32.  MF_XFMR_FP32 launches what it always launched.
 #include "mf_coalesce.h"
 
 static constexpr int XFMR_MAX_L = 64;
@@ -420,6 +425,32 @@ struct XDropRows {
     const int32_t* tok_user;
     const int64_t* tok_off;
 };
+// the wave's 32 x 32 block of the tile (rows m0 + wm 32 .., columns n0 + wn 32 ..) -> memory, fp32 in both precisions
+template <bool DROP>
+__device__ __forceinline__ void xg_epilogue(const XGemm& g, const XDropRows& dr, float* __restrict__ C, const f32x16& acc, int64_t M,
+                                            int64_t m0, int64_t n0, int wm, int wn, int l31, int hh) {
+    const int64_t n = n0 + wn * 32 + l31;
+    if (n < g.N) {
+        const float bias = g.bias ? g.bias[n] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int64_t m = m0 + wm * 32 + mf_acc_row(e, hh);
+            if (m < M) {
+                const int64_t o = m * g.ldc + n;
+                float v = acc[e] + bias;
+                if constexpr (DROP) {
+                    const int64_t b = dr.tok_user[m];
+                    v = v * mf_dropout_mul(xdrop_hidden_word(dr.d, b, (int)(m - dr.tok_off[b]), (int)n), (int)n & 3, dr.d.thr, dr.d.scale);
+                }
+                if (g.R) v += g.R[o];
+                if (g.epi == XEPI_ACT) g.C2[o] = xfmr_act(v, g.act);
+                else if (g.epi == XEPI_DACT) v *= xfmr_dact(g.P[o], g.act);
+                C[o] = v;
+            }
+        }
+    }
+}
+
 template <bool DROP>
 __global__ __launch_bounds__(256) void xfmr_gemm_kernel(XGemm g, XDropRows dr) {
     __shared__ float As[16][XG_LD], Bs[16][XG_LD];
@@ -461,27 +492,93 @@ __global__ __launch_bounds__(256) void xfmr_gemm_kernel(XGemm g, XDropRows dr) {
             for (int kk = 0; kk < 16; ++kk) colsum += As[kk][threadIdx.x];
         }
     }
-    const int64_t n = n0 + wn * 32 + l31;
-    if (n < g.N) {
-        const float bias = g.bias ? g.bias[n] : 0.f;
+    xg_epilogue<DROP>(g, dr, C, acc, M, m0, n0, wm, wn, l31, hh);
+    if (want_colsum && m0 + threadIdx.x < M) C[(int64_t)g.M * g.N + m0 + threadIdx.x] = colsum;
+}
+
+// ---- the bf16-mixed form of the engine (precision MF_XFMR_BF16_MIXED) ----
+// The same tiles, operand forms, slices and epilogue; both operands are rounded to bf16 (round-to-nearest-even, the
+// conversion of (__bf16)) on their way from the fetch registers to LDS, the products are exact and the accumulation is fp32:
+// v_mfma_f32_32x32x16_bf16, whose operand of lane l is row l & 31, k = 8 (l >> 5) .. + 7 of a 16-deep step.  A stage is 64 rows
+// x 32 k, LDS[row][k] in bf16 (half the bytes of the fp32 tile for twice the k); what a fetch finds past the end of k (a token
+// tail, the second half of a 16-token slice) is zero.  The bias gradient stays the fp32 sum of the UNROUNDED dY: every thread
+// adds what it fetched (dyn = 1: A is row-contiguous, thread t holds row t & 63 at k = t / 64 mod 4), four partials per row
+// meet in LDS in a fixed order.
+typedef __bf16 xbf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 xbf16x8 __attribute__((ext_vector_type(8)));
+static constexpr int XGB_K = 32;        // k of a stage: two halves of 16, each one xg_fetch
+static constexpr int XGB_LD = 40;       // LDS row stride in bf16: 80 bytes, 16-byte rows, conflict-free 16-byte reads
+
+__device__ __forceinline__ void xgb_stage(__bf16 (*tile)[XGB_LD], int kc, int half, const f32x4& v) {
+    if (kc) {
+        const int r = threadIdx.x >> 2, k = 16 * half + (threadIdx.x & 3) * 4;
+        *reinterpret_cast<xbf16x4*>(&tile[r][k]) = xbf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+    } else {
+        const int r = threadIdx.x & 63, k = 16 * half + (threadIdx.x >> 6);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int64_t m = m0 + wm * 32 + mf_acc_row(e, hh);
-            if (m < M) {
-                const int64_t o = m * g.ldc + n;
-                float v = acc[e] + bias;
-                if constexpr (DROP) {
-                    const int64_t b = dr.tok_user[m];
-                    v = v * mf_dropout_mul(xdrop_hidden_word(dr.d, b, (int)(m - dr.tok_off[b]), (int)n), (int)n & 3, dr.d.thr, dr.d.scale);
-                }
-                if (g.R) v += g.R[o];
-                if (g.epi == XEPI_ACT) g.C2[o] = xfmr_act(v, g.act);
-                else if (g.epi == XEPI_DACT) v *= xfmr_dact(g.P[o], g.act);
-                C[o] = v;
+        for (int i = 0; i < 4; ++i) tile[r][k + 4 * i] = (__bf16)v[i];
+    }
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(256) void xfmr_gemm_bf16_kernel(XGemm g, XDropRows dr) {
+    __shared__ __attribute__((aligned(16))) __bf16 As[64][XGB_LD], Bs[64][XGB_LD];
+    __shared__ float cs[4][64];
+    const int64_t T = *g.T_dev;
+    const int64_t M = g.dyn == 0 ? T : g.M;
+    const int64_t m0 = (int64_t)blockIdx.x * 64, n0 = (int64_t)blockIdx.y * 64;
+    if (m0 >= M) return;
+    int64_t kbeg = 0, kend = g.K;
+    float* C = g.C;
+    if (g.dyn == 1) {
+        const int64_t len = xfmr_slice_len(T, XFMR_SLICES, 16);
+        kbeg = min((int64_t)blockIdx.z * len, T);
+        kend = min(kbeg + len, T);
+        C += (int64_t)blockIdx.z * g.slice_stride;
+    }
+    const int lane = mf_lane(), wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hh = lane >> 5;
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    float colsum = 0.f;
+    const bool want_colsum = g.dyn == 1 && blockIdx.y == 0;     // (whole workgroup)
+    f32x4 ra[2], rb[2];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        ra[half] = xg_fetch(g.A, g.lda, g.a_kc, m0, M, kbeg + 16 * half, kend);
+        rb[half] = xg_fetch(g.B, g.ldb, g.b_kc, n0, g.N, kbeg + 16 * half, kend);
+    }
+    for (int64_t k0 = kbeg; k0 < kend; k0 += XGB_K) {
+        __syncthreads();
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            xgb_stage(As, g.a_kc, half, ra[half]);
+            xgb_stage(Bs, g.b_kc, half, rb[half]);
+        }
+        if (want_colsum) colsum += ((ra[0][0] + ra[0][1]) + (ra[0][2] + ra[0][3])) + ((ra[1][0] + ra[1][1]) + (ra[1][2] + ra[1][3]));
+        __syncthreads();
+        if (k0 + XGB_K < kend) {                             // the next stage's loads fly under this stage's MFMAs
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                ra[half] = xg_fetch(g.A, g.lda, g.a_kc, m0, M, k0 + XGB_K + 16 * half, kend);
+                rb[half] = xg_fetch(g.B, g.ldb, g.b_kc, n0, g.N, k0 + XGB_K + 16 * half, kend);
             }
         }
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const xbf16x8 a = *reinterpret_cast<const xbf16x8*>(&As[wm * 32 + l31][16 * half + 8 * hh]);
+            const xbf16x8 b = *reinterpret_cast<const xbf16x8*>(&Bs[wn * 32 + l31][16 * half + 8 * hh]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+        }
     }
-    if (want_colsum && m0 + threadIdx.x < M) C[(int64_t)g.M * g.N + m0 + threadIdx.x] = colsum;
+    xg_epilogue<DROP>(g, dr, C, acc, M, m0, n0, wm, wn, l31, hh);
+    if (want_colsum) {
+        cs[wave][lane] = colsum;
+        __syncthreads();
+        if (threadIdx.x < 64 && m0 + threadIdx.x < M)
+            C[(int64_t)g.M * g.N + m0 + threadIdx.x] = (cs[0][threadIdx.x] + cs[1][threadIdx.x]) + (cs[2][threadIdx.x] + cs[3][threadIdx.x]);
+    }
 }
 
 // =========================================================================================== attention ====
@@ -784,20 +881,20 @@ extern "C" size_t mf_xfmr_ws_bytes(int64_t B, int64_t t_cap, int h, int layers, 
     return xfmr_stash(nullptr, B > 0 ? B : 1, t_cap, h, layers, I).total;
 }
 
-static void xfmr_gemm(hipStream_t s, int64_t t_cap, XGemm g) {
-    if (g.dyn == 0) {
-        const dim3 grid((unsigned)((t_cap + 63) / 64), (unsigned)((g.N + 63) / 64));
-        xfmr_gemm_kernel<false><<<grid, 256, 0, s>>>(g, XDropRows{});
-    } else {
-        const dim3 grid((unsigned)((g.M + 63) / 64), (unsigned)((g.N + 63) / 64), XFMR_SLICES);
-        xfmr_gemm_kernel<false><<<grid, 256, 0, s>>>(g, XDropRows{});
-    }
+// prec: MF_XFMR_FP32 launches xfmr_gemm_kernel, as every call did before there was a choice; MF_XFMR_BF16_MIXED its bf16 sibling
+static void xfmr_gemm(hipStream_t s, int64_t t_cap, XGemm g, int prec) {
+    const dim3 grid = g.dyn == 0 ? dim3((unsigned)((t_cap + 63) / 64), (unsigned)((g.N + 63) / 64))
+                                 : dim3((unsigned)((g.M + 63) / 64), (unsigned)((g.N + 63) / 64), XFMR_SLICES);
+    if (prec == MF_XFMR_BF16_MIXED) xfmr_gemm_bf16_kernel<false><<<grid, 256, 0, s>>>(g, XDropRows{});
+    else xfmr_gemm_kernel<false><<<grid, 256, 0, s>>>(g, XDropRows{});
 }
 // a linear whose result is dropped before its residual add (site d; d.thr = 0: the plain kernel)
-static void xfmr_gemm_dropped(hipStream_t s, int64_t t_cap, XGemm g, const XDrop& d, const int32_t* tok_user, const int64_t* tok_off) {
-    if (d.thr == 0) return xfmr_gemm(s, t_cap, g);
+static void xfmr_gemm_dropped(hipStream_t s, int64_t t_cap, XGemm g, int prec, const XDrop& d, const int32_t* tok_user,
+                              const int64_t* tok_off) {
+    if (d.thr == 0) return xfmr_gemm(s, t_cap, g, prec);
     const dim3 grid((unsigned)((t_cap + 63) / 64), (unsigned)((g.N + 63) / 64));
-    xfmr_gemm_kernel<true><<<grid, 256, 0, s>>>(g, XDropRows{d, tok_user, tok_off});
+    if (prec == MF_XFMR_BF16_MIXED) xfmr_gemm_bf16_kernel<true><<<grid, 256, 0, s>>>(g, XDropRows{d, tok_user, tok_off});
+    else xfmr_gemm_kernel<true><<<grid, 256, 0, s>>>(g, XDropRows{d, tok_user, tok_off});
 }
 
 // The dropout of one call: thresholds of the two probabilities (0 = off) and what the keys are made of.
@@ -847,13 +944,13 @@ static XGemm xg_dinput(const float* dY, int N, const float* W, int K, float* dX,
 }
 // dW [N, K] = dY [T, N]^T X [T, K], db [N] = column sums of dY: XFMR_SLICES partials in `part`, then the ordered sum
 static void xfmr_dweight(hipStream_t s, const float* dY, int N, const float* X, int K, float* dW, float* db, float* part,
-                         const int32_t* T_dev) {
+                         const int32_t* T_dev, int prec) {
     XGemm g{};
     g.A = dY; g.lda = N; g.a_kc = 0;
     g.B = X; g.ldb = K; g.b_kc = 0;
     g.C = part; g.ldc = K; g.M = N; g.N = K; g.T_dev = T_dev; g.dyn = 1;
     g.slice_stride = (int64_t)N * K + N;
-    xfmr_gemm(s, 0, g);
+    xfmr_gemm(s, 0, g, prec);
     const int64_t size = g.slice_stride;
     xfmr_reduce_kernel<<<dim3((unsigned)((size + 255) / 256)), 256, 0, s>>>(part, XFMR_SLICES, size, (int64_t)N * K, dW, db);
 }
@@ -877,7 +974,9 @@ static int xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t
                         const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
                         int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
                         float* out_u, float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, const XfmrDropout& drop,
-                        mf_stream_t stream) {
+                        int prec, mf_stream_t stream) {
+    if (prec != MF_XFMR_FP32 && prec != MF_XFMR_BF16_MIXED)
+        return mf_set_error(MF_EINVAL, "mf_xfmr_forward: precision %d is neither MF_XFMR_FP32 nor MF_XFMR_BF16_MIXED", prec);
     if (!table || !seg_start || !seg_end || !items || !params || !out_u || !out_inv || !stash || B <= 0 || n_rows <= 0 ||
         n_items <= 0 || t_cap < 0 || act < 0 || act > 3 || mode < 0 || mode > 2 || (mode == XPOOL_MAX && !out_arg))
         return mf_set_error(MF_EINVAL, "mf_xfmr_forward: bad argument");
@@ -912,9 +1011,9 @@ static int xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t
                 const float* const* w = params + XFMR_GLOBALS + XFMR_PER_LAYER * l;
                 const XfmrLayerStash& y = st.layer[l];
                 MF_TIMED("xfmr_gemm_fwd", s, {
-                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[0], w[1], h, y.q, nullptr, st.T_dev));
-                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[2], w[3], h, y.k, nullptr, st.T_dev));
-                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[4], w[5], h, y.v, nullptr, st.T_dev));
+                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[0], w[1], h, y.q, nullptr, st.T_dev), prec);
+                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[2], w[3], h, y.k, nullptr, st.T_dev), prec);
+                    xfmr_gemm(s, t_cap, xg_linear(x, h, w[4], w[5], h, y.v, nullptr, st.T_dev), prec);
                 });
                 MF_TIMED("xfmr_attn_fwd", s, {
                     if (drop.thr_attn) {
@@ -925,14 +1024,14 @@ static int xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t
                                                  y.q, y.k, y.v, st.tok_off, h, heads, y.ctx, XDrop{}));
                     }
                 });
-                MF_TIMED("xfmr_gemm_fwd", s, xfmr_gemm_dropped(s, t_cap, xg_linear(y.ctx, h, w[6], w[7], h, y.z1, x, st.T_dev),
+                MF_TIMED("xfmr_gemm_fwd", s, xfmr_gemm_dropped(s, t_cap, xg_linear(y.ctx, h, w[6], w[7], h, y.z1, x, st.T_dev), prec,
                                                                drop.attn_out(l), st.tok_user, st.tok_off));
                 XFMR_DISPATCH_H(h, xfmr_ln_kernel<H><<<gt, 256, 0, s>>>(y.z1, st.T_dev, w[8], w[9], y.y1, y.st1));
                 MF_TIMED("xfmr_gemm_fwd", s, {
                     XGemm g = xg_linear(y.y1, h, w[10], w[11], I, y.a, nullptr, st.T_dev);
                     g.epi = XEPI_ACT; g.act = act; g.C2 = y.f;
-                    xfmr_gemm(s, t_cap, g);
-                    xfmr_gemm_dropped(s, t_cap, xg_linear(y.f, I, w[12], w[13], h, y.z2, y.y1, st.T_dev), drop.ffn_out(l), st.tok_user,
+                    xfmr_gemm(s, t_cap, g, prec);
+                    xfmr_gemm_dropped(s, t_cap, xg_linear(y.f, I, w[12], w[13], h, y.z2, y.y1, st.T_dev), prec, drop.ffn_out(l), st.tok_user,
                                       st.tok_off);
                 });
                 XFMR_DISPATCH_H(h, xfmr_ln_kernel<H><<<gt, 256, 0, s>>>(y.z2, st.T_dev, w[14], w[15], y.y2, y.st2));
@@ -951,7 +1050,7 @@ extern "C" int mf_xfmr_forward(const float* table, int64_t n_rows, int h, const 
                                int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
                                float* out_u, float* out_inv, int32_t* out_arg, void* stash, size_t stash_bytes, mf_stream_t stream) {
     return xfmr_forward(table, n_rows, h, seg_start, seg_end, items, n_items, B, t_cap, max_history, layers, heads, intermediate, act, mode,
-                        norm_item, norm_user, params, out_u, out_inv, out_arg, stash, stash_bytes, XfmrDropout{}, stream);
+                        norm_item, norm_user, params, out_u, out_inv, out_arg, stash, stash_bytes, XfmrDropout{}, MF_XFMR_FP32, stream);
 }
 extern "C" int mf_xfmr_forward_dropout(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
                                        const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers,
@@ -959,11 +1058,21 @@ extern "C" int mf_xfmr_forward_dropout(const float* table, int64_t n_rows, int h
                                        const float* const* params, float* out_u, float* out_inv, int32_t* out_arg, void* stash,
                                        size_t stash_bytes, double p_hidden, double p_attn, uint64_t seed, uint64_t call,
                                        mf_stream_t stream) {
+    return mf_xfmr_forward_mixed(table, n_rows, h, seg_start, seg_end, items, n_items, B, t_cap, max_history, layers, heads, intermediate, act,
+                                 mode, norm_item, norm_user, params, out_u, out_inv, out_arg, stash, stash_bytes, p_hidden, p_attn, seed, call,
+                                 MF_XFMR_FP32, stream);
+}
+extern "C" int mf_xfmr_forward_mixed(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                                     const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers,
+                                     int heads, int intermediate, int act, int mode, int norm_item, int norm_user,
+                                     const float* const* params, float* out_u, float* out_inv, int32_t* out_arg, void* stash,
+                                     size_t stash_bytes, double p_hidden, double p_attn, uint64_t seed, uint64_t call, int precision,
+                                     mf_stream_t stream) {
     XfmrDropout drop;
     if (!xfmr_dropout(p_hidden, p_attn, seed, call, &drop))
         return mf_set_error(MF_EINVAL, "mf_xfmr_forward_dropout: dropout probabilities must be in [0, 1): %g, %g", p_hidden, p_attn);
     return xfmr_forward(table, n_rows, h, seg_start, seg_end, items, n_items, B, t_cap, max_history, layers, heads, intermediate, act, mode,
-                        norm_item, norm_user, params, out_u, out_inv, out_arg, stash, stash_bytes, drop, stream);
+                        norm_item, norm_user, params, out_u, out_inv, out_arg, stash, stash_bytes, drop, precision, stream);
 }
 
 // ============================================================================================ backward ====
@@ -1016,7 +1125,9 @@ static void xfmr_ln_bwd(hipStream_t s, const float* dy, const float* z, const fl
 static int xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads, int intermediate,
                          int act, int mode, int norm_user, const float* const* params, float* const* grads, const void* stash,
                          const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
-                         void* ws, size_t ws_bytes, const XfmrDropout& drop, bool dropout_ws, mf_stream_t stream) {
+                         void* ws, size_t ws_bytes, const XfmrDropout& drop, bool dropout_ws, int prec, mf_stream_t stream) {
+    if (prec != MF_XFMR_FP32 && prec != MF_XFMR_BF16_MIXED)
+        return mf_set_error(MF_EINVAL, "mf_xfmr_backward: precision %d is neither MF_XFMR_FP32 nor MF_XFMR_BF16_MIXED", prec);
     if (!params || !grads || !stash || !grad_u || !out_u || !out_inv || !grad_x || !ws || B <= 0 || t_cap <= 0 || act < 0 || act > 3 ||
         mode < 0 || mode > 2 || (mode == XPOOL_MAX && !out_arg) || max_pos < max_history)
         return mf_set_error(MF_EINVAL, "mf_xfmr_backward: bad argument");
@@ -1045,19 +1156,19 @@ static int xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int m
             XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dy, y.z2, y.st2, Td, p[14], w.dz, w.part, g[14], g[15], XLN_DROP_OUT, drop.ffn_out(l),
                                               st.tok_user, st.tok_off, dzm));
             MF_TIMED("xfmr_gemm_bwd", s, {
-                xfmr_dweight(s, dzm, h, y.f, I, g[12], g[13], w.part, Td);
+                xfmr_dweight(s, dzm, h, y.f, I, g[12], g[13], w.part, Td, prec);
                 XGemm d = xg_dinput(dzm, h, p[12], I, w.di, nullptr, Td);         // da = (mask dz2 Wo2) * act'(a)
                 d.epi = XEPI_DACT; d.act = act; d.P = y.a;
-                xfmr_gemm(s, t_cap, d);
-                xfmr_dweight(s, w.di, I, y.y1, h, g[10], g[11], w.part, Td);
-                xfmr_gemm(s, t_cap, xg_dinput(w.di, I, p[10], h, w.dt, w.dz, Td));  // dy1 = da Wi + dz2
+                xfmr_gemm(s, t_cap, d, prec);
+                xfmr_dweight(s, w.di, I, y.y1, h, g[10], g[11], w.part, Td, prec);
+                xfmr_gemm(s, t_cap, xg_dinput(w.di, I, p[10], h, w.dt, w.dz, Td), prec);  // dy1 = da Wi + dz2
             });
             // attention block: y1 = LN(z1), z1 = drop(ctx Wo^T + bo) + x
             XFMR_DISPATCH_H(h, xfmr_ln_bwd<H>(s, w.dt, y.z1, y.st1, Td, p[8], w.dz, w.part, g[8], g[9], XLN_DROP_OUT, drop.attn_out(l),
                                               st.tok_user, st.tok_off, dzm));
             MF_TIMED("xfmr_gemm_bwd", s, {
-                xfmr_dweight(s, dzm, h, y.ctx, h, g[6], g[7], w.part, Td);
-                xfmr_gemm(s, t_cap, xg_dinput(dzm, h, p[6], h, w.dctx, nullptr, Td));
+                xfmr_dweight(s, dzm, h, y.ctx, h, g[6], g[7], w.part, Td, prec);
+                xfmr_gemm(s, t_cap, xg_dinput(dzm, h, p[6], h, w.dctx, nullptr, Td), prec);
             });
             MF_TIMED("xfmr_attn_bwd", s, {
                 if (drop.thr_attn) {
@@ -1069,12 +1180,12 @@ static int xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int m
                 }
             });
             MF_TIMED("xfmr_gemm_bwd", s, {
-                xfmr_dweight(s, w.dq, h, x, h, g[0], g[1], w.part, Td);
-                xfmr_dweight(s, w.dk, h, x, h, g[2], g[3], w.part, Td);
-                xfmr_dweight(s, w.dv, h, x, h, g[4], g[5], w.part, Td);
-                xfmr_gemm(s, t_cap, xg_dinput(w.dq, h, p[0], h, w.dy, w.dz, Td));   // dx = dz1 + dq Wq + dk Wk + dv Wv
-                xfmr_gemm(s, t_cap, xg_dinput(w.dk, h, p[2], h, w.dy, w.dy, Td));
-                xfmr_gemm(s, t_cap, xg_dinput(w.dv, h, p[4], h, w.dy, w.dy, Td));
+                xfmr_dweight(s, w.dq, h, x, h, g[0], g[1], w.part, Td, prec);
+                xfmr_dweight(s, w.dk, h, x, h, g[2], g[3], w.part, Td, prec);
+                xfmr_dweight(s, w.dv, h, x, h, g[4], g[5], w.part, Td, prec);
+                xfmr_gemm(s, t_cap, xg_dinput(w.dq, h, p[0], h, w.dy, w.dz, Td), prec);   // dx = dz1 + dq Wq + dk Wk + dv Wv
+                xfmr_gemm(s, t_cap, xg_dinput(w.dk, h, p[2], h, w.dy, w.dy, Td), prec);
+                xfmr_gemm(s, t_cap, xg_dinput(w.dv, h, p[4], h, w.dy, w.dy, Td), prec);
             });
         }
         // embeddings: x0 = drop(LN(z0)), z0 = (x + tok[0]) + pos[t]
@@ -1094,18 +1205,66 @@ extern "C" int mf_xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history
                                 const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
                                 void* ws, size_t ws_bytes, mf_stream_t stream) {
     return xfmr_backward(h, B, t_cap, max_history, max_pos, layers, heads, intermediate, act, mode, norm_user, params, grads, stash, grad_u,
-                         out_u, out_inv, out_arg, grad_x, ws, ws_bytes, XfmrDropout{}, false, stream);
+                         out_u, out_inv, out_arg, grad_x, ws, ws_bytes, XfmrDropout{}, false, MF_XFMR_FP32, stream);
 }
 extern "C" int mf_xfmr_backward_dropout(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads,
                                         int intermediate, int act, int mode, int norm_user, const float* const* params,
                                         float* const* grads, const void* stash, const float* grad_u, const float* out_u,
                                         const float* out_inv, const int32_t* out_arg, float* grad_x, void* ws, size_t ws_bytes,
                                         double p_hidden, double p_attn, uint64_t seed, uint64_t call, mf_stream_t stream) {
+    return mf_xfmr_backward_mixed(h, B, t_cap, max_history, max_pos, layers, heads, intermediate, act, mode, norm_user, params, grads, stash,
+                                  grad_u, out_u, out_inv, out_arg, grad_x, ws, ws_bytes, p_hidden, p_attn, seed, call, MF_XFMR_FP32, stream);
+}
+extern "C" int mf_xfmr_backward_mixed(int h, int64_t B, int64_t t_cap, int max_history, int max_pos, int layers, int heads,
+                                      int intermediate, int act, int mode, int norm_user, const float* const* params,
+                                      float* const* grads, const void* stash, const float* grad_u, const float* out_u,
+                                      const float* out_inv, const int32_t* out_arg, float* grad_x, void* ws, size_t ws_bytes,
+                                      double p_hidden, double p_attn, uint64_t seed, uint64_t call, int precision, mf_stream_t stream) {
     XfmrDropout drop;
     if (!xfmr_dropout(p_hidden, p_attn, seed, call, &drop))
         return mf_set_error(MF_EINVAL, "mf_xfmr_backward_dropout: dropout probabilities must be in [0, 1): %g, %g", p_hidden, p_attn);
     return xfmr_backward(h, B, t_cap, max_history, max_pos, layers, heads, intermediate, act, mode, norm_user, params, grads, stash, grad_u,
-                         out_u, out_inv, out_arg, grad_x, ws, ws_bytes, drop, true, stream);
+                         out_u, out_inv, out_arg, grad_x, ws, ws_bytes, drop, true, precision, stream);
+}
+
+// =============================================================================================== dense ====
+// ONE dense operation of the engine on the caller's buffers, through the tower's launch helpers: what holds the engine to its
+// arithmetic contract without an encoder around it.  Workspace: the token count the kernels read, then (form 2) the partials.
+struct XfmrDenseWs {
+    int32_t* T_dev;
+    float* part;
+    size_t total;
+};
+static XfmrDenseWs xfmr_dense_ws(void* p, int form, int N, int K) {
+    MfArena a(p);
+    XfmrDenseWs w;
+    w.T_dev = a.take<int32_t>(1);
+    w.part = form == 2 ? a.take<float>((size_t)XFMR_SLICES * ((size_t)N * K + N)) : nullptr;
+    w.total = a.used();
+    return w;
+}
+static bool xfmr_dense_shape(int form, int N, int K) {
+    return form >= 0 && form <= 2 && N >= 32 && N <= 512 && N % 32 == 0 && K >= 32 && K <= 512 && K % 32 == 0;
+}
+extern "C" size_t mf_xfmr_dense_ws_bytes(int form, int N, int K) {
+    return xfmr_dense_shape(form, N, K) ? xfmr_dense_ws(nullptr, form, N, K).total : 0;
+}
+extern "C" int mf_xfmr_dense(int form, int precision, int64_t M, int N, int K, const float* a, const float* b, const float* bias,
+                             float* out, float* out_bias, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    if (form < 0 || form > 2) return mf_set_error(MF_EINVAL, "mf_xfmr_dense: form %d not in 0..2", form);
+    if (precision != MF_XFMR_FP32 && precision != MF_XFMR_BF16_MIXED)
+        return mf_set_error(MF_EINVAL, "mf_xfmr_dense: precision %d is neither MF_XFMR_FP32 nor MF_XFMR_BF16_MIXED", precision);
+    if (!a || !b || !out || !ws || (form == 2 && !out_bias) || M < 1 || M >= (1ll << 31))
+        return mf_set_error(MF_EINVAL, "mf_xfmr_dense: bad argument");
+    if (!xfmr_dense_shape(form, N, K)) return mf_set_error(MF_ENOTSUP, "mf_xfmr_dense: N = %d, K = %d not multiples of 32 in [32, 512]", N, K);
+    if (ws_bytes < xfmr_dense_ws(nullptr, form, N, K).total) return mf_set_error(MF_ENOSPC, "mf_xfmr_dense: workspace too small");
+    const XfmrDenseWs w = xfmr_dense_ws(ws, form, N, K);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.T_dev), (int)M, 1, s) != hipSuccess) return mf_check_launch("mf_xfmr_dense");
+    if (form == 0) xfmr_gemm(s, M, xg_linear(a, K, b, bias, N, out, nullptr, w.T_dev), precision);
+    else if (form == 1) xfmr_gemm(s, M, xg_dinput(a, N, b, K, out, nullptr, w.T_dev), precision);
+    else xfmr_dweight(s, a, N, b, K, out, out_bias, w.part, w.T_dev, precision);
+    return mf_check_launch("mf_xfmr_dense");
 }
 
 // ============================================================================================ coalesce ====

@@ -49,6 +49,9 @@ class ModelConfig(pydantic.BaseModel):
     hidden_dropout_prob: float = 0.0
     attention_probs_dropout_prob: float = 0.0
     dropout_seed: int = 0
+    # arithmetic of that encoder's dense layers: "bf16-mixed" rounds both operands of their GEMMs to bf16 and accumulates in
+    # fp32 (the reference trains under precision "bf16-mixed", xfmr_rec/lightning.py trainer_defaults); see check_precision
+    precision: Literal["fp32", "bf16-mixed"] = "fp32"
     # "features": the vector is the pooled hashed-attribute tokens of the entity (FeatureBagTower); when both towers are
     # feature towers they share ONE bucket table, as the reference's towers share one encoder (lightning.py:60-74)
     item_tower: Literal["table", "features"] = "table"
@@ -79,6 +82,14 @@ class ModelConfig(pydantic.BaseModel):
                 msg = f"{name} is the dropout of user_tower='transformer' (no other tower has dropout): {name} = {p}, {self.user_tower = }"
                 raise ValueError(msg)
         check_dropout_seed(self.dropout_seed)
+        return self
+
+    @pydantic.model_validator(mode="after")
+    def _check_precision(self):
+        if check_precision(self.precision) != "fp32" and self.user_tower != "transformer":
+            msg = (f"precision is the arithmetic of user_tower='transformer' (no other tower has a precision mode): "
+                   f"{self.precision = }, {self.user_tower = }")
+            raise ValueError(msg)
         return self
 
     @pydantic.field_validator("max_history")
@@ -173,6 +184,18 @@ def check_dropout_prob(p: float, name: str = "p") -> float:
         msg = f"{name} must be in [0, 1): {p}"
         raise ValueError(msg)
     return p
+
+
+PRECISIONS = ("fp32", "bf16-mixed")                      # the kernels' precision codes, in this order (include/mf_hip.h)
+
+
+def check_precision(precision: str) -> str:
+    """``"fp32"``, or ``"bf16-mixed"``: both operands of every GEMM of the encoder's six dense layers per layer (forward and
+    both backward forms) rounded to bf16, fp32 accumulation, everything else fp32 (*Mixed precision*)."""
+    if precision not in PRECISIONS:
+        msg = f"precision must be one of {PRECISIONS}: {precision = }"
+        raise ValueError(msg)
+    return precision
 
 
 def check_dropout_seed(seed: int) -> int:
@@ -505,6 +528,7 @@ class _EncodeHistory(torch.autograd.Function):
                 *params: torch.Tensor):
         layers, heads, inter, act, mode, max_history, norm_item, norm_user = cfg[:8]
         drop = cfg[8] if len(cfg) > 8 else None      # (p_hidden, p_attn, seed, call): the *_dropout exports; None: the plain ones
+        prec = cfg[9] if len(cfg) > 9 else _lib.XFMR_FP32    # not fp32: the *_mixed exports (dropout or not)
         _check_table(table, "embedding")
         if torch.cuda.is_current_stream_capturing():
             raise _lib.MfHipError("the transformer tower does not support hipGraph capture")
@@ -524,11 +548,13 @@ class _EncodeHistory(torch.autograd.Function):
         args = (table.data_ptr(), rows, d, start.data_ptr(), end.data_ptr(), items.data_ptr(), items.numel(), b, t_cap, max_history,
                 layers, heads, inter, act, mode, int(norm_item), int(norm_user), _pointer_array(params), u.data_ptr(), inv.data_ptr(),
                 _lib.ptr(arg), stash.data_ptr(), stash.numel())
-        if drop is None:
+        if prec != _lib.XFMR_FP32:
+            _lib.check(lib.mf_xfmr_forward_mixed(*args, *(drop or (0.0, 0.0, 0, 0)), prec, _lib.stream_ptr()))
+        elif drop is None:
             _lib.check(lib.mf_xfmr_forward(*args, _lib.stream_ptr()))
         else:
             _lib.check(lib.mf_xfmr_forward_dropout(*args, *drop, _lib.stream_ptr()))
-        ctx.table, ctx.stash, ctx.arg, ctx.params, ctx.drop = table, stash, arg, params, drop
+        ctx.table, ctx.stash, ctx.arg, ctx.params, ctx.drop, ctx.prec = table, stash, arg, params, drop, prec
         ctx.b, ctx.t_cap, ctx.shape, ctx.mode = b, t_cap, (layers, heads, inter, act), mode
         ctx.max_history, ctx.norm_item, ctx.norm_user = max_history, bool(norm_item), bool(norm_user)
         ctx.save_for_backward(u, inv)
@@ -546,13 +572,16 @@ class _EncodeHistory(torch.autograd.Function):
         lib = _lib.lib()
         g = grad_u.to(torch.float32).contiguous()
         grad_x = torch.empty(ctx.t_cap, d, dtype=torch.float32, device=u.device)
-        drop = ctx.drop
-        ws_bytes = lib.mf_xfmr_backward_ws_bytes if drop is None else lib.mf_xfmr_backward_dropout_ws_bytes
+        drop, prec = ctx.drop, ctx.prec
+        plain = drop is None and prec == _lib.XFMR_FP32
+        ws_bytes = lib.mf_xfmr_backward_ws_bytes if plain else lib.mf_xfmr_backward_dropout_ws_bytes
         ws = _lib.workspace(ws_bytes(ctx.t_cap, d, inter), u.device)
         args = (d, ctx.b, ctx.t_cap, ctx.max_history, params[0].shape[0], layers, heads, inter, act, ctx.mode, int(ctx.norm_user),
                 _pointer_array(params), _pointer_array(grads), ctx.stash.data_ptr(), g.data_ptr(), u.data_ptr(), inv.data_ptr(),
                 _lib.ptr(ctx.arg), grad_x.data_ptr(), ws.data_ptr(), ws.numel())
-        if drop is None:
+        if prec != _lib.XFMR_FP32:                   # the forward's precision
+            _lib.check(lib.mf_xfmr_backward_mixed(*args, *(drop or (0.0, 0.0, 0, 0)), prec, _lib.stream_ptr()))
+        elif drop is None:
             _lib.check(lib.mf_xfmr_backward(*args, _lib.stream_ptr()))
         else:                                        # the same (seed, call): the kernels regenerate the forward's masks
             _lib.check(lib.mf_xfmr_backward_dropout(*args, *drop, _lib.stream_ptr()))
@@ -587,14 +616,21 @@ class HistoryTransformerTower(torch.nn.Module):
     ``mf_xfmr_backward_dropout`` -- no mask tensor exists and the backward regenerates the same bits, so a step is
     bit-reproducible.  Each training forward uses the next ``call`` number (``self.dropout_call``, a Python int);
     :meth:`manual_seed` sets the seed and resets the counter.  Seed and counter are NOT part of ``state_dict`` (its names
-    keep mirroring ``BertModel``): a resumed run that wants the same masks calls ``manual_seed`` itself."""
+    keep mirroring ``BertModel``): a resumed run that wants the same masks calls ``manual_seed`` itself.
+
+    **Precision**: ``precision="bf16-mixed"`` (default ``"fp32"``) rounds both operands of every GEMM of the six dense layers
+    of each encoder layer to bf16 (round-to-nearest-even), forward and backward, and accumulates in fp32
+    (``mf_xfmr_forward_mixed`` / ``mf_xfmr_backward_mixed``); outputs, parameters, gradients and everything else stay fp32,
+    and a step stays bit-reproducible.  This is autocast's treatment of ``nn.Linear`` without the bf16 outputs; the attention
+    matmuls stay fp32.  The mode is the tower's in training, evaluation and serving alike."""
 
     def __init__(self, item_tower: torch.nn.Module, *, num_hidden_layers: int = 1, num_attention_heads: int = 4,
                  intermediate_size: int | None = None, hidden_act: str = "gelu", max_position_embeddings: int = 64,
                  pooling_mode: str = "mean", max_history: int | None = None, normalize: bool = True,
                  initializer_range: float = 0.02, device=None, hidden_dropout_prob: float = 0.0,
-                 attention_probs_dropout_prob: float = 0.0, dropout_seed: int = 0) -> None:
+                 attention_probs_dropout_prob: float = 0.0, dropout_seed: int = 0, precision: str = "fp32") -> None:
         super().__init__()
+        self.precision = check_precision(precision)
         self.hidden_dropout_prob = check_dropout_prob(hidden_dropout_prob, "hidden_dropout_prob")
         self.attention_probs_dropout_prob = check_dropout_prob(attention_probs_dropout_prob, "attention_probs_dropout_prob")
         self.manual_seed(dropout_seed)
@@ -679,12 +715,15 @@ class HistoryTransformerTower(torch.nn.Module):
         if self.training and (self.hidden_dropout_prob > 0.0 or self.attention_probs_dropout_prob > 0.0):
             cfg += ((self.hidden_dropout_prob, self.attention_probs_dropout_prob, self.dropout_seed, self.dropout_call),)
             self.dropout_call += 1
+        if self.precision != "fp32":
+            cfg = cfg[:8] + (cfg[8] if len(cfg) > 8 else None, PRECISIONS.index(self.precision))  # noqa: PLR2004
         return _EncodeHistory.apply(self.weight, start, end, items, n_entries, cfg, *self.encoder_parameters())
 
     def extra_repr(self) -> str:
         return (f"layers={self.num_hidden_layers}, heads={self.num_attention_heads}, intermediate={self.intermediate_size}, "
                 f"act={self.hidden_act}, pooling_mode={self.pooling_mode}, max_history={self.max_history}, normalize={self.normalize}, "
-                f"hidden_dropout_prob={self.hidden_dropout_prob}, attention_probs_dropout_prob={self.attention_probs_dropout_prob}")
+                f"hidden_dropout_prob={self.hidden_dropout_prob}, attention_probs_dropout_prob={self.attention_probs_dropout_prob}"
+                + (f", precision={self.precision}" if self.precision != "fp32" else ""))
 
 
 class FeatureBagGrad(PooledGrad):
@@ -842,7 +881,7 @@ def init_towers(config: ModelConfig, device=None) -> torch.nn.ModuleDict:
                                        pooling_mode=config.pooling_mode, max_history=config.max_history,
                                        normalize=config.normalize, device=device, hidden_dropout_prob=config.hidden_dropout_prob,
                                        attention_probs_dropout_prob=config.attention_probs_dropout_prob,
-                                       dropout_seed=config.dropout_seed)
+                                       dropout_seed=config.dropout_seed, precision=config.precision)
         return torch.nn.ModuleDict({"user": user, "item": item})
     if config.user_tower == "history":
         if config.num_hashes > 0:

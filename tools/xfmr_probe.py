@@ -21,6 +21,11 @@ the step that dropout adds: mask generation, the masked multiplies and the backw
 every step measurement N times (``ms_per_step_runs``: the spread that a comparison between two libraries has to respect);
 ``--transformer-only`` skips the history-tower steps.  A library without the dropout exports (the parent commit's) still runs
 the p = 0 step: the exports it lacks are left unbound.
+
+    python tools/xfmr_probe.py --transformer-only --repeat 3 --precision bf16-mixed --out mixed.json
+
+``--precision`` (default fp32) is passed to the tower; the GEMM spans' rate stays the algorithmic flops over the span time,
+and its fraction stays the one of the fp32 matrix peak, so that the two precisions read on one scale.
 """
 from __future__ import annotations
 
@@ -76,15 +81,18 @@ def main() -> None:
     ap.add_argument("--transformer-only", action="store_true")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--dropout", type=float, nargs=2, metavar=("P_HIDDEN", "P_ATTN"))
+    ap.add_argument("--precision", choices=("fp32", "bf16-mixed"), default="fp32")
     args = ap.parse_args()
     mf = importlib.import_module("matrix-factorization-torch_amd")
     have = ctypes.CDLL(str(mf._lib.LIB_PATH))   # another build of the library may not have the newest exports
-    new = lambda n: "dropout" in n or (args.baseline_only and n.startswith("mf_xfmr_"))  # noqa: E731
+    new = lambda n: "dropout" in n or "mixed" in n or "xfmr_dense" in n or (args.baseline_only and n.startswith("mf_xfmr_"))  # noqa: E731
     missing = [n for n in mf._lib.SIGNATURES if new(n) and not hasattr(have, n)]
     for name in missing:
         del mf._lib.SIGNATURES[name]
     if args.dropout and missing:
         raise SystemExit(f"--dropout needs the dropout exports, which {mf._lib.LIB_PATH} lacks")
+    if args.precision != "fp32" and missing:
+        raise SystemExit(f"--precision {args.precision} needs the mixed exports, which {mf._lib.LIB_PATH} lacks")
     lib = mf._lib.lib()
     torch.manual_seed(0)
     table = hp.synthetic_table(mf, args.ratings)
@@ -100,6 +108,8 @@ def main() -> None:
         plain = None
         for user_tower, dropout in variants:
             kw = {"hidden_dropout_prob": dropout[0], "attention_probs_dropout_prob": dropout[1]} if dropout else {}
+            if user_tower == "transformer" and args.precision != "fp32":
+                kw["precision"] = args.precision
             cfg = mf.models.ModelConfig(num_items=hp.ITEMS, hidden_size=d, user_tower=user_tower, max_history=L, intermediate_size=inter,
                                         num_hidden_layers=1, num_attention_heads=4, **kw)
             towers = mf.models.init_towers(cfg, device="cuda")
@@ -124,6 +134,8 @@ def main() -> None:
             runs = [median_ms(step) for _ in range(max(1, args.repeat))]
             case = {"user_tower": user_tower, "d": d, "L": L, "I": inter, "ms_per_step": statistics.median(runs), "ms_per_step_runs": runs,
                     "spans": spans(mf, lib, step)}
+            if user_tower == "transformer":
+                case["precision"] = args.precision
             if user_tower == "transformer" and dropout is None:
                 plain = case
             if dropout:

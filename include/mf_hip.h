@@ -183,6 +183,22 @@ int mf_loss_bwd(int64_t B, int64_t N, int d, int P, int num_negatives, float sig
  * to compare the two on small shapes); mode 0: the fp32 search everywhere.  MF_MINE_BF=0|1|2 in the environment sets the initial
  * mode.  Process-wide; not a per-stream setting. */
 void mf_set_mining_prefilter(int mode);
+/* The dense (unmined) losses at d = 128 sweep each DISTINCT item column of the batch once, weighted by its copy count
+ * (csrc/mf_loss_cols.h): column j is a copy of the first column f with its item id iff v[j] equals v[f] and logq[j] equals
+ * logq[f] bit for bit -- decided on the values, on the device, per batch.  Loss and gradients hold to the tolerances of the
+ * uncompacted sweeps, not to their bits (each distinct column is summed once with a weight).  mode 1 (default): from 4096
+ * columns upward; mode 2: wherever it can serve (tests); mode 0: never.  Not served, and bit for bit as before: every other
+ * width, the mined losses, masks prepared by mf_loss_masks, a forward that exports its mask.  A backward follows the path
+ * its forward took on that workspace, whatever the mode is by then.  Process-wide. */
+void mf_set_dense_dedup(int mode);
+/* Tests and tools only (a device -> host copy; never inside a step): out[9] = {served, N' (distinct columns), NT' (tiles
+ * streamed), forward (splits, tiles per split), dU (the same), dV (the same)} of the last forward on this workspace. */
+int mf_loss_cols_info(const void* ws, int64_t* out);
+/* Host-only: the geometry the device derives for `ncols` distinct columns of a shape, with what is launched and allocated
+ * around it: out[16] = {can serve, NT', forward (splits, tps), dU (splits, tps), dV (splits, tps), dV X blocks, launched:
+ * forward splits, dU splits, dV workgroups, capacity of the partial buffers: forward splits, dU splits, dV X blocks, 0}.
+ * With ncols = N the geometry is mf_loss_plan's. */
+int mf_loss_cols_plan(int64_t B, int64_t N, int d, int64_t ncols, int64_t* out);
 /* Host-only view of the prefilter's plan for a shape (nothing is launched, no GPU needed): out[8] = {ok (it can serve the
  * shape), pays (mode 1 uses it), item chunks, tiles per chunk, rescoring lanes per chunk, lists per user, capacity of the
  * rescoring wave's key array, its LDS bytes}.  d outside {64, 128}: ok = 0 and the last two are 0. */

@@ -47,6 +47,9 @@ SIGNATURES = {
     "mf_negative_masks_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_negative_masks": (c_int, [c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
     "mf_set_mining_prefilter": (None, [c_int]),
+    "mf_set_dense_dedup": (None, [c_int]),
+    "mf_loss_cols_info": (c_int, [c_vp, ctypes.POINTER(c_i64)]),
+    "mf_loss_cols_plan": (c_int, [c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_i64)]),
     "mf_mining_prefilter_plan": (c_int, [c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64)]),
     "mf_mine_logits": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp]),
     "mf_update_ws_bytes": (c_sz, [c_i64, c_int]),

@@ -15,9 +15,12 @@
 // alignment/contrastive/infonce/mine :164-246, pairwise :324-359, reduction
 // `(loss * target.abs()).sum()`.  Formulas: SURVEY.md Appendix A.
 #include <cfloat>
+#include <mutex>
 #include <type_traits>
+#include <unordered_map>
 
 #include "mf_common.h"
+#include "mf_loss_cols.h"
 #include "mf_loss_math.h"
 #include "mf_mine_bf.h"
 #include "mf_select.h"
@@ -71,6 +74,12 @@ struct LossWs {
     uint32_t* mbf_pcnt;
     long long* dvfix;            // mined backward: exact fixed-point accumulator of dv [N][d]
     float* dvsc;                 // its unit for this batch: {2^E, clamp, 2^-E} (dv_fix_of, mf_loss_math.h)
+    // the column plan (mf_loss_cols.h; dense path at d = 128): geometry words, the plan's scratch, the packed side arrays
+    bool cols_ok;                // the shape can be served by the distinct-column sweeps
+    ColsLaunch cl;               // what those sweeps launch, whatever N' is
+    int wgs_f, wgs_b;            // workgroups the forward / the backward sweeps aim at
+    int32_t *geo, *ckept, *ccnt, *ctcnt, *crank, *cfirst;
+    float *cv, *cnv, *clq, *cw;
     size_t total;
 };
 
@@ -78,14 +87,6 @@ struct LossWs {
 #define BWD_MIN_WG 2      // A/B knob: workgroups per CU the backward sweeps are compiled for at d = 128 ...
 #define BWD_WGS 512       // ... and their grid size
 #endif
-
-static void split_geometry(int x_tiles, int y_tiles, int* nsplit, int* tps, int target_blocks) {
-    int want = (target_blocks + x_tiles - 1) / x_tiles;
-    if (want < 1) want = 1;
-    if (want > y_tiles) want = y_tiles;
-    *tps = (y_tiles + want - 1) / want;
-    *nsplit = (y_tiles + *tps - 1) / *tps;
-}
 
 static bool mining_on(int num_negatives, int64_t N) { return num_negatives > 0 && num_negatives < N; }
 
@@ -99,13 +100,18 @@ static LossWs loss_ws(void* base, int64_t B, int64_t N, int d, int P, int num_ne
     w.mined = mining_on(num_negatives, N);
     // enough workgroups for two waves per SIMD: 256 of eight waves, 512 of four
     const int wgs = 2048 / w.NW;
-    split_geometry(w.BT / w.NW, w.NT, &w.nsplit_f, &w.tps_f, wgs);
-    split_geometry(w.BT / w.NW, w.NT, &w.nsplit_u, &w.tps_u, d == 128 ? BWD_WGS : wgs);
-    split_geometry(w.NT / w.NW, w.BT, &w.nsplit_v, &w.tps_v, d == 128 ? BWD_WGS : wgs);
+    w.wgs_f = wgs; w.wgs_b = d == 128 ? BWD_WGS : wgs;
+    split_geometry(w.BT / w.NW, w.NT, &w.nsplit_f, &w.tps_f, w.wgs_f);
+    split_geometry(w.BT / w.NW, w.NT, &w.nsplit_u, &w.tps_u, w.wgs_b);
+    split_geometry(w.NT / w.NW, w.BT, &w.nsplit_v, &w.tps_v, w.wgs_b);
+    // (a sweep's buffer descriptor may have to cover the whole streamed operand: tiles per split are only known on the device)
+    w.cols_ok = !w.mined && d == 128 && (size_t)w.Np * d * 4 <= MF_SRD_MAX_BYTES;
+    w.cl = cols_launch(w.BT, w.NT, w.NW, w.wgs_f, w.wgs_b);
     const int k = num_negatives;
     w.plan = mf_select_plan(B, N, d, k);
     w.T = w.plan.T; w.CAP = w.plan.CAP; w.nchunk = w.plan.nsets; w.tpc = w.plan.tpc;
     MfArena a(base);
+    w.geo = a.take<int32_t>(CG_WORDS);                            // (first: mf_loss_cols_info finds it without the shape)
     w.nu = a.take<float>(w.Bp); w.nv = a.take<float>(w.Np);
     w.lii = a.take<float>(w.Bp); w.dii = a.take<float>(w.Bp); w.sgn = a.take<float>(w.Bp);
     w.logq = a.take<float>(w.Np);
@@ -122,7 +128,8 @@ static LossWs loss_ws(void* base, int64_t B, int64_t N, int d, int P, int num_ne
     w.bmap = a.take<uint32_t>((size_t)1 << (w.bmbits - 5));
     w.ubits = a.take<uint32_t>((size_t)HITS_PLANES * w.Np * (w.Bp / 32));        // ubits [plane][user / 32][column]
     w.maskW = a.take<uint32_t>((size_t)w.NT * w.Bp);
-    w.part = a.take<float>((size_t)w.nsplit_f * NSTAT * w.Bp);
+    // (the distinct-column sweeps are launched for the most splits any N' <= N can ask for: >= the uncompacted ones)
+    w.part = a.take<float>((size_t)(w.cols_ok ? w.cl.grid_f : w.nsplit_f) * NSTAT * w.Bp);
     w.stats = a.take<float>((size_t)NSTAT * w.Bp);
     w.rowloss = a.take<float>((size_t)MF_NUM_KINDS * w.Bp);
     w.rowc = a.take<float>((size_t)4 * w.Bp);
@@ -158,7 +165,22 @@ static LossWs loss_ws(void* base, int64_t B, int64_t N, int d, int P, int num_ne
         w.dpart = nullptr;
     } else {
         // the two backward sweeps keep their split partials apart: ONE launch adds up both after the second sweep
-        const size_t rows = (size_t)w.nsplit_u * w.Bp, rows_v = (size_t)w.nsplit_v * w.Np;
+        size_t rows = (size_t)w.nsplit_u * w.Bp, rows_v = (size_t)w.nsplit_v * w.Np;
+        if (w.cols_ok) {
+            // the partials are sized by LAUNCHED workgroups (each writes one X block of 32 NW rows), not by nsplit x padded rows
+            const size_t xb = (size_t)32 * w.NW;
+            rows = (size_t)w.cl.grid_u * w.Bp;
+            if ((size_t)w.cl.grid_v * xb > rows_v) rows_v = (size_t)w.cl.grid_v * xb;
+            w.ckept = a.take<int32_t>((size_t)w.Np);
+            w.ccnt = a.take<int32_t>((size_t)w.Np);
+            w.ctcnt = a.take<int32_t>((size_t)w.NT);
+            w.crank = a.take<int32_t>((size_t)w.Np);
+            w.cfirst = a.take<int32_t>((size_t)w.Np);
+            w.cnv = a.take<float>((size_t)w.Np);
+            w.clq = a.take<float>((size_t)w.Np);
+            w.cw = a.take<float>((size_t)w.Np);
+            w.cv = a.take<float>((size_t)w.Np * d);
+        }
         w.dpart = a.take<float>(rows * d);
         w.rpart = a.take<float>(rows);
         w.dpart_v = a.take<float>(rows_v * d);
@@ -587,6 +609,10 @@ struct FwdParams {
     // side inputs of a tile as ONE buffer: byte offsets of maskW / nv / logq from aux_base, and the span covered
     const char* aux_base;
     uint32_t aux_mask, aux_nv, aux_lq, aux_bytes;
+    // distinct-column sweep (CP): v, nv, logq, maskW are the packed arrays, N their padded height; the tile range comes from
+    // the device words, the column weights ride in lanes 24..31 of the side-input DMA
+    const int32_t* geo;
+    uint32_t aux_w;
 };
 
 // Workgroup = 4 waves x 32 users; item tiles arrive through a 2-slot LDS ring filled by LDS-DMA, together with
@@ -601,7 +627,7 @@ struct FwdLds {
     using G = TileGeom<D>;
     // side inputs: one 1-KiB DMA per wave and tile -- lanes 0..7 the wave's 32 mask words, 8..15 the tile's item
     // norms, 16..23 its -logq (every wave keeps its own copy: no cross-wave dependency), the other lanes zeros
-    static constexpr int AUX_NV = 128, AUX_LQ = 256, AUXW = 1024, AUXB = G::NW * AUXW;
+    static constexpr int AUX_NV = 128, AUX_LQ = 256, AUX_CW = 384, AUXW = 1024, AUXB = G::NW * AUXW;
     static constexpr int AUX0 = 2 * G::TILEB;           // 4 side-input slots after the 2 tile slots
     static constexpr int BYTES = AUX0 + 4 * AUXB;
     static constexpr int NG = D / 8;                    // MFMA groups per tile
@@ -632,8 +658,26 @@ __device__ __forceinline__ void stats_add_masked(RowStats& s, float Lm, float sm
         }
     }
 }
+// the same with a column weight (the copies of a distinct column): every summed term times cw (a masked term is 0 x cw = 0)
+template <int NEED>
+__device__ __forceinline__ void stats_add_masked_w(RowStats& s, float Lm, float sm, float lii, float margin, float cw) {
+    if (NEED & NEED_CONTR) s.A = __builtin_fmaf(cw, fmaxf(Lm + sm, 0.f), s.A);
+    if (NEED & (NEED_HINGE | NEED_LOGI)) {
+        const float x = (Lm - lii) + margin;
+        if (NEED & NEED_HINGE) {
+            s.H = __builtin_fmaf(cw, fmaxf(x, 0.f), s.H);
+            s.Hc += x > 0.f ? cw : 0.f;
+        }
+        if (NEED & NEED_LOGI) {
+            float sp, sg;
+            softplus_sigmoid(x, sp, sg);
+            s.Lg = __builtin_fmaf(cw, sp, s.Lg);
+            s.Ls = __builtin_fmaf(cw, sg, s.Ls);
+        }
+    }
+}
 
-template <int D, int NEED>
+template <int D, int NEED, bool CP>
 __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense_kernel(FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using G = TileGeom<D>;
@@ -644,7 +688,9 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
     // differ in the SPLIT, so the workgroups of one XCD stream the same 1/nsplit of V through its L2
     const int64_t i0 = (int64_t)blockIdx.y * G::XB;
     const int64_t i = i0 + wave * 32 + c;
-    const int t0 = blockIdx.x * p.tps, t1 = min(p.NT, t0 + p.tps);
+    // CP: the tile range of N' distinct columns (device words); a workgroup beyond it writes the empty statistics
+    const int nt_e = CP ? p.geo[CG_NT] : p.NT, tps_e = CP ? p.geo[CG_TPSF] : p.tps;
+    const int t0 = blockIdx.x * tps_e, t1 = min(nt_e, t0 + tps_e);
     RowFrag<D> xf;
     mf_load_frag<D>(xf, p.u, i, i < p.B);
     const float nu_i = p.nu[i], s_i = p.sgn[i], lii = p.lii[i];
@@ -662,8 +708,9 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
         const int part = lane >> 3, l8 = lane & 7;
         aoff = part == 0 ? p.aux_mask + (uint32_t)(((int64_t)t0 * p.Bp + i0 + wave * 32) * 4) + l8 * 16
              : part == 1 ? p.aux_nv + (uint32_t)t0 * 128u + l8 * 16
-             : part == 2 ? p.aux_lq + (uint32_t)t0 * 128u + l8 * 16 : MF_SRD_DEAD;
-        astep = part == 0 ? (uint32_t)p.Bp * 4u : part <= 2 ? 128u : 0u;
+             : part == 2 ? p.aux_lq + (uint32_t)t0 * 128u + l8 * 16
+             : (CP && part == 3) ? p.aux_w + (uint32_t)t0 * 128u + l8 * 16 : MF_SRD_DEAD;
+        astep = part == 0 ? (uint32_t)p.Bp * 4u : part <= (CP ? 3 : 2) ? 128u : 0u;
 #if defined(__HIP_DEVICE_COMPILE__)
         arsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.aux_base), 0, (int)p.aux_bytes, 0x00020000);
 #else
@@ -692,7 +739,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
     float Lg[16];
     float tmax = -FLT_MAX, nmx = -FLT_MAX, nmx2 = 0.f;
     uint32_t mw = 0u;
-    f32x4 nv4 = {0.f, 0.f, 0.f, 0.f}, lq4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 nv4 = {0.f, 0.f, 0.f, 0.f}, lq4 = {0.f, 0.f, 0.f, 0.f}, cw4 = {0.f, 0.f, 0.f, 0.f};
     auto slice = [&](int sidx, int te, const f32x16& acc) {
         const char* aux = smem + L::AUX0 + ((te - t0) & 3) * L::AUXB + wave * L::AUXW;
         if (sidx < 16) {
@@ -701,17 +748,19 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
                 mw = reinterpret_cast<const uint32_t*>(aux)[c];
                 tmax = -FLT_MAX;
                 // valid negatives among this lane's 16 rows of the tile (rows (e&3) + 8 (e>>2) + 4 h)
-                st.cnt += (float)(16 - __builtin_popcount(mw & (h ? 0xF0F0F0F0u : 0x0F0F0F0Fu)));
+                if (!CP) st.cnt += (float)(16 - __builtin_popcount(mw & (h ? 0xF0F0F0F0u : 0x0F0F0F0Fu)));
                 mw >>= 4 * h;           // this lane's rows now sit at the compile-time bit (e&3) + 8 (e>>2)
             }
             if (r == 0) {
                 nv4 = *reinterpret_cast<const f32x4*>(aux + L::AUX_NV + (8 * q + 4 * h) * 4);
                 lq4 = *reinterpret_cast<const f32x4*>(aux + L::AUX_LQ + (8 * q + 4 * h) * 4);
+                if (CP) cw4 = *reinterpret_cast<const f32x4*>(aux + L::AUX_CW + (8 * q + 4 * h) * 4);
             }
             // masked logit: -inf where the column is not a valid negative -> every statistic below and
             // every dloss/dL of the backward is exactly 0 there, with no further mask test
             const float Lraw = mf_logit(nu_i, nv4[r], acc[e], s_i, p.sigma, -lq4[r]);      // lq4 holds -logq
             Lg[e] = (mw & (1u << mf_acc_row(e, 0))) ? -INFINITY : Lraw;
+            if (CP) st.cnt += (mw & (1u << mf_acc_row(e, 0))) ? 0.f : cw4[r];      // valid negatives: the copies count
             tmax = fmaxf(tmax, Lg[e]);
             if (r == 3) {   // stash 4 masked logits of the block for the backward sweeps
                 float* blk = p.stash + ((int64_t)(i0 / 32 + wave) * p.NT + te) * 1024 + lane * 4;
@@ -727,8 +776,14 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
                 // keeps the constant finite while nothing valid has been seen (nmx = -FLT_MAX, every L = -inf)
                 nmx2 = -fmaxf(nmx, -1e30f) * 1.44269504088896341f;
             }
-            stats_add_masked<NEED>(st, Lg[e], sm, lii, p.margin);
-            if (NEED & NEED_LSE) st.se += __builtin_amdgcn_exp2f(__builtin_fmaf(Lg[e], 1.44269504088896341f, nmx2));
+            if (CP) {
+                if ((e & 3) == 0) cw4 = *reinterpret_cast<const f32x4*>(aux + L::AUX_CW + (8 * (e >> 2) + 4 * h) * 4);
+                stats_add_masked_w<NEED>(st, Lg[e], sm, lii, p.margin, cw4[e & 3]);
+                if (NEED & NEED_LSE) st.se = __builtin_fmaf(cw4[e & 3], __builtin_amdgcn_exp2f(__builtin_fmaf(Lg[e], 1.44269504088896341f, nmx2)), st.se);
+            } else {
+                stats_add_masked<NEED>(st, Lg[e], sm, lii, p.margin);
+                if (NEED & NEED_LSE) st.se += __builtin_amdgcn_exp2f(__builtin_fmaf(Lg[e], 1.44269504088896341f, nmx2));
+            }
         }
     };
     // one iteration: wait for tile tj + 1 (slot NS), then its 64 MFMAs into `nxt`, interleaved with the slices of tile
@@ -784,21 +839,21 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
     }
 }
 
-template <int D, int NEED>
+template <int D, int NEED, bool CP>
 static void launch_fwd_n(dim3 grid, const FwdParams& fp, hipStream_t s) {
-    auto fn = loss_fwd_dense_kernel<D, NEED>;
+    auto fn = loss_fwd_dense_kernel<D, NEED, CP>;
     if (FwdLds<D>::BYTES > 64 * 1024)
         (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, FwdLds<D>::BYTES);
     fn<<<grid, 64 * mf_nw(D), FwdLds<D>::BYTES, s>>>(fp);
 }
-template <int D>
+template <int D, bool CP = false>
 static void launch_fwd(int need, dim3 grid, const FwdParams& fp, hipStream_t s) {
     switch (need) {   // single-loss calls get a specialised epilogue; anything else computes every statistic
-        case NEED_CONTR: launch_fwd_n<D, NEED_CONTR>(grid, fp, s); break;
-        case NEED_LSE: launch_fwd_n<D, NEED_LSE>(grid, fp, s); break;
-        case NEED_HINGE: launch_fwd_n<D, NEED_HINGE>(grid, fp, s); break;
-        case NEED_LOGI: launch_fwd_n<D, NEED_LOGI>(grid, fp, s); break;
-        default: launch_fwd_n<D, 15>(grid, fp, s); break;
+        case NEED_CONTR: launch_fwd_n<D, NEED_CONTR, CP>(grid, fp, s); break;
+        case NEED_LSE: launch_fwd_n<D, NEED_LSE, CP>(grid, fp, s); break;
+        case NEED_HINGE: launch_fwd_n<D, NEED_HINGE, CP>(grid, fp, s); break;
+        case NEED_LOGI: launch_fwd_n<D, NEED_LOGI, CP>(grid, fp, s); break;
+        default: launch_fwd_n<D, 15, CP>(grid, fp, s); break;
     }
 }
 
@@ -1084,6 +1139,9 @@ struct BwdParams {
     float* rpart;            // [split][Xp] partial row sums of G'
     int64_t B, N, Bp, Np;
     int NT, YT, tps;
+    // distinct-column sweeps (CP): v is the packed v', the streamed / kept extent of the item axis comes from the device words
+    const int32_t* geo;
+    const float* cw;         // column weights (dU: the MFMA operand and the row sum take G' x w; the stash keeps G' itself)
 };
 
 template <int D, bool XU>
@@ -1114,19 +1172,38 @@ struct BwdLds {
 
 // XU = true : lanes hold users, item tiles stream, result d loss / d u   (reads L, writes G' back)
 // XU = false: lanes hold items, user tiles stream, result d loss / d v   (reads G')
-template <int D, bool XU, int GMODE>
+// CP (distinct-column sweeps, mf_loss_cols.h): the item axis holds the N' packed columns.  dU streams the tiles [0, NT')
+// of v' in the splits the device words name, weights G' by the copy count for the contraction and the row sum, and
+// patches no diagonal (a user's own column is masked by id in every copy: G' = 0 there; the epilogue adds the term).
+// dV is launched as a LINEAR grid for the worst case: workgroup id -> (X block, split) by the device geometry.
+template <int D, bool XU, int GMODE, bool CP>
 __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG : 1) void loss_bwd_dense_kernel(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using L = BwdLds<D, XU>;
+    static_assert(!CP || (L::SPREAD && !L::RECOMP), "the distinct-column sweeps are written for the d = 128 schedule");
     const int lane = mf_lane(), c = lane & 31, h = lane >> 5;
     const int wave = mf_wave_id();
-    const int64_t x0 = (int64_t)blockIdx.y * TileGeom<D>::XB + wave * 32;     // this wave's X tile (grid = (Y split, X block))
+    int split = blockIdx.x, tps = p.tps, YT = p.YT;
+    int64_t xblk = blockIdx.y, nX = XU ? p.B : p.N, Xp = XU ? p.Bp : p.Np;
+    if (CP) {
+        if (XU) {
+            YT = p.geo[CG_NT]; tps = p.geo[CG_TPSU];
+            if (split * tps >= YT) return;                  // beyond the splits of N' (the epilogue adds geo's count of them)
+        } else {
+            const int nsv = p.geo[CG_NSV], xbv = p.geo[CG_XBV];
+            tps = p.geo[CG_TPSV];
+            xblk = blockIdx.x / nsv; split = blockIdx.x % nsv;
+            if (xblk >= xbv) return;
+            nX = p.geo[CG_NCOLS]; Xp = (int64_t)xbv * TileGeom<D>::XB;
+        }
+    }
+    const int64_t x0 = xblk * TileGeom<D>::XB + wave * 32;     // this wave's X tile (grid = (Y split, X block))
     const int64_t x = x0 + c;
     const int xt = (int)(x0 >> 5);
-    const int64_t nX = XU ? p.B : p.N, nY = XU ? p.N : p.B;
-    const int64_t Xp = XU ? p.Bp : p.Np;
+    const int64_t nY = XU ? p.N : p.B;
     const float* Y = XU ? p.v : p.u;
-    const int t0 = blockIdx.x * p.tps, t1 = min(p.YT, t0 + p.tps);
+    const int t0 = split * tps, t1 = min(YT, t0 + tps);
+    constexpr int NDMA = L::NDMA + ((CP && XU) ? 4 : 0);       // memory instructions per wave and stage (CP dU: + the weights)
     constexpr bool RECOMP = L::RECOMP;
     float xa = 0.f, xb = 0.f, xc = 0.f, xd = 0.f;
     const float gout = p.grad_out[0];
@@ -1149,12 +1226,14 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
     // piece j of the staging of tile t: 0..3 the wave's 4 KiB stash / G' block (into LDS, or -- SPREAD --
     // straight into the registers Gn), 4.. its share of the Y tile
     constexpr bool SPREAD = L::SPREAD;
-    f32x4 Gn[4];
+    f32x4 Gn[4], Wn[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) Gn[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 4; ++q) { Gn[q] = f32x4{0.f, 0.f, 0.f, 0.f}; Wn[q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     auto stage_piece = [&](int t, int slot_idx, int j) {
         char* slot = smem + slot_idx * L::SLOT;
-        if (L::NCOEF && j >= L::NDMA - L::NCOEF) {
+        if (CP && XU && j >= L::NDMA) {      // the weights of the tile's columns, rows 8 q + 4 h .. + 3 (this lane's registers)
+            Wn[j - L::NDMA] = *reinterpret_cast<const f32x4*>(p.cw + (int64_t)t * 32 + 8 * (j - L::NDMA) + 4 * h);
+        } else if (L::NCOEF && j >= L::NDMA - L::NCOEF) {
             cn[j - (L::NDMA - L::NCOEF)] = p.rowc[(int64_t)(j - (L::NDMA - L::NCOEF)) * p.Bp + (int64_t)t * 32 + c];
         } else if (j < 4) {
             const char* lsrc = reinterpret_cast<const char*>(((XU || RECOMP) ? p.stash : p.gstash) + block_of(t) * 1024) + lane * 16;
@@ -1166,7 +1245,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
     };
     auto stage = [&](int t, int slot_idx) {
 #pragma unroll
-        for (int j = 0; j < L::NDMA; ++j) stage_piece(t, slot_idx, j);
+        for (int j = 0; j < NDMA; ++j) stage_piece(t, slot_idx, j);
     };
     // Two schedules.  SPREAD (2-slot ring, d >= 64): the loads of tile ty+1 are issued ONE PER MFMA STEP
     // inside the contraction of tile ty, the tile pieces into the slot tile ty-1 left; no second barrier.
@@ -1187,12 +1266,12 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
         if (!SPREAD && L::NSLOT == 3 && ty + 2 < t1) stage(ty + 2, cur >= 1 ? cur - 1 : 2);
         const char* slot = smem + cur * L::SLOT;
         const char* lt = slot + L::LT + wave * 4096;
-        float Gv[16];
+        float Gv[16], Wv[16];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const f32x4 t4 = SPREAD ? Gn[q] : *reinterpret_cast<const f32x4*>(lt + q * 1024 + lane * 16);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) Gv[4 * q + t] = t4[t];
+            for (int t = 0; t < 4; ++t) { Gv[4 * q + t] = t4[t]; Wv[4 * q + t] = Wn[q][t]; }
         }
         if (!XU && RECOMP) {            // this tile's users' coefficients (asked for one tile ago)
             xa = cn[0]; xb = cn[1]; xc = gout * cn[2]; xd = gout * cn[3];
@@ -1205,7 +1284,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
                 if (GMODE == G_EXP) Gv[e] = xc * __builtin_amdgcn_exp2f(__builtin_fmaf(Gv[e] - xa, 1.44269504088896341f, xb2));
                 else Gv[e] = xc * g_of(GMODE, (Gv[e] - xa) + xb);
             }
-            if (ty == xt) {             // only the diagonal tile holds the user's own positive
+            if (!CP && ty == xt) {      // only the diagonal tile holds the user's own positive
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
                     if (mf_acc_row(e, h) == c) Gv[e] = xd;
@@ -1216,6 +1295,10 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 *reinterpret_cast<f32x4*>(blk + q * 256) = f32x4{Gv[4 * q], Gv[4 * q + 1], Gv[4 * q + 2], Gv[4 * q + 3]};
+            if (CP) {                   // (the stash keeps the per-copy gradient: dV needs it unweighted)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) Gv[e] *= Wv[e];
+            }
         }
         if (!XU) {
             // block layout is (lane = user, register = item row): transpose to (lane = item, register = user row)
@@ -1236,7 +1319,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
         for (int t = 0; t < 16; ++t) {
             float yn[D / 32];
             if (t + 1 < 16) mf_lds_cols<D>(yn, slot, mf_acc_row(t + 1, h), c);
-            if (SPREAD && t < L::NDMA && more) stage_piece(ty + 1, cur ^ 1, t);
+            if (SPREAD && t < NDMA && more) stage_piece(ty + 1, cur ^ 1, t);
 #pragma unroll
             for (int j = 0; j < D / 32; ++j)
                 dacc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(yv[j], Gv[t], dacc[j], 0, 0, 0);
@@ -1258,7 +1341,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
     // sum_parts_kernel adds the splits in order and applies the X term once.
     if (x < nX) {
         constexpr int NB = D / 32;
-        float* o = p.dpart + ((int64_t)blockIdx.x * Xp + x) * D;
+        float* o = p.dpart + ((int64_t)split * Xp + x) * D;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int m0 = NB * mf_acc_row(e, h);
@@ -1272,7 +1355,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
                 for (int j = 0; j < NB; ++j) o[m0 + j] = dacc[j][e];
             }
         }
-        if (h == 0) p.rpart[(int64_t)blockIdx.x * Xp + x] = rsum;
+        if (h == 0) p.rpart[(int64_t)split * Xp + x] = rsum;
     }
 }
 
@@ -1299,6 +1382,49 @@ __global__ __launch_bounds__(256) void sum_parts_kernel(SumJob ja, SumJob jb, in
     }
     const f32x4 xr = reinterpret_cast<const f32x4*>(j.X + r * d)[cidx];
     reinterpret_cast<f32x4*>(j.out + r * d)[cidx] = acc - rs * xr;
+}
+
+// The same for the distinct-column sweeps (mf_loss_cols.h): the split counts and dV's row stride come from the device words,
+// the diagonal term -- no longer patched inside the sweeps -- is added here, and dV is written for ALL N original columns,
+// each taking the partials of its representative's slot k = rank[j] (a copy holds ~first: rank[first] is its slot):
+//   dU row i: acc = sum_s dpart[s][i] + xd_i v[i],    rs = sum_s rpart[s][i] + xd_i,    out = acc - rs u[i]
+//   dV row j: acc = sum_s dpart_v[s][k] (+ xd_j u[j]), rs = sum_s rpart_v[s][k] (+ xd_j), out = acc - rs v[j]     (j < B)
+// with xd = grad_out * rowc[3 Bp + .].  Fixed split order, no float atomics.
+struct SumColsParams {
+    const float *dpart, *rpart, *dpart_v, *rpart_v, *u, *v, *rowc, *grad_out;
+    const int32_t *geo, *rank;
+    int64_t B, N, Bp;
+    float *du, *dv;
+    int nb_a, xb;
+};
+__global__ __launch_bounds__(256) void sum_parts_cols_kernel(SumColsParams p, int d) {
+    const bool first = (int)blockIdx.x < p.nb_a;
+    const int64_t t = (int64_t)(blockIdx.x - (first ? 0 : p.nb_a)) * 256 + threadIdx.x;   // one float4 each
+    const int64_t per_row = d / 4;
+    if (t >= (first ? p.B : p.N) * per_row) return;
+    const int64_t r = t / per_row, cidx = t % per_row;
+    int64_t row = r, stride = p.Bp;
+    int nsplit = p.geo[CG_NSU];
+    if (!first) {
+        int32_t k = p.rank[r];
+        if (k < 0) k = p.rank[~k];
+        row = k; stride = (int64_t)p.geo[CG_XBV] * p.xb; nsplit = p.geo[CG_NSV];
+    }
+    const float* dpart = first ? p.dpart : p.dpart_v;
+    const float* rpart = first ? p.rpart : p.rpart_v;
+    f32x4 acc = reinterpret_cast<const f32x4*>(dpart + row * d)[cidx];
+    float rs = rpart[row];
+    for (int s = 1; s < nsplit; ++s) {
+        acc += reinterpret_cast<const f32x4*>(dpart + ((int64_t)s * stride + row) * d)[cidx];
+        rs += rpart[(int64_t)s * stride + row];
+    }
+    const f32x4 xr = reinterpret_cast<const f32x4*>((first ? p.u : p.v) + r * d)[cidx];
+    if (r < p.B) {
+        const float xd = p.grad_out[0] * p.rowc[3 * p.Bp + r];
+        acc += xd * reinterpret_cast<const f32x4*>((first ? p.v : p.u) + r * d)[cidx];
+        rs += xd;
+    }
+    reinterpret_cast<f32x4*>((first ? p.du : p.dv) + r * d)[cidx] = acc - rs * xr;
 }
 
 // alignment-only backward: only the diagonal carries gradient
@@ -1482,7 +1608,8 @@ static int hits_split(const PosSrc& src) {
 }
 
 // expects gtab / gfirst / bmap cleared (ubits needs no clearing: every word in use is written)
-static void build_masks(const LossWs& w, const int64_t* item_idx, const PosSrc& src, int64_t B, int64_t N, hipStream_t s) {
+static void build_masks(const LossWs& w, const int64_t* item_idx, const PosSrc& src, int64_t B, int64_t N, hipStream_t s,
+                        bool sweep = true) {
     gt_insert_kernel<<<dim3((unsigned)((N + 63) / 64)), 64, 0, s>>>(item_idx, N, w.M, w.gtab, w.gfirst, w.colslot, w.bmap, w.bmbits);
     const int split = hits_split(src);
     const int nb_col = (int)((w.Np + HITS_THREADS - 1) / HITS_THREADS);
@@ -1496,25 +1623,94 @@ static void build_masks(const LossWs& w, const int64_t* item_idx, const PosSrc& 
     }
     hits_kernel<<<dim3((unsigned)(nb_col + nb_u)), HITS_THREADS, lds, s>>>(item_idx, src, B, N, w.Bp, w.Np, w.M, nb_col, split, win, w.gtab,
                                                                            w.gfirst, w.colslot, w.colfirst, w.ubits, w.bmap, w.bmbits);
+    if (!sweep) return;                  // (the distinct-column plan sweeps the masks of the packed columns instead)
     const int64_t units = (int64_t)w.NT * (w.Bp >> 7);
     mask_sweep_kernel<<<dim3((unsigned)((units + 7) / 8)), 256, 0, s>>>(w.colfirst, w.ubits, B, w.Bp, w.Np, w.NT, w.maskW, split);
 }
 
-template <int D, bool XU>
+template <int D, bool XU, bool CP = false>
 static void launch_bwd(int gmode, dim3 grid, const BwdParams& bp, hipStream_t s);
 
-template <int D, bool XU, int GMODE>
+template <int D, bool XU, int GMODE, bool CP>
 static void launch_bwd_g(dim3 grid, const BwdParams& bp, hipStream_t s) {
-    auto fn = loss_bwd_dense_kernel<D, XU, GMODE>;
+    auto fn = loss_bwd_dense_kernel<D, XU, GMODE, CP>;
     if (BwdLds<D, XU>::BYTES > 64 * 1024)
         (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, BwdLds<D, XU>::BYTES);
     fn<<<grid, 64 * mf_nw(D), BwdLds<D, XU>::BYTES, s>>>(bp);
 }
-template <int D, bool XU>
+template <int D, bool XU, bool CP>
 static void launch_bwd(int gmode, dim3 grid, const BwdParams& bp, hipStream_t s) {
-    if (gmode == G_EXP) launch_bwd_g<D, XU, G_EXP>(grid, bp, s);
-    else if (gmode == G_STEP) launch_bwd_g<D, XU, G_STEP>(grid, bp, s);
-    else launch_bwd_g<D, XU, G_SIGM>(grid, bp, s);
+    if (gmode == G_EXP) launch_bwd_g<D, XU, G_EXP, CP>(grid, bp, s);
+    else if (gmode == G_STEP) launch_bwd_g<D, XU, G_STEP, CP>(grid, bp, s);
+    else launch_bwd_g<D, XU, G_SIGM, CP>(grid, bp, s);
+}
+
+// ---- the distinct-column sweeps' switch (mf_loss_cols.h) ----
+// 0 never, 1 where it pays (default), 2 wherever it can serve (tests).  Served: the dense (unmined) path at d = 128, all
+// seven kinds, masks built inside the forward, no mask export; mode 1 from COLS_MIN_N columns upward.
+static int g_dense_dedup = 1;
+static constexpr int64_t COLS_MIN_N = 4096;
+extern "C" void mf_set_dense_dedup(int mode) { g_dense_dedup = mode <= 0 ? 0 : (mode >= 2 ? 2 : 1); }
+static bool cols_serve(const LossWs& w, bool masks_ready, bool export_masks) {
+    if (!w.cols_ok || masks_ready || export_masks || g_dense_dedup == 0) return false;
+    return g_dense_dedup == 2 || w.N >= COLS_MIN_N;
+}
+// Which path the LAST forward on a workspace took: its backward must contract the stashes that forward wrote, whatever the
+// switch says by then (and the backward's arguments do not tell, e.g., that the masks had been prepared ahead).
+static std::mutex g_cols_mu;
+static std::unordered_map<const void*, bool> g_cols_served;
+static void cols_note(const void* ws, bool served) {
+    std::lock_guard<std::mutex> lk(g_cols_mu);
+    g_cols_served[ws] = served;
+}
+static bool cols_served(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_cols_mu);
+    const auto it = g_cols_served.find(ws);
+    return it != g_cols_served.end() && it->second;
+}
+
+// tests and tools only (a device -> host copy: never inside a step): out[9] = {served, N', NT', forward (nsplit, tps),
+// dU (nsplit, tps), dV (nsplit, tps)} of the last forward on this workspace; not served: the rest is 0
+extern "C" int mf_loss_cols_info(const void* ws, int64_t* out9) {
+    if (!ws || !out9) return mf_set_error(MF_EINVAL, "mf_loss_cols_info: bad argument");
+    for (int i = 0; i < 9; ++i) out9[i] = 0;
+    if (!cols_served(ws)) return MF_OK;
+    int32_t g[CG_WORDS];
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(g, ws, sizeof(g), hipMemcpyDeviceToHost) != hipSuccess)
+        return mf_set_error(MF_ELAUNCH, "mf_loss_cols_info: copy failed");
+    out9[0] = 1;
+    for (int i = 0; i < 8; ++i) out9[1 + i] = g[i];
+    return MF_OK;
+}
+// host-only: the geometry the device derives for `ncols` distinct columns of this shape, and what is launched and allocated
+// around it: out[16] = {can serve, NT', forward (nsplit, tps), dU (nsplit, tps), dV (nsplit, tps), dV X blocks,
+// launched: forward splits, dU splits, dV workgroups, capacity: forward partial splits, dU partial splits, dV partial X blocks, 0}
+extern "C" int mf_loss_cols_plan(int64_t B, int64_t N, int d, int64_t ncols, int64_t* out16) {
+    if (!out16) return mf_set_error(MF_EINVAL, "mf_loss_cols_plan: out is NULL");
+    if (B <= 0 || N < B || ncols < 1 || ncols > N || !mf_width_ok(d))
+        return mf_set_error(MF_EINVAL, "mf_loss_cols_plan: need 0 < B <= N, 1 <= ncols <= N and a supported width");
+    const LossWs w = loss_ws(nullptr, B, N, d, 0, 0);
+    const ColsGeom g = cols_geometry(w.BT, w.NT, w.NW, ncols, w.wgs_f, w.wgs_b);
+    const size_t xb = (size_t)32 * w.NW;
+    size_t rows_v = (size_t)w.nsplit_v * w.Np;
+    if ((size_t)w.cl.grid_v * xb > rows_v) rows_v = (size_t)w.cl.grid_v * xb;
+    const int64_t o[16] = {w.cols_ok ? 1 : 0, g.nt, g.nsf, g.tpsf, g.nsu, g.tpsu, g.nsv, g.tpsv, g.xbv,
+                           w.cl.grid_f, w.cl.grid_u, w.cl.grid_v, w.cl.grid_f, w.cl.grid_u, (int64_t)(rows_v / xb), 0};
+    for (int i = 0; i < 16; ++i) out16[i] = o[i];
+    return MF_OK;
+}
+
+// the plan behind build_masks' table and first-column kernels: kept columns, their slots, the packed side arrays, the
+// geometry words; then the mask words of the PACKED columns (mask_sweep_kernel fed first')
+template <int D>
+static void cols_plan_launch(const LossWs& w, const float* v, int64_t B, int64_t N, int split, hipStream_t s) {
+    cols_mark_kernel<D><<<dim3((unsigned)w.NT), 1024, 0, s>>>(v, w.logq, w.colfirst, N, w.ckept, w.ctcnt);
+    const ColsPack cp{v, w.nv, w.logq, w.colfirst, w.ckept, w.ctcnt, N, w.Np, w.NT, w.BT, w.NW, w.wgs_f, w.wgs_b,
+                      w.crank, w.cfirst, w.geo, w.ccnt, w.cnv, w.clq};
+    cols_pack_kernel<D><<<dim3((unsigned)((w.Np + 1023) / 1024)), 1024, 0, s>>>(cp);
+    cols_rows_kernel<D><<<dim3((unsigned)w.NT), 1024, 0, s>>>(v, w.crank, w.ccnt, w.geo, N, w.cv, w.cw);
+    const int64_t units = (int64_t)w.NT * (w.Bp >> 7);
+    mask_sweep_kernel<<<dim3((unsigned)((units + 7) / 8)), 256, 0, s>>>(w.cfirst, w.ubits, B, w.Bp, w.Np, w.NT, w.maskW, split);
 }
 
 static int check_loss_args(const char* what, int64_t B, int64_t N, int d, int P, int num_negatives,
@@ -1696,6 +1892,8 @@ static int loss_fwd_impl(const char* what, int64_t B, int64_t N, int d, const Po
     LossWs w = loss_ws(ws, B, N, d, 0, num_negatives);
     const int need = need_flags(kind_mask);
     const bool scores_needed = (kind_mask & ~(1 << MF_ALIGNMENT)) != 0 || out_mask_bits;
+    const bool cols = scores_needed && cols_serve(w, masks_ready, out_mask_bits != nullptr);   // the distinct-column sweeps
+    cols_note(ws, cols);
 
     {
         PrepParams pp{u, v, target, logq, item_idx, logq_rows, (flags & MF_LOSS_TARGET_I64) ? 1 : 0,
@@ -1703,6 +1901,7 @@ static int loss_fwd_impl(const char* what, int64_t B, int64_t N, int d, const Po
                       nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, w.ticket};
         int nb = (int)((w.Np + 63) / 64);
         if (scores_needed && !masks_ready) prep_clears(pp, w);
+        if (cols) { pp.ubits = reinterpret_cast<uint4*>(w.ccnt); pp.ubits16 = w.Np * 4 / 16; }      // the copy counts start at 0
         if (scores_needed && w.mined) {
             // the mined path's counters and bounds (gtau .. cand_cnt, and behind them the prefilter's maxima, copy bitmaps, spill
             // cursors and gate: one contiguous range of the workspace) are cleared here too -- it used to be a launch of its own
@@ -1715,28 +1914,43 @@ static int loss_fwd_impl(const char* what, int64_t B, int64_t N, int d, const Po
         }
         MF_DISPATCH_D(d, { prep_kernel<D><<<dim3((unsigned)nb), 64, 0, s>>>(pp); });
     }
-    if (scores_needed && !masks_ready) build_masks(w, item_idx, src, B, N, s);
+    if (scores_needed && !masks_ready) build_masks(w, item_idx, src, B, N, s, !cols);
+    if (cols) cols_plan_launch<128>(w, v, B, N, hits_split(src), s);
     // logq is read by whole float4s up to the padded width: prep_kernel keeps a zero-padded copy in ws
     // (all zeros when there is no logQ correction: L - 0 is exact, and the kernels stay branch-free)
     const float* logq_p = w.logq;
     int merge_splits = 0;
     if (scores_needed && !w.mined) {
         FwdParams fp{u, v, w.nu, w.nv, w.lii, w.sgn, logq_p, w.maskW, w.part, w.stash, B, N, w.Bp, w.NT, w.tps_f, need, sigma, margin};
+        if (cols) { fp.v = w.cv; fp.nv = w.cnv; fp.logq = w.clq; fp.N = w.Np; fp.geo = w.geo; }
         {   // the three side inputs live in the workspace: one descriptor over their span
-            const char *pm = (const char*)w.maskW, *pn = (const char*)w.nv, *pl = (const char*)logq_p;
+            const char *pm = (const char*)w.maskW, *pn = (const char*)fp.nv, *pl = (const char*)fp.logq;
             const char* lo = pm < pn ? (pm < pl ? pm : pl) : (pn < pl ? pn : pl);
             const char *em = pm + (size_t)w.NT * w.Bp * 4, *en = pn + (size_t)w.NT * 128, *el = pl + (size_t)w.NT * 128;
             const char* hi = em > en ? (em > el ? em : el) : (en > el ? en : el);
+            if (cols) {                                   // ... and the column weights
+                const char* pw = (const char*)w.cw;
+                if (pw < lo) lo = pw;
+                if (pw + (size_t)w.NT * 128 > hi) hi = pw + (size_t)w.NT * 128;
+                fp.aux_w = (uint32_t)(pw - lo);
+            }
             if ((size_t)(hi - lo) > MF_SRD_MAX_BYTES || (size_t)w.tps_f * 32 * d * 4 > MF_SRD_MAX_BYTES)
                 return mf_set_error(MF_EINVAL, "mf_loss_fwd: batch x catalog too large for one sweep (mask words beyond 4 GiB)");
             fp.aux_base = lo; fp.aux_mask = (uint32_t)(pm - lo); fp.aux_nv = (uint32_t)(pn - lo); fp.aux_lq = (uint32_t)(pl - lo);
             fp.aux_bytes = (uint32_t)(hi - lo);
         }
-        MF_DISPATCH_D(d, {
-            dim3 grid((unsigned)w.nsplit_f, (unsigned)(w.BT / w.NW));
-            MF_TIMED("loss_fwd_dense", s, (launch_fwd<D>(need, grid, fp, s)));
-        });
-        merge_splits = w.nsplit_f;
+        if (cols) {
+            // launched for the most splits any N' can ask for; a split beyond N''s writes the empty statistics, which merge as nothing
+            dim3 grid((unsigned)w.cl.grid_f, (unsigned)(w.BT / w.NW));
+            MF_TIMED("loss_fwd_dense", s, (launch_fwd<128, true>(need, grid, fp, s)));
+            merge_splits = w.cl.grid_f;
+        } else {
+            MF_DISPATCH_D(d, {
+                dim3 grid((unsigned)w.nsplit_f, (unsigned)(w.BT / w.NW));
+                MF_TIMED("loss_fwd_dense", s, (launch_fwd<D>(need, grid, fp, s)));
+            });
+            merge_splits = w.nsplit_f;
+        }
         if (out_mask_bits)
             mask_export_dense_kernel<<<dim3((unsigned)((B * ((N + 31) / 32) + 255) / 256)), 256, 0, s>>>(w.maskW, B, N, w.Bp, (int)((N + 31) / 32), out_mask_bits);
     } else if (scores_needed) {
@@ -1820,10 +2034,20 @@ extern "C" int mf_loss_bwd(int64_t B, int64_t N, int d, int P, int num_negatives
                                                                                                               grad_out, B, w.Bp, gmode, du, w.dvfix, w.dvsc);
         });
         dv_fix_to_f32_kernel<<<dim3((unsigned)((N * d + 255) / 256)), 256, 0, s>>>(w.dvfix, N * d, dv, w.dvsc, u, v, w.rowc, grad_out, B, w.Bp, d);
+    } else if (cols_served(ws)) {
+        // the forward on this workspace swept the distinct columns: so do dU and dV (the stashes hold packed columns)
+        BwdParams bp{u, w.cv, w.rowc, grad_out, w.stash, w.gstash, w.dpart, w.rpart, B, w.Np, w.Bp, w.Np, w.NT, 0, 0, w.geo, w.cw};
+        bp.YT = w.NT;
+        MF_TIMED("loss_bwd_du", s, (launch_bwd<128, true, true>(gmode, dim3((unsigned)w.cl.grid_u, (unsigned)(w.BT / w.NW)), bp, s)));
+        bp.YT = w.BT; bp.dpart = w.dpart_v; bp.rpart = w.rpart_v;
+        MF_TIMED("loss_bwd_dv", s, (launch_bwd<128, false, true>(G_EXP, dim3((unsigned)w.cl.grid_v), bp, s)));
+        const int nb_a = (int)((B * (d / 4) + 255) / 256), nb_b = (int)((N * (d / 4) + 255) / 256);
+        const SumColsParams sp{w.dpart, w.rpart, w.dpart_v, w.rpart_v, u, v, w.rowc, grad_out, w.geo, w.crank, B, N, w.Bp, du, dv, nb_a, 32 * w.NW};
+        sum_parts_cols_kernel<<<dim3((unsigned)(nb_a + nb_b)), 256, 0, s>>>(sp, d);
     } else {
         if ((size_t)w.tps_u * 32 * d * 4 > MF_SRD_MAX_BYTES || (size_t)w.tps_v * 32 * d * 4 > MF_SRD_MAX_BYTES)
             return mf_set_error(MF_ENOTSUP, "mf_loss_bwd: a sweep's share of the batch exceeds 4 GiB (buffer descriptor)");
-        BwdParams bp{u, v, w.rowc, grad_out, w.stash, w.gstash, w.dpart, w.rpart, B, N, w.Bp, w.Np, w.NT, 0, 0};
+        BwdParams bp{u, v, w.rowc, grad_out, w.stash, w.gstash, w.dpart, w.rpart, B, N, w.Bp, w.Np, w.NT, 0, 0, nullptr, nullptr};
         MF_DISPATCH_D(d, {
             bp.YT = w.NT; bp.tps = w.tps_u;
             MF_TIMED("loss_bwd_du", s, (launch_bwd<D, true>(gmode, dim3((unsigned)w.nsplit_u, (unsigned)(w.BT / w.NW)), bp, s)));

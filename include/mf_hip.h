@@ -497,6 +497,16 @@ int mf_xfmr_backward_mixed(int h, int64_t B, int64_t t_cap, int max_history, int
                            const float* grad_u, const float* out_u, const float* out_inv, const int32_t* out_arg, float* grad_x,
                            void* ws, size_t ws_bytes, double p_hidden, double p_attn, uint64_t seed, uint64_t call, int precision,
                            mf_stream_t stream);
+/* Serving encode: out_u [B, h] of mf_xfmr_forward -- the eval-mode function, fp32 -- and nothing else, in ONE launch: one
+ * workgroup per user carries the user's <= 64 tokens from the cut of the list to the pooled, normalised vector in LDS.  No t_cap,
+ * no stash, no workspace, no out_inv / out_arg, no host read; nothing per token is written to memory.  Same lists, params
+ * (4 + 16 * layers pointers, same order), shape rules and MF_ENOTSUP cases as mf_xfmr_forward; null pointers, B <= 0, act
+ * outside 0..3 or mode outside 0..2 are MF_EINVAL; all decided before any GPU call.  It calls the forward's own arithmetic in
+ * the forward's order (each GEMM element one k-ascending v_mfma_f32_32x32x2_f32 chain): out_u is BIT-IDENTICAL to
+ * mf_xfmr_forward's on the same inputs.  An empty list gives a zero row.  fp32 only: there is no bf16-mixed form. */
+int mf_xfmr_encode(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                   const int64_t* items, int64_t n_items, int64_t B, int max_history, int layers, int heads, int intermediate,
+                   int act, int mode, int norm_item, int norm_user, const float* const* params, float* out_u, mf_stream_t stream);
 /* ONE dense operation of that engine on the caller's row-major fp32 buffers, through the tower's own launches (for tests of
  * the arithmetic contract).  M tokens in [1, 2^31), N and K multiples of 32 in [32, 512] (MF_ENOTSUP otherwise).
  *   form 0: out [M, N] = a [M, K] b[N, K]^T + bias [N] (bias may be null)

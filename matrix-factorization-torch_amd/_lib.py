@@ -115,6 +115,8 @@ SIGNATURES = {
                                       c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_f64, c_f64, c_u64, c_u64, c_int, c_vp]),
     "mf_xfmr_backward_mixed": (c_int, [c_int, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_f64, c_f64, c_u64, c_u64, c_int, c_vp]),
+    "mf_xfmr_encode": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_int, c_vp, c_vp, c_vp]),
     "mf_xfmr_dense_ws_bytes": (c_sz, [c_int, c_int, c_int]),
     "mf_xfmr_dense": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mf_dropout_words": (c_int, [c_u64, c_u64, c_u64, c_u64, c_i64, c_vp]),

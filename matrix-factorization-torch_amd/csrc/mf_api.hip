@@ -21,7 +21,7 @@ int mf_check_launch(const char* what) {
 }
 
 extern "C" const char* mf_last_error(void) { return g_err; }
-extern "C" int mf_version(void) { return 100; }
+extern "C" int mf_version(void) { return 101; }
 
 // ---------------------------------------------------------------- kernel timing --
 // Optional HIP-event timing of the dominant kernels, recorded on the stream the

@@ -32,19 +32,13 @@ __device__ __forceinline__ int64_t list_owner(const int64_t* __restrict__ off, i
     return l;
 }
 
-// One wave per owner: walk back from hi, 64 entries at a time, until the L-th valid entry; cut_out[b] = its position (lo
-// when the list has fewer), and with COUNT also nb_out[b] = min(valid entries, L).
-template <bool COUNT>
-__global__ __launch_bounds__(256) void list_cut_kernel(const int64_t* __restrict__ seg_start, const int64_t* __restrict__ seg_end,
-                                                       const int64_t* __restrict__ items, int64_t n_items, int64_t B, int64_t n_rows,
-                                                       int L, int64_t* __restrict__ cut_out, int32_t* __restrict__ nb_out) {
+// One wave, the list items[lo, hi): walk back from hi, 64 entries at a time, until the L-th valid entry; returns its position
+// (lo when the list has fewer) and leaves need = L - min(valid entries, L).  Every lane gets both.
+__device__ __forceinline__ int64_t list_cut_walk(const int64_t* __restrict__ items, int64_t lo, int64_t hi, int64_t n_rows, int L,
+                                                 int& need) {
     const int lane = mf_lane();
-    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= B) return;
-    int64_t lo, hi;
-    list_clamp(seg_start[b], seg_end[b], n_items, lo, hi);
     int64_t cut = lo;
-    int need = L;
+    need = L;
     for (int64_t top = hi; top > lo; top -= 64) {
         const int64_t pos = top - 1 - lane;                  // lane 0 = the most recent entry of this block
         const bool ok = pos >= lo && list_valid(items[pos >= lo ? pos : lo], n_rows);
@@ -58,6 +52,21 @@ __global__ __launch_bounds__(256) void list_cut_kernel(const int64_t* __restrict
         }
         need -= c;
     }
+    return cut;
+}
+
+// One wave per owner: cut_out[b] = list_cut_walk's position, and with COUNT also nb_out[b] = min(valid entries, L).
+template <bool COUNT>
+__global__ __launch_bounds__(256) void list_cut_kernel(const int64_t* __restrict__ seg_start, const int64_t* __restrict__ seg_end,
+                                                       const int64_t* __restrict__ items, int64_t n_items, int64_t B, int64_t n_rows,
+                                                       int L, int64_t* __restrict__ cut_out, int32_t* __restrict__ nb_out) {
+    const int lane = mf_lane();
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    int64_t lo, hi;
+    list_clamp(seg_start[b], seg_end[b], n_items, lo, hi);
+    int need;
+    const int64_t cut = list_cut_walk(items, lo, hi, n_rows, L, need);
     if (lane == 0) {
         cut_out[b] = cut;
         if (COUNT) nb_out[b] = L - need;

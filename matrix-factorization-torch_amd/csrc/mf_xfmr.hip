@@ -32,6 +32,10 @@
 // generated where they are applied; nothing is stored and the backward regenerates the same bits.  Every kernel that can
 // drop is a template on that (DROP = false is the code the plain exports always ran), chosen per site on the host.
 //
+// Serving encode (mf_xfmr_encode, xfmr_encode_kernel): out_u of the eval-mode fp32 forward and nothing else, ONE launch, one
+// workgroup per user with the user's <= 64 tokens in LDS from the cut of the list to the pooled vector -- no packing, no
+// stash, no host read.  It calls the forward's own __device__ arithmetic in the forward's order: bit-identical to it.
+//
 // Mixed precision (mf_xfmr_forward_mixed / mf_xfmr_backward_mixed, precision MF_XFMR_BF16_MIXED): the GEMMs of the six dense
 // layers per encoder layer, in all three forms, run on xfmr_gemm_bf16_kernel -- both operands rounded to bf16 (nearest even)
 // where they are staged, exact products, fp32 accumulation (v_mfma_f32_32x32x16_bf16), the same fp32 epilogue; db, outputs,
@@ -599,28 +603,37 @@ __device__ __forceinline__ float xattn_wave_max(float x) {
     x = fmaxf(x, mf_xor_lane<4>(x)); x = fmaxf(x, mf_xor_lane<2>(x)); x = fmaxf(x, mf_xor_lane<1>(x));
     return x;
 }
-// softmax probability of this lane's key (LDS row `row`) for the query row qv (lane c holds q[c]); inactive lanes give 0
+// softmax probability of this lane's key (its DH floats at krow) for the query row qv (lane c holds q[c]); inactive lanes give 0
 template <int DH>
-__device__ __forceinline__ float xattn_prob(float qv, const float (*Ks)[DH + 1], int row, bool active) {
+__device__ __forceinline__ float xattn_prob(float qv, const float* krow, bool active) {
     float s = 0.f;
 #pragma unroll
-    for (int c = 0; c < DH; ++c) s += xattn_bcast(qv, c) * Ks[row][c];
+    for (int c = 0; c < DH; ++c) s += xattn_bcast(qv, c) * krow[c];
     s = active ? s / sqrtf((float)DH) : -__builtin_huge_valf();
     const float mx = xattn_wave_max(s);
     const float e = active ? expf(s - mx) : 0.f;
     return e / mf_wave_sum(e);
 }
-// out[c] = sum_j w[j] M[j][c] for c < DH: 64 / DH lane groups take every (64 / DH)-th key, then a fixed butterfly
 template <int DH>
-__device__ __forceinline__ float xattn_mix(const float* w, const float (*Ms)[DH + 1], int lane, int n) {
+__device__ __forceinline__ float xattn_prob(float qv, const float (*Ks)[DH + 1], int row, bool active) {
+    return xattn_prob<DH>(qv, &Ks[row][0], active);
+}
+// out[c] = sum_j w[j] M[j][c] for c < DH (row j of M at m + j ld): 64 / DH lane groups take every (64 / DH)-th key, then a fixed
+// butterfly
+template <int DH>
+__device__ __forceinline__ float xattn_mix(const float* w, const float* m, int ld, int lane, int n) {
     constexpr int G = 64 / DH;
     const int c = lane % DH, jg = lane / DH;
     float acc = 0.f;
-    for (int j = jg; j < n; j += G) acc += w[j] * Ms[j][c];
+    for (int j = jg; j < n; j += G) acc += w[j] * m[j * ld + c];
     if constexpr (DH <= 32) acc += mf_xor_lane<32>(acc);
     if constexpr (DH <= 16) acc += mf_xor_lane<16>(acc);
     if constexpr (DH <= 8) acc += mf_xor_lane<8>(acc);
     return acc;
+}
+template <int DH>
+__device__ __forceinline__ float xattn_mix(const float* w, const float (*Ms)[DH + 1], int lane, int n) {
+    return xattn_mix<DH>(w, &Ms[0][0], DH + 1, lane, n);
 }
 
 template <int DH, bool DROP>
@@ -828,6 +841,270 @@ __global__ __launch_bounds__(128) void xfmr_tok_bwd_kernel(const float* __restri
     for (int t = 0; t < L; ++t) acc += dpos[(int64_t)t * H + c];
     dtok[c] = acc;
     dtok[H + c] = 0.f;
+}
+
+// ====================================================================================== serving encode ====
+// mf_xfmr_encode: the eval-mode forward of ONE user per workgroup (256 threads), cut to pooled vector in one launch, every
+// activation in LDS, nothing per token in global memory.  Four [64][H + 4] buffers (x, q, k, v by their first use) carry a layer:
+//   q, k, v = x W^T + b                      (one pass over the 3 H / 32 column blocks, one wave per block)
+//   ctx     = attention, one wave per head, K and V read in place; ctx overwrites q (a query row is read before it is written)
+//   z1      = ctx Wo^T + bo + x  -> k;  y1 = LN(z1) in place
+//   FFN in chunks of <= H intermediate columns: f = act(y1 Wi^T + bi) -> q;  acc += f Wo2^T with the [64, H] accumulators in
+//             registers across the chunks (each output element stays one ascending-k chain)
+//   z2      = acc + bo2 + y1 -> v;  y2 = LN(z2) in place; v is the next layer's x
+// A GEMM column block is v_mfma_f32_32x32x2_f32 over k ascending from 0 into zeroed accumulators, the A operand from LDS, the
+// weight rows from global memory (L2), lanes 0..31 feeding k and 32..63 k + 1: xfmr_gemm_kernel's chain, followed by
+// xg_epilogue<false>'s expressions.  Every other float expression is the forward's own __device__ function, so at fp32 u is
+// bit-identical to mf_xfmr_forward's out_u.  Rows >= n_b of a buffer hold whatever was there: no output depends on them (a
+// GEMM row, a LayerNorm row and a softmax over the n_b valid keys read their own rows only), and with n_b <= 32 the second 32-row
+// block is skipped.
+static constexpr int XENC_PAD = 4;          // row stride H + 4 floats: rows stay 16-byte aligned
+struct XEnc {
+    const float* table; int64_t n_rows;
+    const int64_t *seg_start, *seg_end, *items; int64_t n_items;
+    int L, layers, heads, I, act, mode, norm_item, norm_user;
+    const float* prm[XFMR_GLOBALS + XFMR_PER_LAYER * XFMR_MAX_LAYERS];
+    float* out_u;
+};
+static size_t xenc_lds_bytes(int h) {
+    return ((size_t)4 * XFMR_MAX_L * (h + XENC_PAD) + 4 * 64) * sizeof(float) + XFMR_MAX_L * sizeof(int64_t) + 16;
+}
+// LDS writes of this wave -> LDS reads of this wave's other lanes (the waves of a workgroup walk different heads: no barrier)
+__device__ __forceinline__ void xenc_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// One wave, one 32-column block: acc[rb][.] += sum_k A[rb 32 + row][k] w[col][k], k ascending over [0, K) (K a multiple of 16);
+// a = the A rows in LDS (row stride lda), wrow = this lane's weight row at its first k.  The next 16 k of the weights are
+// fetched under the MFMAs of the current ones.
+__device__ __forceinline__ void xenc_mma(const float* a, int lda, const float* __restrict__ wrow, int K, int nrb, int l31, int hh,
+                                         f32x16 (&acc)[2]) {
+    f32x4 w[4], wn[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w[q] = reinterpret_cast<const f32x4*>(wrow)[q];
+#pragma unroll 1
+    for (int k0 = 0; k0 < K; k0 += 16) {
+        if (k0 + 16 < K) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) wn[q] = reinterpret_cast<const f32x4*>(wrow + k0 + 16)[q];
+        }
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            if (rb < nrb) {
+                const f32x4* ar = reinterpret_cast<const f32x4*>(a + (rb * 32 + l31) * lda + k0);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 x = ar[q];
+                    acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(hh ? x[1] : x[0], hh ? w[q][1] : w[q][0], acc[rb], 0, 0, 0);
+                    acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(hh ? x[3] : x[2], hh ? w[q][3] : w[q][2], acc[rb], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[q] = wn[q];
+    }
+}
+__device__ __forceinline__ void xenc_zero(f32x16 (&acc)[2]) {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[rb][e] = 0.f;
+}
+// xg_epilogue<false> on LDS: out[m][n] = act((acc + bias[n]) + r[m][n]) for the wave's column block n0 (r null: no residual;
+// act < 0: none); out and r have row stride ld
+__device__ __forceinline__ void xenc_store(const f32x16 (&acc)[2], int nrb, int n0, const float* __restrict__ bias, const float* r,
+                                           int act, float* out, int ld, int l31, int hh) {
+    const int n = n0 + l31;
+    const float bv = bias[n];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        if (rb < nrb) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int o = (rb * 32 + mf_acc_row(e, hh)) * ld + n;
+                float v = acc[rb][e] + bv;
+                if (r) v += r[o];
+                out[o] = v;
+            }
+        }
+    }
+    if (act >= 0) {                // each lane over its own elements again, as a loop: one copy of xfmr_act's code, not 32
+#pragma unroll 1
+        for (int i = 0; i < 16 * nrb; ++i) {
+            const int o = ((i >> 4) * 32 + mf_acc_row(i & 15, hh)) * ld + n;
+            out[o] = xfmr_act(out[o], act);
+        }
+    }
+}
+// out = a w^T + bias (+ r) (act), w [N, K]: the N / 32 column blocks over the four waves
+__device__ __forceinline__ void xenc_linear(const float* a, int ld, int K, const float* __restrict__ w, const float* __restrict__ bias,
+                                            int N, const float* r, int act, float* out, int nrb) {
+    const int lane = mf_lane(), l31 = lane & 31, hh = lane >> 5;
+    for (int cb = threadIdx.x >> 6; cb < N / 32; cb += 4) {
+        f32x16 acc[2];
+        xenc_zero(acc);
+        xenc_mma(a, ld, w + (int64_t)(cb * 32 + l31) * K, K, nrb, l31, hh, acc);
+        xenc_store(acc, nrb, cb * 32, bias, r, act, out, ld, l31, hh);
+    }
+}
+// attention of the heads hd = wave, wave + 4, ..: xfmr_attn_kernel<DH, false>'s loop with K and V read in place; ctx -> q
+template <int DH>
+__device__ __forceinline__ void xenc_attention(float* q, const float* k, const float* v, int ld, int heads, int n, float* ps) {
+    const int lane = mf_lane();
+    for (int hd = threadIdx.x >> 6; hd < heads; hd += 4) {
+        const int col0 = hd * DH;
+        for (int i = 0; i < n; ++i) {
+            const float qv = q[i * ld + col0 + (lane & (DH - 1))];              // (lanes >= DH: never read by xattn_prob)
+            const float p = xattn_prob<DH>(qv, k + (lane < n ? lane : 0) * ld + col0, lane < n);
+            xenc_wave_sync();
+            ps[lane] = p;
+            xenc_wave_sync();
+            const float o = xattn_mix<DH>(ps, v + col0, ld, lane, n);
+            if (lane < DH) q[i * ld + col0 + lane] = o;
+        }
+    }
+}
+// 32 lanes per row: rows [0, n) of z (row stride ld) -> LayerNorm in place, eight rows at a time (whole waves in the row sums)
+template <int E>
+__device__ __forceinline__ void xenc_layernorm(float* z, int ld, int n, const float* __restrict__ gamma, const float* __restrict__ beta) {
+    const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const XRow<E> gm = xrow_load<E>(gamma, c), bt = xrow_load<E>(beta, c);
+    for (int t0 = 0; t0 < n; t0 += 8) {
+        const int t = t0 + g;
+        float* row = z + t * ld;                                 // (t <= 63: a row past n is read for nothing)
+        float mean, rstd;
+        const XRow<E> y = xrow_layernorm<E>(xrow_load<E>(row, c), gm, bt, mean, rstd);
+        if (t < n) xrow_store<E>(row, c, y);
+    }
+}
+
+template <int H>
+__global__ __launch_bounds__(256) void xfmr_encode_kernel(XEnc p) {
+    constexpr int E = H / 32, S = H + XENC_PAD, BUF = XFMR_MAX_L * S;
+    extern __shared__ __attribute__((aligned(16))) float xenc_lds[];
+    float* const ps = xenc_lds + 4 * BUF + 64 * (threadIdx.x >> 6);          // the wave's 64 probabilities
+    int64_t* const ids = reinterpret_cast<int64_t*>(xenc_lds + 4 * BUF + 4 * 64);
+    int* const n_sh = reinterpret_cast<int*>(ids + XFMR_MAX_L);
+    const int64_t b = blockIdx.x;
+    const int lane = mf_lane(), wave = threadIdx.x >> 6;
+    // ---- cut: list_cut_kernel<true> + xfmr_pack_kernel for this user, on wave 0
+    if (wave == 0) {
+        int64_t lo, hi;
+        list_clamp(p.seg_start[b], p.seg_end[b], p.n_items, lo, hi);
+        int need;
+        const int64_t cut = list_cut_walk(p.items, lo, hi, p.n_rows, p.L, need);
+        const int nb = p.L - need;
+        int done = 0;
+        for (int64_t base = cut; base < hi && done < nb; base += 64) {
+            const int64_t pos = base + lane;
+            const long long id = pos < hi ? p.items[pos] : 0;
+            const bool ok = list_valid(id, p.n_rows);
+            const unsigned long long m = __ballot(ok);
+            const int t = done + __popcll(m & ((1ull << lane) - 1ull));
+            if (ok && t < nb) ids[t] = id;
+            done += __popcll(m);
+        }
+        if (lane == 0) *n_sh = nb;
+    }
+    __syncthreads();
+    const int n = *n_sh;
+    if (n <= 0) {                                                // (whole workgroup) an empty list: u = 0
+        if (threadIdx.x < H) p.out_u[b * H + threadIdx.x] = 0.f;
+        return;
+    }
+    const int nrb = n > 32 ? 2 : 1;
+    float *bx = xenc_lds, *bq = xenc_lds + BUF, *bk = xenc_lds + 2 * BUF, *bv = xenc_lds + 3 * BUF;
+    // ---- embed: xfmr_embed_kernel<H, false>'s arithmetic, eight tokens at a time
+    {
+        const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
+        const XRow<E> te = xrow_load<E>(p.prm[1], c), gm = xrow_load<E>(p.prm[2], c), bt = xrow_load<E>(p.prm[3], c);
+        for (int t0 = 0; t0 < n; t0 += 8) {
+            const int t = t0 + g;
+            const bool valid = t < n;
+            const int tt = valid ? t : 0;
+            XRow<E> x = xrow_load<E>(p.table + ids[tt] * H, c);
+            if (p.norm_item) {
+                const float inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(x, x)), 1e-12f);
+#pragma unroll
+                for (int e = 0; e < E; ++e) x.v[e] = x.v[e] * inv;
+            }
+            const XRow<E> pe = xrow_load<E>(p.prm[0] + (int64_t)tt * H, c);
+            XRow<E> z;
+#pragma unroll
+            for (int e = 0; e < E; ++e) z.v[e] = (x.v[e] + te.v[e]) + pe.v[e];
+            float mean, rstd;
+            const XRow<E> y = xrow_layernorm<E>(z, gm, bt, mean, rstd);
+            if (valid) xrow_store<E>(bx + t * S, c, y);
+        }
+    }
+    __syncthreads();
+    const int l31 = lane & 31, hh = lane >> 5, dh = H / p.heads;
+    for (int l = 0; l < p.layers; ++l) {
+        const float* const* w = p.prm + XFMR_GLOBALS + XFMR_PER_LAYER * l;
+        // q, k, v: 3 H / 32 column blocks
+        for (int j = wave; j < 3 * (H / 32); j += 4) {
+            const int which = j / (H / 32), cb = j % (H / 32);
+            f32x16 acc[2];
+            xenc_zero(acc);
+            xenc_mma(bx, S, w[2 * which] + (int64_t)(cb * 32 + l31) * H, H, nrb, l31, hh, acc);
+            xenc_store(acc, nrb, cb * 32, w[2 * which + 1], nullptr, -1, which == 0 ? bq : which == 1 ? bk : bv, S, l31, hh);
+        }
+        __syncthreads();
+        switch (dh) {
+            case 8: xenc_attention<8>(bq, bk, bv, S, p.heads, n, ps); break;
+            case 16: xenc_attention<16>(bq, bk, bv, S, p.heads, n, ps); break;
+            case 32: xenc_attention<32>(bq, bk, bv, S, p.heads, n, ps); break;
+            default:
+                if constexpr (H >= 64) xenc_attention<64>(bq, bk, bv, S, p.heads, n, ps);
+                break;
+        }
+        __syncthreads();
+        xenc_linear(bq, S, H, w[6], w[7], H, bx, -1, bk, nrb);                 // z1 = ctx Wo^T + bo + x
+        __syncthreads();
+        xenc_layernorm<E>(bk, S, n, w[8], w[9]);                               // y1
+        __syncthreads();
+        f32x16 acc[2];                                                         // z2's column block `wave` (H / 32 <= 4 blocks)
+        xenc_zero(acc);
+        for (int c0 = 0; c0 < p.I; c0 += H) {
+            const int ic = min(H, p.I - c0);
+            xenc_linear(bk, S, H, w[10] + (int64_t)c0 * H, w[11] + c0, ic, nullptr, p.act, bq, nrb);   // f = act(y1 Wi^T + bi)
+            __syncthreads();
+            if (wave < H / 32) xenc_mma(bq, S, w[12] + (int64_t)(wave * 32 + l31) * p.I + c0, ic, nrb, l31, hh, acc);
+            __syncthreads();
+        }
+        if (wave < H / 32) xenc_store(acc, nrb, wave * 32, w[13], bk, -1, bv, S, l31, hh);   // z2 = acc + bo2 + y1
+        __syncthreads();
+        xenc_layernorm<E>(bv, S, n, w[14], w[15]);                             // y2
+        __syncthreads();
+        float* const t = bx; bx = bv; bv = t;
+    }
+    // ---- pool: xfmr_pool_kernel's arithmetic over the n rows, on one wave (both halves compute, the lower one stores) -- the
+    // last one: wave 0's mask, made for the cut, would stay in two SGPRs across the whole kernel
+    if (wave == 3) {
+        const int c = lane & 31;
+        XRow<E> pr = xrow_load<E>(bx, c);
+        if (p.mode != XPOOL_CLS) {
+            for (int j = 1; j < n; ++j) {
+                const XRow<E> r = xrow_load<E>(bx + j * S, c);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    if (p.mode == XPOOL_MEAN) pr.v[e] += r.v[e];
+                    else if (r.v[e] > pr.v[e]) pr.v[e] = r.v[e];
+                }
+            }
+            if (p.mode == XPOOL_MEAN) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) pr.v[e] = pr.v[e] / (float)n;
+            }
+        }
+        if (p.norm_user) {
+            const float inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(pr, pr)), 1e-12f);
+#pragma unroll
+            for (int e = 0; e < E; ++e) pr.v[e] = pr.v[e] * inv;
+        }
+        if (lane < 32) xrow_store<E>(p.out_u + b * H, c, pr);
+    }
 }
 
 // ======================================================================================== host: layout ====
@@ -1073,6 +1350,38 @@ extern "C" int mf_xfmr_forward_mixed(const float* table, int64_t n_rows, int h, 
         return mf_set_error(MF_EINVAL, "mf_xfmr_forward_dropout: dropout probabilities must be in [0, 1): %g, %g", p_hidden, p_attn);
     return xfmr_forward(table, n_rows, h, seg_start, seg_end, items, n_items, B, t_cap, max_history, layers, heads, intermediate, act, mode,
                         norm_item, norm_user, params, out_u, out_inv, out_arg, stash, stash_bytes, drop, precision, stream);
+}
+
+// one launch, one workgroup per user: no t_cap, no stash, no host read; everything below is decided before any GPU call
+extern "C" int mf_xfmr_encode(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
+                              const int64_t* items, int64_t n_items, int64_t B, int max_history, int layers, int heads,
+                              int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
+                              float* out_u, mf_stream_t stream) {
+    if (!table || !seg_start || !seg_end || !items || !params || !out_u || B <= 0 || n_rows <= 0 || n_items <= 0 || act < 0 || act > 3 ||
+        mode < 0 || mode > 2)
+        return mf_set_error(MF_EINVAL, "mf_xfmr_encode: bad argument");
+    if (const char* why = xfmr_check_shape(h, layers, heads, intermediate, max_history))
+        return mf_set_error(MF_ENOTSUP, "mf_xfmr_encode: %s", why);
+    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_xfmr_encode: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
+    if (B >= (1ll << 31) / 64) return mf_set_error(MF_ENOTSUP, "mf_xfmr_encode: too many users");
+    XEnc p{};
+    for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i) {
+        if (!params[i]) return mf_set_error(MF_EINVAL, "mf_xfmr_encode: parameter %d is null", i);
+        p.prm[i] = params[i];
+    }
+    p.table = table; p.n_rows = n_rows; p.seg_start = seg_start; p.seg_end = seg_end; p.items = items; p.n_items = n_items;
+    p.L = max_history; p.layers = layers; p.heads = heads; p.I = intermediate; p.act = act; p.mode = mode;
+    p.norm_item = norm_item; p.norm_user = norm_user; p.out_u = out_u;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t lds = xenc_lds_bytes(h);
+    MF_TIMED("xfmr_encode", s, {
+        XFMR_DISPATCH_H(h, {
+            auto fn = xfmr_encode_kernel<H>;
+            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            fn<<<dim3((unsigned)B), 256, lds, s>>>(p);
+        });
+    });
+    return mf_check_launch("mf_xfmr_encode");
 }
 
 // ============================================================================================ backward ====

@@ -110,8 +110,11 @@ class MatrixFactorizationLitModule(_Base):
         proc = self.item_processor
         rows = [proc.row_of(i) for i in item_ids] if (proc is not None and proc._row_of_id is not None) else [int(i) for i in item_ids]
         device = self.towers["item"].weight.device
+        history = torch.tensor([rows or [0]], dtype=torch.int64, device=device)
+        if isinstance(self.towers["user"], models.HistoryTransformerTower):      # its serving path: eval mode whatever the tower's
+            return self.towers["user"].encode(history)
         with self._user_tower_eval() as tower:
-            return tower(torch.tensor([rows or [0]], dtype=torch.int64, device=device))
+            return tower(history)
 
     @torch.inference_mode()
     def recommend_with_history(self, item_ids: list[int], *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
@@ -334,6 +337,9 @@ class MatrixFactorizationLitModule(_Base):
     def _queries(self, batch) -> torch.Tensor:
         """The users' query vectors: their table rows, or (history tower) their pooled history -- the same CSR
         ``(offsets, item rows)`` that is excluded from retrieval (``InteractionTable.eval_sets``)."""
+        if self.towers is not None and isinstance(self.towers["user"], models.HistoryTransformerTower):   # its serving path
+            off, items = batch["history"]
+            return self.towers["user"].encode((off[:-1], off[1:], items))
         with self._user_tower_eval():
             if self.config.user_tower not in HISTORY_TOWERS:
                 return self(batch["user"]["idx"], tower="user")

@@ -140,6 +140,13 @@ def check_pooling_mode(mode: str) -> str:
 TRANSFORMER_POOLING_MODES = ("mean", "max", "cls")
 HIDDEN_ACTS = ("gelu", "relu", "silu", "gelu_new")      # the kernels' activation codes, in this order
 XFMR_MAX_POSITIONS = 64
+# ``HistoryTransformerTower.encode(path="auto")`` takes the one-launch kernel (``mf_xfmr_encode``) up to this many users and
+# the training forward above it; None: at every batch size.  The two are bit-identical, so this is a speed decision only.
+# Measured on an MI355X (``tools/xfmr_encode_probe.py``, ``profiles/xfmr_encode_probe.json``; the table is in DESIGN.md section
+# 4, *Serving encode*): fused is 1.02-3.4 x faster at B = 1, 8 and 64 at all three probe shapes, slower at B = 512 at (128, 64,
+# 512) and at B >= 4096 everywhere (a workgroup per user re-reads the weights; the forward's GEMMs share them).
+XFMR_ENCODE_FUSED_MAX_USERS: int | None = 64
+ENCODE_PATHS = ("auto", "fused", "forward")
 
 
 def check_transformer_shape(hidden_size: int, num_hidden_layers: int, num_attention_heads: int, intermediate_size: int | None,
@@ -393,8 +400,9 @@ class PooledHistoryGrad(PooledGrad):
                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr())
 
 
-def _history_segments(dev, history):
-    """``(start, end, items, n_entries)`` of either input form (one host read of the entry count for segments)."""
+def _history_segments(dev, history, count: bool = True):
+    """``(start, end, items, n_entries)`` of either input form (one host read of the entry count for segments; ``count=False``
+    leaves it out: ``n_entries`` is then None)."""
     if isinstance(history, (tuple, list)):
         start, end, items = (_lib.dev_i64(t, name) for t, name in zip(history, ("start", "end", "items")))
         start, end = start.reshape(-1), end.reshape(-1)
@@ -402,7 +410,7 @@ def _history_segments(dev, history):
             msg = f"start and end must have the same length: {start.numel()} != {end.numel()}"
             raise ValueError(msg)
         items = items.reshape(-1)
-        n_entries = int((end - start).clamp_min(0).sum()) if start.numel() else 0
+        n_entries = (int((end - start).clamp_min(0).sum()) if start.numel() else 0) if count else None
     else:
         pad = _lib.dev_i64(history, "history")
         if pad.dim() != 2:  # noqa: PLR2004
@@ -602,7 +610,8 @@ class HistoryTransformerTower(torch.nn.Module):
     table (its backward lands on that table's sparse update) and owns the encoder's dense parameters, named as
     ``transformers.BertModel``'s ``state_dict`` names them (no word-embedding table, no pooler dense); those receive ordinary
     ``.grad`` tensors.  fp32 throughout, LayerNorm eps 1e-12.  HIP kernels ``mf_xfmr_forward`` / ``mf_xfmr_backward`` /
-    ``mf_xfmr_coalesce``.  The tower may be applied more than once before a step (each call parks its own table gradient;
+    ``mf_xfmr_coalesce``; :meth:`encode` is the serving path (``mf_xfmr_encode``: one launch, no stash).  The tower may be
+    applied more than once before a step (each call parks its own table gradient;
     the optimiser chains the coalesces, the dense gradients accumulate).  No hipGraph capture: ``forward`` raises
     ``MfHipError`` when the stream is capturing.
 
@@ -704,20 +713,69 @@ class HistoryTransformerTower(torch.nn.Module):
         """As :meth:`HistoryPoolingTower.segments`."""
         return _history_segments(self.weight.device, history)
 
-    def forward(self, history) -> torch.Tensor:
+    def _config(self) -> tuple:
+        """The kernels' view of the tower, without dropout or precision: the eval-mode fp32 function."""
+        return (self.num_hidden_layers, self.num_attention_heads, self.intermediate_size, HIDDEN_ACTS.index(self.hidden_act),
+                TRANSFORMER_POOLING_MODES.index(self.pooling_mode), self.max_history, self.item_tower.normalize, self.normalize)
+
+    def _forward(self, history, dropout: bool) -> torch.Tensor:
         if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():    # (before ``segments``: its host read would fail first)
             raise _lib.MfHipError("the transformer tower does not support hipGraph capture")
         start, end, items, n_entries = self.segments(history)
         if start.numel() == 0:
             return torch.zeros(0, self.weight.shape[1], device=self.weight.device)
-        cfg = (self.num_hidden_layers, self.num_attention_heads, self.intermediate_size, HIDDEN_ACTS.index(self.hidden_act),
-               TRANSFORMER_POOLING_MODES.index(self.pooling_mode), self.max_history, self.item_tower.normalize, self.normalize)
-        if self.training and (self.hidden_dropout_prob > 0.0 or self.attention_probs_dropout_prob > 0.0):
+        cfg = self._config()
+        if dropout and (self.hidden_dropout_prob > 0.0 or self.attention_probs_dropout_prob > 0.0):
             cfg += ((self.hidden_dropout_prob, self.attention_probs_dropout_prob, self.dropout_seed, self.dropout_call),)
             self.dropout_call += 1
         if self.precision != "fp32":
             cfg = cfg[:8] + (cfg[8] if len(cfg) > 8 else None, PRECISIONS.index(self.precision))  # noqa: PLR2004
         return _EncodeHistory.apply(self.weight, start, end, items, n_entries, cfg, *self.encoder_parameters())
+
+    def forward(self, history) -> torch.Tensor:
+        return self._forward(history, self.training)
+
+    def encode(self, history, *, path: str = "auto") -> torch.Tensor:
+        """``[B, d]`` query vectors for serving and metrics: the eval-mode function of :meth:`forward` (no dropout even when
+        ``tower.training``; ``dropout_call`` does not advance), detached -- no graph, no stash kept, nothing parked on the
+        table, no ``torch.no_grad()`` needed around it.  ``history`` as for :meth:`forward`.
+
+        ``path="fused"``: ``mf_xfmr_encode`` -- one launch, one workgroup per user, every activation in LDS, no per-token memory
+        and no host read; fp32 only (``ValueError`` on a ``bf16-mixed`` tower).  ``path="forward"``: the training forward's
+        kernels in eval mode at the tower's precision.  At fp32 the two are bit-identical.  ``path="auto"``: ``"forward"`` when
+        the tower is not fp32 (the precision stays the tower's own in serving) or there are more than
+        ``XFMR_ENCODE_FUSED_MAX_USERS`` users, ``"fused"`` otherwise."""
+        if path not in ENCODE_PATHS:
+            msg = f"path must be one of {ENCODE_PATHS}: {path = }"
+            raise ValueError(msg)
+        if path == "fused" and self.precision != "fp32":
+            msg = f"the fused encode kernel is fp32: a {self.precision!r} tower encodes through path='forward' (or 'auto')"
+            raise ValueError(msg)
+        start, end, items, _ = _history_segments(self.weight.device, history, count=False)      # (no host read)
+        if path == "auto":
+            limit = XFMR_ENCODE_FUSED_MAX_USERS
+            fused = self.precision == "fp32" and (limit is None or start.numel() <= limit)
+            path = "fused" if fused else "forward"
+        if path == "forward":
+            with torch.no_grad():
+                return self._forward(history, dropout=False)
+        table = self.weight.detach()
+        _check_table(table, "embedding")
+        params = tuple(p.detach() for p in self.encoder_parameters())
+        for p in params:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.MfHipError("encoder parameters must be contiguous fp32 tensors on the GPU")
+        rows, d = table.shape
+        b = start.numel()
+        u = torch.empty(b, d, dtype=torch.float32, device=table.device)
+        if b == 0:
+            return u
+        layers, heads, inter, act, mode, max_history, norm_item, norm_user = self._config()
+        lib = _lib.lib()
+        _lib.check(lib.mf_xfmr_encode(table.data_ptr(), rows, d, start.data_ptr(), end.data_ptr(), items.data_ptr(), items.numel(), b,
+                                      max_history, layers, heads, inter, act, mode, int(norm_item), int(norm_user),
+                                      _pointer_array(params), u.data_ptr(), _lib.stream_ptr()))
+        return u
 
     def extra_repr(self) -> str:
         return (f"layers={self.num_hidden_layers}, heads={self.num_attention_heads}, intermediate={self.intermediate_size}, "

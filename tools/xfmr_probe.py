@@ -85,7 +85,7 @@ def main() -> None:
     args = ap.parse_args()
     mf = importlib.import_module("matrix-factorization-torch_amd")
     have = ctypes.CDLL(str(mf._lib.LIB_PATH))   # another build of the library may not have the newest exports
-    new = lambda n: "dropout" in n or "mixed" in n or "xfmr_dense" in n or (args.baseline_only and n.startswith("mf_xfmr_"))  # noqa: E731
+    new = lambda n: "dropout" in n or "mixed" in n or "xfmr_dense" in n or "xfmr_encode" in n or (args.baseline_only and n.startswith("mf_xfmr_"))  # noqa: E731
     missing = [n for n in mf._lib.SIGNATURES if new(n) and not hasattr(have, n)]
     for name in missing:
         del mf._lib.SIGNATURES[name]

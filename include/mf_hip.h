@@ -274,7 +274,7 @@ int mf_step_small(float* user_table, float* user_m, float* user_v, int64_t num_u
  * GLOBAL item row indices in any order; both nullable), best first, ties by lowest
  * item index.  `idx_base` is the global index of items[0] (row-sharded catalogs).
  * out_scores[Q,k] fp32, out_idx[Q,k] int64 global indices (-1 / -inf padding when
- * fewer than k candidates).  k <= 64. */
+ * fewer than k candidates).  k <= 64 (deeper lists: mf_topk_deep below). */
 size_t mf_topk_ws_bytes(int64_t Q, int64_t N, int d, int k);
 /* Host-only geometry query: the number of catalog chunks (one workgroup column each) mf_topk would use for this shape, and
  * the rows per chunk -- a chunk is staged through one 32-bit buffer descriptor, so rows_per_chunk * d * 4 <= ~4 GiB always
@@ -325,6 +325,25 @@ int mf_topk_bf3(const float* q, int64_t Q, const float* items, const void* index
                 const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
                 float* out_scores, int64_t* out_idx, mf_stream_t stream);
 
+/* Deep candidate lists: the same exact top-k for 1 <= k <= MF_TOPK_DEEP_MAX_K (the three engines above stop at 64: one
+ * wavefront holds a row's result).  Scores once, then selects from the scores, in blocks of queries: the fp32 MFMA chain
+ * writes a slab of 32-bit ranks [queries per block][N rounded up to 32], exclusions are stored over it, and one workgroup
+ * per query finds the k-th best rank by an MSB-first radix select (integer LDS histograms), collects what ranks above it,
+ * takes ties in ascending row order and sorts.  Scores, order, rows, exclusion semantics, idx_base and the -inf / -1 tail are
+ * IDENTICAL to mf_topk's.  The workspace is the slab: the number of query blocks follows from its size --
+ * mf_topk_deep_ws_bytes is the preferred size (one slab of at most 256 MiB), mf_topk_deep_min_ws_bytes one block of 32
+ * queries; both are 0 for invalid shapes (k outside 1..1024 included).  mf_topk_deep_plan is host-only: out[0] = queries per
+ * block (a multiple of 32), out[1] = blocks, out[2] = slab bytes per block for a workspace of ws_bytes.  Limits as mf_topk
+ * (N < 2^31, idx_base + N <= 2^32, d in {32, 64, 128, 256}), and a 32-query slab must stay below 4 GiB (N <= ~33.5 M):
+ * MF_ENOTSUP beyond, as for k outside 1..1024; MF_ENOSPC below the minimum workspace; all decided before any launch. */
+#define MF_TOPK_DEEP_MAX_K 1024
+size_t mf_topk_deep_ws_bytes(int64_t Q, int64_t N, int d, int k);
+size_t mf_topk_deep_min_ws_bytes(int64_t Q, int64_t N, int d, int k);
+int mf_topk_deep_plan(int64_t Q, int64_t N, int d, int k, size_t ws_bytes, int64_t* out);
+int mf_topk_deep(const float* q, int64_t Q, const float* items, int64_t N, int d, int k,
+                 const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base,
+                 void* ws, size_t ws_bytes, float* out_scores, int64_t* out_idx, mf_stream_t stream);
+
 /* Retrieval metrics @k on device, straight from the top-k output.  Replaces the
  * per-example torchmetrics updates of `update_metrics` / `get_metrics` (xfmr_rec/lightning.py:149-187,
  * :289-306: RetrievalNormalizedDCG / Recall / Precision / MAP / HitRate / MRR, top_k = 20).
@@ -333,7 +352,8 @@ int mf_topk_bf3(const float* q, int64_t Q, const float* items, const void* index
  * every retrieved item (the reference gives it -U(0,1): the same whenever retrieved scores are
  * positive).  out[q][6] = {ndcg, recall, precision, map, hit_rate, mrr} of query q with torchmetrics'
  * definitions: linear gain / log2 discount, binary relevance = rating > 0 for the other five,
- * precision divided by k, a query without positive target scores 0 everywhere. */
+ * precision divided by k, a query without positive target scores 0 everywhere.  k <= 1024 (k <= 64: one rank per lane;
+ * beyond, lane t walks ranks t, t + 64, ...); MF_ENOTSUP above. */
 int mf_retrieval_metrics(const int64_t* topk_idx, int64_t Q, int k, const int64_t* tgt_off,
                          const int64_t* tgt_idx, const float* tgt_rel, float* out, mf_stream_t stream);
 

@@ -87,6 +87,10 @@ SIGNATURES = {
     "mf_topk_bf3_build": (c_int, [c_vp, c_i64, c_int, c_vp, c_sz, c_vp]),
     "mf_topk_bf3_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "mf_topk_bf3": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "mf_topk_deep_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
+    "mf_topk_deep_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
+    "mf_topk_deep_plan": (c_int, [c_i64, c_i64, c_int, c_int, c_sz, ctypes.POINTER(c_i64)]),
+    "mf_topk_deep": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "mf_pool_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "mf_pool_forward": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -126,6 +130,7 @@ SIGNATURES = {
 }
 
 MF_OK, MF_EINVAL, MF_ENOSPC, MF_ELAUNCH, MF_ENOTSUP = 0, -1, -2, -3, -4       # return codes (include/mf_hip.h)
+MF_TOPK_DEEP_MAX_K = 1024                                 # deepest top-k any engine serves: mf_topk_deep (include/mf_hip.h)
 XFMR_FP32, XFMR_BF16_MIXED = 0, 1                         # precision of the transformer tower's dense layers (include/mf_hip.h)
 LOSS_TARGET_I64, LOSS_ROWC, LOSS_MASKS_READY = 1, 2, 4     # flags of mf_loss_fwd / mf_loss_bwd (include/mf_hip.h)
 

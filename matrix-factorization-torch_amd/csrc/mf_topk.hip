@@ -311,10 +311,17 @@ __global__ __launch_bounds__(64) void retrieval_metrics_kernel(const int64_t* __
     }
 }
 
+void mf_retrieval_metrics_deep_launch(const int64_t* topk_idx, int64_t Q, int k, const int64_t* tgt_off, const int64_t* tgt_idx,
+                                      const float* tgt_rel, float* out, hipStream_t s);       // mf_topk_deep.hip
+
 extern "C" int mf_retrieval_metrics(const int64_t* topk_idx, int64_t Q, int k, const int64_t* tgt_off,
                                     const int64_t* tgt_idx, const float* tgt_rel, float* out, mf_stream_t stream) {
     if (!topk_idx || !tgt_off || !tgt_idx || !tgt_rel || !out || Q <= 0) return mf_set_error(MF_EINVAL, "mf_retrieval_metrics: bad argument");
-    if (k <= 0 || k > 64) return mf_set_error(MF_ENOTSUP, "mf_retrieval_metrics: k = %d outside 1..64", k);
+    if (k <= 0 || k > MF_TOPK_DEEP_MAX_K) return mf_set_error(MF_ENOTSUP, "mf_retrieval_metrics: k = %d outside 1..%d", k, MF_TOPK_DEEP_MAX_K);
+    if (k > 64) {                 // lane t walks ranks t, t + 64, ...: same definitions, same layout (mf_topk_deep.hip)
+        mf_retrieval_metrics_deep_launch(topk_idx, Q, k, tgt_off, tgt_idx, tgt_rel, out, static_cast<hipStream_t>(stream));
+        return mf_check_launch("mf_retrieval_metrics");
+    }
     retrieval_metrics_kernel<<<dim3((unsigned)Q), 64, 0, static_cast<hipStream_t>(stream)>>>(topk_idx, k, tgt_off, tgt_idx, tgt_rel, out);
     return mf_check_launch("mf_retrieval_metrics");
 }

@@ -58,6 +58,10 @@ class ItemIndex:
     AUTO_SMALL_Q = 32  # scan up to here, then the bf16 prefilter (d >= 64), else the fp32 tile engine
     SCAN_MAX_EXCL = 8192     # exclusion entries (all queries of a call) the scan stages in LDS: EX_CAP of mf_topk_small.hip
 
+    PATHS = ("auto", "scan", "tiles", "bf16", "deep")
+    TILE_MAX_K = 64    # "scan", "tiles" and "bf16" hold a row's result in one wavefront; "auto" sends deeper lists to "deep"
+    DEEP_MAX_K = _lib.MF_TOPK_DEEP_MAX_K
+
     def blocked(self) -> torch.Tensor:
         """The catalog in the blocked layout of ``mf_topk_small`` (``[64-row block][chunk][row]``), built once."""
         if self._blocked is None:
@@ -101,8 +105,10 @@ class ItemIndex:
         """``(scores [Q, k] fp32, rows [Q, k] int64)``, best first; ``exclude`` holds GLOBAL
         item rows per query (or pass a prebuilt device CSR with sorted ids).  ``path``: "scan" = the
         matrix-vector kernel (at most ``SMALL_Q`` queries), "tiles" = the fp32 MFMA tile engine, "bf16" = two bf16
-        MFMA scans that pick the few dozen rows per query worth an exact fp32 score (d >= 64), "auto" picks by the
-        number of queries; all three give the same bits."""
+        MFMA scans that pick the few dozen rows per query worth an exact fp32 score (d >= 64), "deep" = score once, then
+        a radix select per query (``mf_topk_deep``: any ``top_k`` up to ``DEEP_MAX_K``; the other three stop at
+        ``TILE_MAX_K``); "auto" takes "deep" exactly when ``top_k > TILE_MAX_K`` and otherwise picks by the number of
+        queries; all four give the same bits."""
         q = _lib.dev_f32(queries, "queries")
         if q.dim() != 2 or q.shape[1] != self.dim:
             msg = f"queries should be (num_queries, {self.dim}): {tuple(q.shape) = }"
@@ -114,8 +120,8 @@ class ItemIndex:
         lib = _lib.lib()
         scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
         rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
-        if path not in ("auto", "scan", "tiles", "bf16"):
-            msg = f"path must be 'auto', 'scan', 'tiles' or 'bf16': {path = }"
+        if path not in self.PATHS:
+            msg = f"path must be 'auto', 'scan', 'tiles', 'bf16' or 'deep': {path = }"
             raise ValueError(msg)
         if path == "bf16" and d < 64:
             msg = f"the bf16 path needs an embedding width of at least 64: {d = }"
@@ -123,6 +129,12 @@ class ItemIndex:
         if path == "scan" and nq > self.SMALL_Q:
             msg = f"the scan path takes at most {self.SMALL_Q} queries: {nq = }"
             raise ValueError(msg)
+        if path == "deep" or (path == "auto" and top_k > self.TILE_MAX_K):
+            ws = self._workspace(("deep", nq, top_k), lib.mf_topk_deep_ws_bytes(nq, n, d, top_k))
+            _lib.check(lib.mf_topk_deep(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, top_k, _lib.ptr(off), _lib.ptr(ids),
+                                        self.idx_base, ws.data_ptr(), ws.numel(), scores.data_ptr(), rows.data_ptr(),
+                                        _lib.stream_ptr()))
+            return scores, rows
         # the few-query scan matches exclusion entries against every 64-row block: staged in LDS up to SCAN_MAX_EXCL entries
         # (all queries together), a walk over each query's list per block beyond -- measured at N = 62,423: Q = 8 x 2,000 ids
         # 89 us, Q = 32 x 30,000 ids 4 ms, against 46 / 85 us through the prefilter (which builds bit rows once).  So "auto"

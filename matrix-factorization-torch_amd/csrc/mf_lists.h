@@ -1,6 +1,6 @@
 // mf_lists.h -- what the list towers (mf_pool.hip: history, mf_bag.hip: feature bags, mf_xfmr.hip: transformer) and their
-// coalesce (mf_coalesce.h) share: which ids count, where owner b's list lies, the cut to its last L valid entries, the owner
-// of a numbered work item, a block-wide exclusive scan, the lane groups' butterfly sum and the final row normalisation.
+// coalesce (mf_coalesce.h) share: which ids count, where owner b's list lies, the cut to its last L valid entries and the walk
+// that packs them, the owner of a numbered work item, a block-wide exclusive scan, the lane groups' butterfly sum and the final row normalisation.
 // Everything here is integer arithmetic or one float expression in one fixed order: a caller's results do not depend on
 // which tower it is.
 #pragma once
@@ -53,6 +53,24 @@ __device__ __forceinline__ int64_t list_cut_walk(const int64_t* __restrict__ ite
         need -= c;
     }
     return cut;
+}
+
+// One wave, the list items[lo, hi): its valid entries in list order, the first `count` of them; entry number slot (0 ..) goes
+// to emit(slot, id) on the lane that read it.  After list_cut_walk: lo = the cut, count = L - need.
+template <class F>
+__device__ __forceinline__ void list_pack_walk(const int64_t* __restrict__ items, int64_t lo, int64_t hi, int64_t n_rows, int count,
+                                               F emit) {
+    const int lane = mf_lane();
+    int done = 0;
+    for (int64_t base = lo; base < hi && done < count; base += 64) {
+        const int64_t pos = base + lane;
+        const long long id = pos < hi ? items[pos] : 0;
+        const bool ok = list_valid(id, n_rows);
+        const unsigned long long m = __ballot(ok);
+        const int slot = done + __popcll(m & ((1ull << lane) - 1ull));
+        if (ok && slot < count) emit(slot, id);
+        done += __popcll(m);
+    }
 }
 
 // One wave per owner: cut_out[b] = list_cut_walk's position, and with COUNT also nb_out[b] = min(valid entries, L).

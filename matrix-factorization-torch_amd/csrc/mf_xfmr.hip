@@ -91,25 +91,15 @@ __global__ __launch_bounds__(256) void xfmr_pack_kernel(const int64_t* __restric
                                                         const int64_t* __restrict__ items, int64_t n_items, int64_t B, int64_t n_rows,
                                                         const int64_t* __restrict__ tok_off, int64_t* __restrict__ tok_item,
                                                         int32_t* __restrict__ tok_user) {
-    const int lane = mf_lane();
     const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
     int64_t lo, hi;
     list_clamp(cut[b], seg_end[b], n_items, lo, hi);            // (cut[b] lies in the list: lo = cut[b])
-    const int64_t t0 = tok_off[b], t1 = tok_off[b + 1];
-    int64_t done = 0;
-    for (int64_t base = lo; base < hi && t0 + done < t1; base += 64) {
-        const int64_t pos = base + lane;
-        const long long id = pos < hi ? items[pos] : 0;
-        const bool ok = list_valid(id, n_rows);
-        const unsigned long long m = __ballot(ok);
-        const int64_t t = t0 + done + __popcll(m & ((1ull << lane) - 1ull));
-        if (ok && t < t1) {
-            tok_item[t] = id;
-            tok_user[t] = (int32_t)b;
-        }
-        done += __popcll(m);
-    }
+    const int64_t t0 = tok_off[b];
+    list_pack_walk(items, lo, hi, n_rows, (int)(tok_off[b + 1] - t0), [&](int slot, long long id) {   // (at most n_b <= 64 tokens)
+        tok_item[t0 + slot] = id;
+        tok_user[t0 + slot] = (int32_t)b;
+    });
 }
 
 // ================================================================================== rows of 32 lanes ====
@@ -163,6 +153,56 @@ __device__ __forceinline__ XRow<E> xrow_layernorm(const XRow<E>& z, const XRow<E
     for (int e = 0; e < E; ++e) y.v[e] = (z.v[e] - mean) * rstd * gamma.v[e] + beta.v[e];
     return y;
 }
+// r = r / max(|r|, 1e-12) iff do_norm (gather_rows_kernel's arithmetic); returns the factor, 1 when there is none
+template <int E>
+__device__ __forceinline__ float xrow_normalize(XRow<E>& r, int do_norm) {
+    float inv = 1.f;
+    if (do_norm) {
+        inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(r, r)), 1e-12f);
+#pragma unroll
+        for (int e = 0; e < E; ++e) r.v[e] = r.v[e] * inv;
+    }
+    return inv;
+}
+// the embeddings of one token: z = (x + te) + pe over its item row x (normalised iff norm_item), the token-type row te and its
+// position's row pe; returns LN(z), leaves z and the LayerNorm's row statistics
+template <int E>
+__device__ __forceinline__ XRow<E> xrow_embed(XRow<E> x, int norm_item, const XRow<E>& te, const XRow<E>& pe, const XRow<E>& gamma,
+                                              const XRow<E>& beta, XRow<E>& z, float& mean, float& rstd) {
+    xrow_normalize<E>(x, norm_item);
+#pragma unroll
+    for (int e = 0; e < E; ++e) z.v[e] = (x.v[e] + te.v[e]) + pe.v[e];
+    return xrow_layernorm<E>(z, gamma, beta, mean, rstd);
+}
+enum { XPOOL_MEAN = 0, XPOOL_MAX = 1, XPOOL_CLS = 2 };
+// the pool of the n > 0 rows at y (row stride ld): their mean, their max (the first position wins ties; ARG: arg[e] = where it
+// is) or row 0
+template <int E, bool ARG>
+__device__ __forceinline__ XRow<E> xrow_pool(const float* y, int ld, int c, int n, int mode, int* arg) {
+    XRow<E> p = xrow_load<E>(y, c);
+    if constexpr (ARG) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) arg[e] = 0;
+    }
+    if (mode != XPOOL_CLS) {
+        for (int j = 1; j < n; ++j) {
+            const XRow<E> r = xrow_load<E>(y + j * ld, c);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                if (mode == XPOOL_MEAN) p.v[e] += r.v[e];
+                else if (r.v[e] > p.v[e]) {
+                    p.v[e] = r.v[e];
+                    if constexpr (ARG) arg[e] = j;
+                }
+            }
+        }
+        if (mode == XPOOL_MEAN) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) p.v[e] = p.v[e] / (float)n;
+        }
+    }
+    return p;
+}
 
 // ============================================================================================== embed ====
 // token t of user b: x = the item row (normalised iff norm_item, gather_rows_kernel's arithmetic), z0 = (x + tok[0]) + pos[t],
@@ -184,18 +224,10 @@ __global__ __launch_bounds__(256) void xfmr_embed_kernel(const float* __restrict
     const int64_t id = any ? tok_item[tt] : 0;
     const int64_t b = any ? tok_user[tt] : 0;
     const int p = any ? (int)(tt - tok_off[b]) : 0;
-    XRow<E> x = xrow_load<E>(table + id * H, c);
-    if (norm_item) {
-        const float inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(x, x)), 1e-12f);
-#pragma unroll
-        for (int e = 0; e < E; ++e) x.v[e] = x.v[e] * inv;
-    }
-    const XRow<E> pe = xrow_load<E>(pos + (int64_t)p * H, c), te = xrow_load<E>(tok, c);
     XRow<E> z;
-#pragma unroll
-    for (int e = 0; e < E; ++e) z.v[e] = (x.v[e] + te.v[e]) + pe.v[e];
     float mean, rstd;
-    XRow<E> y = xrow_layernorm<E>(z, xrow_load<E>(gamma, c), xrow_load<E>(beta, c), mean, rstd);
+    XRow<E> y = xrow_embed<E>(xrow_load<E>(table + id * H, c), norm_item, xrow_load<E>(tok, c), xrow_load<E>(pos + (int64_t)p * H, c),
+                              xrow_load<E>(gamma, c), xrow_load<E>(beta, c), z, mean, rstd);
     if constexpr (DROP) {                                      // (the lane's E <= 4 columns share one word)
         const unsigned long long wd = xdrop_hidden_word(dr, b, p, c * E);
 #pragma unroll
@@ -429,17 +461,43 @@ struct XDropRows {
     const int32_t* tok_user;
     const int64_t* tok_off;
 };
+// What both forms of the engine begin with: the workgroup's 64 x 64 tile (rows m0 .. of M, columns n0 ..), its k range and output
+// (dyn = 1: slice blockIdx.z of the T tokens and that slice's partials), the wave's 32 x 32 block (wm, wn) and the lane's place
+// in an MFMA operand (row l31, k half hh).  empty: the tile lies past the M rows, the whole workgroup leaves.
+struct XgTile {
+    int64_t T, M, m0, n0, kbeg, kend;
+    float* C;
+    int wm, wn, l31, hh;
+    bool empty;
+};
+__device__ __forceinline__ XgTile xg_tile(const XGemm& g) {
+    XgTile t;
+    t.T = *g.T_dev;
+    t.M = g.dyn == 0 ? t.T : g.M;
+    t.m0 = (int64_t)blockIdx.x * 64, t.n0 = (int64_t)blockIdx.y * 64;
+    t.empty = t.m0 >= t.M;
+    t.kbeg = 0, t.kend = g.K, t.C = g.C;
+    if (g.dyn == 1) {
+        const int64_t len = xfmr_slice_len(t.T, XFMR_SLICES, 16);
+        t.kbeg = min((int64_t)blockIdx.z * len, t.T);
+        t.kend = min(t.kbeg + len, t.T);
+        t.C += (int64_t)blockIdx.z * g.slice_stride;
+    }
+    const int lane = mf_lane(), wave = threadIdx.x >> 6;
+    t.wm = wave >> 1, t.wn = wave & 1, t.l31 = lane & 31, t.hh = lane >> 5;
+    return t;
+}
 // the wave's 32 x 32 block of the tile (rows m0 + wm 32 .., columns n0 + wn 32 ..) -> memory, fp32 in both precisions
 template <bool DROP>
-__device__ __forceinline__ void xg_epilogue(const XGemm& g, const XDropRows& dr, float* __restrict__ C, const f32x16& acc, int64_t M,
-                                            int64_t m0, int64_t n0, int wm, int wn, int l31, int hh) {
-    const int64_t n = n0 + wn * 32 + l31;
+__device__ __forceinline__ void xg_epilogue(const XGemm& g, const XDropRows& dr, const XgTile& t, const f32x16& acc) {
+    float* __restrict__ C = t.C;
+    const int64_t n = t.n0 + t.wn * 32 + t.l31;
     if (n < g.N) {
         const float bias = g.bias ? g.bias[n] : 0.f;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int64_t m = m0 + wm * 32 + mf_acc_row(e, hh);
-            if (m < M) {
+            const int64_t m = t.m0 + t.wm * 32 + mf_acc_row(e, t.hh);
+            if (m < t.M) {
                 const int64_t o = m * g.ldc + n;
                 float v = acc[e] + bias;
                 if constexpr (DROP) {
@@ -458,46 +516,34 @@ __device__ __forceinline__ void xg_epilogue(const XGemm& g, const XDropRows& dr,
 template <bool DROP>
 __global__ __launch_bounds__(256) void xfmr_gemm_kernel(XGemm g, XDropRows dr) {
     __shared__ float As[16][XG_LD], Bs[16][XG_LD];
-    const int64_t T = *g.T_dev;
-    const int64_t M = g.dyn == 0 ? T : g.M;
-    const int64_t m0 = (int64_t)blockIdx.x * 64, n0 = (int64_t)blockIdx.y * 64;
-    if (m0 >= M) return;
-    int64_t kbeg = 0, kend = g.K;
-    float* C = g.C;
-    if (g.dyn == 1) {
-        const int64_t len = xfmr_slice_len(T, XFMR_SLICES, 16);
-        kbeg = min((int64_t)blockIdx.z * len, T);
-        kend = min(kbeg + len, T);
-        C += (int64_t)blockIdx.z * g.slice_stride;
-    }
-    const int lane = mf_lane(), wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hh = lane >> 5;
+    const XgTile t = xg_tile(g);
+    if (t.empty) return;
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
     float colsum = 0.f;
     const bool want_colsum = g.dyn == 1 && blockIdx.y == 0 && threadIdx.x < 64;
-    f32x4 ra = xg_fetch(g.A, g.lda, g.a_kc, m0, M, kbeg, kend);
-    f32x4 rb = xg_fetch(g.B, g.ldb, g.b_kc, n0, g.N, kbeg, kend);
-    for (int64_t k0 = kbeg; k0 < kend; k0 += 16) {
+    f32x4 ra = xg_fetch(g.A, g.lda, g.a_kc, t.m0, t.M, t.kbeg, t.kend);
+    f32x4 rb = xg_fetch(g.B, g.ldb, g.b_kc, t.n0, g.N, t.kbeg, t.kend);
+    for (int64_t k0 = t.kbeg; k0 < t.kend; k0 += 16) {
         __syncthreads();
         xg_stage(As, g.a_kc, ra);
         xg_stage(Bs, g.b_kc, rb);
         __syncthreads();
-        if (k0 + 16 < kend) {                                // the next tile's loads fly under this tile's MFMAs
-            ra = xg_fetch(g.A, g.lda, g.a_kc, m0, M, k0 + 16, kend);
-            rb = xg_fetch(g.B, g.ldb, g.b_kc, n0, g.N, k0 + 16, kend);
+        if (k0 + 16 < t.kend) {                              // the next tile's loads fly under this tile's MFMAs
+            ra = xg_fetch(g.A, g.lda, g.a_kc, t.m0, t.M, k0 + 16, t.kend);
+            rb = xg_fetch(g.B, g.ldb, g.b_kc, t.n0, g.N, k0 + 16, t.kend);
         }
 #pragma unroll
         for (int kk = 0; kk < 16; kk += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + hh][wm * 32 + l31], Bs[kk + hh][wn * 32 + l31], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + t.hh][t.wm * 32 + t.l31], Bs[kk + t.hh][t.wn * 32 + t.l31], acc, 0, 0, 0);
         if (want_colsum) {
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk) colsum += As[kk][threadIdx.x];
         }
     }
-    xg_epilogue<DROP>(g, dr, C, acc, M, m0, n0, wm, wn, l31, hh);
-    if (want_colsum && m0 + threadIdx.x < M) C[(int64_t)g.M * g.N + m0 + threadIdx.x] = colsum;
+    xg_epilogue<DROP>(g, dr, t, acc);
+    if (want_colsum && t.m0 + threadIdx.x < t.M) t.C[(int64_t)g.M * g.N + t.m0 + threadIdx.x] = colsum;
 }
 
 // ---- the bf16-mixed form of the engine (precision MF_XFMR_BF16_MIXED) ----
@@ -528,20 +574,8 @@ template <bool DROP>
 __global__ __launch_bounds__(256) void xfmr_gemm_bf16_kernel(XGemm g, XDropRows dr) {
     __shared__ __attribute__((aligned(16))) __bf16 As[64][XGB_LD], Bs[64][XGB_LD];
     __shared__ float cs[4][64];
-    const int64_t T = *g.T_dev;
-    const int64_t M = g.dyn == 0 ? T : g.M;
-    const int64_t m0 = (int64_t)blockIdx.x * 64, n0 = (int64_t)blockIdx.y * 64;
-    if (m0 >= M) return;
-    int64_t kbeg = 0, kend = g.K;
-    float* C = g.C;
-    if (g.dyn == 1) {
-        const int64_t len = xfmr_slice_len(T, XFMR_SLICES, 16);
-        kbeg = min((int64_t)blockIdx.z * len, T);
-        kend = min(kbeg + len, T);
-        C += (int64_t)blockIdx.z * g.slice_stride;
-    }
-    const int lane = mf_lane(), wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hh = lane >> 5;
+    const XgTile t = xg_tile(g);
+    if (t.empty) return;
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
@@ -550,10 +584,10 @@ __global__ __launch_bounds__(256) void xfmr_gemm_bf16_kernel(XGemm g, XDropRows 
     f32x4 ra[2], rb[2];
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        ra[half] = xg_fetch(g.A, g.lda, g.a_kc, m0, M, kbeg + 16 * half, kend);
-        rb[half] = xg_fetch(g.B, g.ldb, g.b_kc, n0, g.N, kbeg + 16 * half, kend);
+        ra[half] = xg_fetch(g.A, g.lda, g.a_kc, t.m0, t.M, t.kbeg + 16 * half, t.kend);
+        rb[half] = xg_fetch(g.B, g.ldb, g.b_kc, t.n0, g.N, t.kbeg + 16 * half, t.kend);
     }
-    for (int64_t k0 = kbeg; k0 < kend; k0 += XGB_K) {
+    for (int64_t k0 = t.kbeg; k0 < t.kend; k0 += XGB_K) {
         __syncthreads();
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
@@ -562,26 +596,26 @@ __global__ __launch_bounds__(256) void xfmr_gemm_bf16_kernel(XGemm g, XDropRows 
         }
         if (want_colsum) colsum += ((ra[0][0] + ra[0][1]) + (ra[0][2] + ra[0][3])) + ((ra[1][0] + ra[1][1]) + (ra[1][2] + ra[1][3]));
         __syncthreads();
-        if (k0 + XGB_K < kend) {                             // the next stage's loads fly under this stage's MFMAs
+        if (k0 + XGB_K < t.kend) {                           // the next stage's loads fly under this stage's MFMAs
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
-                ra[half] = xg_fetch(g.A, g.lda, g.a_kc, m0, M, k0 + XGB_K + 16 * half, kend);
-                rb[half] = xg_fetch(g.B, g.ldb, g.b_kc, n0, g.N, k0 + XGB_K + 16 * half, kend);
+                ra[half] = xg_fetch(g.A, g.lda, g.a_kc, t.m0, t.M, k0 + XGB_K + 16 * half, t.kend);
+                rb[half] = xg_fetch(g.B, g.ldb, g.b_kc, t.n0, g.N, k0 + XGB_K + 16 * half, t.kend);
             }
         }
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            const xbf16x8 a = *reinterpret_cast<const xbf16x8*>(&As[wm * 32 + l31][16 * half + 8 * hh]);
-            const xbf16x8 b = *reinterpret_cast<const xbf16x8*>(&Bs[wn * 32 + l31][16 * half + 8 * hh]);
+            const xbf16x8 a = *reinterpret_cast<const xbf16x8*>(&As[t.wm * 32 + t.l31][16 * half + 8 * t.hh]);
+            const xbf16x8 b = *reinterpret_cast<const xbf16x8*>(&Bs[t.wn * 32 + t.l31][16 * half + 8 * t.hh]);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
         }
     }
-    xg_epilogue<DROP>(g, dr, C, acc, M, m0, n0, wm, wn, l31, hh);
+    xg_epilogue<DROP>(g, dr, t, acc);
     if (want_colsum) {
-        cs[wave][lane] = colsum;
+        cs[threadIdx.x >> 6][mf_lane()] = colsum;
         __syncthreads();
-        if (threadIdx.x < 64 && m0 + threadIdx.x < M)
-            C[(int64_t)g.M * g.N + m0 + threadIdx.x] = (cs[0][threadIdx.x] + cs[1][threadIdx.x]) + (cs[2][threadIdx.x] + cs[3][threadIdx.x]);
+        if (threadIdx.x < 64 && t.m0 + threadIdx.x < t.M)
+            t.C[(int64_t)g.M * g.N + t.m0 + threadIdx.x] = (cs[0][threadIdx.x] + cs[1][threadIdx.x]) + (cs[2][threadIdx.x] + cs[3][threadIdx.x]);
     }
 }
 
@@ -732,8 +766,7 @@ __global__ __launch_bounds__(64) void xfmr_attn_bwd_kernel(const float* __restri
 }
 
 // ================================================================================================ pool ====
-enum { XPOOL_MEAN = 0, XPOOL_MAX = 1, XPOOL_CLS = 2 };
-// 32 lanes per user: p = mean / max (first position wins ties) / position 0 of the n_b rows, u = p / max(|p|, 1e-12)
+// 32 lanes per user: p = xrow_pool of the n_b rows (0 when there is none), u = p / max(|p|, 1e-12)
 template <int H>
 __global__ __launch_bounds__(256) void xfmr_pool_kernel(const float* __restrict__ y, const int64_t* __restrict__ tok_off, int64_t B, int mode,
                                                         int norm_user, float* __restrict__ out_u, float* __restrict__ out_inv,
@@ -751,31 +784,8 @@ __global__ __launch_bounds__(256) void xfmr_pool_kernel(const float* __restrict_
         p.v[e] = 0.f;
         arg[e] = -1;
     }
-    if (n > 0) {
-        p = xrow_load<E>(y + t0 * H, c);
-#pragma unroll
-        for (int e = 0; e < E; ++e) arg[e] = 0;
-        if (mode != XPOOL_CLS) {
-            for (int j = 1; j < n; ++j) {
-                const XRow<E> r = xrow_load<E>(y + (t0 + j) * H, c);
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if (mode == XPOOL_MEAN) p.v[e] += r.v[e];
-                    else if (r.v[e] > p.v[e]) { p.v[e] = r.v[e]; arg[e] = j; }
-                }
-            }
-            if (mode == XPOOL_MEAN) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) p.v[e] = p.v[e] / (float)n;
-            }
-        }
-    }
-    float inv = 1.f;
-    if (norm_user) {
-        inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(p, p)), 1e-12f);
-#pragma unroll
-        for (int e = 0; e < E; ++e) p.v[e] = p.v[e] * inv;
-    }
+    if (n > 0) p = xrow_pool<E, true>(y + t0 * H, H, c, n, mode, arg);
+    const float inv = xrow_normalize<E>(p, norm_user);
     if (valid) {
         xrow_store<E>(out_u + b * H, c, p);
         if (c == 0) out_inv[b] = inv;
@@ -853,8 +863,12 @@ __global__ __launch_bounds__(128) void xfmr_tok_bwd_kernel(const float* __restri
 //             registers across the chunks (each output element stays one ascending-k chain)
 //   z2      = acc + bo2 + y1 -> v;  y2 = LN(z2) in place; v is the next layer's x
 // A GEMM column block is v_mfma_f32_32x32x2_f32 over k ascending from 0 into zeroed accumulators, the A operand from LDS, the
-// weight rows from global memory (L2), lanes 0..31 feeding k and 32..63 k + 1: xfmr_gemm_kernel's chain, followed by
-// xg_epilogue<false>'s expressions.  Every other float expression is the forward's own __device__ function, so at fp32 u is
+// weight rows from global memory (L2), lanes 0..31 feeding k and 32..63 k + 1: xfmr_gemm_kernel's chain, and xenc_store spells
+// xg_epilogue<false>'s (acc + bias) + r and act(.) again, on LDS -- the one piece of the forward's arithmetic written twice.
+// Every other float expression is a __device__ function that the forward's kernels call too: xrow_embed (xrow_normalize, then
+// xrow_layernorm) as in xfmr_embed_kernel, xrow_layernorm as in xfmr_ln_kernel, xattn_prob and xattn_mix as in xfmr_attn_kernel,
+// xfmr_act, xrow_pool and xrow_normalize as in xfmr_pool_kernel; the token ids come from list_cut_walk and list_pack_walk
+// (mf_lists.h), the walks of list_cut_kernel and xfmr_pack_kernel.  The library is built with -ffp-contract=off, so at fp32 u is
 // bit-identical to mf_xfmr_forward's out_u.  Rows >= n_b of a buffer hold whatever was there: no output depends on them (a
 // GEMM row, a LayerNorm row and a softmax over the n_b valid keys read their own rows only), and with n_b <= 32 the second 32-row
 // block is skipped.
@@ -988,24 +1002,14 @@ __global__ __launch_bounds__(256) void xfmr_encode_kernel(XEnc p) {
     int* const n_sh = reinterpret_cast<int*>(ids + XFMR_MAX_L);
     const int64_t b = blockIdx.x;
     const int lane = mf_lane(), wave = threadIdx.x >> 6;
-    // ---- cut: list_cut_kernel<true> + xfmr_pack_kernel for this user, on wave 0
+    // ---- cut: list_cut_kernel<true>'s and xfmr_pack_kernel's walks for this user, on wave 0
     if (wave == 0) {
         int64_t lo, hi;
         list_clamp(p.seg_start[b], p.seg_end[b], p.n_items, lo, hi);
         int need;
         const int64_t cut = list_cut_walk(p.items, lo, hi, p.n_rows, p.L, need);
-        const int nb = p.L - need;
-        int done = 0;
-        for (int64_t base = cut; base < hi && done < nb; base += 64) {
-            const int64_t pos = base + lane;
-            const long long id = pos < hi ? p.items[pos] : 0;
-            const bool ok = list_valid(id, p.n_rows);
-            const unsigned long long m = __ballot(ok);
-            const int t = done + __popcll(m & ((1ull << lane) - 1ull));
-            if (ok && t < nb) ids[t] = id;
-            done += __popcll(m);
-        }
-        if (lane == 0) *n_sh = nb;
+        list_pack_walk(p.items, cut, hi, p.n_rows, p.L - need, [&](int slot, long long id) { ids[slot] = id; });
+        if (lane == 0) *n_sh = p.L - need;
     }
     __syncthreads();
     const int n = *n_sh;
@@ -1015,7 +1019,7 @@ __global__ __launch_bounds__(256) void xfmr_encode_kernel(XEnc p) {
     }
     const int nrb = n > 32 ? 2 : 1;
     float *bx = xenc_lds, *bq = xenc_lds + BUF, *bk = xenc_lds + 2 * BUF, *bv = xenc_lds + 3 * BUF;
-    // ---- embed: xfmr_embed_kernel<H, false>'s arithmetic, eight tokens at a time
+    // ---- embed: xrow_embed, as xfmr_embed_kernel<H, false> calls it, eight tokens at a time
     {
         const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
         const XRow<E> te = xrow_load<E>(p.prm[1], c), gm = xrow_load<E>(p.prm[2], c), bt = xrow_load<E>(p.prm[3], c);
@@ -1023,18 +1027,10 @@ __global__ __launch_bounds__(256) void xfmr_encode_kernel(XEnc p) {
             const int t = t0 + g;
             const bool valid = t < n;
             const int tt = valid ? t : 0;
-            XRow<E> x = xrow_load<E>(p.table + ids[tt] * H, c);
-            if (p.norm_item) {
-                const float inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(x, x)), 1e-12f);
-#pragma unroll
-                for (int e = 0; e < E; ++e) x.v[e] = x.v[e] * inv;
-            }
-            const XRow<E> pe = xrow_load<E>(p.prm[0] + (int64_t)tt * H, c);
             XRow<E> z;
-#pragma unroll
-            for (int e = 0; e < E; ++e) z.v[e] = (x.v[e] + te.v[e]) + pe.v[e];
             float mean, rstd;
-            const XRow<E> y = xrow_layernorm<E>(z, gm, bt, mean, rstd);
+            const XRow<E> y = xrow_embed<E>(xrow_load<E>(p.table + ids[tt] * H, c), p.norm_item, te,
+                                            xrow_load<E>(p.prm[0] + (int64_t)tt * H, c), gm, bt, z, mean, rstd);
             if (valid) xrow_store<E>(bx + t * S, c, y);
         }
     }
@@ -1079,31 +1075,12 @@ __global__ __launch_bounds__(256) void xfmr_encode_kernel(XEnc p) {
         __syncthreads();
         float* const t = bx; bx = bv; bv = t;
     }
-    // ---- pool: xfmr_pool_kernel's arithmetic over the n rows, on one wave (both halves compute, the lower one stores) -- the
-    // last one: wave 0's mask, made for the cut, would stay in two SGPRs across the whole kernel
+    // ---- pool: xrow_pool and xrow_normalize over the n rows, as xfmr_pool_kernel calls them, on one wave (both halves compute,
+    // the lower one stores) -- the last one: wave 0's mask, made for the cut, would stay in two SGPRs across the whole kernel
     if (wave == 3) {
-        const int c = lane & 31;
-        XRow<E> pr = xrow_load<E>(bx, c);
-        if (p.mode != XPOOL_CLS) {
-            for (int j = 1; j < n; ++j) {
-                const XRow<E> r = xrow_load<E>(bx + j * S, c);
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if (p.mode == XPOOL_MEAN) pr.v[e] += r.v[e];
-                    else if (r.v[e] > pr.v[e]) pr.v[e] = r.v[e];
-                }
-            }
-            if (p.mode == XPOOL_MEAN) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) pr.v[e] = pr.v[e] / (float)n;
-            }
-        }
-        if (p.norm_user) {
-            const float inv = 1.f / fmaxf(sqrtf(xrow_dot<E>(pr, pr)), 1e-12f);
-#pragma unroll
-            for (int e = 0; e < E; ++e) pr.v[e] = pr.v[e] * inv;
-        }
-        if (lane < 32) xrow_store<E>(p.out_u + b * H, c, pr);
+        XRow<E> pr = xrow_pool<E, false>(bx, S, lane & 31, n, p.mode, nullptr);
+        xrow_normalize<E>(pr, p.norm_user);
+        if (lane < 32) xrow_store<E>(p.out_u + b * H, lane & 31, pr);
     }
 }
 
@@ -1152,26 +1129,60 @@ static const char* xfmr_check_shape(int h, int layers, int heads, int I, int L) 
     if (L < 1 || L > XFMR_MAX_L) return "max_history not in 1..64";
     return nullptr;
 }
+// What mf_xfmr_forward* and mf_xfmr_encode check alike, in this order, under the caller's name: the pointers and ranges, the
+// shape, the table rows the coalesce covers and the users (and packed tokens; t_cap < 0: none are packed) an index can hold.
+static int xfmr_check_inputs(const char* what, const float* table, int64_t n_rows, const int64_t* seg_start, const int64_t* seg_end,
+                             const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int h, int layers, int heads, int I, int L,
+                             int act, int mode, const float* const* params, const float* out_u) {
+    if (!table || !seg_start || !seg_end || !items || !params || !out_u || B <= 0 || n_rows <= 0 || n_items <= 0 || act < 0 || act > 3 ||
+        mode < 0 || mode > 2)
+        return mf_set_error(MF_EINVAL, "%s: bad argument", what);
+    if (const char* why = xfmr_check_shape(h, layers, heads, I, L)) return mf_set_error(MF_ENOTSUP, "%s: %s", what, why);
+    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "%s: %lld table rows > %d", what, (long long)n_rows, COALESCE_MAX_ROWS);
+    if (t_cap >= (1ll << 31) || B >= (1ll << 31) / 64)
+        return mf_set_error(MF_ENOTSUP, t_cap < 0 ? "%s: too many users" : "%s: too many tokens or users", what);
+    return MF_OK;
+}
+// every entry point's last check, after its own space check: no parameter (grads: and no gradient) of the `layers` layers is null
+static int xfmr_check_params(const char* what, const float* const* params, float* const* grads, int layers) {
+    for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i)
+        if (!params[i] || (grads && !grads[i]))
+            return mf_set_error(MF_EINVAL, grads ? "%s: parameter or gradient %d is null" : "%s: parameter %d is null", what, i);
+    return MF_OK;
+}
 
 extern "C" size_t mf_xfmr_ws_bytes(int64_t B, int64_t t_cap, int h, int layers, int I) {
     if (layers < 1 || layers > XFMR_MAX_LAYERS) return 0;
     return xfmr_stash(nullptr, B > 0 ? B : 1, t_cap, h, layers, I).total;
 }
 
-// prec: MF_XFMR_FP32 launches xfmr_gemm_kernel, as every call did before there was a choice; MF_XFMR_BF16_MIXED its bf16 sibling
-static void xfmr_gemm(hipStream_t s, int64_t t_cap, XGemm g, int prec) {
+#define XFMR_DISPATCH_H(h, ...)                                  \
+    switch (h) {                                                 \
+        case 32: { constexpr int H = 32; __VA_ARGS__; } break;   \
+        case 64: { constexpr int H = 64; __VA_ARGS__; } break;   \
+        default: { constexpr int H = 128; __VA_ARGS__; } break;  \
+    }
+#define XFMR_DISPATCH_DH(dh, ...)                                \
+    switch (dh) {                                                \
+        case 8: { constexpr int DH = 8; __VA_ARGS__; } break;    \
+        case 16: { constexpr int DH = 16; __VA_ARGS__; } break;  \
+        case 32: { constexpr int DH = 32; __VA_ARGS__; } break;  \
+        default: { constexpr int DH = 64; __VA_ARGS__; } break;  \
+    }
+// one dropout site: DROP = false launches the code the plain exports always ran, and the call hands it an XDrop{}
+#define XFMR_DISPATCH_DROP(on, ...)                              \
+    if (on) { constexpr bool DROP = true; __VA_ARGS__; }         \
+    else { constexpr bool DROP = false; __VA_ARGS__; }
+
+// prec: MF_XFMR_FP32 launches xfmr_gemm_kernel, as every call did before there was a choice; MF_XFMR_BF16_MIXED its bf16 sibling.
+// dr: a linear (dyn = 0) whose result is dropped before its residual add names its site (dr.d.thr = 0: the plain kernel).
+static void xfmr_gemm(hipStream_t s, int64_t t_cap, XGemm g, int prec, const XDropRows& dr = XDropRows{}) {
     const dim3 grid = g.dyn == 0 ? dim3((unsigned)((t_cap + 63) / 64), (unsigned)((g.N + 63) / 64))
                                  : dim3((unsigned)((g.M + 63) / 64), (unsigned)((g.N + 63) / 64), XFMR_SLICES);
-    if (prec == MF_XFMR_BF16_MIXED) xfmr_gemm_bf16_kernel<false><<<grid, 256, 0, s>>>(g, XDropRows{});
-    else xfmr_gemm_kernel<false><<<grid, 256, 0, s>>>(g, XDropRows{});
-}
-// a linear whose result is dropped before its residual add (site d; d.thr = 0: the plain kernel)
-static void xfmr_gemm_dropped(hipStream_t s, int64_t t_cap, XGemm g, int prec, const XDrop& d, const int32_t* tok_user,
-                              const int64_t* tok_off) {
-    if (d.thr == 0) return xfmr_gemm(s, t_cap, g, prec);
-    const dim3 grid((unsigned)((t_cap + 63) / 64), (unsigned)((g.N + 63) / 64));
-    if (prec == MF_XFMR_BF16_MIXED) xfmr_gemm_bf16_kernel<true><<<grid, 256, 0, s>>>(g, XDropRows{d, tok_user, tok_off});
-    else xfmr_gemm_kernel<true><<<grid, 256, 0, s>>>(g, XDropRows{d, tok_user, tok_off});
+    XFMR_DISPATCH_DROP(dr.d.thr != 0, {
+        if (prec == MF_XFMR_BF16_MIXED) xfmr_gemm_bf16_kernel<DROP><<<grid, 256, 0, s>>>(g, DROP ? dr : XDropRows{});
+        else xfmr_gemm_kernel<DROP><<<grid, 256, 0, s>>>(g, DROP ? dr : XDropRows{});
+    });
 }
 
 // The dropout of one call: thresholds of the two probabilities (0 = off) and what the keys are made of.
@@ -1232,20 +1243,6 @@ static void xfmr_dweight(hipStream_t s, const float* dY, int N, const float* X, 
     xfmr_reduce_kernel<<<dim3((unsigned)((size + 255) / 256)), 256, 0, s>>>(part, XFMR_SLICES, size, (int64_t)N * K, dW, db);
 }
 
-#define XFMR_DISPATCH_H(h, ...)                                  \
-    switch (h) {                                                 \
-        case 32: { constexpr int H = 32; __VA_ARGS__; } break;   \
-        case 64: { constexpr int H = 64; __VA_ARGS__; } break;   \
-        default: { constexpr int H = 128; __VA_ARGS__; } break;  \
-    }
-#define XFMR_DISPATCH_DH(dh, ...)                                \
-    switch (dh) {                                                \
-        case 8: { constexpr int DH = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int DH = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int DH = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int DH = 64; __VA_ARGS__; } break;  \
-    }
-
 // ============================================================================================= forward ====
 static int xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t* seg_start, const int64_t* seg_end,
                         const int64_t* items, int64_t n_items, int64_t B, int64_t t_cap, int max_history, int layers, int heads,
@@ -1254,35 +1251,24 @@ static int xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t
                         int prec, mf_stream_t stream) {
     if (prec != MF_XFMR_FP32 && prec != MF_XFMR_BF16_MIXED)
         return mf_set_error(MF_EINVAL, "mf_xfmr_forward: precision %d is neither MF_XFMR_FP32 nor MF_XFMR_BF16_MIXED", prec);
-    if (!table || !seg_start || !seg_end || !items || !params || !out_u || !out_inv || !stash || B <= 0 || n_rows <= 0 ||
-        n_items <= 0 || t_cap < 0 || act < 0 || act > 3 || mode < 0 || mode > 2 || (mode == XPOOL_MAX && !out_arg))
-        return mf_set_error(MF_EINVAL, "mf_xfmr_forward: bad argument");
-    if (const char* why = xfmr_check_shape(h, layers, heads, intermediate, max_history))
-        return mf_set_error(MF_ENOTSUP, "mf_xfmr_forward: %s", why);
-    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_xfmr_forward: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
-    if (t_cap >= (1ll << 31) || B >= (1ll << 31) / 64)
-        return mf_set_error(MF_ENOTSUP, "mf_xfmr_forward: too many tokens or users");
+    if (!out_inv || !stash || t_cap < 0 || (mode == XPOOL_MAX && !out_arg)) return mf_set_error(MF_EINVAL, "mf_xfmr_forward: bad argument");
+    if (int rc = xfmr_check_inputs("mf_xfmr_forward", table, n_rows, seg_start, seg_end, items, n_items, B, t_cap, h, layers, heads,
+                                   intermediate, max_history, act, mode, params, out_u))
+        return rc;
     if (stash_bytes < mf_xfmr_ws_bytes(B, t_cap, h, layers, intermediate)) return mf_set_error(MF_ENOSPC, "mf_xfmr_forward: stash too small");
-    for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i)
-        if (!params[i]) return mf_set_error(MF_EINVAL, "mf_xfmr_forward: parameter %d is null", i);
+    if (int rc = xfmr_check_params("mf_xfmr_forward", params, nullptr, layers)) return rc;
     const XfmrStash st = xfmr_stash(stash, B, t_cap, h, layers, intermediate);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int I = intermediate, dh = h / heads;
-    const unsigned gu = (unsigned)((B + 3) / 4), gt = (unsigned)((t_cap + 7) / 8);
+    const unsigned gu = (unsigned)((B + 3) / 4), gt = (unsigned)((t_cap + 7) / 8), ga = (unsigned)(B * heads);
     MF_TIMED("xfmr_forward", s, {
         list_cut_kernel<true><<<gu, 256, 0, s>>>(seg_start, seg_end, items, n_items, B, n_rows, max_history, st.cut, st.nb);
         xfmr_scan_kernel<<<1, 256, 0, s>>>(st.nb, B, t_cap, st.tok_off, st.T_dev);
         xfmr_pack_kernel<<<gu, 256, 0, s>>>(seg_end, st.cut, items, n_items, B, n_rows, st.tok_off, st.tok_item, st.tok_user);
         if (t_cap > 0) {
-            if (drop.thr_hidden) {
-                XFMR_DISPATCH_H(h, xfmr_embed_kernel<H, true><<<gt, 256, 0, s>>>(table, st.tok_item, st.tok_user, st.tok_off, st.T_dev,
-                                                                                norm_item, params[0], params[1], params[2], params[3],
-                                                                                st.z0, st.st0, st.x0, drop.embeddings()));
-            } else {
-                XFMR_DISPATCH_H(h, xfmr_embed_kernel<H, false><<<gt, 256, 0, s>>>(table, st.tok_item, st.tok_user, st.tok_off, st.T_dev,
-                                                                                 norm_item, params[0], params[1], params[2], params[3],
-                                                                                 st.z0, st.st0, st.x0, XDrop{}));
-            }
+            XFMR_DISPATCH_DROP(drop.thr_hidden, XFMR_DISPATCH_H(h, xfmr_embed_kernel<H, DROP><<<gt, 256, 0, s>>>(
+                                                       table, st.tok_item, st.tok_user, st.tok_off, st.T_dev, norm_item, params[0], params[1],
+                                                       params[2], params[3], st.z0, st.st0, st.x0, DROP ? drop.embeddings() : XDrop{})));
             const float* x = st.x0;
             for (int l = 0; l < layers; ++l) {
                 const float* const* w = params + XFMR_GLOBALS + XFMR_PER_LAYER * l;
@@ -1292,24 +1278,17 @@ static int xfmr_forward(const float* table, int64_t n_rows, int h, const int64_t
                     xfmr_gemm(s, t_cap, xg_linear(x, h, w[2], w[3], h, y.k, nullptr, st.T_dev), prec);
                     xfmr_gemm(s, t_cap, xg_linear(x, h, w[4], w[5], h, y.v, nullptr, st.T_dev), prec);
                 });
-                MF_TIMED("xfmr_attn_fwd", s, {
-                    if (drop.thr_attn) {
-                        XFMR_DISPATCH_DH(dh, xfmr_attn_kernel<DH, true><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
-                                                 y.q, y.k, y.v, st.tok_off, h, heads, y.ctx, drop.attn(l)));
-                    } else {
-                        XFMR_DISPATCH_DH(dh, xfmr_attn_kernel<DH, false><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
-                                                 y.q, y.k, y.v, st.tok_off, h, heads, y.ctx, XDrop{}));
-                    }
-                });
-                MF_TIMED("xfmr_gemm_fwd", s, xfmr_gemm_dropped(s, t_cap, xg_linear(y.ctx, h, w[6], w[7], h, y.z1, x, st.T_dev), prec,
-                                                               drop.attn_out(l), st.tok_user, st.tok_off));
+                MF_TIMED("xfmr_attn_fwd", s, XFMR_DISPATCH_DROP(drop.thr_attn, XFMR_DISPATCH_DH(dh, xfmr_attn_kernel<DH, DROP><<<ga, 64, 0, s>>>(
+                                                 y.q, y.k, y.v, st.tok_off, h, heads, y.ctx, DROP ? drop.attn(l) : XDrop{}))));
+                MF_TIMED("xfmr_gemm_fwd", s, xfmr_gemm(s, t_cap, xg_linear(y.ctx, h, w[6], w[7], h, y.z1, x, st.T_dev), prec,
+                                                       XDropRows{drop.attn_out(l), st.tok_user, st.tok_off}));
                 XFMR_DISPATCH_H(h, xfmr_ln_kernel<H><<<gt, 256, 0, s>>>(y.z1, st.T_dev, w[8], w[9], y.y1, y.st1));
                 MF_TIMED("xfmr_gemm_fwd", s, {
                     XGemm g = xg_linear(y.y1, h, w[10], w[11], I, y.a, nullptr, st.T_dev);
                     g.epi = XEPI_ACT; g.act = act; g.C2 = y.f;
                     xfmr_gemm(s, t_cap, g, prec);
-                    xfmr_gemm_dropped(s, t_cap, xg_linear(y.f, I, w[12], w[13], h, y.z2, y.y1, st.T_dev), prec, drop.ffn_out(l), st.tok_user,
-                                      st.tok_off);
+                    xfmr_gemm(s, t_cap, xg_linear(y.f, I, w[12], w[13], h, y.z2, y.y1, st.T_dev), prec,
+                              XDropRows{drop.ffn_out(l), st.tok_user, st.tok_off});
                 });
                 XFMR_DISPATCH_H(h, xfmr_ln_kernel<H><<<gt, 256, 0, s>>>(y.z2, st.T_dev, w[14], w[15], y.y2, y.st2));
                 x = y.y2;
@@ -1357,18 +1336,12 @@ extern "C" int mf_xfmr_encode(const float* table, int64_t n_rows, int h, const i
                               const int64_t* items, int64_t n_items, int64_t B, int max_history, int layers, int heads,
                               int intermediate, int act, int mode, int norm_item, int norm_user, const float* const* params,
                               float* out_u, mf_stream_t stream) {
-    if (!table || !seg_start || !seg_end || !items || !params || !out_u || B <= 0 || n_rows <= 0 || n_items <= 0 || act < 0 || act > 3 ||
-        mode < 0 || mode > 2)
-        return mf_set_error(MF_EINVAL, "mf_xfmr_encode: bad argument");
-    if (const char* why = xfmr_check_shape(h, layers, heads, intermediate, max_history))
-        return mf_set_error(MF_ENOTSUP, "mf_xfmr_encode: %s", why);
-    if (n_rows > COALESCE_MAX_ROWS) return mf_set_error(MF_ENOTSUP, "mf_xfmr_encode: %lld table rows > %d", (long long)n_rows, COALESCE_MAX_ROWS);
-    if (B >= (1ll << 31) / 64) return mf_set_error(MF_ENOTSUP, "mf_xfmr_encode: too many users");
+    if (int rc = xfmr_check_inputs("mf_xfmr_encode", table, n_rows, seg_start, seg_end, items, n_items, B, -1, h, layers, heads,
+                                   intermediate, max_history, act, mode, params, out_u))
+        return rc;
+    if (int rc = xfmr_check_params("mf_xfmr_encode", params, nullptr, layers)) return rc;
     XEnc p{};
-    for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i) {
-        if (!params[i]) return mf_set_error(MF_EINVAL, "mf_xfmr_encode: parameter %d is null", i);
-        p.prm[i] = params[i];
-    }
+    for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i) p.prm[i] = params[i];
     p.table = table; p.n_rows = n_rows; p.seg_start = seg_start; p.seg_end = seg_end; p.items = items; p.n_items = n_items;
     p.L = max_history; p.layers = layers; p.heads = heads; p.I = intermediate; p.act = act; p.mode = mode;
     p.norm_item = norm_item; p.norm_user = norm_user; p.out_u = out_u;
@@ -1444,14 +1417,13 @@ static int xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int m
         return mf_set_error(MF_ENOTSUP, "mf_xfmr_backward: %s", why);
     if (ws_bytes < xfmr_bwd_ws(nullptr, t_cap, h, intermediate, dropout_ws).total)
         return mf_set_error(MF_ENOSPC, "mf_xfmr_backward: workspace too small");
-    for (int i = 0; i < XFMR_GLOBALS + XFMR_PER_LAYER * layers; ++i)
-        if (!params[i] || !grads[i]) return mf_set_error(MF_EINVAL, "mf_xfmr_backward: parameter or gradient %d is null", i);
+    if (int rc = xfmr_check_params("mf_xfmr_backward", params, grads, layers)) return rc;
     const XfmrStash st = xfmr_stash(const_cast<void*>(stash), B, t_cap, h, layers, intermediate);
     const XfmrBwdWs w = xfmr_bwd_ws(ws, t_cap, h, intermediate, dropout_ws);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int I = intermediate, dh = h / heads, L = max_history;
     float* const dzm = drop.thr_hidden ? w.dzm : w.dz;      // what a dropped dense's backward reads (the residual path reads dz)
-    const unsigned gt = (unsigned)((t_cap + 7) / 8);
+    const unsigned gt = (unsigned)((t_cap + 7) / 8), ga = (unsigned)(B * heads);
     const int32_t* Td = st.T_dev;
     MF_TIMED("xfmr_backward", s, {
         XFMR_DISPATCH_H(h, xfmr_pool_bwd_kernel<H><<<gt, 256, 0, s>>>(grad_u, out_u, out_inv, out_arg, st.tok_off, st.tok_user, Td, mode,
@@ -1479,15 +1451,8 @@ static int xfmr_backward(int h, int64_t B, int64_t t_cap, int max_history, int m
                 xfmr_dweight(s, dzm, h, y.ctx, h, g[6], g[7], w.part, Td, prec);
                 xfmr_gemm(s, t_cap, xg_dinput(dzm, h, p[6], h, w.dctx, nullptr, Td), prec);
             });
-            MF_TIMED("xfmr_attn_bwd", s, {
-                if (drop.thr_attn) {
-                    XFMR_DISPATCH_DH(dh, xfmr_attn_bwd_kernel<DH, true><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
-                                             y.q, y.k, y.v, w.dctx, st.tok_off, h, heads, w.dq, w.dk, w.dv, drop.attn(l)));
-                } else {
-                    XFMR_DISPATCH_DH(dh, xfmr_attn_bwd_kernel<DH, false><<<dim3((unsigned)(B * heads)), 64, 0, s>>>(
-                                             y.q, y.k, y.v, w.dctx, st.tok_off, h, heads, w.dq, w.dk, w.dv, XDrop{}));
-                }
-            });
+            MF_TIMED("xfmr_attn_bwd", s, XFMR_DISPATCH_DROP(drop.thr_attn, XFMR_DISPATCH_DH(dh, xfmr_attn_bwd_kernel<DH, DROP><<<ga, 64, 0, s>>>(
+                                             y.q, y.k, y.v, w.dctx, st.tok_off, h, heads, w.dq, w.dk, w.dv, DROP ? drop.attn(l) : XDrop{}))));
             MF_TIMED("xfmr_gemm_bwd", s, {
                 xfmr_dweight(s, w.dq, h, x, h, g[0], g[1], w.part, Td, prec);
                 xfmr_dweight(s, w.dk, h, x, h, g[2], g[3], w.part, Td, prec);

@@ -185,6 +185,42 @@ def test_hard_worlds_match_the_spec(mf, case):
         assert torch.equal(got, user.encode(hist, path="forward"))
 
 
+def _sparse_list(rng, n_rows, length, n_valid=None):
+    """``length`` ids with one valid id at a random place of every three entries (``n_valid``: with exactly that many valid ids, at
+    random places); every other id is 0, negative or >= ``n_rows``."""
+    if n_valid is None:
+        keep = {3 * g + int(rng.integers(0, 3)) for g in range(length // 3)}
+    else:
+        keep = set(rng.choice(length, n_valid, replace=False).tolist())
+    bad = lambda: (0, -int(rng.integers(1, 1000)), n_rows + int(rng.integers(0, 1000)))[int(rng.integers(0, 3))]  # noqa: E731
+    return [int(rng.integers(1, n_rows)) if i in keep else bad() for i in range(length)]
+
+
+def test_long_sparse_lists_pack_the_same_tokens(mf):
+    """The pack walk (``list_pack_walk``: shared by ``xfmr_pack_kernel`` and the encode kernel's wave 0) over lists whose kept
+    entries lie far apart: the last 64 valid of 66 among 200 entries, exactly 64 and 63 valid among 150, and an empty list."""
+    h, heads, L, inter = 32, 4, 64, 32
+    rng = np.random.default_rng(64)
+    lists = [_sparse_list(rng, ROWS, 200), _sparse_list(rng, ROWS, 200), _sparse_list(rng, ROWS, 150, 64), _sparse_list(rng, ROWS, 150, 63), []]
+    kept = [[i for i, x in enumerate(lst) if 1 <= x < ROWS][-L:] for lst in lists]       # the entries the spec keeps, by place
+    assert [len(k) for k in kept] == [64, 64, 64, 63, 0]
+    for lst, k in zip(lists[:2], kept[:2]):
+        assert len(lst) == 200 and sum(1 <= x < ROWS for x in lst) == 66  # noqa: PLR2004
+        assert any(x == 0 for x in lst) and any(x < 0 for x in lst) and any(x >= ROWS for x in lst)
+        assert len({(len(lst) - 1 - i) // 64 for i in k}) >= 3  # noqa: PLR2004  (blocks of the cut's walk, from the end)
+        assert len({(i - k[0]) // 64 for i in k}) >= 3  # noqa: PLR2004          (blocks of the pack's walk, from the cut)
+    w, sd = _world(21, ROWS, h, 1, inter)
+    _, user = _towers(mf, w, sd, heads=heads, act="gelu", mode="mean", L=L)
+    kw = {"heads": heads, "act": "gelu", "mode": "mean", "n_i": True, "n_u": True, "max_history": L}
+    s32, ref = spec_tower(w.float(), lists, {k: v.float() for k, v in sd.items()}, **kw), spec_tower(w, lists, sd, **kw)
+    hist = _segments(lists)
+    fused, fwd = user.encode(hist, path="fused"), user.encode(hist, path="forward")
+    assert torch.equal(fused, fwd), float((fused - fwd).abs().max())
+    assert torch.equal(fused[4].cpu(), torch.zeros(h)) and bool((fused[:4].abs().sum(1) > 0).all())
+    _check("u fused, long sparse lists", fused, s32, ref)
+    _check("u forward, long sparse lists", fwd, s32, ref)
+
+
 def test_batch_shapes(mf):
     w, sd = _world(5, ROWS, 32, 1, 32)
     _, user = _towers(mf, w, sd, heads=4, act="gelu", mode="mean", L=16)

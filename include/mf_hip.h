@@ -248,6 +248,24 @@ int mf_update_pair(int adam, int d, float* table_a, float* exp_avg_a, float* exp
                    int normalized_b, void* ws_b, size_t ws_b_bytes, int64_t step, const int64_t* step_dev, float lr, float beta1,
                    float beta2, float eps, float weight_decay, mf_stream_t stream);
 
+/* Row-wise Adagrad (the "exact row-wise Adagrad" of FBGEMM / torchrec; no reference implementation, our spec: DESIGN.md 2): ONE
+ * fp32 of state per row, `sum` [n_rows], instead of Adam's two moment tables.  With acc the row's summed gradient (summed exactly as
+ * for sgd / adam), w the row of stored width d, s = sum[row], all in fp32:
+ *   g = acc                               (normalized == 0; else the normalisation Jacobian, as for sgd / adam)
+ *   g = g + weight_decay * w              (coupled L2; skipped as a whole when weight_decay == 0)
+ *   s = s + (1/d) * sum_c g_c^2           (the mean runs over the STORED width: zero padding channels dilute it)
+ *   w = w - lr * g / (sqrtf(s) + eps)
+ * No step counter, no lr decay: nothing depends on the step number, so a launch captured in a hipGraph replays as it is.
+ * MF_EINVAL for sum == NULL, lr < 0, eps <= 0, weight_decay < 0 (and what mf_update_sgd refuses); workspace: mf_update_ws_bytes.
+ * mf_update_pair_adagrad: both tables of a step in ONE launch, like mf_update_pair (1..65,536 ids per table, one width, one set of
+ * hyper-parameters; MF_ENOTSUP otherwise); same results as two mf_update_adagrad calls. */
+int mf_update_adagrad(float* table, float* sum, int64_t n_rows, int d, const int64_t* idx, int64_t n, const float* grad,
+                      int normalized, float lr, float eps, float weight_decay, void* ws, size_t ws_bytes, mf_stream_t stream);
+int mf_update_pair_adagrad(int d, float* table_a, float* sum_a, int64_t n_rows_a, const int64_t* idx_a, int64_t n_a,
+                           const float* grad_a, int normalized_a, void* ws_a, size_t ws_a_bytes, float* table_b, float* sum_b,
+                           int64_t n_rows_b, const int64_t* idx_b, int64_t n_b, const float* grad_b, int normalized_b, void* ws_b,
+                           size_t ws_b_bytes, float lr, float eps, float weight_decay, mf_stream_t stream);
+
 /* -------------------------------------------------- the default step in one launch ---
  * The reference trains with BATCH_SIZE = 32 pairs (xfmr_rec/params.py:18), PairwiseHingeLoss and 4 mined negatives
  * (xfmr_rec/lightning.py:38-39): a step of ~0.5 MFLOP that the multi-kernel path spends in launch latency.  mf_step_small

@@ -413,7 +413,8 @@ extern "C" int mf_group_keys(const int64_t* keys, int64_t n, int nkeys, int32_t*
 #include "mf_update.h"
 
 
-template <int D, bool ADAM, int PHASE>
+// (ADAGRAD: `exp_avg` is the per-row state `sum` [n_rows], `exp_avg_sq` NULL -- apply_row_update)
+template <int D, bool ADAM, int PHASE, bool ADAGRAD = false>
 __global__ __launch_bounds__(256) void update_rows_kernel(float* __restrict__ table,
                                                           float* __restrict__ exp_avg,
                                                           float* __restrict__ exp_avg_sq,
@@ -466,7 +467,7 @@ __global__ __launch_bounds__(256) void update_rows_kernel(float* __restrict__ ta
             apply = true;
         }
     }
-    apply_row_update<D, ADAM>(apply, row, c, acc, table, exp_avg, exp_avg_sq, normalized, hp);
+    apply_row_update<D, ADAM, ADAGRAD>(apply, row, c, acc, table, exp_avg, exp_avg_sq, normalized, hp);
 }
 
 
@@ -494,11 +495,11 @@ static UpdateWs update_ws(void* ws, int64_t n, int d) {
 
 extern "C" size_t mf_update_ws_bytes(int64_t n, int d) { return update_ws(nullptr, n > 0 ? n : 1, d).total; }
 
-template <bool ADAM>
+template <bool ADAM, bool ADAGRAD = false>
 static int update_common(float* table, float* m, float* v, int64_t n_rows, int d, const int64_t* idx,
                          int64_t n, const float* grad, int normalized, AdamHyper hp, void* ws,
                          size_t ws_bytes, mf_stream_t stream, const char* what) {
-    if (!table || !idx || !grad || !ws || n < 0 || n_rows <= 0 || (ADAM && (!m || !v)))
+    if (!table || !idx || !grad || !ws || n < 0 || n_rows <= 0 || (ADAM && (!m || !v)) || (ADAGRAD && !m))
         return mf_set_error(MF_EINVAL, "%s: bad argument", what);
     if (n_rows >= (1ll << 39)) return mf_set_error(MF_ENOTSUP, "%s: table too large", what);
     if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "%s: embedding width %d not in {32,64,128,256}", what, d);
@@ -511,7 +512,7 @@ static int update_common(float* table, float* m, float* v, int64_t n_rows, int d
         FusedUpdateParams fp{table, m, v, (long long)n_rows, reinterpret_cast<const long long*>(idx), (int)n, bits, grad,
                              w.partial, w.gk0, w.gk1, normalized, hp};
         MF_DISPATCH_D(d, {
-            auto fn = update_fused_kernel<D, ADAM>;
+            auto fn = update_fused_kernel<D, ADAM, ADAGRAD>;
             static bool attr_set = false;           // (per instantiation)
             if (!attr_set) {
                 (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_CAP * 8);
@@ -535,8 +536,8 @@ static int update_common(float* table, float* m, float* v, int64_t n_rows, int d
         constexpr int RPB = (64 / (D / 4)) * 4;
         dim3 grid((unsigned)((n + RPB - 1) / RPB));
         MF_TIMED("update_rows", s, {
-            (update_rows_kernel<D, ADAM, 1><<<grid, 256, 0, s>>>(table, m, v, n_rows, w.perm, w.skeys, n, grad, w.partial, normalized, hp));
-            (update_rows_kernel<D, ADAM, 2><<<grid, 256, 0, s>>>(table, m, v, n_rows, w.perm, w.skeys, n, grad, w.partial, normalized, hp));
+            (update_rows_kernel<D, ADAM, 1, ADAGRAD><<<grid, 256, 0, s>>>(table, m, v, n_rows, w.perm, w.skeys, n, grad, w.partial, normalized, hp));
+            (update_rows_kernel<D, ADAM, 2, ADAGRAD><<<grid, 256, 0, s>>>(table, m, v, n_rows, w.perm, w.skeys, n, grad, w.partial, normalized, hp));
         });
     });
     return mf_check_launch(what);
@@ -561,20 +562,20 @@ extern "C" int mf_update_adam(float* table, float* exp_avg, float* exp_avg_sq, i
                                ws_bytes, stream, "mf_update_adam");
 }
 
-template <bool ADAM>
+template <bool ADAM, bool ADAGRAD = false>
 static int update_pair_common(int d, float* ta, float* ma, float* va, int64_t rows_a, const int64_t* idx_a, int64_t n_a, const float* grad_a,
                               int norm_a, void* ws_a, size_t ws_a_bytes, float* tb, float* mb, float* vb, int64_t rows_b,
                               const int64_t* idx_b, int64_t n_b, const float* grad_b, int norm_b, void* ws_b, size_t ws_b_bytes,
-                              AdamHyper hp, mf_stream_t stream) {
+                              AdamHyper hp, mf_stream_t stream, const char* what = "mf_update_pair") {
     if (!ta || !tb || !idx_a || !idx_b || !grad_a || !grad_b || !ws_a || !ws_b || rows_a <= 0 || rows_b <= 0 ||
-        (ADAM && (!ma || !va || !mb || !vb)))
-        return mf_set_error(MF_EINVAL, "mf_update_pair: bad argument");
-    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_update_pair: embedding width %d not in {32,64,128,256}", d);
-    if (rows_a >= (1ll << 39) || rows_b >= (1ll << 39)) return mf_set_error(MF_ENOTSUP, "mf_update_pair: table too large");
+        (ADAM && (!ma || !va || !mb || !vb)) || (ADAGRAD && (!ma || !mb)))
+        return mf_set_error(MF_EINVAL, "%s: bad argument", what);
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "%s: embedding width %d not in {32,64,128,256}", what, d);
+    if (rows_a >= (1ll << 39) || rows_b >= (1ll << 39)) return mf_set_error(MF_ENOTSUP, "%s: table too large", what);
     if (n_a <= 0 || n_b <= 0 || n_a > FUSED_MAX_N || n_b > FUSED_MAX_N)
-        return mf_set_error(MF_ENOTSUP, "mf_update_pair: list lengths outside 1..%d (update the tables one by one)", FUSED_MAX_N);
+        return mf_set_error(MF_ENOTSUP, "%s: list lengths outside 1..%d (update the tables one by one)", what, FUSED_MAX_N);
     if (ws_a_bytes < mf_update_ws_bytes(n_a, d) || ws_b_bytes < mf_update_ws_bytes(n_b, d))
-        return mf_set_error(MF_ENOSPC, "mf_update_pair: workspace too small");
+        return mf_set_error(MF_ENOSPC, "%s: workspace too small", what);
     UpdateWs wa = update_ws(ws_a, n_a, d), wb = update_ws(ws_b, n_b, d);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int bits_a = fused_bucket_bits(n_a), bits_b = fused_bucket_bits(n_b);
@@ -583,7 +584,7 @@ static int update_pair_common(int d, float* ta, float* ma, float* va, int64_t ro
     FusedUpdateParams fb{tb, mb, vb, (long long)rows_b, reinterpret_cast<const long long*>(idx_b), (int)n_b, bits_b, grad_b,
                          wb.partial, wb.gk0, wb.gk1, norm_b, hp};
     MF_DISPATCH_D(d, {
-        auto fn = update_fused_pair_kernel<D, ADAM>;
+        auto fn = update_fused_pair_kernel<D, ADAM, ADAGRAD>;
         static bool attr_set = false;           // (per instantiation)
         if (!attr_set) {
             (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_CAP * 8);
@@ -591,7 +592,7 @@ static int update_pair_common(int d, float* ta, float* ma, float* va, int64_t ro
         }
         MF_TIMED("update_rows", s, (fn<<<dim3((1u << bits_a) + (1u << bits_b)), FUSED_THREADS, FUSED_CAP * 8, s>>>(fa, fb, 1 << bits_a)));
     });
-    return mf_check_launch("mf_update_pair");
+    return mf_check_launch(what);
 }
 
 extern "C" int mf_update_pair(int adam, int d, float* table_a, float* exp_avg_a, float* exp_avg_sq_a, int64_t n_rows_a, const int64_t* idx_a,
@@ -609,6 +610,35 @@ extern "C" int mf_update_pair(int adam, int d, float* table_a, float* exp_avg_a,
     AdamHyper hp{lr, 0.f, 0.f, 0.f, weight_decay, 1, nullptr, 0.0, 0.0};
     return update_pair_common<false>(d, table_a, nullptr, nullptr, n_rows_a, idx_a, n_a, grad_a, normalized_a, ws_a, ws_a_bytes, table_b, nullptr,
                                      nullptr, n_rows_b, idx_b, n_b, grad_b, normalized_b, ws_b, ws_b_bytes, hp, stream);
+}
+
+// Row-wise Adagrad: ONE fp32 of state per row (`sum` [n_rows]).  The hyper-parameters are checked on the host, before any launch.
+static int adagrad_hyper(const char* what, float lr, float eps, float weight_decay, AdamHyper* hp) {
+    if (!(lr >= 0.f) || !(eps > 0.f) || !(weight_decay >= 0.f))
+        return mf_set_error(MF_EINVAL, "%s: lr >= 0, eps > 0 and weight_decay >= 0 are required (lr %g, eps %g, weight_decay %g)", what,
+                            (double)lr, (double)eps, (double)weight_decay);
+    *hp = AdamHyper{lr, 0.f, 0.f, eps, weight_decay, 1, nullptr, 0.0, 0.0};
+    return MF_OK;
+}
+
+extern "C" int mf_update_adagrad(float* table, float* sum, int64_t n_rows, int d, const int64_t* idx, int64_t n, const float* grad,
+                                 int normalized, float lr, float eps, float weight_decay, void* ws, size_t ws_bytes,
+                                 mf_stream_t stream) {
+    AdamHyper hp;
+    if (int rc = adagrad_hyper("mf_update_adagrad", lr, eps, weight_decay, &hp)) return rc;
+    return update_common<false, true>(table, sum, nullptr, n_rows, d, idx, n, grad, normalized, hp, ws, ws_bytes, stream,
+                                      "mf_update_adagrad");
+}
+
+extern "C" int mf_update_pair_adagrad(int d, float* table_a, float* sum_a, int64_t n_rows_a, const int64_t* idx_a, int64_t n_a,
+                                      const float* grad_a, int normalized_a, void* ws_a, size_t ws_a_bytes, float* table_b, float* sum_b,
+                                      int64_t n_rows_b, const int64_t* idx_b, int64_t n_b, const float* grad_b, int normalized_b, void* ws_b,
+                                      size_t ws_b_bytes, float lr, float eps, float weight_decay, mf_stream_t stream) {
+    AdamHyper hp;
+    if (int rc = adagrad_hyper("mf_update_pair_adagrad", lr, eps, weight_decay, &hp)) return rc;
+    return update_pair_common<false, true>(d, table_a, sum_a, nullptr, n_rows_a, idx_a, n_a, grad_a, normalized_a, ws_a, ws_a_bytes, table_b,
+                                           sum_b, nullptr, n_rows_b, idx_b, n_b, grad_b, normalized_b, ws_b, ws_b_bytes, hp, stream,
+                                           "mf_update_pair_adagrad");
 }
 
 // ---- lab: the DPP / permlane lane exchanges of mf_common.h against the `__shfl_xor` they replace ----------------------

@@ -34,9 +34,13 @@ __device__ __forceinline__ void adam_bias(const AdamHyper& hp, float& bc1, float
 // launch.  Chunk boundaries depend on sorted positions only: deterministic.
 // The arithmetic of one row update on values already in registers (lane c of the row's D/4-lane group holds
 // floats 4c .. 4c+3 of the row, its moments and its summed gradient).
-template <int D, bool ADAM>
+// ADAGRAD (never with ADAM): row-wise Adagrad -- ONE fp32 of state per row, `s`, the running sum of the mean squared gradient
+// of the row (every lane of the group holds the same value going in and coming out: the butterfly leaves the same sum in each
+// lane).  Uses hp.lr, hp.eps, hp.wd (coupled L2, skipped as a whole when wd == 0: not a single rounding, no 0 * inf).
+template <int D, bool ADAM, bool ADAGRAD = false>
 __device__ __forceinline__ void row_update_math(f32x4& w, f32x4& m, f32x4& v, f32x4 acc, int normalized,
-                                                const AdamHyper& hp, float bc1, float bc2) {
+                                                const AdamHyper& hp, float bc1, float bc2, float& s) {
+    static_assert(!(ADAM && ADAGRAD), "one optimiser kind");
     constexpr int LPR = D / 4;
     f32x4 g = acc;
     if (normalized) {   // grad is w.r.t. w / max(||w||, 1e-12): apply the Jacobian
@@ -46,7 +50,13 @@ __device__ __forceinline__ void row_update_math(f32x4& w, f32x4& m, f32x4& v, f3
         float pr = mf_group_sum(acc[0] * uh[0] + acc[1] * uh[1] + acc[2] * uh[2] + acc[3] * uh[3], LPR);
         g = (acc - uh * pr) * inv;
     }
-    if (!ADAM) {
+    if (ADAGRAD) {
+        if (hp.wd != 0.f) g = g + hp.wd * w;
+        const float q = (1.f / D) * mf_group_sum(g[0] * g[0] + g[1] * g[1] + g[2] * g[2] + g[3] * g[3], LPR);
+        s = s + q;
+        const float den = sqrtf(s) + hp.eps;
+        w = w - hp.lr * g / den;
+    } else if (!ADAM) {
         w = w - hp.lr * (g + hp.wd * w);
     } else {
         w = w * (1.f - hp.lr * hp.wd);
@@ -59,7 +69,8 @@ __device__ __forceinline__ void row_update_math(f32x4& w, f32x4& m, f32x4& v, f3
     }
 }
 
-template <int D, bool ADAM>
+// (ADAGRAD: `exp_avg` is the per-row state `sum` [rows], `exp_avg_sq` unused)
+template <int D, bool ADAM, bool ADAGRAD = false>
 __device__ __forceinline__ void apply_row_update(bool active, int64_t row, int c, f32x4 acc,
                                                  float* __restrict__ table, float* __restrict__ exp_avg,
                                                  float* __restrict__ exp_avg_sq, int normalized,
@@ -75,7 +86,10 @@ __device__ __forceinline__ void apply_row_update(bool active, int64_t row, int c
         v = reinterpret_cast<const f32x4*>(exp_avg_sq + row * D)[c];
         adam_bias(hp, bc1, bc2);
     }
-    row_update_math<D, ADAM>(w, m, v, acc, normalized, hp, bc1, bc2);
+    float s = 0.f;
+    if (ADAGRAD) s = exp_avg[row];      // one address per group: a broadcast load
+    row_update_math<D, ADAM, ADAGRAD>(w, m, v, acc, normalized, hp, bc1, bc2, s);
+    if (ADAGRAD && c == 0) exp_avg[row] = s;
     if (ADAM) {
         reinterpret_cast<f32x4*>(exp_avg + row * D)[c] = m;
         reinterpret_cast<f32x4*>(exp_avg_sq + row * D)[c] = v;
@@ -119,7 +133,7 @@ __device__ __forceinline__ unsigned fused_bucket(long long id, int bucket_bits) 
 }
 
 struct FusedUpdateParams {
-    float *table, *exp_avg, *exp_avg_sq;
+    float *table, *exp_avg, *exp_avg_sq;     // (row-wise Adagrad: exp_avg is the state `sum` [n_rows], exp_avg_sq NULL)
     long long n_rows;
     const long long* idx;
     int n, bucket_bits;
@@ -150,11 +164,12 @@ __device__ __forceinline__ void fused_append(bool mine, unsigned long long key, 
 // `params(k)`: the table / gradient / hyper-parameter set of sorted position k, `params.row(key)`: the row a key addresses
 // (FusedOneTable for update_fused_kernel; the one-launch step lays the lists of its two tables end to end and updates
 // both in one pass: FusedTwoTables)
-template <int D, bool ADAM, int NFLIGHT, class Keys, class Params>
+template <int D, bool ADAM, int NFLIGHT, bool ADAGRAD = false, class Keys, class Params>
 __device__ __forceinline__ void fused_runs_of(Keys K, int m, Params params, float bc1, float bc2) {
     constexpr int LPR = D / 4, GPW = 64 / LPR, NWAVE = FUSED_THREADS / 64;
     // gradient rows in flight per lane group.  1024 threads leave 128 registers per lane; with Adam the row and its two
-    // moments are in flight beside the gradients (12 registers): sixteen rows spilled 20 registers, twelve fit
+    // moments are in flight beside the gradients (12 registers): sixteen rows spilled 20 registers, twelve fit.  Row-wise
+    // Adagrad has the row and ONE float beside them (5 registers; SGD 4): sixteen, like SGD
     constexpr int NF = NFLIGHT;      // (rows are added in order whatever NF is: the sums do not depend on it)
     const int lane = mf_lane(), wave = threadIdx.x >> 6;
     const int grp = lane / LPR, c = lane % LPR;
@@ -194,8 +209,10 @@ __device__ __forceinline__ void fused_runs_of(Keys K, int m, Params params, floa
                 // the row and its moments are asked for before the gradient rows: one memory round trip, not two
                 const bool will_apply = pass == 1 || head;
                 f32x4 w = {0.f, 0.f, 0.f, 0.f}, mm = w, vv = w;
+                float ss = 0.f;
                 if (will_apply) {
                     w = reinterpret_cast<const f32x4*>(p.table + ri * D)[c];
+                    if (ADAGRAD) ss = p.exp_avg[ri];                   // (the group's lanes ask for one address: a broadcast)
                     if (ADAM) {
                         mm = reinterpret_cast<const f32x4*>(p.exp_avg + ri * D)[c];
                         vv = reinterpret_cast<const f32x4*>(p.exp_avg_sq + ri * D)[c];
@@ -249,7 +266,8 @@ __device__ __forceinline__ void fused_runs_of(Keys K, int m, Params params, floa
                     apply = true;
                 }
                 if (apply) {
-                    row_update_math<D, ADAM>(w, mm, vv, acc, p.normalized, p.hp, bc1, bc2);
+                    row_update_math<D, ADAM, ADAGRAD>(w, mm, vv, acc, p.normalized, p.hp, bc1, bc2, ss);
+                    if (ADAGRAD && c == 0) p.exp_avg[ri] = ss;
                     if (ADAM) {
                         reinterpret_cast<f32x4*>(p.exp_avg + ri * D)[c] = mm;
                         reinterpret_cast<f32x4*>(p.exp_avg_sq + ri * D)[c] = vv;
@@ -278,13 +296,20 @@ struct FusedTwoTables {
     __device__ __forceinline__ const FusedUpdateParams& operator()(int k) const { return k < split ? pa : pb; }
     __device__ __forceinline__ int64_t row(unsigned long long key) const { return (int64_t)((key >> 24) & FUSED_ROW_MASK); }
 };
-template <int D, bool ADAM, int NFLIGHT, class Keys>
+template <int D, bool ADAM, int NFLIGHT, bool ADAGRAD, class Keys>
 __device__ __forceinline__ void fused_runs(Keys K, int m, const FusedUpdateParams& p, float bc1, float bc2) {
-    fused_runs_of<D, ADAM, NFLIGHT>(K, m, FusedOneTable{p}, bc1, bc2);
+    fused_runs_of<D, ADAM, NFLIGHT, ADAGRAD>(K, m, FusedOneTable{p}, bc1, bc2);
 }
 
+#ifndef FUSED_NF_ADAGRAD
+#define FUSED_NF_ADAGRAD 16
+#endif
+// gradient rows in flight per lane group in the one-launch kernels (fused_runs_of)
+template <bool ADAM, bool ADAGRAD>
+static constexpr int FUSED_NF = ADAGRAD ? FUSED_NF_ADAGRAD : ADAM ? FUSED_NF_ADAM : 16;
+
 // The work of ONE bucket `myb` by a workgroup of FUSED_THREADS threads; `lk`: FUSED_CAP keys of LDS.
-template <int D, bool ADAM, int NFLIGHT = (ADAM ? FUSED_NF_ADAM : 16)>
+template <int D, bool ADAM, int NFLIGHT = (ADAM ? FUSED_NF_ADAM : 16), bool ADAGRAD = false>
 __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, const unsigned myb, unsigned long long* lk) {
     __shared__ int s_count, s_lower;
     __shared__ float s_bias[2];
@@ -334,7 +359,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
             sorted[rank] = mine;
         }
         __syncthreads();
-        fused_runs<D, ADAM, NFLIGHT>(sorted, m, p, bc1, bc2);
+        fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(sorted, m, p, bc1, bc2);
     } else if (m <= FUSED_CAP) {
         int P = 1024;
         while (P < m) P <<= 1;
@@ -355,7 +380,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
                 else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             }
         }
-        fused_runs<D, ADAM, NFLIGHT>(lk, m, p, bc1, bc2);
+        fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(lk, m, p, bc1, bc2);
     } else {
         // the bucket does not fit: its segment of the global lists starts after every key of a lower bucket
         int low = 0;
@@ -383,7 +408,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
             g1[rank] = mine;
         }
         __syncthreads();
-        fused_runs<D, ADAM, NFLIGHT>(static_cast<const unsigned long long*>(g1), m, p, bc1, bc2);
+        fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(static_cast<const unsigned long long*>(g1), m, p, bc1, bc2);
     }
 }
 
@@ -468,21 +493,21 @@ __device__ __forceinline__ void fused_update_small(const FusedUpdateParams& pa, 
     fused_runs_of<D, ADAM, NFLIGHT>(sorted, total, FusedTwoTables{pa, pb, split}, bc1, bc2);
 }
 
-template <int D, bool ADAM>
+template <int D, bool ADAM, bool ADAGRAD = false>
 __global__ __launch_bounds__(FUSED_THREADS) void update_fused_kernel(FusedUpdateParams p) {
     extern __shared__ __attribute__((aligned(16))) char fused_smem[];
-    fused_update_body<D, ADAM>(p, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
+    fused_update_body<D, ADAM, FUSED_NF<ADAM, ADAGRAD>, ADAGRAD>(p, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
 }
 
 // BOTH tables of a step in one launch: workgroups [0, nb_a) take table A's buckets, the rest table B's.  The two updates are
 // independent; side by side the long pole of one (a popular item's run of 700 duplicates: one workgroup busy for 35 us) no
 // longer delays the other's launch, and one launch's fixed cost goes (round 4: 13.8 + 35.7 us in sequence -> one launch).
-template <int D, bool ADAM>
+template <int D, bool ADAM, bool ADAGRAD = false>
 __global__ __launch_bounds__(FUSED_THREADS) void update_fused_pair_kernel(FusedUpdateParams pa, FusedUpdateParams pb, int nb_a) {
     extern __shared__ __attribute__((aligned(16))) char fused_smem[];
     // (two calls, not one call on a selected parameter set: the selection moved the set out of scalar registers and spilled)
-    if ((int)blockIdx.x < nb_a) fused_update_body<D, ADAM>(pa, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
-    else fused_update_body<D, ADAM>(pb, blockIdx.x - nb_a, reinterpret_cast<unsigned long long*>(fused_smem));
+    if ((int)blockIdx.x < nb_a) fused_update_body<D, ADAM, FUSED_NF<ADAM, ADAGRAD>, ADAGRAD>(pa, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
+    else fused_update_body<D, ADAM, FUSED_NF<ADAM, ADAGRAD>, ADAGRAD>(pb, blockIdx.x - nb_a, reinterpret_cast<unsigned long long*>(fused_smem));
 }
 
 // buckets (= workgroups) of a list of n ids: ~32 ids each, at most 2^FUSED_MAX_BITS

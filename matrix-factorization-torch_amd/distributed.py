@@ -309,6 +309,10 @@ class HipOps:
             _lib.check(lib.mf_update_sgd(table.data_ptr(), table.shape[0], d, ids.data_ptr(), n, grad.data_ptr(),
                                          int(normalized), hyper["lr"], hyper["weight_decay"], ws.data_ptr(), ws.numel(),
                                          _lib.stream_ptr()))
+        elif optimizer == "adagrad":
+            _lib.check(lib.mf_update_adagrad(table.data_ptr(), state["sum"].data_ptr(), table.shape[0], d, ids.data_ptr(), n,
+                                             grad.data_ptr(), int(normalized), hyper["lr"], hyper["eps"], hyper["weight_decay"],
+                                             ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
         else:
             b1, b2 = hyper["betas"]
             _lib.check(lib.mf_update_adam(table.data_ptr(), state["m"].data_ptr(), state["v"].data_ptr(), table.shape[0], d,
@@ -346,9 +350,12 @@ class HipOps:
 
 
 def optimizer_hyper(optimizer: str, lr: float | None = None, **over) -> dict:
-    """The hyper-parameters of ``optim.SparseSGD`` / ``optim.RowAdam`` (their constructor defaults), in one place."""
+    """The hyper-parameters of ``optim.SparseSGD`` / ``optim.RowAdagrad`` / ``optim.RowAdam`` (their constructor defaults), in one
+    place."""
     if optimizer == "sgd":
         h = {"lr": 1e-2, "weight_decay": 0.0}
+    elif optimizer == "adagrad":
+        h = {"lr": 1e-2, "eps": 1e-10, "weight_decay": 0.0, "initial_accumulator_value": 0.0}
     else:
         h = {"lr": 1e-4, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.01}
     if lr is not None:
@@ -535,8 +542,13 @@ class ShardedTrainer:
             self.user_table = self.ops.init_rows(self.user_hi - self.user_lo, dim, self.user_lo, 1, seed, std, device)
         self.item_table = self.ops.init_rows(cyclic_rows(num_items, self.world, self.rank), dim, self.rank, self.world, seed + 1,
                                              std, device)           # rows rank, rank + world, ...
-        self.state = {name: {"m": torch.zeros_like(t), "v": torch.zeros_like(t)}
-                      for name, t in (("user", self.user_table), ("item", self.item_table))}
+        if optimizer == "adagrad":      # row-wise Adagrad: one fp32 per LOCAL row, no table-sized state
+            self.state = {name: {"sum": torch.full((t.shape[0],), float(self.hyper["initial_accumulator_value"]), dtype=torch.float32,
+                                                   device=t.device)}
+                          for name, t in (("user", self.user_table), ("item", self.item_table))}
+        else:
+            self.state = {name: {"m": torch.zeros_like(t), "v": torch.zeros_like(t)}
+                          for name, t in (("user", self.user_table), ("item", self.item_table))}
         self.logq = logq
         self.steps = 0
         self._plans: dict = {}

@@ -52,7 +52,7 @@ class MatrixFactorizationLitConfig(models.ModelConfig):
     margin: float = 1.0
     learning_rate: float = 0.0001
     top_k: int = TOP_K
-    optimizer: str = "adam"        # "adam" = row-wise AdamW (the reference's optimiser class), "sgd"
+    optimizer: str = "adam"        # "adam" = row-wise AdamW (the reference's optimiser class), "sgd", "adagrad" = row-wise Adagrad
     fused_losses: bool = True      # all seven losses from one sweep instead of seven sweeps
     use_logq: bool = False         # logQ correction (absent upstream)
 
@@ -367,7 +367,8 @@ class MatrixFactorizationLitModule(_Base):
         """``training_step`` + ``loss.backward()`` + ``optimizer.step()`` (xfmr_rec/lightning.py:189-192 and Lightning's
         automatic optimisation around it) in ONE launch when the configuration is the reference's kind -- B <= 128 pairs,
         plain embedding towers, a mined loss, ``optim.SparseSGD`` / ``optim.RowAdam`` -- through ``fused.FusedSmallStep``
-        (``mf_step_small``: bit-identical to the three calls); any other configuration runs those three calls.  Returns
+        (``mf_step_small``: bit-identical to the three calls); any other configuration (``optim.RowAdagrad`` among them) runs
+        those three calls.  Returns
         the trained loss, detached (its gradient has been applied); logs all seven losses like ``training_step``."""
         if self.loss_fns is None or self.towers is None:
             msg = "`loss_fns` must be initialised first"
@@ -402,10 +403,13 @@ class MatrixFactorizationLitModule(_Base):
     # ------------------------------------------------------------------- setup ---
     def configure_optimizers(self) -> torch.optim.Optimizer:
         if self.config.user_tower == "transformer":     # tables + the encoder's dense weights: one object steps both
-            return optim.tower_optimizer(self.towers, "sgd" if self.config.optimizer == "sgd" else "adam", self.config.learning_rate)
+            kind = self.config.optimizer if self.config.optimizer in ("sgd", "adagrad") else "adam"
+            return optim.tower_optimizer(self.towers, kind, self.config.learning_rate)
         params = list(self.towers.parameters())
         if self.config.optimizer == "sgd":
             return optim.SparseSGD(params, lr=self.config.learning_rate)
+        if self.config.optimizer == "adagrad":
+            return optim.RowAdagrad(params, lr=self.config.learning_rate)
         return optim.RowAdam(params, lr=self.config.learning_rate)
 
     def configure_model(self, device=None) -> None:

@@ -3,10 +3,11 @@
 ``configure_optimizers`` of the reference returns dense ``torch.optim.AdamW``
 (xfmr_rec/lightning.py:238-239).  With embedding tables only the gathered rows
 receive gradient, so the update is a scatter over the touched rows
-(``mf_update_sgd`` / ``mf_update_adam``): duplicate ids are summed first, every
-touched row is read and written once.  Spec: ``oracle/embed.py`` (no reference
-implementation).  Both classes are ``torch.optim.Optimizer``
-subclasses, so Lightning's automatic optimisation can drive them.
+(``mf_update_sgd`` / ``mf_update_adam`` / ``mf_update_adagrad``): duplicate ids are
+summed first, every touched row is read and written once.  Spec: ``oracle/embed.py``
+(no reference implementation); row-wise Adagrad's: DESIGN.md 2.  The
+classes are ``torch.optim.Optimizer`` subclasses, so Lightning's automatic
+optimisation can drive them.
 """
 from __future__ import annotations
 
@@ -252,6 +253,99 @@ class RowAdam(_SparseRowOptimizer):
         return loss
 
 
+def _pair_update_adagrad(jobs, hyper: dict) -> bool:
+    """:func:`_pair_update` for :class:`RowAdagrad` (``mf_update_pair_adagrad``), under the same conditions; ``jobs``: (table,
+    state, ids, grad, normalized)."""
+    if len(jobs) != 2 or os.environ.get("MF_UPDATE_PAIR", "1") != "1":
+        return False
+    (pa, sa, ia, ga, na), (pb, sb, ib, gb, nb) = jobs
+    d = pa.shape[1]
+    if pb.shape[1] != d or not (0 < ia.numel() <= 65536 and 0 < ib.numel() <= 65536):
+        return False
+    lib = _lib.lib()
+    wa = _lib.workspace(lib.mf_update_ws_bytes(ia.numel(), d), pa.device)
+    wb = _lib.workspace(lib.mf_update_ws_bytes(ib.numel(), d), pb.device)
+    _lib.check(lib.mf_update_pair_adagrad(
+        d, pa.data_ptr(), sa["sum"].data_ptr(), pa.shape[0], ia.data_ptr(), ia.numel(), ga.data_ptr(), int(na), wa.data_ptr(), wa.numel(),
+        pb.data_ptr(), sb["sum"].data_ptr(), pb.shape[0], ib.data_ptr(), ib.numel(), gb.data_ptr(), int(nb), wb.data_ptr(), wb.numel(),
+        hyper["lr"], hyper["eps"], hyper["weight_decay"], _lib.stream_ptr()))
+    return True
+
+
+class RowAdagrad(_SparseRowOptimizer):
+    """Row-wise Adagrad (the "exact row-wise Adagrad" of FBGEMM / torchrec): ONE fp32 of state per table row, ``sum``, where
+    :class:`RowAdam` keeps two tables of moments.  For a touched row ``w`` with summed gradient ``g`` (plus the coupled L2 term
+    ``weight_decay * w``, like :class:`SparseSGD` and ``torch.optim.Adagrad``)::
+
+        sum[row] += mean(g ** 2);  w -= lr * g / (sqrt(sum[row]) + eps)
+
+    The defaults are ``torch.optim.Adagrad``'s; there is no ``lr_decay`` and no step counter, so a step captured in a hipGraph
+    (``graph.CapturedStep``) replays as it is.  The mean runs over the table's STORED width: a model width padded to the next of
+    32, 64, 128, 256 has zero channels with zero gradient, which dilute it (a stored width of 2 x the model's halves ``sum``)."""
+
+    def __init__(self, params, lr: float = 1e-2, eps: float = 1e-10, weight_decay: float = 0.0,
+                 initial_accumulator_value: float = 0.0) -> None:
+        if not lr >= 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not eps > 0.0:
+            raise ValueError(f"Invalid epsilon value (must be > 0): {eps}")
+        if not weight_decay >= 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not initial_accumulator_value >= 0.0:
+            raise ValueError(f"Invalid initial_accumulator_value value: {initial_accumulator_value}")
+        super().__init__(params, {"lr": lr, "eps": eps, "weight_decay": weight_decay,
+                                  "initial_accumulator_value": initial_accumulator_value})
+
+    def _state_of(self, p: torch.Tensor, group: dict) -> dict:
+        state = self.state[p]
+        if not state:
+            state["sum"] = torch.full((p.shape[0],), float(group["initial_accumulator_value"]), dtype=torch.float32, device=p.device)
+        return state
+
+    def init_state(self) -> None:
+        """Allocate every table's ``sum`` (fp32 ``[rows]``) now instead of inside the first ``step``."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                self._state_of(p, group)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.lib()
+        jobs, done, pairs = [], [], []
+        for group in self.param_groups:
+            if not (group["lr"] >= 0.0 and group["eps"] > 0.0 and group["weight_decay"] >= 0.0):
+                raise ValueError(f"RowAdagrad needs lr >= 0, eps > 0 and weight_decay >= 0: {group['lr'] = }, {group['eps'] = }, "
+                                 f"{group['weight_decay'] = }")
+            for p in group["params"]:
+                self._check(p)
+                pend = _pending(p)
+                if pend is None:
+                    continue
+                state = self._state_of(p, group)
+                pairs.append((p, state, pend[0], pend[1], pend[2], group))
+
+                def job(p=p, pend=pend, group=group, state=state):
+                    ids, g, norm = pend
+                    n, d = ids.numel(), p.shape[1]
+                    ws = _lib.workspace(lib.mf_update_ws_bytes(n, d), p.device)
+                    _lib.check(lib.mf_update_adagrad(p.data_ptr(), state["sum"].data_ptr(), p.shape[0], d, ids.data_ptr(), n,
+                                                     g.data_ptr(), int(norm), group["lr"], group["eps"], group["weight_decay"],
+                                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+
+                jobs.append(job)
+                done.append(p)
+        one_group = len({id(x[5]) for x in pairs}) == 1
+        if not (one_group and _pair_update_adagrad([x[:5] for x in pairs], pairs[0][5] if pairs else {})):
+            run_table_jobs(jobs)
+        for p in done:
+            p._mf_pending.clear()
+        return loss
+
+
 class TowerOptimizer(torch.optim.Optimizer):
     """ONE optimiser for towers that own both embedding tables and dense parameters (:class:`models.HistoryTransformerTower`):
     ``sparse`` (:class:`SparseSGD` / :class:`RowAdam`) steps the tables from the rows their backwards parked, ``dense``
@@ -287,12 +381,13 @@ class TowerOptimizer(torch.optim.Optimizer):
 
 
 def tower_optimizer(towers: torch.nn.ModuleDict, kind: str, lr: float) -> torch.optim.Optimizer:
-    """The optimiser of a tower dict: ``kind`` "adam" -> :class:`RowAdam`, "sgd" -> :class:`SparseSGD` over the tables; when a
-    tower owns dense parameters (``encoder_parameters``), a :class:`TowerOptimizer` that also steps those with AdamW."""
-    if kind not in ("adam", "sgd"):
-        msg = f"the towers' optimiser must be 'adam' or 'sgd': {kind = }"
+    """The optimiser of a tower dict: ``kind`` "adam" -> :class:`RowAdam`, "sgd" -> :class:`SparseSGD`, "adagrad" ->
+    :class:`RowAdagrad` over the tables; when a tower owns dense parameters (``encoder_parameters``), a :class:`TowerOptimizer`
+    that also steps those with AdamW."""
+    if kind not in ("adam", "sgd", "adagrad"):
+        msg = f"the towers' optimiser must be 'adam', 'sgd' or 'adagrad': {kind = }"
         raise ValueError(msg)
     dense = [p for t in towers.values() if hasattr(t, "encoder_parameters") for p in t.encoder_parameters()]
     tables = [p for p in towers.parameters() if not any(p is q for q in dense)]
-    sparse = SparseSGD(tables, lr=lr) if kind == "sgd" else RowAdam(tables, lr=lr)
+    sparse = {"sgd": SparseSGD, "adam": RowAdam, "adagrad": RowAdagrad}[kind](tables, lr=lr)
     return TowerOptimizer(sparse, torch.optim.AdamW(dense, lr=lr)) if dense else sparse

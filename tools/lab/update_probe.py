@@ -1,47 +1,159 @@
-"""Time mf_update_adam alone on the bench's id distributions (Zipf item ids + uniform negatives; log-normal users).
+"""Time the sparse row updates alone on the bench's id distributions (Zipf item ids + uniform negatives; log-normal users).
 
-    python tools/lab/update_probe.py
+    python tools/lab/update_probe.py                                   # mf_update_adam, the four lists (as before)
+    python tools/lab/update_probe.py --optimizer adagrad               # mf_update_adagrad
+    python tools/lab/update_probe.py --optimizer all --pair --regions 7 --other-lib parent/libmf_hip.so --json out.json
+
+``--optimizer``: adam | sgd | adagrad | all.  ``--pair``: also the two-table launch (mf_update_pair / mf_update_pair_adagrad) on
+the C3 lists (8,192 user ids + 16,384 item ids, d = 128).  ``--other-lib``: a second build of the library (for instance the
+parent commit's) whose SGD and Adam are timed on the same lists, its regions alternating with this build's.  Every figure is
+device time per call: HIP events around ``--calls`` back-to-back calls, after a warm-up; the median of ``--regions`` regions
+with their minimum and maximum.
 """
+import argparse
+import ctypes
+import importlib
+import json
 import os
+import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-import importlib
 
 mf = importlib.import_module("matrix-factorization-torch_amd")
 import bench  # noqa: E402
 
-dev = torch.device("cuda:0")
-lib = mf._lib.lib()
-d = 128
-batches, _ = bench.make_batches(4, 8192, seed=1000, device=dev)
-cases = {"user 8192 (log-normal)": (bench.NUM_USERS, [b["user"] for b in batches]),
-         "item 16384 (zipf + uniform)": (bench.NUM_ITEMS, [b["item"] for b in batches]),
-         "item 16384 uniform": (bench.NUM_ITEMS, [torch.randint(1, bench.NUM_ITEMS, (16384,), device=dev) for _ in range(4)]),
-         "32 ids": (bench.NUM_ITEMS, [torch.randint(1, bench.NUM_ITEMS, (32,), device=dev) for _ in range(4)])}
-for name, (rows, ids) in cases.items():
-    n = ids[0].numel()
-    table = torch.randn(rows, d, device=dev)
-    m, v = torch.zeros_like(table), torch.zeros_like(table)
-    grad = torch.randn(n, d, device=dev)
-    ws = mf._lib.workspace(lib.mf_update_ws_bytes(n, d), dev)
-    uniq = sum(int(torch.unique(i).numel()) for i in ids) / len(ids)
-    top = max(int(torch.bincount(i).max()) for i in ids)
+KINDS = ("sgd", "adagrad", "adam")
 
-    def call(i, step):
-        mf._lib.check(lib.mf_update_adam(table.data_ptr(), m.data_ptr(), v.data_ptr(), rows, d, ids[i % 4].data_ptr(), n, grad.data_ptr(),
-                                         0, step, None, 1e-4, 0.9, 0.999, 1e-8, 0.0, ws.data_ptr(), ws.numel(), None))
-    for i in range(20):
-        call(i, i + 1)
-    torch.cuda.synchronize()
+
+def load_other(path):
+    """A second library, bound with this build's signatures for the exports it has."""
+    handle = ctypes.CDLL(os.path.abspath(path))
+    for name, (res, args) in mf._lib.SIGNATURES.items():
+        if hasattr(handle, name):
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = res, args
+    return handle
+
+
+class Table:
+    def __init__(self, rows, d, dev):
+        self.rows, self.d = rows, d
+        self.w = torch.randn(rows, d, device=dev)
+        self.m, self.v = torch.zeros_like(self.w), torch.zeros_like(self.w)
+        self.s = torch.zeros(rows, device=dev)
+
+
+def single_call(lib, kind, t, ids, grad, ws):
+    n = ids.numel()
+    if kind == "adam":
+        return lambda step: mf._lib.check(lib.mf_update_adam(t.w.data_ptr(), t.m.data_ptr(), t.v.data_ptr(), t.rows, t.d, ids.data_ptr(), n,
+                                                              grad.data_ptr(), 0, step, None, 1e-4, 0.9, 0.999, 1e-8, 0.0, ws.data_ptr(),
+                                                              ws.numel(), None))
+    if kind == "sgd":
+        return lambda step: mf._lib.check(lib.mf_update_sgd(t.w.data_ptr(), t.rows, t.d, ids.data_ptr(), n, grad.data_ptr(), 0, 1e-4, 0.0,
+                                                             ws.data_ptr(), ws.numel(), None))
+    return lambda step: mf._lib.check(lib.mf_update_adagrad(t.w.data_ptr(), t.s.data_ptr(), t.rows, t.d, ids.data_ptr(), n, grad.data_ptr(), 0,
+                                                             1e-4, 1e-10, 0.0, ws.data_ptr(), ws.numel(), None))
+
+
+def pair_call(lib, kind, ta, ia, ga, wa, tb, ib, gb, wb):
+    if kind == "adagrad":
+        return lambda step: mf._lib.check(lib.mf_update_pair_adagrad(
+            ta.d, ta.w.data_ptr(), ta.s.data_ptr(), ta.rows, ia.data_ptr(), ia.numel(), ga.data_ptr(), 0, wa.data_ptr(), wa.numel(),
+            tb.w.data_ptr(), tb.s.data_ptr(), tb.rows, ib.data_ptr(), ib.numel(), gb.data_ptr(), 0, wb.data_ptr(), wb.numel(), 1e-4, 1e-10, 0.0,
+            None))
+    adam = kind == "adam"
+    p = (lambda x: x.data_ptr()) if adam else (lambda x: None)
+    return lambda step: mf._lib.check(lib.mf_update_pair(
+        int(adam), ta.d, ta.w.data_ptr(), p(ta.m), p(ta.v), ta.rows, ia.data_ptr(), ia.numel(), ga.data_ptr(), 0, wa.data_ptr(), wa.numel(),
+        tb.w.data_ptr(), p(tb.m), p(tb.v), tb.rows, ib.data_ptr(), ib.numel(), gb.data_ptr(), 0, wb.data_ptr(), wb.numel(), step, None, 1e-4,
+        0.9, 0.999, 1e-8, 0.0, None))
+
+
+def region(calls_of, n_calls, step0):
+    """Device microseconds per call of one region: ``calls_of[i % len]`` in turn."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    for i in range(200):
-        call(i, i + 21)
+    for i in range(n_calls):
+        calls_of[i % len(calls_of)](step0 + i)
     e1.record()
     torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / 200
-    moved = (n * d * 4 + uniq * d * 4 * 6) / 1e9
-    print(f"{name:30s} n {n:6d} unique {uniq:8.0f} largest run {top:5d}: {us:7.1f} us / call  ({moved / (us * 1e-6):7.0f} GB/s algorithmic)")
+    return e0.elapsed_time(e1) * 1e3 / n_calls
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--optimizer", default="adam", choices=(*KINDS, "all"))
+    ap.add_argument("--pair", action="store_true")
+    ap.add_argument("--other-lib", default=None)
+    ap.add_argument("--regions", type=int, default=1)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    d = 128
+    libs = {"this": mf._lib.lib()}
+    if args.other_lib:
+        libs["other"] = load_other(args.other_lib)
+    kinds = KINDS if args.optimizer == "all" else (args.optimizer,)
+    batches, _ = bench.make_batches(4, 8192, seed=1000, device=dev)
+    lists = {"user 8192 (log-normal)": (bench.NUM_USERS, [b["user"] for b in batches]),
+             "item 16384 (zipf + uniform)": (bench.NUM_ITEMS, [b["item"] for b in batches]),
+             "item 16384 uniform": (bench.NUM_ITEMS, [torch.randint(1, bench.NUM_ITEMS, (16384,), device=dev) for _ in range(4)]),
+             "32 ids": (bench.NUM_ITEMS, [torch.randint(1, bench.NUM_ITEMS, (32,), device=dev) for _ in range(4)])}
+    tables = {rows: Table(rows, d, dev) for rows in {r for r, _ in lists.values()}}
+    ws_of = lambda n: mf._lib.workspace(libs["this"].mf_update_ws_bytes(n, d), dev)      # noqa: E731
+    # what to time: name -> {(lib, kind): [one closure per id list]}
+    todo = {}
+    for name, (rows, ids) in lists.items():
+        n = ids[0].numel()
+        grad, ws = torch.randn(n, d, device=dev), ws_of(n)
+        uniq = sum(int(torch.unique(i).numel()) for i in ids) / len(ids)
+        top = max(int(torch.bincount(i).max()) for i in ids)
+        entry = todo[name] = {"n": n, "unique": uniq, "largest_run": top, "calls": {}}
+        for lname, lib in libs.items():
+            for kind in kinds:
+                if hasattr(lib, f"mf_update_{kind}"):
+                    entry["calls"][(lname, kind)] = [single_call(lib, kind, tables[rows], i, grad, ws) for i in ids]
+    if args.pair:
+        users, items = lists["user 8192 (log-normal)"][1], lists["item 16384 (zipf + uniform)"][1]
+        ta, tb = tables[bench.NUM_USERS], tables[bench.NUM_ITEMS]
+        ga, gb = torch.randn(8192, d, device=dev), torch.randn(16384, d, device=dev)
+        wa, wb = ws_of(8192), ws_of(16384)
+        entry = todo["pair: user 8192 + item 16384"] = {"n": 8192 + 16384, "calls": {}}
+        for lname, lib in libs.items():
+            for kind in kinds:
+                if hasattr(lib, "mf_update_pair_adagrad" if kind == "adagrad" else "mf_update_pair"):
+                    entry["calls"][(lname, kind)] = [pair_call(lib, kind, ta, ia, ga, wa, tb, ib, gb, wb) for ia, ib in zip(users, items)]
+    out = {"d": d, "regions": args.regions, "calls_per_region": args.calls, "device": torch.cuda.get_device_name(0), "lists": {}}
+    for name, entry in todo.items():
+        for calls_of in entry["calls"].values():                       # warm-up: every (library, kind) of this list
+            for i in range(20):
+                calls_of[i % len(calls_of)](i + 1)
+        torch.cuda.synchronize()
+        times = {key: [] for key in entry["calls"]}
+        for r in range(args.regions):                                   # the (library, kind) pairs alternate inside every round
+            for key, calls_of in entry["calls"].items():
+                times[key].append(region(calls_of, args.calls, 21 + r * args.calls))
+        res = out["lists"][name] = {k: v for k, v in entry.items() if k != "calls"}
+        for (lname, kind), us in times.items():
+            med = statistics.median(us)
+            res[f"{lname}:{kind}"] = {"median_us": round(med, 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2)}
+            extra = ""
+            if "unique" in entry:       # bytes the update must move: the gradient rows once, each touched row (and its state) in and out
+                per_row = {"sgd": 2 * d * 4, "adagrad": 2 * d * 4 + 8, "adam": 6 * d * 4}[kind]
+                moved = (entry["n"] * d * 4 + entry["unique"] * per_row) / 1e9
+                extra = f"  ({moved / (med * 1e-6):7.0f} GB/s algorithmic)"
+                res[f"{lname}:{kind}"]["algorithmic_GBps"] = round(moved / (med * 1e-6), 1)
+            print(f"{name:30s} {lname:5s} {kind:8s} n {entry['n']:6d}: {med:7.1f} us / call  [{min(us):.1f} .. {max(us):.1f}]{extra}")
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

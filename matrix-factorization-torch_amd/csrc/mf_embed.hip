@@ -508,7 +508,8 @@ static int update_common(float* table, float* m, float* v, int64_t n_rows, int d
     UpdateWs w = update_ws(ws, n, d);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n <= FUSED_MAX_N) {
-        const int bits = fused_bucket_bits(n);      // buckets (= workgroups): ~32 ids each, at most two per CU
+        const int bits = fused_bucket_bits(n);      // buckets (= workgroups): ~32 ids each, at most 256: one per CU (1024 threads at
+                                                    // ~126 registers: a CU holds one workgroup at a time)
         FusedUpdateParams fp{table, m, v, (long long)n_rows, reinterpret_cast<const long long*>(idx), (int)n, bits, grad,
                              w.partial, w.gk0, w.gk1, normalized, hp};
         MF_DISPATCH_D(d, {
@@ -583,6 +584,11 @@ static int update_pair_common(int d, float* ta, float* ma, float* va, int64_t ro
                          wa.partial, wa.gk0, wa.gk1, norm_a, hp};
     FusedUpdateParams fb{tb, mb, vb, (long long)rows_b, reinterpret_cast<const long long*>(idx_b), (int)n_b, bits_b, grad_b,
                          wb.partial, wb.gk0, wb.gk1, norm_b, hp};
+    // the list with more ids goes first (a tie: A): workgroups start in block order, one per CU, so the longer list's long
+    // pole starts at once and the shorter list's buckets fill the CUs as they fall free.  The tables are independent: same bits
+    const bool b_first = n_b > n_a;
+    const FusedUpdateParams &f0 = b_first ? fb : fa, &f1 = b_first ? fa : fb;
+    const unsigned nb0 = 1u << f0.bucket_bits, nb1 = 1u << f1.bucket_bits;
     MF_DISPATCH_D(d, {
         auto fn = update_fused_pair_kernel<D, ADAM, ADAGRAD>;
         static bool attr_set = false;           // (per instantiation)
@@ -590,7 +596,7 @@ static int update_pair_common(int d, float* ta, float* ma, float* va, int64_t ro
             (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_CAP * 8);
             attr_set = true;
         }
-        MF_TIMED("update_rows", s, (fn<<<dim3((1u << bits_a) + (1u << bits_b)), FUSED_THREADS, FUSED_CAP * 8, s>>>(fa, fb, 1 << bits_a)));
+        MF_TIMED("update_rows", s, (fn<<<dim3(nb0 + nb1), FUSED_THREADS, FUSED_CAP * 8, s>>>(f0, f1, (int)nb0)));
     });
     return mf_check_launch(what);
 }
@@ -611,6 +617,19 @@ extern "C" int mf_update_pair(int adam, int d, float* table_a, float* exp_avg_a,
     return update_pair_common<false>(d, table_a, nullptr, nullptr, n_rows_a, idx_a, n_a, grad_a, normalized_a, ws_a, ws_a_bytes, table_b, nullptr,
                                      nullptr, n_rows_b, idx_b, n_b, grad_b, normalized_b, ws_b, ws_b_bytes, hp, stream);
 }
+
+#ifdef MF_PROBE
+// tools/lab/update_probe.py --stamps: the phase stamps the workgroups of the LAST one-launch update left (8 values per
+// workgroup: entry, after the scan, the sort, pass 0, the barrier, pass 1; the bucket's size m; unused), and the clock's kHz
+extern "C" int mf_probe_update_stamps(unsigned long long* out, int n_blocks, int* clock_khz) {
+    if (!out || n_blocks < 0 || n_blocks > 1024) return MF_EINVAL;
+    (void)hipDeviceSynchronize();
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (clock_khz) (void)hipDeviceGetAttribute(clock_khz, hipDeviceAttributeWallClockRate, dev);
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(mf_upd_stamps), (size_t)n_blocks * 8 * sizeof(unsigned long long)) == hipSuccess ? MF_OK : MF_ELAUNCH;
+}
+#endif
 
 // Row-wise Adagrad: ONE fp32 of state per row (`sum` [n_rows]).  The hyper-parameters are checked on the host, before any launch.
 static int adagrad_hyper(const char* what, float lr, float eps, float weight_decay, AdamHyper* hp) {

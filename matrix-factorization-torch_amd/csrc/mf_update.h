@@ -144,6 +144,18 @@ struct FusedUpdateParams {
     AdamHyper hp;
 };
 
+// (lab builds, -DMF_PROBE: thread 0 of every workgroup leaves a 100 MHz clock value at each phase boundary of its bucket --
+// 0 entry, 1 after the scan, 2 after the sort, 3 after pass 0 (its own wave), 4 after the barrier, 5 after pass 1 (every
+// wave) -- and the bucket's size in word 6; tools/lab/update_probe.py --stamps)
+#ifdef MF_PROBE
+static __device__ unsigned long long mf_upd_stamps[1024 * 8];
+#define MF_UPD_STAMP(i) do { if (threadIdx.x == 0) mf_upd_stamps[(blockIdx.x & 1023) * 8 + (i)] = wall_clock64(); } while (0)
+#define MF_UPD_NOTE(i, val_) do { if (threadIdx.x == 0) mf_upd_stamps[(blockIdx.x & 1023) * 8 + (i)] = (unsigned long long)(val_); } while (0)
+#else
+#define MF_UPD_STAMP(i)
+#define MF_UPD_NOTE(i, val_)
+#endif
+
 // append this thread's key (if `mine`) to the list; the order of the list is irrelevant (it is sorted next)
 template <class List>
 __device__ __forceinline__ void fused_append(bool mine, unsigned long long key, int* counter, List list, int cap) {
@@ -278,8 +290,16 @@ __device__ __forceinline__ void fused_runs_of(Keys K, int m, Params params, floa
         }
         // parked chunk sums are visible to the workgroup's other waves -- and when nobody parked one (no run longer than a
         // chunk: the usual batch) there is no second pass; nor a barrier behind it (every caller begins with one)
-        if (pass == 0 && !__syncthreads_or(parked)) return;
+        if (pass == 0) {
+            MF_UPD_STAMP(3);
+            if (!__syncthreads_or(parked)) return;
+            MF_UPD_STAMP(4);
+        }
     }
+#ifdef MF_PROBE
+    __syncthreads();                    // (the stamp below: when the LAST wave is through the second pass)
+    MF_UPD_STAMP(5);
+#endif
 }
 
 struct FusedOneTable {
@@ -314,6 +334,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
     __shared__ int s_count, s_lower;
     __shared__ float s_bias[2];
     const int tid = threadIdx.x, lane = mf_lane();
+    MF_UPD_STAMP(0);
     __syncthreads();                    // (a caller running several buckets: the previous one is done with the shared state)
     if (tid == 0) { s_count = 0; s_lower = 0; }
     __syncthreads();
@@ -342,6 +363,8 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
     const int m = s_count;
     const float bc1 = ADAM ? s_bias[0] : 1.f, bc2 = ADAM ? s_bias[1] : 1.f;
     __syncthreads();                    // (s_count is reused below)
+    MF_UPD_STAMP(1);
+    MF_UPD_NOTE(6, m);
     if (m == 0) return;
     if (m <= FUSED_RANK_MAX) {
         // short list: every key counts the keys below it (LDS broadcast reads) and drops into its place
@@ -359,6 +382,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
             sorted[rank] = mine;
         }
         __syncthreads();
+        MF_UPD_STAMP(2);
         fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(sorted, m, p, bc1, bc2);
     } else if (m <= FUSED_CAP) {
         int P = 1024;
@@ -380,6 +404,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
                 else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             }
         }
+        MF_UPD_STAMP(2);
         fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(lk, m, p, bc1, bc2);
     } else {
         // the bucket does not fit: its segment of the global lists starts after every key of a lower bucket
@@ -408,6 +433,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
             g1[rank] = mine;
         }
         __syncthreads();
+        MF_UPD_STAMP(2);
         fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(static_cast<const unsigned long long*>(g1), m, p, bc1, bc2);
     }
 }
@@ -499,9 +525,13 @@ __global__ __launch_bounds__(FUSED_THREADS) void update_fused_kernel(FusedUpdate
     fused_update_body<D, ADAM, FUSED_NF<ADAM, ADAGRAD>, ADAGRAD>(p, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
 }
 
-// BOTH tables of a step in one launch: workgroups [0, nb_a) take table A's buckets, the rest table B's.  The two updates are
-// independent; side by side the long pole of one (a popular item's run of 700 duplicates: one workgroup busy for 35 us) no
-// longer delays the other's launch, and one launch's fixed cost goes (round 4: 13.8 + 35.7 us in sequence -> one launch).
+// BOTH tables of a step in one launch: workgroups [0, nb_a) take the first parameter set's buckets, the rest the second's.
+// The kernel holds 1024 threads at ~126 registers: ONE workgroup per CU, and the dispatcher hands workgroups out in block
+// order as CUs fall free.  With 256 + 256 buckets on 256 CUs the second range starts only as workgroups of the first retire
+// -- so the host passes the LONGER list first (update_pair_common): its long pole (a popular item's run of 700 duplicates:
+// one workgroup busy for 35 us, the other 255 through after ~10) starts at once and the shorter list's buckets fill the CUs
+// that fall free beside it: the launch costs what the longer list costs alone.  (User table first, the pole started only
+// when a user bucket retired: 13.6 + 35.7 us alone, 44.7 us as a pair; item list first: 36.2.)
 template <int D, bool ADAM, bool ADAGRAD = false>
 __global__ __launch_bounds__(FUSED_THREADS) void update_fused_pair_kernel(FusedUpdateParams pa, FusedUpdateParams pb, int nb_a) {
     extern __shared__ __attribute__((aligned(16))) char fused_smem[];

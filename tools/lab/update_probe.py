@@ -3,12 +3,18 @@
     python tools/lab/update_probe.py                                   # mf_update_adam, the four lists (as before)
     python tools/lab/update_probe.py --optimizer adagrad               # mf_update_adagrad
     python tools/lab/update_probe.py --optimizer all --pair --regions 7 --other-lib parent/libmf_hip.so --json out.json
+    MF_HIP_LIB=<a -DMF_PROBE build> python tools/lab/update_probe.py --stamps --json stamps.json      # the phases of one workgroup
 
 ``--optimizer``: adam | sgd | adagrad | all.  ``--pair``: also the two-table launch (mf_update_pair / mf_update_pair_adagrad) on
 the C3 lists (8,192 user ids + 16,384 item ids, d = 128).  ``--other-lib``: a second build of the library (for instance the
 parent commit's) whose SGD and Adam are timed on the same lists, its regions alternating with this build's.  Every figure is
 device time per call: HIP events around ``--calls`` back-to-back calls, after a warm-up; the median of ``--regions`` regions
-with their minimum and maximum.
+with their minimum and maximum.  ``--multi``: also a list of 131,072 ids (the multi-launch path).
+
+``--stamps`` (a library built with -DMF_PROBE): instead of timing, the phase stamps of single Adam launches on the Zipf and the
+uniform item list -- for the workgroup with the most keys and for one with the median number, the microseconds from the
+workgroup's start to the end of the scan, the sort, pass 0 (thread 0's wave), the barrier behind it and pass 1 (every wave);
+the median over ``--regions`` launches.
 """
 import argparse
 import ctypes
@@ -84,6 +90,35 @@ def region(calls_of, n_calls, step0):
     return e0.elapsed_time(e1) * 1e3 / n_calls
 
 
+PHASES = ("scan", "sort", "pass0", "barrier", "pass1")
+
+
+def stamps(lib, call, n_blocks, reps):
+    """Phase durations (us) of the workgroup with the largest m and of one with the median m, medians over `reps` launches."""
+    fn = lib.mf_probe_update_stamps
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    buf, khz = (ctypes.c_uint64 * (8 * n_blocks))(), ctypes.c_int(0)
+    rows = {"largest": [], "median": []}
+    for r in range(reps):
+        call(100 + r)
+        mf._lib.check(fn(buf, n_blocks, ctypes.byref(khz)))
+        wg = [buf[8 * b: 8 * b + 8] for b in range(n_blocks)]
+        order = sorted(range(n_blocks), key=lambda b: wg[b][6])
+        for which, b in (("largest", order[-1]), ("median", order[n_blocks // 2])):
+            t = wg[b]
+            ends = [t[i] if t[i] else t[i - 1] for i in range(1, 6)]             # (no second pass: stamps 4 and 5 stay 0)
+            ends = [max(e, t[0]) for e in ends]
+            prev, cut = t[0], {}
+            for name, e in zip(PHASES, ends):
+                e = max(e, prev)
+                cut[name] = (e - prev) * 1e3 / khz.value
+                prev = e
+            cut["total"] = (prev - t[0]) * 1e3 / khz.value
+            cut["m"] = int(t[6])
+            rows[which].append(cut)
+    return {which: {k: round(statistics.median(x[k] for x in xs), 2) for k in (*PHASES, "total", "m")} for which, xs in rows.items()}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--optimizer", default="adam", choices=(*KINDS, "all"))
@@ -92,6 +127,8 @@ def main() -> None:
     ap.add_argument("--regions", type=int, default=1)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--multi", action="store_true")
+    ap.add_argument("--stamps", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     d = 128
@@ -104,6 +141,28 @@ def main() -> None:
              "item 16384 (zipf + uniform)": (bench.NUM_ITEMS, [b["item"] for b in batches]),
              "item 16384 uniform": (bench.NUM_ITEMS, [torch.randint(1, bench.NUM_ITEMS, (16384,), device=dev) for _ in range(4)]),
              "32 ids": (bench.NUM_ITEMS, [torch.randint(1, bench.NUM_ITEMS, (32,), device=dev) for _ in range(4)])}
+    if args.multi:
+        lists["item 131072 uniform (multi-launch)"] = (bench.NUM_ITEMS, [torch.randint(1, bench.NUM_ITEMS, (131072,), device=dev) for _ in range(4)])
+    if args.stamps:
+        if not hasattr(libs["this"], "mf_probe_update_stamps"):
+            raise SystemExit("--stamps needs a library built with -DMF_PROBE (MF_HIP_LIB=...)")
+        out = {"d": d, "launches": max(args.regions, 5), "device": torch.cuda.get_device_name(0), "unit": "us", "lists": {}}
+        t = Table(bench.NUM_ITEMS, d, dev)
+        for name in ("item 16384 (zipf + uniform)", "item 16384 uniform"):
+            ids = lists[name][1][0]
+            n = ids.numel()
+            grad, ws = torch.randn(n, d, device=dev), mf._lib.workspace(libs["this"].mf_update_ws_bytes(n, d), dev)
+            call = single_call(libs["this"], "adam", t, ids, grad, ws)
+            for i in range(10):
+                call(i + 1)
+            res = out["lists"][name] = stamps(libs["this"], call, 256, max(args.regions, 5))
+            for which, row in res.items():
+                print(f"{name:30s} {which:8s} m {row['m']:5d}: " + "  ".join(f"{k} {row[k]:6.2f}" for k in (*PHASES, "total")))
+        if args.json:
+            os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+            with open(args.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     tables = {rows: Table(rows, d, dev) for rows in {r for r, _ in lists.values()}}
     ws_of = lambda n: mf._lib.workspace(libs["this"].mf_update_ws_bytes(n, d), dev)      # noqa: E731
     # what to time: name -> {(lib, kind): [one closure per id list]}

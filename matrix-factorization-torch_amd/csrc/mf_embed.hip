@@ -412,18 +412,16 @@ extern "C" int mf_group_keys(const int64_t* keys, int64_t n, int nkeys, int32_t*
 
 #include "mf_update.h"
 
-
-// (ADAGRAD: `exp_avg` is the per-row state `sum` [n_rows], `exp_avg_sq` NULL -- apply_row_update)
-template <int D, bool ADAM, int PHASE, bool ADAGRAD = false>
+template <int D, RowOpt OPT, int PHASE>
 __global__ __launch_bounds__(256) void update_rows_kernel(float* __restrict__ table,
-                                                          float* __restrict__ exp_avg,
-                                                          float* __restrict__ exp_avg_sq,
+                                                          float* __restrict__ state0,
+                                                          float* __restrict__ state1,
                                                           int64_t n_rows,
                                                           const int32_t* __restrict__ perm,
                                                           const int64_t* __restrict__ skeys, int64_t n,
                                                           const float* __restrict__ grad,
                                                           float* __restrict__ partial,
-                                                          int normalized, AdamHyper hp) {
+                                                          int normalized, RowHyper hp) {
     constexpr int LPR = D / 4;
     constexpr int RPW = 64 / LPR;
     const int lane = mf_lane();
@@ -467,7 +465,7 @@ __global__ __launch_bounds__(256) void update_rows_kernel(float* __restrict__ ta
             apply = true;
         }
     }
-    apply_row_update<D, ADAM, ADAGRAD>(apply, row, c, acc, table, exp_avg, exp_avg_sq, normalized, hp);
+    apply_row_update<D, OPT>(apply, row, c, acc, table, state0, state1, normalized, hp);
 }
 
 
@@ -495,34 +493,49 @@ static UpdateWs update_ws(void* ws, int64_t n, int d) {
 
 extern "C" size_t mf_update_ws_bytes(int64_t n, int d) { return update_ws(nullptr, n > 0 ? n : 1, d).total; }
 
-template <bool ADAM, bool ADAGRAD = false>
-static int update_common(float* table, float* m, float* v, int64_t n_rows, int d, const int64_t* idx,
-                         int64_t n, const float* grad, int normalized, AdamHyper hp, void* ws,
-                         size_t ws_bytes, mf_stream_t stream, const char* what) {
-    if (!table || !idx || !grad || !ws || n < 0 || n_rows <= 0 || (ADAM && (!m || !v)) || (ADAGRAD && !m))
-        return mf_set_error(MF_EINVAL, "%s: bad argument", what);
+// ONE table of an update call, as the exports receive it (state0 / state1: what the kind keeps per row -- RowOpt)
+struct UpdateTable {
+    float *table, *state0, *state1;
+    int64_t n_rows;
+    const int64_t* idx;
+    int64_t n;
+    const float* grad;
+    int normalized;
+    void* ws;
+    size_t ws_bytes;
+};
+// the pointers and the row count of a table are usable, the state of the kind is there (the list's length: the callers)
+template <RowOpt OPT>
+static bool update_table_ok(const UpdateTable& t) {
+    return t.table && t.idx && t.grad && t.ws && t.n_rows > 0 && (OPT == RowOpt::SGD || t.state0) && (OPT != RowOpt::ADAM || t.state1);
+}
+// what a one-launch kernel is handed for a table: ~32 ids per bucket (= workgroup), at most 256: one per CU (1024 threads at
+// ~126 registers: a CU holds one workgroup at a time)
+static FusedUpdateParams fused_params(const UpdateTable& t, int d, const RowHyper& hp) {
+    const UpdateWs w = update_ws(t.ws, t.n, d);
+    return FusedUpdateParams{t.table, t.state0, t.state1, (long long)t.n_rows, reinterpret_cast<const long long*>(t.idx), (int)t.n,
+                             fused_bucket_bits(t.n), t.grad, w.partial, w.gk0, w.gk1, t.normalized, hp};
+}
+
+template <RowOpt OPT>
+static int update_common(const UpdateTable& t, int d, const RowHyper& hp, mf_stream_t stream, const char* what) {
+    const int64_t n = t.n, n_rows = t.n_rows;
+    if (!update_table_ok<OPT>(t) || n < 0) return mf_set_error(MF_EINVAL, "%s: bad argument", what);
     if (n_rows >= (1ll << 39)) return mf_set_error(MF_ENOTSUP, "%s: table too large", what);
     if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "%s: embedding width %d not in {32,64,128,256}", what, d);
-    if (ws_bytes < mf_update_ws_bytes(n, d)) return mf_set_error(MF_ENOSPC, "%s: workspace too small", what);
+    if (t.ws_bytes < mf_update_ws_bytes(n, d)) return mf_set_error(MF_ENOSPC, "%s: workspace too small", what);
     if (n == 0) return MF_OK;
-    UpdateWs w = update_ws(ws, n, d);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n <= FUSED_MAX_N) {
-        const int bits = fused_bucket_bits(n);      // buckets (= workgroups): ~32 ids each, at most 256: one per CU (1024 threads at
-                                                    // ~126 registers: a CU holds one workgroup at a time)
-        FusedUpdateParams fp{table, m, v, (long long)n_rows, reinterpret_cast<const long long*>(idx), (int)n, bits, grad,
-                             w.partial, w.gk0, w.gk1, normalized, hp};
+        const FusedUpdateParams fp = fused_params(t, d, hp);
         MF_DISPATCH_D(d, {
-            auto fn = update_fused_kernel<D, ADAM, ADAGRAD>;
-            static bool attr_set = false;           // (per instantiation)
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_CAP * 8);
-                attr_set = true;
-            }
-            MF_TIMED("update_rows", s, (fn<<<dim3(1u << bits), FUSED_THREADS, FUSED_CAP * 8, s>>>(fp)));
+            mf_allow_dynamic_lds<update_fused_kernel<D, OPT>>(FUSED_CAP * 8);
+            MF_TIMED("update_rows", s, (update_fused_kernel<D, OPT><<<dim3(1u << fp.bucket_bits), FUSED_THREADS, FUSED_CAP * 8, s>>>(fp)));
         });
         return mf_check_launch(what);
     }
+    const UpdateWs w = update_ws(t.ws, n, d);
+    const int64_t* idx = t.idx;
     const int posbits = sort_packed_posbits(n, n_rows);
     if (posbits >= 0) {
         const int stripes = sort_stripes(n);
@@ -537,9 +550,31 @@ static int update_common(float* table, float* m, float* v, int64_t n_rows, int d
         constexpr int RPB = (64 / (D / 4)) * 4;
         dim3 grid((unsigned)((n + RPB - 1) / RPB));
         MF_TIMED("update_rows", s, {
-            (update_rows_kernel<D, ADAM, 1, ADAGRAD><<<grid, 256, 0, s>>>(table, m, v, n_rows, w.perm, w.skeys, n, grad, w.partial, normalized, hp));
-            (update_rows_kernel<D, ADAM, 2, ADAGRAD><<<grid, 256, 0, s>>>(table, m, v, n_rows, w.perm, w.skeys, n, grad, w.partial, normalized, hp));
+            (update_rows_kernel<D, OPT, 1><<<grid, 256, 0, s>>>(t.table, t.state0, t.state1, n_rows, w.perm, w.skeys, n, t.grad, w.partial, t.normalized, hp));
+            (update_rows_kernel<D, OPT, 2><<<grid, 256, 0, s>>>(t.table, t.state0, t.state1, n_rows, w.perm, w.skeys, n, t.grad, w.partial, t.normalized, hp));
         });
+    });
+    return mf_check_launch(what);
+}
+
+template <RowOpt OPT>
+static int update_pair_common(int d, const UpdateTable& a, const UpdateTable& b, const RowHyper& hp, mf_stream_t stream, const char* what) {
+    if (!update_table_ok<OPT>(a) || !update_table_ok<OPT>(b)) return mf_set_error(MF_EINVAL, "%s: bad argument", what);
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "%s: embedding width %d not in {32,64,128,256}", what, d);
+    if (a.n_rows >= (1ll << 39) || b.n_rows >= (1ll << 39)) return mf_set_error(MF_ENOTSUP, "%s: table too large", what);
+    if (a.n <= 0 || b.n <= 0 || a.n > FUSED_MAX_N || b.n > FUSED_MAX_N)
+        return mf_set_error(MF_ENOTSUP, "%s: list lengths outside 1..%d (update the tables one by one)", what, FUSED_MAX_N);
+    if (a.ws_bytes < mf_update_ws_bytes(a.n, d) || b.ws_bytes < mf_update_ws_bytes(b.n, d))
+        return mf_set_error(MF_ENOSPC, "%s: workspace too small", what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the list with more ids goes first (a tie: A): workgroups start in block order, one per CU, so the longer list's long
+    // pole starts at once and the shorter list's buckets fill the CUs as they fall free.  The tables are independent: same bits
+    const bool b_first = b.n > a.n;
+    const FusedUpdateParams f0 = fused_params(b_first ? b : a, d, hp), f1 = fused_params(b_first ? a : b, d, hp);
+    const unsigned nb0 = 1u << f0.bucket_bits, nb1 = 1u << f1.bucket_bits;
+    MF_DISPATCH_D(d, {
+        mf_allow_dynamic_lds<update_fused_pair_kernel<D, OPT>>(FUSED_CAP * 8);
+        MF_TIMED("update_rows", s, (update_fused_pair_kernel<D, OPT><<<dim3(nb0 + nb1), FUSED_THREADS, FUSED_CAP * 8, s>>>(f0, f1, (int)nb0)));
     });
     return mf_check_launch(what);
 }
@@ -547,9 +582,8 @@ static int update_common(float* table, float* m, float* v, int64_t n_rows, int d
 extern "C" int mf_update_sgd(float* table, int64_t n_rows, int d, const int64_t* idx, int64_t n,
                              const float* grad, int normalized, float lr, float weight_decay,
                              void* ws, size_t ws_bytes, mf_stream_t stream) {
-    AdamHyper hp{lr, 0.f, 0.f, 0.f, weight_decay, 1, nullptr, 0.0, 0.0};
-    return update_common<false>(table, nullptr, nullptr, n_rows, d, idx, n, grad, normalized, hp, ws,
-                                ws_bytes, stream, "mf_update_sgd");
+    return update_common<RowOpt::SGD>({table, nullptr, nullptr, n_rows, idx, n, grad, normalized, ws, ws_bytes}, d,
+                                      row_hyper_sgd(lr, weight_decay), stream, "mf_update_sgd");
 }
 
 extern "C" int mf_update_adam(float* table, float* exp_avg, float* exp_avg_sq, int64_t n_rows, int d,
@@ -557,48 +591,17 @@ extern "C" int mf_update_adam(float* table, float* exp_avg, float* exp_avg_sq, i
                               int64_t step, const int64_t* step_dev, float lr, float beta1, float beta2, float eps,
                               float weight_decay, void* ws, size_t ws_bytes, mf_stream_t stream) {
     if (!step_dev && step < 1) return mf_set_error(MF_EINVAL, "mf_update_adam: step must be >= 1");
-    AdamHyper hp{lr, beta1, beta2, eps, weight_decay, (long long)step, reinterpret_cast<const long long*>(step_dev),
-                 log((double)beta1), log((double)beta2)};
-    return update_common<true>(table, exp_avg, exp_avg_sq, n_rows, d, idx, n, grad, normalized, hp, ws,
-                               ws_bytes, stream, "mf_update_adam");
+    return update_common<RowOpt::ADAM>({table, exp_avg, exp_avg_sq, n_rows, idx, n, grad, normalized, ws, ws_bytes}, d,
+                                       row_hyper_adam(lr, beta1, beta2, eps, weight_decay, step, step_dev), stream, "mf_update_adam");
 }
 
-template <bool ADAM, bool ADAGRAD = false>
-static int update_pair_common(int d, float* ta, float* ma, float* va, int64_t rows_a, const int64_t* idx_a, int64_t n_a, const float* grad_a,
-                              int norm_a, void* ws_a, size_t ws_a_bytes, float* tb, float* mb, float* vb, int64_t rows_b,
-                              const int64_t* idx_b, int64_t n_b, const float* grad_b, int norm_b, void* ws_b, size_t ws_b_bytes,
-                              AdamHyper hp, mf_stream_t stream, const char* what = "mf_update_pair") {
-    if (!ta || !tb || !idx_a || !idx_b || !grad_a || !grad_b || !ws_a || !ws_b || rows_a <= 0 || rows_b <= 0 ||
-        (ADAM && (!ma || !va || !mb || !vb)) || (ADAGRAD && (!ma || !mb)))
-        return mf_set_error(MF_EINVAL, "%s: bad argument", what);
-    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "%s: embedding width %d not in {32,64,128,256}", what, d);
-    if (rows_a >= (1ll << 39) || rows_b >= (1ll << 39)) return mf_set_error(MF_ENOTSUP, "%s: table too large", what);
-    if (n_a <= 0 || n_b <= 0 || n_a > FUSED_MAX_N || n_b > FUSED_MAX_N)
-        return mf_set_error(MF_ENOTSUP, "%s: list lengths outside 1..%d (update the tables one by one)", what, FUSED_MAX_N);
-    if (ws_a_bytes < mf_update_ws_bytes(n_a, d) || ws_b_bytes < mf_update_ws_bytes(n_b, d))
-        return mf_set_error(MF_ENOSPC, "%s: workspace too small", what);
-    UpdateWs wa = update_ws(ws_a, n_a, d), wb = update_ws(ws_b, n_b, d);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int bits_a = fused_bucket_bits(n_a), bits_b = fused_bucket_bits(n_b);
-    FusedUpdateParams fa{ta, ma, va, (long long)rows_a, reinterpret_cast<const long long*>(idx_a), (int)n_a, bits_a, grad_a,
-                         wa.partial, wa.gk0, wa.gk1, norm_a, hp};
-    FusedUpdateParams fb{tb, mb, vb, (long long)rows_b, reinterpret_cast<const long long*>(idx_b), (int)n_b, bits_b, grad_b,
-                         wb.partial, wb.gk0, wb.gk1, norm_b, hp};
-    // the list with more ids goes first (a tie: A): workgroups start in block order, one per CU, so the longer list's long
-    // pole starts at once and the shorter list's buckets fill the CUs as they fall free.  The tables are independent: same bits
-    const bool b_first = n_b > n_a;
-    const FusedUpdateParams &f0 = b_first ? fb : fa, &f1 = b_first ? fa : fb;
-    const unsigned nb0 = 1u << f0.bucket_bits, nb1 = 1u << f1.bucket_bits;
-    MF_DISPATCH_D(d, {
-        auto fn = update_fused_pair_kernel<D, ADAM, ADAGRAD>;
-        static bool attr_set = false;           // (per instantiation)
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_CAP * 8);
-            attr_set = true;
-        }
-        MF_TIMED("update_rows", s, (fn<<<dim3(nb0 + nb1), FUSED_THREADS, FUSED_CAP * 8, s>>>(f0, f1, (int)nb0)));
-    });
-    return mf_check_launch(what);
+extern "C" int mf_update_adagrad(float* table, float* sum, int64_t n_rows, int d, const int64_t* idx, int64_t n, const float* grad,
+                                 int normalized, float lr, float eps, float weight_decay, void* ws, size_t ws_bytes,
+                                 mf_stream_t stream) {
+    RowHyper hp;
+    if (int rc = row_hyper_adagrad("mf_update_adagrad", lr, eps, weight_decay, &hp)) return rc;
+    return update_common<RowOpt::ADAGRAD>({table, sum, nullptr, n_rows, idx, n, grad, normalized, ws, ws_bytes}, d, hp, stream,
+                                          "mf_update_adagrad");
 }
 
 extern "C" int mf_update_pair(int adam, int d, float* table_a, float* exp_avg_a, float* exp_avg_sq_a, int64_t n_rows_a, const int64_t* idx_a,
@@ -606,16 +609,22 @@ extern "C" int mf_update_pair(int adam, int d, float* table_a, float* exp_avg_a,
                               float* exp_avg_b, float* exp_avg_sq_b, int64_t n_rows_b, const int64_t* idx_b, int64_t n_b, const float* grad_b,
                               int normalized_b, void* ws_b, size_t ws_b_bytes, int64_t step, const int64_t* step_dev, float lr, float beta1,
                               float beta2, float eps, float weight_decay, mf_stream_t stream) {
-    if (adam) {
-        if (!step_dev && step < 1) return mf_set_error(MF_EINVAL, "mf_update_pair: step must be >= 1");
-        AdamHyper hp{lr, beta1, beta2, eps, weight_decay, (long long)step, reinterpret_cast<const long long*>(step_dev),
-                     log((double)beta1), log((double)beta2)};
-        return update_pair_common<true>(d, table_a, exp_avg_a, exp_avg_sq_a, n_rows_a, idx_a, n_a, grad_a, normalized_a, ws_a, ws_a_bytes, table_b,
-                                        exp_avg_b, exp_avg_sq_b, n_rows_b, idx_b, n_b, grad_b, normalized_b, ws_b, ws_b_bytes, hp, stream);
-    }
-    AdamHyper hp{lr, 0.f, 0.f, 0.f, weight_decay, 1, nullptr, 0.0, 0.0};
-    return update_pair_common<false>(d, table_a, nullptr, nullptr, n_rows_a, idx_a, n_a, grad_a, normalized_a, ws_a, ws_a_bytes, table_b, nullptr,
-                                     nullptr, n_rows_b, idx_b, n_b, grad_b, normalized_b, ws_b, ws_b_bytes, hp, stream);
+    if (adam && !step_dev && step < 1) return mf_set_error(MF_EINVAL, "mf_update_pair: step must be >= 1");
+    const RowHyper hp = adam ? row_hyper_adam(lr, beta1, beta2, eps, weight_decay, step, step_dev) : row_hyper_sgd(lr, weight_decay);
+    const UpdateTable a{table_a, exp_avg_a, exp_avg_sq_a, n_rows_a, idx_a, n_a, grad_a, normalized_a, ws_a, ws_a_bytes};
+    const UpdateTable b{table_b, exp_avg_b, exp_avg_sq_b, n_rows_b, idx_b, n_b, grad_b, normalized_b, ws_b, ws_b_bytes};
+    MF_DISPATCH_OPT(adam, return update_pair_common<OPT>(d, a, b, hp, stream, "mf_update_pair"));      // (SGD: the moments are not looked at)
+}
+
+extern "C" int mf_update_pair_adagrad(int d, float* table_a, float* sum_a, int64_t n_rows_a, const int64_t* idx_a, int64_t n_a,
+                                      const float* grad_a, int normalized_a, void* ws_a, size_t ws_a_bytes, float* table_b, float* sum_b,
+                                      int64_t n_rows_b, const int64_t* idx_b, int64_t n_b, const float* grad_b, int normalized_b, void* ws_b,
+                                      size_t ws_b_bytes, float lr, float eps, float weight_decay, mf_stream_t stream) {
+    RowHyper hp;
+    if (int rc = row_hyper_adagrad("mf_update_pair_adagrad", lr, eps, weight_decay, &hp)) return rc;
+    const UpdateTable a{table_a, sum_a, nullptr, n_rows_a, idx_a, n_a, grad_a, normalized_a, ws_a, ws_a_bytes};
+    const UpdateTable b{table_b, sum_b, nullptr, n_rows_b, idx_b, n_b, grad_b, normalized_b, ws_b, ws_b_bytes};
+    return update_pair_common<RowOpt::ADAGRAD>(d, a, b, hp, stream, "mf_update_pair_adagrad");
 }
 
 #ifdef MF_PROBE
@@ -630,35 +639,6 @@ extern "C" int mf_probe_update_stamps(unsigned long long* out, int n_blocks, int
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(mf_upd_stamps), (size_t)n_blocks * 8 * sizeof(unsigned long long)) == hipSuccess ? MF_OK : MF_ELAUNCH;
 }
 #endif
-
-// Row-wise Adagrad: ONE fp32 of state per row (`sum` [n_rows]).  The hyper-parameters are checked on the host, before any launch.
-static int adagrad_hyper(const char* what, float lr, float eps, float weight_decay, AdamHyper* hp) {
-    if (!(lr >= 0.f) || !(eps > 0.f) || !(weight_decay >= 0.f))
-        return mf_set_error(MF_EINVAL, "%s: lr >= 0, eps > 0 and weight_decay >= 0 are required (lr %g, eps %g, weight_decay %g)", what,
-                            (double)lr, (double)eps, (double)weight_decay);
-    *hp = AdamHyper{lr, 0.f, 0.f, eps, weight_decay, 1, nullptr, 0.0, 0.0};
-    return MF_OK;
-}
-
-extern "C" int mf_update_adagrad(float* table, float* sum, int64_t n_rows, int d, const int64_t* idx, int64_t n, const float* grad,
-                                 int normalized, float lr, float eps, float weight_decay, void* ws, size_t ws_bytes,
-                                 mf_stream_t stream) {
-    AdamHyper hp;
-    if (int rc = adagrad_hyper("mf_update_adagrad", lr, eps, weight_decay, &hp)) return rc;
-    return update_common<false, true>(table, sum, nullptr, n_rows, d, idx, n, grad, normalized, hp, ws, ws_bytes, stream,
-                                      "mf_update_adagrad");
-}
-
-extern "C" int mf_update_pair_adagrad(int d, float* table_a, float* sum_a, int64_t n_rows_a, const int64_t* idx_a, int64_t n_a,
-                                      const float* grad_a, int normalized_a, void* ws_a, size_t ws_a_bytes, float* table_b, float* sum_b,
-                                      int64_t n_rows_b, const int64_t* idx_b, int64_t n_b, const float* grad_b, int normalized_b, void* ws_b,
-                                      size_t ws_b_bytes, float lr, float eps, float weight_decay, mf_stream_t stream) {
-    AdamHyper hp;
-    if (int rc = adagrad_hyper("mf_update_pair_adagrad", lr, eps, weight_decay, &hp)) return rc;
-    return update_pair_common<false, true>(d, table_a, sum_a, nullptr, n_rows_a, idx_a, n_a, grad_a, normalized_a, ws_a, ws_a_bytes, table_b,
-                                           sum_b, nullptr, n_rows_b, idx_b, n_b, grad_b, normalized_b, ws_b, ws_b_bytes, hp, stream,
-                                           "mf_update_pair_adagrad");
-}
 
 // ---- lab: the DPP / permlane lane exchanges of mf_common.h against the `__shfl_xor` they replace ----------------------
 // (tests/test_gpu_parity.py: every butterfly sum, the 64-bit wave maximum and every single exchange, bit for bit)

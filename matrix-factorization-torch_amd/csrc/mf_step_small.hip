@@ -72,7 +72,7 @@ struct StepSmallParams {
     int B, N, kind, kind_mask, k, normalize;
     float sigma, margin;
     const float* logq; long long logq_rows;
-    AdamHyper hp;
+    RowHyper hp;
     StepSmallWs w;
     float* out;
 };
@@ -90,8 +90,9 @@ __device__ __forceinline__ void ss_lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-template <int D, bool ADAM>
+template <int D, RowOpt OPT>
 __global__ __launch_bounds__(SS_THREADS) void step_small_kernel(StepSmallParams p) {
+    constexpr bool ADAM = OPT == RowOpt::ADAM;                                  // (SGD or Adam: the moments' warming loads, the bias corrections)
     extern __shared__ __attribute__((aligned(16))) char smem[];                 // FUSED_CAP * 8 bytes (the update body's key list)
     const int tid = threadIdx.x, lane = mf_lane(), wave = tid >> 6;
     const int B = p.B, N = p.N;
@@ -614,7 +615,7 @@ __global__ __launch_bounds__(SS_THREADS) void step_small_kernel(StepSmallParams 
                              w.partial, w.gk0, w.gk1, p.normalize, p.hp};
         FusedUpdateParams fu{p.ut, p.um, p.uv, p.n_users, reinterpret_cast<const long long*>(p.user_ids), B, fused_bucket_bits(B), dup,
                              w.partial + (size_t)SS_MAXN * D, w.gk0, w.gk1, p.normalize, p.hp};
-        fused_update_small<D, ADAM, 4>(fi, fu, bias_l, lk);
+        fused_update_small<D, OPT, 4>(fi, fu, bias_l, lk);
     }
     stamp();
     if (warm == 0x7FC5A5A5u) w.stamps[15] = warm;               // (keeps the warming loads; practically never true, harmless when it is)
@@ -648,24 +649,13 @@ extern "C" int mf_step_small(float* user_table, float* user_m, float* user_v, in
     sp.pos_idx = pos_idx; sp.P = P; sp.pos_off = pos_off; sp.pos_items = pos_items; sp.pos_users = pos_users;
     sp.B = (int)B; sp.N = (int)N; sp.kind = kind; sp.kind_mask = kind_mask; sp.k = num_negatives; sp.normalize = normalize;
     sp.sigma = sigma; sp.margin = margin; sp.logq = logq; sp.logq_rows = logq_rows;
-    sp.hp = adam ? AdamHyper{lr, beta1, beta2, eps, weight_decay, (long long)step, reinterpret_cast<const long long*>(step_dev),
-                             log((double)beta1), log((double)beta2)}
-                 : AdamHyper{lr, 0.f, 0.f, 0.f, weight_decay, 1, nullptr, 0.0, 0.0};
+    sp.hp = adam ? row_hyper_adam(lr, beta1, beta2, eps, weight_decay, step, step_dev) : row_hyper_sgd(lr, weight_decay);
     sp.w = step_small_ws(ws, d);
     sp.out = out_losses;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    MF_DISPATCH_D(d, {
-        if (adam) {
-            auto fn = step_small_kernel<D, true>;
-            static bool set = false;
-            if (!set) { (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, SS_ROWS0 + SS_ROWS_BYTES); set = true; }
-            fn<<<dim3(1), SS_THREADS, SS_ROWS0 + SS_ROWS_BYTES, s>>>(sp);
-        } else {
-            auto fn = step_small_kernel<D, false>;
-            static bool set = false;
-            if (!set) { (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, SS_ROWS0 + SS_ROWS_BYTES); set = true; }
-            fn<<<dim3(1), SS_THREADS, SS_ROWS0 + SS_ROWS_BYTES, s>>>(sp);
-        }
-    });
+    MF_DISPATCH_D(d, MF_DISPATCH_OPT(adam, {
+        mf_allow_dynamic_lds<step_small_kernel<D, OPT>>(SS_ROWS0 + SS_ROWS_BYTES);
+        step_small_kernel<D, OPT><<<dim3(1), SS_THREADS, SS_ROWS0 + SS_ROWS_BYTES, s>>>(sp);
+    }));
     return mf_check_launch("mf_step_small");
 }

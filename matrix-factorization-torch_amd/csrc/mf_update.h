@@ -10,20 +10,79 @@
 static constexpr int RUN_CHUNK = 32;
 
 // ---------------------------------------------------------- sparse updates ----
-struct AdamHyper {
+// The optimiser kind: THE template parameter of everything below (and of the kernels and host paths in mf_embed.hip and
+// mf_step_small.hip).  What a kind keeps per table row (FusedUpdateParams::state0 / state1, update_rows_kernel's arguments):
+//   SGD      nothing (both NULL)
+//   ADAGRAD  state0 = `sum` [n_rows]: ONE fp32 per row, the running sum of the row's mean squared gradient; state1 NULL
+//   ADAM     state0 = exp_avg, state1 = exp_avg_sq, [n_rows][D] each
+enum class RowOpt { SGD, ADAGRAD, ADAM };
+
+struct RowHyper {                // built by row_hyper_sgd / row_hyper_adagrad / row_hyper_adam, nowhere else
     float lr, beta1, beta2, eps, wd;
     long long step;              // global step (1-based) ...
     const long long* step_dev;   // ... or, when non-NULL, where to read it on the device (hipGraph replays: a captured
                                  // launch freezes its by-value arguments, a device counter keeps counting)
     double ln_beta1, ln_beta2;   // log(beta), evaluated once on the host
 };
+static inline RowHyper row_hyper_sgd(float lr, float wd) { return RowHyper{lr, 0.f, 0.f, 0.f, wd, 1, nullptr, 0.0, 0.0}; }
+static inline RowHyper row_hyper_adam(float lr, float beta1, float beta2, float eps, float wd, int64_t step, const int64_t* step_dev) {
+    return RowHyper{lr, beta1, beta2, eps, wd, (long long)step, reinterpret_cast<const long long*>(step_dev), log((double)beta1),
+                    log((double)beta2)};
+}
+// (row-wise Adagrad's hyper-parameters are checked on the host, before any launch)
+static inline int row_hyper_adagrad(const char* what, float lr, float eps, float wd, RowHyper* hp) {
+    if (!(lr >= 0.f) || !(eps > 0.f) || !(wd >= 0.f))
+        return mf_set_error(MF_EINVAL, "%s: lr >= 0, eps > 0 and weight_decay >= 0 are required (lr %g, eps %g, weight_decay %g)", what,
+                            (double)lr, (double)eps, (double)wd);
+    *hp = RowHyper{lr, 0.f, 0.f, eps, wd, 1, nullptr, 0.0, 0.0};
+    return MF_OK;
+}
+// a kind picked at run time (the `adam` flag of mf_update_pair and mf_step_small), like MF_DISPATCH_D
+#define MF_DISPATCH_OPT(adam, ...)                                       \
+    if (adam) { constexpr RowOpt OPT = RowOpt::ADAM; __VA_ARGS__; }     \
+    else { constexpr RowOpt OPT = RowOpt::SGD; __VA_ARGS__; }
+// a kernel that needs more dynamic LDS than the default limit is allowed it once (per kernel: FN is the instantiation)
+template <auto FN>
+static inline void mf_allow_dynamic_lds(int bytes) {
+    static bool set = false;
+    if (!set) { (void)hipFuncSetAttribute((const void*)FN, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); set = true; }
+}
+
 // bias corrections 1 - beta^step = -expm1(step * ln beta), evaluated on the device in both modes (so an eager step and a
 // replayed one agree bit for bit); double precision, but one expm1 each instead of a pow
-__device__ __forceinline__ void adam_bias(const AdamHyper& hp, float& bc1, float& bc2) {
+__device__ __forceinline__ void adam_bias(const RowHyper& hp, float& bc1, float& bc2) {
     const double st = (double)(hp.step_dev ? *hp.step_dev : hp.step);
     bc1 = (float)(-expm1(st * hp.ln_beta1));
     bc2 = (float)(-expm1(st * hp.ln_beta2));
 }
+
+// A table row and what its kind keeps for it, in registers: lane c of the row's D/4-lane group holds floats 4c .. 4c+3 of the
+// row and of Adam's two moment rows; every lane of the group holds Adagrad's one float (one address per group: a broadcast
+// load; lane 0 stores it).  THE place that reads and writes table / state0 / state1 (`p`: anything with those three pointers);
+// the row and its state are asked for together and written together.
+template <RowOpt OPT>
+struct RowState {
+    f32x4 w = {0.f, 0.f, 0.f, 0.f}, m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
+    float s = 0.f;
+    template <int D, class P>
+    __device__ __forceinline__ void load(const P& p, int64_t row, int c) {
+        w = reinterpret_cast<const f32x4*>(p.table + row * D)[c];
+        if constexpr (OPT == RowOpt::ADAGRAD) s = p.state0[row];
+        if constexpr (OPT == RowOpt::ADAM) {
+            m = reinterpret_cast<const f32x4*>(p.state0 + row * D)[c];
+            v = reinterpret_cast<const f32x4*>(p.state1 + row * D)[c];
+        }
+    }
+    template <int D, class P>
+    __device__ __forceinline__ void store(const P& p, int64_t row, int c) const {
+        if constexpr (OPT == RowOpt::ADAGRAD) { if (c == 0) p.state0[row] = s; }
+        if constexpr (OPT == RowOpt::ADAM) {
+            reinterpret_cast<f32x4*>(p.state0 + row * D)[c] = m;
+            reinterpret_cast<f32x4*>(p.state1 + row * D)[c] = v;
+        }
+        reinterpret_cast<f32x4*>(p.table + row * D)[c] = w;
+    }
+};
 
 // One d/4-lane group per sorted position.  Runs of equal ids are summed in two
 // deterministic levels so that a very popular row (Zipf: hundreds of duplicates in
@@ -32,16 +91,15 @@ __device__ __forceinline__ void adam_bias(const AdamHyper& hp, float& bc1, float
 // rows in sorted (= batch) order.  A run that is one chunk is applied at once; otherwise the
 // chunk sums are parked and the run's first position adds them up, in order, in a second
 // launch.  Chunk boundaries depend on sorted positions only: deterministic.
-// The arithmetic of one row update on values already in registers (lane c of the row's D/4-lane group holds
-// floats 4c .. 4c+3 of the row, its moments and its summed gradient).
-// ADAGRAD (never with ADAM): row-wise Adagrad -- ONE fp32 of state per row, `s`, the running sum of the mean squared gradient
-// of the row (every lane of the group holds the same value going in and coming out: the butterfly leaves the same sum in each
-// lane).  Uses hp.lr, hp.eps, hp.wd (coupled L2, skipped as a whole when wd == 0: not a single rounding, no 0 * inf).
-template <int D, bool ADAM, bool ADAGRAD = false>
-__device__ __forceinline__ void row_update_math(f32x4& w, f32x4& m, f32x4& v, f32x4 acc, int normalized,
-                                                const AdamHyper& hp, float bc1, float bc2, float& s) {
-    static_assert(!(ADAM && ADAGRAD), "one optimiser kind");
+// The arithmetic of one row update on values already in registers (`r`: the row and its state; lane c of the row's D/4-lane
+// group holds floats 4c .. 4c+3 of the summed gradient `acc`).
+// ADAGRAD: row-wise Adagrad -- `r.s` is the same value in every lane of the group going in and coming out (the butterfly
+// leaves the same sum in each lane).  Uses hp.lr, hp.eps, hp.wd (coupled L2, skipped as a whole when wd == 0: not a single
+// rounding, no 0 * inf).
+template <int D, RowOpt OPT>
+__device__ __forceinline__ void row_update_math(RowState<OPT>& r, f32x4 acc, int normalized, const RowHyper& hp, float bc1, float bc2) {
     constexpr int LPR = D / 4;
+    f32x4& w = r.w;
     f32x4 g = acc;
     if (normalized) {   // grad is w.r.t. w / max(||w||, 1e-12): apply the Jacobian
         float ss = mf_group_sum(w[0] * w[0] + w[1] * w[1] + w[2] * w[2] + w[3] * w[3], LPR);
@@ -50,51 +108,39 @@ __device__ __forceinline__ void row_update_math(f32x4& w, f32x4& m, f32x4& v, f3
         float pr = mf_group_sum(acc[0] * uh[0] + acc[1] * uh[1] + acc[2] * uh[2] + acc[3] * uh[3], LPR);
         g = (acc - uh * pr) * inv;
     }
-    if (ADAGRAD) {
+    if constexpr (OPT == RowOpt::ADAGRAD) {
         if (hp.wd != 0.f) g = g + hp.wd * w;
         const float q = (1.f / D) * mf_group_sum(g[0] * g[0] + g[1] * g[1] + g[2] * g[2] + g[3] * g[3], LPR);
-        s = s + q;
-        const float den = sqrtf(s) + hp.eps;
+        r.s = r.s + q;
+        const float den = sqrtf(r.s) + hp.eps;
         w = w - hp.lr * g / den;
-    } else if (!ADAM) {
+    } else if constexpr (OPT == RowOpt::SGD) {
         w = w - hp.lr * (g + hp.wd * w);
     } else {
         w = w * (1.f - hp.lr * hp.wd);
-        m = m * hp.beta1 + (1.f - hp.beta1) * g;
-        v = v * hp.beta2 + (1.f - hp.beta2) * g * g;
+        r.m = r.m * hp.beta1 + (1.f - hp.beta1) * g;
+        r.v = r.v * hp.beta2 + (1.f - hp.beta2) * g * g;
         f32x4 den;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) den[t] = sqrtf(v[t] / bc2) + hp.eps;
-        w = w - (hp.lr / bc1) * m / den;
+        for (int t = 0; t < 4; ++t) den[t] = sqrtf(r.v[t] / bc2) + hp.eps;
+        w = w - (hp.lr / bc1) * r.m / den;
     }
 }
 
-// (ADAGRAD: `exp_avg` is the per-row state `sum` [rows], `exp_avg_sq` unused)
-template <int D, bool ADAM, bool ADAGRAD = false>
-__device__ __forceinline__ void apply_row_update(bool active, int64_t row, int c, f32x4 acc,
-                                                 float* __restrict__ table, float* __restrict__ exp_avg,
-                                                 float* __restrict__ exp_avg_sq, int normalized,
-                                                 const AdamHyper& hp) {
+template <int D, RowOpt OPT>
+__device__ __forceinline__ void apply_row_update(bool active, int64_t row, int c, f32x4 acc, float* __restrict__ table,
+                                                 float* __restrict__ state0, float* __restrict__ state1, int normalized,
+                                                 const RowHyper& hp) {
     // a group (the D/4 lanes of one row) is active or not as a whole: idle groups leave before touching memory
     // (they used to read row 0 -- half a million lanes on one 512-byte line)
     if (!active) return;
-    f32x4 w = reinterpret_cast<const f32x4*>(table + row * D)[c];
-    f32x4 m = {0.f, 0.f, 0.f, 0.f}, v = m;
+    const struct { float *table, *state0, *state1; } p{table, state0, state1};
+    RowState<OPT> r;
+    r.template load<D>(p, row, c);
     float bc1 = 1.f, bc2 = 1.f;
-    if (ADAM) {
-        m = reinterpret_cast<const f32x4*>(exp_avg + row * D)[c];
-        v = reinterpret_cast<const f32x4*>(exp_avg_sq + row * D)[c];
-        adam_bias(hp, bc1, bc2);
-    }
-    float s = 0.f;
-    if (ADAGRAD) s = exp_avg[row];      // one address per group: a broadcast load
-    row_update_math<D, ADAM, ADAGRAD>(w, m, v, acc, normalized, hp, bc1, bc2, s);
-    if (ADAGRAD && c == 0) exp_avg[row] = s;
-    if (ADAM) {
-        reinterpret_cast<f32x4*>(exp_avg + row * D)[c] = m;
-        reinterpret_cast<f32x4*>(exp_avg_sq + row * D)[c] = v;
-    }
-    reinterpret_cast<f32x4*>(table + row * D)[c] = w;
+    if constexpr (OPT == RowOpt::ADAM) adam_bias(hp, bc1, bc2);
+    row_update_math<D>(r, acc, normalized, hp, bc1, bc2);
+    r.template store<D>(p, row, c);
 }
 
 // ------------------------------------------------- one-launch sparse update ----
@@ -125,6 +171,14 @@ static constexpr int FUSED_SCAN_UNROLL = 8;
 #ifndef FUSED_NF_ADAM
 #define FUSED_NF_ADAM 12
 #endif
+#ifndef FUSED_NF_ADAGRAD
+#define FUSED_NF_ADAGRAD 16
+#endif
+// gradient rows in flight per lane group in the one-launch kernels (fused_runs_of).  1024 threads leave 128 registers per
+// lane; with Adam the row and its two moments are in flight beside the gradients (12 registers): sixteen rows spilled 20
+// registers, twelve fit.  Row-wise Adagrad has the row and ONE float beside them (5 registers; SGD 4): sixteen, like SGD
+template <RowOpt OPT>
+static constexpr int FUSED_NF = OPT == RowOpt::ADAGRAD ? FUSED_NF_ADAGRAD : OPT == RowOpt::ADAM ? FUSED_NF_ADAM : 16;
 static constexpr unsigned long long FUSED_PAD = ~0ull;
 static constexpr unsigned FUSED_POS_MASK = 0xFFFFFFu;
 
@@ -133,7 +187,7 @@ __device__ __forceinline__ unsigned fused_bucket(long long id, int bucket_bits) 
 }
 
 struct FusedUpdateParams {
-    float *table, *exp_avg, *exp_avg_sq;     // (row-wise Adagrad: exp_avg is the state `sum` [n_rows], exp_avg_sq NULL)
+    float *table, *state0, *state1;     // (the state of a kind: the table at RowOpt)
     long long n_rows;
     const long long* idx;
     int n, bucket_bits;
@@ -141,7 +195,7 @@ struct FusedUpdateParams {
     float* partial;                     // [n][d] parked chunk sums (by batch position of the chunk's first row)
     unsigned long long *gk0, *gk1;      // [n] each: the global-memory lists of an overflowing bucket
     int normalized;
-    AdamHyper hp;
+    RowHyper hp;
 };
 
 // (lab builds, -DMF_PROBE: thread 0 of every workgroup leaves a 100 MHz clock value at each phase boundary of its bucket --
@@ -176,13 +230,11 @@ __device__ __forceinline__ void fused_append(bool mine, unsigned long long key, 
 // `params(k)`: the table / gradient / hyper-parameter set of sorted position k, `params.row(key)`: the row a key addresses
 // (FusedOneTable for update_fused_kernel; the one-launch step lays the lists of its two tables end to end and updates
 // both in one pass: FusedTwoTables)
-template <int D, bool ADAM, int NFLIGHT, bool ADAGRAD = false, class Keys, class Params>
+// NF: gradient rows in flight per lane group (FUSED_NF<OPT> in the one-launch kernels; rows are added in order whatever NF
+// is: the sums do not depend on it)
+template <int D, RowOpt OPT, int NF, class Keys, class Params>
 __device__ __forceinline__ void fused_runs_of(Keys K, int m, Params params, float bc1, float bc2) {
     constexpr int LPR = D / 4, GPW = 64 / LPR, NWAVE = FUSED_THREADS / 64;
-    // gradient rows in flight per lane group.  1024 threads leave 128 registers per lane; with Adam the row and its two
-    // moments are in flight beside the gradients (12 registers): sixteen rows spilled 20 registers, twelve fit.  Row-wise
-    // Adagrad has the row and ONE float beside them (5 registers; SGD 4): sixteen, like SGD
-    constexpr int NF = NFLIGHT;      // (rows are added in order whatever NF is: the sums do not depend on it)
     const int lane = mf_lane(), wave = threadIdx.x >> 6;
     const int grp = lane / LPR, c = lane % LPR;
     int parked = 0;                     // this thread left a chunk sum for the second pass
@@ -218,18 +270,10 @@ __device__ __forceinline__ void fused_runs_of(Keys K, int m, Params params, floa
                 const int64_t ri = params.row(key);                    // the row to address
                 const bool head = kk == 0 || (K[kk - 1] >> 24) != row;
                 const int chunk_end = min(m, (kk / RUN_CHUNK + 1) * RUN_CHUNK);
-                // the row and its moments are asked for before the gradient rows: one memory round trip, not two
+                // the row and its state are asked for before the gradient rows: one memory round trip, not two
                 const bool will_apply = pass == 1 || head;
-                f32x4 w = {0.f, 0.f, 0.f, 0.f}, mm = w, vv = w;
-                float ss = 0.f;
-                if (will_apply) {
-                    w = reinterpret_cast<const f32x4*>(p.table + ri * D)[c];
-                    if (ADAGRAD) ss = p.exp_avg[ri];                   // (the group's lanes ask for one address: a broadcast)
-                    if (ADAM) {
-                        mm = reinterpret_cast<const f32x4*>(p.exp_avg + ri * D)[c];
-                        vv = reinterpret_cast<const f32x4*>(p.exp_avg_sq + ri * D)[c];
-                    }
-                }
+                RowState<OPT> r;
+                if (will_apply) r.template load<D>(p, ri, c);
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 bool apply = false;
                 float* park = p.partial + (int64_t)((unsigned)key & FUSED_POS_MASK) * D;
@@ -278,13 +322,8 @@ __device__ __forceinline__ void fused_runs_of(Keys K, int m, Params params, floa
                     apply = true;
                 }
                 if (apply) {
-                    row_update_math<D, ADAM, ADAGRAD>(w, mm, vv, acc, p.normalized, p.hp, bc1, bc2, ss);
-                    if (ADAGRAD && c == 0) p.exp_avg[ri] = ss;
-                    if (ADAM) {
-                        reinterpret_cast<f32x4*>(p.exp_avg + ri * D)[c] = mm;
-                        reinterpret_cast<f32x4*>(p.exp_avg_sq + ri * D)[c] = vv;
-                    }
-                    reinterpret_cast<f32x4*>(p.table + ri * D)[c] = w;
+                    row_update_math<D>(r, acc, p.normalized, p.hp, bc1, bc2);
+                    r.template store<D>(p, ri, c);
                 }
             }
         }
@@ -316,21 +355,15 @@ struct FusedTwoTables {
     __device__ __forceinline__ const FusedUpdateParams& operator()(int k) const { return k < split ? pa : pb; }
     __device__ __forceinline__ int64_t row(unsigned long long key) const { return (int64_t)((key >> 24) & FUSED_ROW_MASK); }
 };
-template <int D, bool ADAM, int NFLIGHT, bool ADAGRAD, class Keys>
+template <int D, RowOpt OPT, class Keys>
 __device__ __forceinline__ void fused_runs(Keys K, int m, const FusedUpdateParams& p, float bc1, float bc2) {
-    fused_runs_of<D, ADAM, NFLIGHT, ADAGRAD>(K, m, FusedOneTable{p}, bc1, bc2);
+    fused_runs_of<D, OPT, FUSED_NF<OPT>>(K, m, FusedOneTable{p}, bc1, bc2);
 }
 
-#ifndef FUSED_NF_ADAGRAD
-#define FUSED_NF_ADAGRAD 16
-#endif
-// gradient rows in flight per lane group in the one-launch kernels (fused_runs_of)
-template <bool ADAM, bool ADAGRAD>
-static constexpr int FUSED_NF = ADAGRAD ? FUSED_NF_ADAGRAD : ADAM ? FUSED_NF_ADAM : 16;
-
 // The work of ONE bucket `myb` by a workgroup of FUSED_THREADS threads; `lk`: FUSED_CAP keys of LDS.
-template <int D, bool ADAM, int NFLIGHT = (ADAM ? FUSED_NF_ADAM : 16), bool ADAGRAD = false>
+template <int D, RowOpt OPT>
 __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, const unsigned myb, unsigned long long* lk) {
+    constexpr bool ADAM = OPT == RowOpt::ADAM;          // (the bias corrections: once per workgroup, through LDS)
     __shared__ int s_count, s_lower;
     __shared__ float s_bias[2];
     const int tid = threadIdx.x, lane = mf_lane();
@@ -383,7 +416,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
         }
         __syncthreads();
         MF_UPD_STAMP(2);
-        fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(sorted, m, p, bc1, bc2);
+        fused_runs<D, OPT>(sorted, m, p, bc1, bc2);
     } else if (m <= FUSED_CAP) {
         int P = 1024;
         while (P < m) P <<= 1;
@@ -405,7 +438,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
             }
         }
         MF_UPD_STAMP(2);
-        fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(lk, m, p, bc1, bc2);
+        fused_runs<D, OPT>(lk, m, p, bc1, bc2);
     } else {
         // the bucket does not fit: its segment of the global lists starts after every key of a lower bucket
         int low = 0;
@@ -434,7 +467,7 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
         }
         __syncthreads();
         MF_UPD_STAMP(2);
-        fused_runs<D, ADAM, NFLIGHT, ADAGRAD>(static_cast<const unsigned long long*>(g1), m, p, bc1, bc2);
+        fused_runs<D, OPT>(static_cast<const unsigned long long*>(g1), m, p, bc1, bc2);
     }
 }
 
@@ -445,11 +478,12 @@ __device__ __forceinline__ void fused_update_body(const FusedUpdateParams& p, co
 // multiple of RUN_CHUNK (the gap filled with FUSED_PAD), so that every run is cut into the same chunks, summed in the same
 // order, as in its own bucket's list.  `bias`: the two Adam bias corrections, evaluated by the caller.
 static constexpr int FUSED_SMALL_N = 256;
-template <int D, bool ADAM, int NFLIGHT>
+template <int D, RowOpt OPT, int NFLIGHT>
 __device__ __forceinline__ void fused_update_small(const FusedUpdateParams& pa, const FusedUpdateParams& pb, const float* bias,
                                                    unsigned long long* lk) {
     __shared__ int s_n[2], s_cnt[16], s_pad[17];
     const int tid = threadIdx.x;
+    constexpr bool ADAM = OPT == RowOpt::ADAM;
     const float bc1 = ADAM ? bias[0] : 1.f, bc2 = ADAM ? bias[1] : 1.f;      // (read first: `bias` may lie inside `lk`)
     __syncthreads();
     if (tid < 16) s_cnt[tid] = 0;
@@ -516,13 +550,13 @@ __device__ __forceinline__ void fused_update_small(const FusedUpdateParams& pa, 
     }
     __syncthreads();
     const int split = s_pad[8], total = s_pad[16];
-    fused_runs_of<D, ADAM, NFLIGHT>(sorted, total, FusedTwoTables{pa, pb, split}, bc1, bc2);
+    fused_runs_of<D, OPT, NFLIGHT>(sorted, total, FusedTwoTables{pa, pb, split}, bc1, bc2);
 }
 
-template <int D, bool ADAM, bool ADAGRAD = false>
+template <int D, RowOpt OPT>
 __global__ __launch_bounds__(FUSED_THREADS) void update_fused_kernel(FusedUpdateParams p) {
     extern __shared__ __attribute__((aligned(16))) char fused_smem[];
-    fused_update_body<D, ADAM, FUSED_NF<ADAM, ADAGRAD>, ADAGRAD>(p, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
+    fused_update_body<D, OPT>(p, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
 }
 
 // BOTH tables of a step in one launch: workgroups [0, nb_a) take the first parameter set's buckets, the rest the second's.
@@ -532,12 +566,12 @@ __global__ __launch_bounds__(FUSED_THREADS) void update_fused_kernel(FusedUpdate
 // one workgroup busy for 35 us, the other 255 through after ~10) starts at once and the shorter list's buckets fill the CUs
 // that fall free beside it: the launch costs what the longer list costs alone.  (User table first, the pole started only
 // when a user bucket retired: 13.6 + 35.7 us alone, 44.7 us as a pair; item list first: 36.2.)
-template <int D, bool ADAM, bool ADAGRAD = false>
+template <int D, RowOpt OPT>
 __global__ __launch_bounds__(FUSED_THREADS) void update_fused_pair_kernel(FusedUpdateParams pa, FusedUpdateParams pb, int nb_a) {
     extern __shared__ __attribute__((aligned(16))) char fused_smem[];
     // (two calls, not one call on a selected parameter set: the selection moved the set out of scalar registers and spilled)
-    if ((int)blockIdx.x < nb_a) fused_update_body<D, ADAM, FUSED_NF<ADAM, ADAGRAD>, ADAGRAD>(pa, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
-    else fused_update_body<D, ADAM, FUSED_NF<ADAM, ADAGRAD>, ADAGRAD>(pb, blockIdx.x - nb_a, reinterpret_cast<unsigned long long*>(fused_smem));
+    if ((int)blockIdx.x < nb_a) fused_update_body<D, OPT>(pa, blockIdx.x, reinterpret_cast<unsigned long long*>(fused_smem));
+    else fused_update_body<D, OPT>(pb, blockIdx.x - nb_a, reinterpret_cast<unsigned long long*>(fused_smem));
 }
 
 // buckets (= workgroups) of a list of n ids: ~32 ids each, at most 2^FUSED_MAX_BITS

@@ -47,7 +47,10 @@ import math
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, optim
+
+# a trainer's per-table state (``ShardedTrainer.state[name]``), in the order ``optim.row_update`` takes the tensors
+STATE_KEYS = {"sgd": (), "adagrad": ("sum",), "adam": ("m", "v")}
 
 
 # --------------------------------------------------------------------------- exchanges ---
@@ -300,24 +303,8 @@ class HipOps:
         return loss.detach(), u.grad, v.grad
 
     def update(self, optimizer, table, state, ids, grad, normalized, step, hyper):
-        lib = _lib.lib()
-        n, d = ids.numel(), table.shape[1]
-        if n == 0:
-            return
-        ws = _lib.workspace(lib.mf_update_ws_bytes(n, d), table.device)
-        if optimizer == "sgd":
-            _lib.check(lib.mf_update_sgd(table.data_ptr(), table.shape[0], d, ids.data_ptr(), n, grad.data_ptr(),
-                                         int(normalized), hyper["lr"], hyper["weight_decay"], ws.data_ptr(), ws.numel(),
-                                         _lib.stream_ptr()))
-        elif optimizer == "adagrad":
-            _lib.check(lib.mf_update_adagrad(table.data_ptr(), state["sum"].data_ptr(), table.shape[0], d, ids.data_ptr(), n,
-                                             grad.data_ptr(), int(normalized), hyper["lr"], hyper["eps"], hyper["weight_decay"],
-                                             ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-        else:
-            b1, b2 = hyper["betas"]
-            _lib.check(lib.mf_update_adam(table.data_ptr(), state["m"].data_ptr(), state["v"].data_ptr(), table.shape[0], d,
-                                          ids.data_ptr(), n, grad.data_ptr(), int(normalized), step, None, hyper["lr"], b1, b2,
-                                          hyper["eps"], hyper["weight_decay"], ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        if ids.numel():
+            optim.row_update(optimizer, table, tuple(state[k] for k in STATE_KEYS[optimizer]), ids, grad, normalized, hyper, step)
 
     def topk(self, queries, items, k, exclude_csr, idx_base):
         # ONE ItemIndex for the shard tensor last searched: its derived copies (bf16 rows, blocked rows) and workspaces are
@@ -350,14 +337,9 @@ class HipOps:
 
 
 def optimizer_hyper(optimizer: str, lr: float | None = None, **over) -> dict:
-    """The hyper-parameters of ``optim.SparseSGD`` / ``optim.RowAdagrad`` / ``optim.RowAdam`` (their constructor defaults), in one
-    place."""
-    if optimizer == "sgd":
-        h = {"lr": 1e-2, "weight_decay": 0.0}
-    elif optimizer == "adagrad":
-        h = {"lr": 1e-2, "eps": 1e-10, "weight_decay": 0.0, "initial_accumulator_value": 0.0}
-    else:
-        h = {"lr": 1e-4, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.01}
+    """The hyper-parameters of ``optim.KINDS[optimizer]``: its constructor's defaults, read off an instance over a placeholder
+    parameter."""
+    h = dict(optim.KINDS[optimizer]([torch.nn.Parameter(torch.empty(0))]).defaults)
     if lr is not None:
         h["lr"] = lr
     h.update(over)

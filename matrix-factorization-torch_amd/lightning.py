@@ -402,15 +402,9 @@ class MatrixFactorizationLitModule(_Base):
 
     # ------------------------------------------------------------------- setup ---
     def configure_optimizers(self) -> torch.optim.Optimizer:
-        if self.config.user_tower == "transformer":     # tables + the encoder's dense weights: one object steps both
-            kind = self.config.optimizer if self.config.optimizer in ("sgd", "adagrad") else "adam"
-            return optim.tower_optimizer(self.towers, kind, self.config.learning_rate)
-        params = list(self.towers.parameters())
-        if self.config.optimizer == "sgd":
-            return optim.SparseSGD(params, lr=self.config.learning_rate)
-        if self.config.optimizer == "adagrad":
-            return optim.RowAdagrad(params, lr=self.config.learning_rate)
-        return optim.RowAdam(params, lr=self.config.learning_rate)
+        # (a transformer tower: tables + the encoder's dense weights, one object steps both; otherwise the bare row optimiser)
+        kind = self.config.optimizer if self.config.optimizer in ("sgd", "adagrad") else "adam"
+        return optim.tower_optimizer(self.towers, kind, self.config.learning_rate)
 
     def configure_model(self, device=None) -> None:
         if self.towers is None:

@@ -8,9 +8,14 @@ summed first, every touched row is read and written once.  Spec: ``oracle/embed.
 (no reference implementation); row-wise Adagrad's: DESIGN.md 2.  The
 classes are ``torch.optim.Optimizer`` subclasses, so Lightning's automatic
 optimisation can drive them.
+
+The optimiser kind is named in ``KINDS`` ("sgd" / "adagrad" / "adam" -> class); :func:`row_update` (one table) and
+:func:`row_update_pair` (two tables, one launch) are the only callers of the update exports, for the optimisers' one
+``step()``, the sharded trainer (``distributed.HipOps.update``) and tools/lab/update_probe.py alike.
 """
 from __future__ import annotations
 
+import functools
 import os
 
 import torch
@@ -92,31 +97,61 @@ def run_table_jobs(jobs) -> None:
         cur.wait_event(done)
 
 
-def _pair_update(adam: bool, jobs, step: int, step_dev, hyper: dict) -> bool:
-    """Both tables of the step in ONE launch (``mf_update_pair``) when there are exactly two pending tables of one width and one
-    parameter group -- the usual step: user rows and item rows.  ``jobs``: (table, state or None, ids, grad, normalized).
-    False: not that shape (or lists beyond the one-launch range): the caller updates the tables one by one."""
-    if len(jobs) != 2 or os.environ.get("MF_UPDATE_PAIR", "1") != "1":
+def _hyper_args(kind: str, hyper: dict, step: int, step_dev, pair: bool = False) -> tuple:
+    """The hyper-parameter arguments of ``kind``'s export, in its order.  (``mf_update_pair`` serves SGD too, with Adam's list:
+    step, betas and eps unused.)"""
+    if kind == "adagrad":
+        return hyper["lr"], hyper["eps"], hyper["weight_decay"]
+    if kind == "adam":
+        return step, step_dev, hyper["lr"], *hyper["betas"], hyper["eps"], hyper["weight_decay"]
+    return (1, None, hyper["lr"], 0.0, 0.0, 0.0, hyper["weight_decay"]) if pair else (hyper["lr"], hyper["weight_decay"])
+
+
+def _table_args(lib, job: tuple, state_slots: int) -> tuple:
+    """One job -- (table, state, ids, grad, normalized) -- as the exports take it, in three parts: (table, its state tensors
+    [NULL up to ``state_slots``], rows), (ids, their number, gradient rows, normalised or not), (workspace, its bytes)."""
+    table, state, ids, grad, normalized = job
+    n = ids.numel()
+    ws = _lib.workspace(lib.mf_update_ws_bytes(n, table.shape[1]), table.device)
+    ptrs = [s.data_ptr() for s in state] + [None] * (state_slots - len(state))
+    return (table.data_ptr(), *ptrs, table.shape[0]), (ids.data_ptr(), n, grad.data_ptr(), int(normalized)), (ws.data_ptr(), ws.numel())
+
+
+def row_update(kind: str, table, state: tuple, ids, grad, normalized, hyper: dict, step: int = 1, step_dev=None, *, lib=None) -> None:
+    """ONE table through its export (``mf_update_sgd`` / ``mf_update_adagrad`` / ``mf_update_adam``) on the current stream.
+    ``state``: the kind's state tensors in the export's order -- ``()``, ``(sum,)``, ``(exp_avg, exp_avg_sq)``; ``hyper``: a
+    parameter group (or ``distributed.optimizer_hyper``); ``step`` / ``step_dev``: Adam's global step, by value or (non-None)
+    the address of a device counter.  ``lib``: another build of the library (tools/lab/update_probe.py)."""
+    lib = lib or _lib.lib()
+    rows, lst, ws = _table_args(lib, (table, state, ids, grad, normalized), len(state))
+    _lib.check(getattr(lib, "mf_update_" + kind)(*rows, table.shape[1], *lst, *_hyper_args(kind, hyper, step, step_dev), *ws,
+                                                 _lib.stream_ptr()))
+
+
+def row_update_pair(kind: str, job_a: tuple, job_b: tuple, hyper: dict, step: int = 1, step_dev=None, *, lib=None) -> bool:
+    """Two tables in ONE launch (``mf_update_pair`` / ``mf_update_pair_adagrad``) -- the usual step: user rows and item rows.
+    A job: (table, state, ids, grad, normalized), as :func:`row_update` takes them.  False, and nothing launched: the tables'
+    widths differ, a list is empty or beyond the one-launch range, or ``MF_UPDATE_PAIR`` is not "1" -- the caller updates the
+    tables one by one."""
+    if os.environ.get("MF_UPDATE_PAIR", "1") != "1":
         return False
-    (pa, sa, ia, ga, na), (pb, sb, ib, gb, nb) = jobs
-    d = pa.shape[1]
-    if pb.shape[1] != d or not (0 < ia.numel() <= 65536 and 0 < ib.numel() <= 65536):
+    d = job_a[0].shape[1]
+    if job_b[0].shape[1] != d or not (0 < job_a[2].numel() <= 65536 and 0 < job_b[2].numel() <= 65536):
         return False
-    lib = _lib.lib()
-    wa = _lib.workspace(lib.mf_update_ws_bytes(ia.numel(), d), pa.device)
-    wb = _lib.workspace(lib.mf_update_ws_bytes(ib.numel(), d), pb.device)
-    b1, b2 = hyper.get("betas", (0.0, 0.0))
-    _lib.check(lib.mf_update_pair(
-        int(adam), d,
-        pa.data_ptr(), sa["exp_avg"].data_ptr() if adam else None, sa["exp_avg_sq"].data_ptr() if adam else None, pa.shape[0],
-        ia.data_ptr(), ia.numel(), ga.data_ptr(), int(na), wa.data_ptr(), wa.numel(),
-        pb.data_ptr(), sb["exp_avg"].data_ptr() if adam else None, sb["exp_avg_sq"].data_ptr() if adam else None, pb.shape[0],
-        ib.data_ptr(), ib.numel(), gb.data_ptr(), int(nb), wb.data_ptr(), wb.numel(),
-        step, step_dev, hyper["lr"], b1, b2, hyper.get("eps", 0.0), hyper["weight_decay"], _lib.stream_ptr()))
+    lib = lib or _lib.lib()
+    fn, head, slots = (lib.mf_update_pair_adagrad, (d,), 1) if kind == "adagrad" else (lib.mf_update_pair, (int(kind == "adam"), d), 2)
+    tables = [x for job in (job_a, job_b) for part in _table_args(lib, job, slots) for x in part]
+    _lib.check(fn(*head, *tables, *_hyper_args(kind, hyper, step, step_dev, pair=True), _lib.stream_ptr()))
     return True
 
 
 class _SparseRowOptimizer(torch.optim.Optimizer):
+    """What the sparse row optimisers share: THE ``step``.  A subclass names its ``kind`` (the exports :func:`row_update` and
+    :func:`row_update_pair` reach) and says what state a table has (``_state_of``); where it needs to, it checks a parameter
+    group before anything is launched (``_check_group``) and opens a table's step (``_begin``)."""
+
+    kind: str
+
     def zero_grad(self, set_to_none: bool = True) -> None:
         super().zero_grad(set_to_none=set_to_none)
         for group in self.param_groups:
@@ -131,12 +166,23 @@ class _SparseRowOptimizer(torch.optim.Optimizer):
         if p.dim() != 2 or not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
             raise _lib.MfHipError("embedding table must be a contiguous 2-D fp32 tensor on the GPU")
 
+    def _check_group(self, group: dict) -> None:
+        pass
 
-class SparseSGD(_SparseRowOptimizer):
-    """row -= lr * (sum of the row's gradients + weight_decay * row), touched rows only."""
+    def _state_of(self, p: torch.Tensor, group: dict) -> tuple:
+        """The state tensors of table ``p`` in the export's order, allocated on first use."""
+        return ()
 
-    def __init__(self, params, lr: float = 1e-2, weight_decay: float = 0.0) -> None:
-        super().__init__(params, {"lr": lr, "weight_decay": weight_decay})
+    def _begin(self, p: torch.Tensor) -> tuple:
+        """Opens the step of a table with pending rows: (step, step_dev) for its update call."""
+        return 1, None
+
+    def init_state(self) -> None:
+        """Allocate every table's state now instead of inside the first ``step`` (Adam: two table-sized allocations and
+        memsets per table -- a multi-millisecond stall in the middle of an otherwise steady first step)."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                self._state_of(p, group)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -144,37 +190,38 @@ class SparseSGD(_SparseRowOptimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.lib()
-        jobs, done, pairs = [], [], []
+        jobs = []       # (table, state, ids, grad, normalized, group, step, step_dev) of every table with pending rows
         for group in self.param_groups:
+            self._check_group(group)
             for p in group["params"]:
                 self._check(p)
                 pend = _pending(p)
-                if pend is None:
-                    continue
-                pairs.append((p, None, pend[0], pend[1], pend[2], group))
-
-                def job(p=p, pend=pend, group=group):
-                    ids, g, norm = pend
-                    n, d = ids.numel(), p.shape[1]
-                    ws = _lib.workspace(lib.mf_update_ws_bytes(n, d), p.device)
-                    _lib.check(lib.mf_update_sgd(p.data_ptr(), p.shape[0], d, ids.data_ptr(), n, g.data_ptr(), int(norm),
-                                                 group["lr"], group["weight_decay"], ws.data_ptr(), ws.numel(),
-                                                 _lib.stream_ptr()))
-
-                jobs.append(job)
-                done.append(p)
-        one_group = len({id(x[5]) for x in pairs}) == 1
-        if not (one_group and _pair_update(False, [x[:5] for x in pairs], 1, None, pairs[0][5] if pairs else {})):
-            run_table_jobs(jobs)
-        for p in done:
-            p._mf_pending.clear()
+                if pend is not None:
+                    jobs.append((p, self._state_of(p, group), *pend, group, *self._begin(p)))
+        # the usual step -- user rows and item rows, one parameter group, the same global step -- is ONE launch
+        a, b = jobs if len(jobs) == 2 else (None, None)
+        if not (a and a[5] is b[5] and a[6] == b[6] and (a[7] is None) == (b[7] is None)
+                and row_update_pair(self.kind, a[:5], b[:5], *a[5:])):
+            run_table_jobs([functools.partial(row_update, self.kind, *job) for job in jobs])
+        for job in jobs:
+            job[0]._mf_pending.clear()
         return loss
+
+
+class SparseSGD(_SparseRowOptimizer):
+    """row -= lr * (sum of the row's gradients + weight_decay * row), touched rows only."""
+
+    kind = "sgd"
+
+    def __init__(self, params, lr: float = 1e-2, weight_decay: float = 0.0) -> None:
+        super().__init__(params, {"lr": lr, "weight_decay": weight_decay})
 
 
 class RowAdam(_SparseRowOptimizer):
     """Lazy row-wise AdamW: moments of touched rows only, global step for the bias
     correction, decoupled weight decay (torch.optim.AdamW's defaults otherwise)."""
+
+    kind = "adam"
 
     def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01) -> None:
@@ -191,85 +238,25 @@ class RowAdam(_SparseRowOptimizer):
                 if self.state[p] and "step_t" in self.state[p]:
                     self.state[p]["step"] += 1
 
-    def init_state(self) -> None:
-        """Allocate the moment tables now instead of inside the first ``step`` (two table-sized allocations and
-        memsets per table: a multi-millisecond stall in the middle of an otherwise steady first step)."""
-        for group in self.param_groups:
-            for p in group["params"]:
-                state = self.state[p]
-                if not state:
-                    state["step"] = 0
-                    state["exp_avg"] = torch.zeros_like(p)
-                    state["exp_avg_sq"] = torch.zeros_like(p)
+    def _state_of(self, p: torch.Tensor, group: dict) -> tuple:
+        state = self.state[p]
+        if not state:
+            state["step"] = 0
+            state["exp_avg"] = torch.zeros_like(p)
+            state["exp_avg_sq"] = torch.zeros_like(p)
+        return state["exp_avg"], state["exp_avg_sq"]
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        lib = _lib.lib()
-        jobs, done, pairs = [], [], []
-        for group in self.param_groups:
-            for p in group["params"]:
-                self._check(p)
-                pend = _pending(p)
-                if pend is None:
-                    continue
-                state = self.state[p]
-                if not state:
-                    state["step"] = 0
-                    state["exp_avg"] = torch.zeros_like(p)
-                    state["exp_avg_sq"] = torch.zeros_like(p)
-                step_dev = None
-                if self.capturable:
-                    if "step_t" not in state:
-                        state["step_t"] = torch.full((1,), state["step"], dtype=torch.int64, device=p.device)
-                    state["step_t"] += 1                   # a kernel: replayed with the graph
-                    step_dev = state["step_t"].data_ptr()
-                if not (self.capturable and torch.cuda.is_current_stream_capturing()):
-                    state["step"] += 1                     # (a capture runs no kernel: the replays count, via on_replay)
-                pairs.append((p, state, pend[0], pend[1], pend[2], group, step_dev))
-
-                def job(p=p, pend=pend, group=group, state=state, step_dev=step_dev):
-                    ids, g, norm = pend
-                    n, d = ids.numel(), p.shape[1]
-                    ws = _lib.workspace(lib.mf_update_ws_bytes(n, d), p.device)
-                    b1, b2 = group["betas"]
-                    _lib.check(lib.mf_update_adam(p.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
-                                                  p.shape[0], d, ids.data_ptr(), n, g.data_ptr(), int(norm), state["step"],
-                                                  step_dev, group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-
-                jobs.append(job)
-                done.append(p)
-        # the usual step -- user rows and item rows, one parameter group, the same global step -- is ONE launch
-        same = (len(pairs) == 2 and pairs[0][5] is pairs[1][5] and pairs[0][1]["step"] == pairs[1][1]["step"]
-                and (pairs[0][6] is None) == (pairs[1][6] is None))
-        if not (same and _pair_update(True, [x[:5] for x in pairs], pairs[0][1]["step"], pairs[0][6], pairs[0][5])):
-            run_table_jobs(jobs)
-        for p in done:
-            p._mf_pending.clear()
-        return loss
-
-
-def _pair_update_adagrad(jobs, hyper: dict) -> bool:
-    """:func:`_pair_update` for :class:`RowAdagrad` (``mf_update_pair_adagrad``), under the same conditions; ``jobs``: (table,
-    state, ids, grad, normalized)."""
-    if len(jobs) != 2 or os.environ.get("MF_UPDATE_PAIR", "1") != "1":
-        return False
-    (pa, sa, ia, ga, na), (pb, sb, ib, gb, nb) = jobs
-    d = pa.shape[1]
-    if pb.shape[1] != d or not (0 < ia.numel() <= 65536 and 0 < ib.numel() <= 65536):
-        return False
-    lib = _lib.lib()
-    wa = _lib.workspace(lib.mf_update_ws_bytes(ia.numel(), d), pa.device)
-    wb = _lib.workspace(lib.mf_update_ws_bytes(ib.numel(), d), pb.device)
-    _lib.check(lib.mf_update_pair_adagrad(
-        d, pa.data_ptr(), sa["sum"].data_ptr(), pa.shape[0], ia.data_ptr(), ia.numel(), ga.data_ptr(), int(na), wa.data_ptr(), wa.numel(),
-        pb.data_ptr(), sb["sum"].data_ptr(), pb.shape[0], ib.data_ptr(), ib.numel(), gb.data_ptr(), int(nb), wb.data_ptr(), wb.numel(),
-        hyper["lr"], hyper["eps"], hyper["weight_decay"], _lib.stream_ptr()))
-    return True
+    def _begin(self, p: torch.Tensor) -> tuple:
+        state = self.state[p]
+        step_dev = None
+        if self.capturable:
+            if "step_t" not in state:
+                state["step_t"] = torch.full((1,), state["step"], dtype=torch.int64, device=p.device)
+            state["step_t"] += 1                   # a kernel: replayed with the graph
+            step_dev = state["step_t"].data_ptr()
+        if not (self.capturable and torch.cuda.is_current_stream_capturing()):
+            state["step"] += 1                     # (a capture runs no kernel: the replays count, via on_replay)
+        return state["step"], step_dev
 
 
 class RowAdagrad(_SparseRowOptimizer):
@@ -282,6 +269,8 @@ class RowAdagrad(_SparseRowOptimizer):
     The defaults are ``torch.optim.Adagrad``'s; there is no ``lr_decay`` and no step counter, so a step captured in a hipGraph
     (``graph.CapturedStep``) replays as it is.  The mean runs over the table's STORED width: a model width padded to the next of
     32, 64, 128, 256 has zero channels with zero gradient, which dilute it (a stored width of 2 x the model's halves ``sum``)."""
+
+    kind = "adagrad"
 
     def __init__(self, params, lr: float = 1e-2, eps: float = 1e-10, weight_decay: float = 0.0,
                  initial_accumulator_value: float = 0.0) -> None:
@@ -296,59 +285,24 @@ class RowAdagrad(_SparseRowOptimizer):
         super().__init__(params, {"lr": lr, "eps": eps, "weight_decay": weight_decay,
                                   "initial_accumulator_value": initial_accumulator_value})
 
-    def _state_of(self, p: torch.Tensor, group: dict) -> dict:
+    def _check_group(self, group: dict) -> None:
+        if not (group["lr"] >= 0.0 and group["eps"] > 0.0 and group["weight_decay"] >= 0.0):
+            raise ValueError(f"RowAdagrad needs lr >= 0, eps > 0 and weight_decay >= 0: {group['lr'] = }, {group['eps'] = }, "
+                             f"{group['weight_decay'] = }")
+
+    def _state_of(self, p: torch.Tensor, group: dict) -> tuple:
         state = self.state[p]
         if not state:
             state["sum"] = torch.full((p.shape[0],), float(group["initial_accumulator_value"]), dtype=torch.float32, device=p.device)
-        return state
+        return (state["sum"],)
 
-    def init_state(self) -> None:
-        """Allocate every table's ``sum`` (fp32 ``[rows]``) now instead of inside the first ``step``."""
-        for group in self.param_groups:
-            for p in group["params"]:
-                self._state_of(p, group)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        lib = _lib.lib()
-        jobs, done, pairs = [], [], []
-        for group in self.param_groups:
-            if not (group["lr"] >= 0.0 and group["eps"] > 0.0 and group["weight_decay"] >= 0.0):
-                raise ValueError(f"RowAdagrad needs lr >= 0, eps > 0 and weight_decay >= 0: {group['lr'] = }, {group['eps'] = }, "
-                                 f"{group['weight_decay'] = }")
-            for p in group["params"]:
-                self._check(p)
-                pend = _pending(p)
-                if pend is None:
-                    continue
-                state = self._state_of(p, group)
-                pairs.append((p, state, pend[0], pend[1], pend[2], group))
-
-                def job(p=p, pend=pend, group=group, state=state):
-                    ids, g, norm = pend
-                    n, d = ids.numel(), p.shape[1]
-                    ws = _lib.workspace(lib.mf_update_ws_bytes(n, d), p.device)
-                    _lib.check(lib.mf_update_adagrad(p.data_ptr(), state["sum"].data_ptr(), p.shape[0], d, ids.data_ptr(), n,
-                                                     g.data_ptr(), int(norm), group["lr"], group["eps"], group["weight_decay"],
-                                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-
-                jobs.append(job)
-                done.append(p)
-        one_group = len({id(x[5]) for x in pairs}) == 1
-        if not (one_group and _pair_update_adagrad([x[:5] for x in pairs], pairs[0][5] if pairs else {})):
-            run_table_jobs(jobs)
-        for p in done:
-            p._mf_pending.clear()
-        return loss
+KINDS = {"sgd": SparseSGD, "adagrad": RowAdagrad, "adam": RowAdam}
 
 
 class TowerOptimizer(torch.optim.Optimizer):
     """ONE optimiser for towers that own both embedding tables and dense parameters (:class:`models.HistoryTransformerTower`):
-    ``sparse`` (:class:`SparseSGD` / :class:`RowAdam`) steps the tables from the rows their backwards parked, ``dense``
+    ``sparse`` (one of ``KINDS``) steps the tables from the rows their backwards parked, ``dense``
     (``torch.optim.AdamW``, the reference's own optimiser, xfmr_rec/lightning.py:238-239) steps the parameters that received
     ordinary ``.grad`` tensors.  ``step`` / ``zero_grad`` / ``state_dict`` / ``load_state_dict`` drive both; ``param_groups`` are
     the two optimisers' own group dicts, so a scheduler that edits them reaches both."""
@@ -381,13 +335,12 @@ class TowerOptimizer(torch.optim.Optimizer):
 
 
 def tower_optimizer(towers: torch.nn.ModuleDict, kind: str, lr: float) -> torch.optim.Optimizer:
-    """The optimiser of a tower dict: ``kind`` "adam" -> :class:`RowAdam`, "sgd" -> :class:`SparseSGD`, "adagrad" ->
-    :class:`RowAdagrad` over the tables; when a tower owns dense parameters (``encoder_parameters``), a :class:`TowerOptimizer`
-    that also steps those with AdamW."""
-    if kind not in ("adam", "sgd", "adagrad"):
+    """The optimiser of a tower dict: ``KINDS[kind]`` over the tables; when a tower owns dense parameters
+    (``encoder_parameters``), a :class:`TowerOptimizer` that also steps those with AdamW."""
+    if kind not in KINDS:
         msg = f"the towers' optimiser must be 'adam', 'sgd' or 'adagrad': {kind = }"
         raise ValueError(msg)
     dense = [p for t in towers.values() if hasattr(t, "encoder_parameters") for p in t.encoder_parameters()]
     tables = [p for p in towers.parameters() if not any(p is q for q in dense)]
-    sparse = {"sgd": SparseSGD, "adam": RowAdam, "adagrad": RowAdagrad}[kind](tables, lr=lr)
+    sparse = KINDS[kind](tables, lr=lr)
     return TowerOptimizer(sparse, torch.optim.AdamW(dense, lr=lr)) if dense else sparse

@@ -135,8 +135,8 @@ CASES = [("plain", 32, 32, "1"), ("plain", 128, 256, "1"), ("plain", 32, 32, "0"
 def test_three_steps_match_the_specification(mf, monkeypatch, tower, d, B, pair_env):
     monkeypatch.setenv("MF_UPDATE_PAIR", pair_env)
     pair_calls = []
-    inner = mf.optim._pair_update_adagrad
-    monkeypatch.setattr(mf.optim, "_pair_update_adagrad", lambda jobs, hyper: pair_calls.append(inner(jobs, hyper)) or pair_calls[-1])
+    inner = mf.optim.row_update_pair
+    monkeypatch.setattr(mf.optim, "row_update_pair", lambda *a: pair_calls.append(inner(*a)) or pair_calls[-1])
     towers, batch = _world(mf, tower, d, B)
     opt = mf.optim.tower_optimizer(towers, "adagrad", 0.05)
     assert isinstance(opt, mf.optim.TowerOptimizer) == (tower == "transformer")
@@ -145,12 +145,16 @@ def test_three_steps_match_the_specification(mf, monkeypatch, tower, d, B, pair_
     sparse.init_state()
     _no_table_sized_state(sparse)
     two_tables = tower in ("plain", "hashed")
+    launched = []                       # per step: the step was ONE two-table launch
     for k in range(3):
+        del pair_calls[:]
         stepped = _checked_step(mf, opt, _forward_backward(mf, towers, batch(k)), f"{tower}-d{d}-B{B}-pair{pair_env}-step{k}")
         assert stepped == (2 if two_tables else 1)
+        assert pair_calls in ([], [False], [True])      # (a single table: not even asked for)
+        launched.append(pair_calls == [True])
     _no_table_sized_state(sparse)
     # two tables of one width in one group: ONE launch (mf_update_pair_adagrad), unless MF_UPDATE_PAIR=0
-    assert pair_calls == [two_tables and pair_env == "1"] * 3
+    assert launched == [two_tables and pair_env == "1"] * 3
     saved = sparse.state_dict()
     again = mf.optim.RowAdagrad([p for g in sparse.param_groups for p in g["params"]])
     again.load_state_dict(saved)

@@ -35,7 +35,7 @@ def test_the_mirror_has_the_kernels_constants():
     assert _header_int(h, r"#define MF_FUSED_RANK_MAX (\d+)") == uc.FUSED_RANK_MAX
     assert _header_int(h, r"#define MF_FUSED_MAX_BITS (\d+)") == uc.FUSED_MAX_BITS
     assert _header_int(h, r"#define FUSED_NF_ADAM (\d+)") == uc.NF_ADAM
-    assert _header_int(h, r"int NFLIGHT = \(ADAM \? FUSED_NF_ADAM : (\d+)\)") == uc.NF_SGD
+    assert _header_int(h, r"OPT == RowOpt::ADAM \? FUSED_NF_ADAM : (\d+);") == uc.NF_SGD
     # The rules the mirror restates, as literal source lines: a tripwire.  If one of these fails after a mere reformatting,
     # update the string.  If the rule itself changed, re-derive in tests/_update_cases.py: `fused_bucket_bits` (buckets per n),
     # `regime` (rank / bitonic with its padded size / overflow per bucket size), the n at which the multi-launch path starts,

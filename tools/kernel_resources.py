@@ -8,9 +8,15 @@ code object whose ``NT_AMDGPU_METADATA`` note lists, per kernel, ``.vgpr_count``
 of the product paths spills.
 
     python tools/kernel_resources.py [path/to/libmf_hip.so] [--spills]
+    python tools/kernel_resources.py [path/to/libmf_hip.so] --text-digest [--only=update_fused,update_rows]   # JSON
+
+``--text-digest``: beside the figures, one sha256 of each kernel's disassembled instruction text -- to show that a refactor
+left the generated code of a kernel as it was (compare two builds' outputs).
 """
 from __future__ import annotations
 
+import hashlib
+import json
 import pathlib
 import re
 import struct
@@ -79,8 +85,41 @@ def kernel_resources(lib: pathlib.Path = DEFAULT_LIB) -> dict[str, dict[str, int
     return dict(zip(demangle(names), table.values()))
 
 
+def text_digests(lib: pathlib.Path = DEFAULT_LIB) -> dict[str, str]:
+    """{demangled function name: sha256 of its disassembled instruction text} for every function of the library's code
+    objects.  The text is what ``llvm-objdump -d`` prints without addresses and encodings, comments dropped and the
+    function's own symbol replaced by a fixed word: two builds whose kernels differ in name only (a template argument that
+    changed its type) give the same digests.  Whole texts are hashed; nothing is searched for."""
+    table: dict[str, str] = {}
+    for co in code_objects(pathlib.Path(lib)):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            dis = subprocess.run([str(LLVM / "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr", f.name],
+                                 capture_output=True, text=True, check=True).stdout
+        name, lines = None, []
+        for line in dis.splitlines() + ["<end>:"]:
+            label = re.fullmatch(r"(?:[0-9a-f]+ )?<(\S+)>:", line.strip())
+            if label:
+                if name is not None:
+                    text = "\n".join(x for x in lines if x).replace(name, "SELF")
+                    table[name] = hashlib.sha256(text.encode()).hexdigest()
+                name, lines = label.group(1), []
+            elif name is not None:
+                lines.append(line.split("//")[0].strip())
+    names = list(table)
+    return dict(zip(demangle(names), table.values()))
+
+
 def main() -> None:
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if "--text-digest" in sys.argv:     # JSON: {kernel: {"text_sha256": ..., the resource figures}}, kernels whose name has one of --only=a,b,..
+        lib = pathlib.Path(args[0]) if args else DEFAULT_LIB
+        only = next((a.split("=", 1)[1].split(",") for a in sys.argv if a.startswith("--only=")), [""])
+        res, dig = kernel_resources(lib), text_digests(lib)
+        print(json.dumps({k: {"text_sha256": dig.get(k), **{f: v for f, v in r.items() if f != "max_flat_workgroup_size"}}
+                          for k, r in sorted(res.items()) if any(o in k for o in only)}, indent=1))
+        return
     res = kernel_resources(pathlib.Path(args[0]) if args else DEFAULT_LIB)
     only_spills = "--spills" in sys.argv
     print(f"{'vgpr':>5} {'agpr':>5} {'sgpr':>5} {'vspill':>6} {'sspill':>6} {'scratch':>7} {'lds':>7}  kernel")

@@ -51,32 +51,25 @@ class Table:
         self.m, self.v = torch.zeros_like(self.w), torch.zeros_like(self.w)
         self.s = torch.zeros(rows, device=dev)
 
-
-def single_call(lib, kind, t, ids, grad, ws):
-    n = ids.numel()
-    if kind == "adam":
-        return lambda step: mf._lib.check(lib.mf_update_adam(t.w.data_ptr(), t.m.data_ptr(), t.v.data_ptr(), t.rows, t.d, ids.data_ptr(), n,
-                                                              grad.data_ptr(), 0, step, None, 1e-4, 0.9, 0.999, 1e-8, 0.0, ws.data_ptr(),
-                                                              ws.numel(), None))
-    if kind == "sgd":
-        return lambda step: mf._lib.check(lib.mf_update_sgd(t.w.data_ptr(), t.rows, t.d, ids.data_ptr(), n, grad.data_ptr(), 0, 1e-4, 0.0,
-                                                             ws.data_ptr(), ws.numel(), None))
-    return lambda step: mf._lib.check(lib.mf_update_adagrad(t.w.data_ptr(), t.s.data_ptr(), t.rows, t.d, ids.data_ptr(), n, grad.data_ptr(), 0,
-                                                             1e-4, 1e-10, 0.0, ws.data_ptr(), ws.numel(), None))
+    def state(self, kind):
+        return {"sgd": (), "adagrad": (self.s,), "adam": (self.m, self.v)}[kind]
 
 
-def pair_call(lib, kind, ta, ia, ga, wa, tb, ib, gb, wb):
-    if kind == "adagrad":
-        return lambda step: mf._lib.check(lib.mf_update_pair_adagrad(
-            ta.d, ta.w.data_ptr(), ta.s.data_ptr(), ta.rows, ia.data_ptr(), ia.numel(), ga.data_ptr(), 0, wa.data_ptr(), wa.numel(),
-            tb.w.data_ptr(), tb.s.data_ptr(), tb.rows, ib.data_ptr(), ib.numel(), gb.data_ptr(), 0, wb.data_ptr(), wb.numel(), 1e-4, 1e-10, 0.0,
-            None))
-    adam = kind == "adam"
-    p = (lambda x: x.data_ptr()) if adam else (lambda x: None)
-    return lambda step: mf._lib.check(lib.mf_update_pair(
-        int(adam), ta.d, ta.w.data_ptr(), p(ta.m), p(ta.v), ta.rows, ia.data_ptr(), ia.numel(), ga.data_ptr(), 0, wa.data_ptr(), wa.numel(),
-        tb.w.data_ptr(), p(tb.m), p(tb.v), tb.rows, ib.data_ptr(), ib.numel(), gb.data_ptr(), 0, wb.data_ptr(), wb.numel(), step, None, 1e-4,
-        0.9, 0.999, 1e-8, 0.0, None))
+# lr 1e-4, no weight decay, otherwise the optimisers' defaults.  The calls go through optim.row_update / row_update_pair, like a
+# step of the optimisers: the workspace comes from torch's caching allocator at every call
+HYPER = {kind: mf.distributed.optimizer_hyper(kind, 1e-4, weight_decay=0.0) for kind in KINDS}
+
+
+def single_call(lib, kind, t, ids, grad):
+    return lambda step: mf.optim.row_update(kind, t.w, t.state(kind), ids, grad, False, HYPER[kind], step, lib=lib)
+
+
+def pair_call(lib, kind, ta, ia, ga, tb, ib, gb):
+    def call(step):
+        if not mf.optim.row_update_pair(kind, (ta.w, ta.state(kind), ia, ga, False), (tb.w, tb.state(kind), ib, gb, False), HYPER[kind],
+                                        step, lib=lib):
+            raise SystemExit("the two-table launch was refused (MF_UPDATE_PAIR=0?)")
+    return call
 
 
 def region(calls_of, n_calls, step0):
@@ -151,8 +144,8 @@ def main() -> None:
         for name in ("item 16384 (zipf + uniform)", "item 16384 uniform"):
             ids = lists[name][1][0]
             n = ids.numel()
-            grad, ws = torch.randn(n, d, device=dev), mf._lib.workspace(libs["this"].mf_update_ws_bytes(n, d), dev)
-            call = single_call(libs["this"], "adam", t, ids, grad, ws)
+            grad = torch.randn(n, d, device=dev)
+            call = single_call(libs["this"], "adam", t, ids, grad)
             for i in range(10):
                 call(i + 1)
             res = out["lists"][name] = stamps(libs["this"], call, 256, max(args.regions, 5))
@@ -164,29 +157,27 @@ def main() -> None:
                 json.dump(out, f, indent=1)
         return
     tables = {rows: Table(rows, d, dev) for rows in {r for r, _ in lists.values()}}
-    ws_of = lambda n: mf._lib.workspace(libs["this"].mf_update_ws_bytes(n, d), dev)      # noqa: E731
     # what to time: name -> {(lib, kind): [one closure per id list]}
     todo = {}
     for name, (rows, ids) in lists.items():
         n = ids[0].numel()
-        grad, ws = torch.randn(n, d, device=dev), ws_of(n)
+        grad = torch.randn(n, d, device=dev)
         uniq = sum(int(torch.unique(i).numel()) for i in ids) / len(ids)
         top = max(int(torch.bincount(i).max()) for i in ids)
         entry = todo[name] = {"n": n, "unique": uniq, "largest_run": top, "calls": {}}
         for lname, lib in libs.items():
             for kind in kinds:
                 if hasattr(lib, f"mf_update_{kind}"):
-                    entry["calls"][(lname, kind)] = [single_call(lib, kind, tables[rows], i, grad, ws) for i in ids]
+                    entry["calls"][(lname, kind)] = [single_call(lib, kind, tables[rows], i, grad) for i in ids]
     if args.pair:
         users, items = lists["user 8192 (log-normal)"][1], lists["item 16384 (zipf + uniform)"][1]
         ta, tb = tables[bench.NUM_USERS], tables[bench.NUM_ITEMS]
         ga, gb = torch.randn(8192, d, device=dev), torch.randn(16384, d, device=dev)
-        wa, wb = ws_of(8192), ws_of(16384)
         entry = todo["pair: user 8192 + item 16384"] = {"n": 8192 + 16384, "calls": {}}
         for lname, lib in libs.items():
             for kind in kinds:
                 if hasattr(lib, "mf_update_pair_adagrad" if kind == "adagrad" else "mf_update_pair"):
-                    entry["calls"][(lname, kind)] = [pair_call(lib, kind, ta, ia, ga, wa, tb, ib, gb, wb) for ia, ib in zip(users, items)]
+                    entry["calls"][(lname, kind)] = [pair_call(lib, kind, ta, ia, ga, tb, ib, gb) for ia, ib in zip(users, items)]
     out = {"d": d, "regions": args.regions, "calls_per_region": args.calls, "device": torch.cuda.get_device_name(0), "lists": {}}
     for name, entry in todo.items():
         for calls_of in entry["calls"].values():                       # warm-up: every (library, kind) of this list

@@ -4,14 +4,16 @@
 // ANN + prefilter) by an exact scan: score tiles from the fp32 MFMA engine, streaming
 // per-query selection (mf_select.h), exclusion lists scattered once into a
 // bitmask (one coalesced word per query and tile), then an exact ordered merge per query.
-// The same merge kernel joins the all-gathered partial top-k of a row-sharded
-// catalog (mf_topk_merge).
+// One merge kernel joins the partial top-k of a row-sharded catalog, from (scores, rows) or from
+// the packed exchange form (mf_topk_merge, mf_topk_merge_packed); one metrics kernel serves every k.
+// Argument checks and the result store are shared with the other engines: mf_topk_io.h.
 #include <cmath>
 
 #include "mf_common.h"
 #include <vector>
 
 #include "mf_select.h"
+#include "mf_topk_io.h"
 
 // Exclusion prefilter as a bitmask: exclW[tile][query] holds the 32 "excluded" bits of
 // that query for that item tile (the lists are sparse -- ~10^2 of 10^4..10^8 rows --
@@ -113,39 +115,43 @@ __global__ __launch_bounds__(64) void topk_merge_cand_kernel(const unsigned long
     const int m = mf_row_topk<8>(cand + r * (int64_t)rowcap, cand_cnt[r], k, win, sorted);
     const int t = mf_lane();
     if (t < k) {
-        if (t < m) {
-            out_scores[r * k + t] = mf_key_retrieval_score(sorted[t]);
-            out_idx[r * k + t] = idx_base + (int64_t)mf_key_retrieval_col(sorted[t]);
-        } else {
-            out_scores[r * k + t] = -INFINITY;
-            out_idx[r * k + t] = -1;
-        }
+        if (t < m) mf_store_topk_entry(out_scores, out_idx, r, k, t, sorted[t], idx_base);
+        else mf_store_topk_none(out_scores, out_idx, r, k, t);
     }
 }
 
-// merge of G already-ordered partial results with GLOBAL indices (< 2^32)
-__global__ __launch_bounds__(64) void topk_merge_parts_kernel(const float* __restrict__ ps, const int64_t* __restrict__ pi,
-                                                              int G, int64_t Q, int k, float* __restrict__ out_scores,
-                                                              int64_t* __restrict__ out_idx) {
+// merge of G already-ordered partial results with GLOBAL indices (< 2^32); load(entry) gives the entry's key, 0 for none
+struct MergeParts {                     // (scores, rows), -1 for none
+    const float* ps;
+    const int64_t* pi;
+    __device__ unsigned long long operator()(int64_t at) const { return pi[at] >= 0 ? mf_key_retrieval(ps[at], (unsigned)pi[at]) : 0ull; }
+};
+struct MergePacked {                    // what topk_pack_kernel below writes
+    const int64_t* packed;
+    __device__ unsigned long long operator()(int64_t at) const {
+        const int64_t v = packed[at];
+        return v != -1ll ? mf_key_retrieval(__builtin_bit_cast(float, (unsigned)((unsigned long long)v >> 32)), (unsigned)v) : 0ull;
+    }
+};
+template <class Load>
+__global__ __launch_bounds__(64) void topk_merge_kernel(Load load, int G, int64_t Q, int k, float* __restrict__ out_scores,
+                                                        int64_t* __restrict__ out_idx) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_keys[];
     const int64_t r = blockIdx.x;
     const int lane = mf_lane();
     const int total = G * k;
     for (int t = lane; t < total; t += 64) {
         const int g = t / k, e = t % k;
-        const int64_t id = pi[((int64_t)g * Q + r) * k + e];
-        s_keys[t] = id >= 0 ? mf_key_retrieval(ps[((int64_t)g * Q + r) * k + e], (unsigned)id) : 0ull;
+        s_keys[t] = load(((int64_t)g * Q + r) * k + e);
     }
     __syncthreads();
-    mf_wave_select(s_keys, total, k, [&](int t, unsigned long long key) {
-        if (key != 0ull) {
-            out_scores[r * k + t] = mf_key_retrieval_score(key);
-            out_idx[r * k + t] = (int64_t)mf_key_retrieval_col(key);
-        } else {
-            out_scores[r * k + t] = -INFINITY;
-            out_idx[r * k + t] = -1;
-        }
-    });
+    mf_wave_select(s_keys, total, k, [&](int t, unsigned long long key) { mf_store_topk(out_scores, out_idx, r, k, t, key, 0); });
+}
+template <class Load>
+static int topk_merge_launch(const char* who, Load load, int G, int64_t Q, int k, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
+    if ((size_t)G * k * 8 > 64 * 1024) return mf_set_error(MF_ENOTSUP, "%s: G * k too large", who);       // the keys of a query sit in LDS
+    topk_merge_kernel<<<dim3((unsigned)Q), 64, (size_t)G * k * 8, static_cast<hipStream_t>(stream)>>>(load, G, Q, k, out_scores, out_idx);
+    return mf_check_launch(who);
 }
 
 // Sharded retrieval, one exchange instead of two: a rank's partial result (scores, LOCAL rows) becomes one int64 per entry
@@ -160,29 +166,6 @@ __global__ __launch_bounds__(256) void topk_pack_kernel(const float* __restrict_
                     : -1ll;
 }
 
-__global__ __launch_bounds__(64) void topk_merge_packed_kernel(const int64_t* __restrict__ packed, int G, int64_t Q, int k,
-                                                               float* __restrict__ out_scores, int64_t* __restrict__ out_idx) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long s_keys[];
-    const int64_t r = blockIdx.x;
-    const int lane = mf_lane();
-    const int total = G * k;
-    for (int t = lane; t < total; t += 64) {
-        const int g = t / k, e = t % k;
-        const int64_t v = packed[((int64_t)g * Q + r) * k + e];
-        s_keys[t] = v != -1ll ? mf_key_retrieval(__builtin_bit_cast(float, (unsigned)((unsigned long long)v >> 32)), (unsigned)v) : 0ull;
-    }
-    __syncthreads();
-    mf_wave_select(s_keys, total, k, [&](int t, unsigned long long key) {
-        if (key != 0ull) {
-            out_scores[r * k + t] = mf_key_retrieval_score(key);
-            out_idx[r * k + t] = (int64_t)mf_key_retrieval_col(key);
-        } else {
-            out_scores[r * k + t] = -INFINITY;
-            out_idx[r * k + t] = -1;
-        }
-    });
-}
-
 extern "C" int mf_topk_pack(const float* scores, const int64_t* rows, int64_t n, int64_t stride, int64_t offset, int64_t* out_packed,
                             mf_stream_t stream) {
     if (!scores || !rows || !out_packed || n < 0 || stride <= 0 || offset < 0) return mf_set_error(MF_EINVAL, "mf_topk_pack: bad argument");
@@ -193,9 +176,7 @@ extern "C" int mf_topk_pack(const float* scores, const int64_t* rows, int64_t n,
 
 extern "C" int mf_topk_merge_packed(const int64_t* packed, int G, int64_t Q, int k, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
     if (!packed || !out_scores || !out_idx || G <= 0 || Q <= 0 || k <= 0) return mf_set_error(MF_EINVAL, "mf_topk_merge_packed: bad argument");
-    if ((size_t)G * k * 8 > 64 * 1024) return mf_set_error(MF_ENOTSUP, "mf_topk_merge_packed: G * k too large");
-    topk_merge_packed_kernel<<<dim3((unsigned)Q), 64, (size_t)G * k * 8, static_cast<hipStream_t>(stream)>>>(packed, G, Q, k, out_scores, out_idx);
-    return mf_check_launch("mf_topk_merge_packed");
+    return topk_merge_launch("mf_topk_merge_packed", MergePacked{packed}, G, Q, k, out_scores, out_idx, stream);
 }
 
 #ifdef MF_PROBE
@@ -222,13 +203,8 @@ extern "C" void mf_probe_sel_counters(unsigned long long* out16, int reset) {
 extern "C" int mf_topk(const float* q, int64_t Q, const float* items, int64_t N, int d, int k,
                        const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws,
                        size_t ws_bytes, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
-    if (!q || !items || !out_scores || !out_idx || !ws || Q <= 0 || N <= 0)
-        return mf_set_error(MF_EINVAL, "mf_topk: bad argument");
-    if (k <= 0 || k > 64) return mf_set_error(MF_ENOTSUP, "mf_topk: k = %d outside 1..64", k);
-    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_topk: embedding width %d not in {32,64,128,256}", d);
-    if (N >= (1ll << 31) || idx_base < 0 || idx_base + N > (1ll << 32))
-        return mf_set_error(MF_ENOTSUP, "mf_topk: item indices must fit 32 bits");
-    if ((excl_off == nullptr) != (excl_idx == nullptr)) return mf_set_error(MF_EINVAL, "mf_topk: excl_off/excl_idx mismatch");
+    if (const int rc = mf_topk_check_args("mf_topk", {64, 32, 31, 0}, q, Q, items, N, d, k, excl_off, excl_idx, idx_base, ws, out_scores, out_idx))
+        return rc;
     if (ws_bytes < mf_topk_ws_bytes(Q, N, d, k)) return mf_set_error(MF_ENOSPC, "mf_topk: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     TopkWs w = topk_ws(ws, Q, N, d, k);
@@ -249,14 +225,12 @@ extern "C" int mf_topk_merge(const float* part_scores, const int64_t* part_idx, 
                              float* out_scores, int64_t* out_idx, mf_stream_t stream) {
     if (!part_scores || !part_idx || !out_scores || !out_idx || G <= 0 || Q <= 0 || k <= 0)
         return mf_set_error(MF_EINVAL, "mf_topk_merge: bad argument");
-    if ((size_t)G * k * 8 > 64 * 1024) return mf_set_error(MF_ENOTSUP, "mf_topk_merge: G * k too large");
-    topk_merge_parts_kernel<<<dim3((unsigned)Q), 64, (size_t)G * k * 8, static_cast<hipStream_t>(stream)>>>(
-        part_scores, part_idx, G, Q, k, out_scores, out_idx);
-    return mf_check_launch("mf_topk_merge");
+    return topk_merge_launch("mf_topk_merge", MergeParts{part_scores, part_idx}, G, Q, k, out_scores, out_idx, stream);
 }
 
 // ------------------------------------------------------------ retrieval metrics ----
-// one wave per query; lane t holds the item retrieved at rank t
+// one wave per query; lane t holds the items retrieved at ranks t + 64 j, j < R (register j)
+template <int R>
 __global__ __launch_bounds__(64) void retrieval_metrics_kernel(const int64_t* __restrict__ topk_idx, int k,
                                                                const int64_t* __restrict__ tgt_off,
                                                                const int64_t* __restrict__ tgt_idx,
@@ -264,16 +238,34 @@ __global__ __launch_bounds__(64) void retrieval_metrics_kernel(const int64_t* __
     const int64_t q = blockIdx.x;
     const int lane = mf_lane();
     const int64_t e0 = tgt_off[q], e1 = tgt_off[q + 1];
-    const int64_t item = lane < k ? topk_idx[q * k + lane] : -1;
-    float rel = 0.f;                                   // rating of the item at this rank (0: not a target)
+    int64_t item[R];
+    float rel[R];                                      // rating of the item at this rank (0: not a target)
     // a target the search missed ranks right below the retrieved items (list order): it only enters the
     // top k when fewer than k items were retrieved, exactly as in the reference's union of both sets
-    int slot = __popcll(__ballot(item >= 0));
+    int slot = 0;                                      // number of retrieved items: where the first missed target ranks
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int t = lane + 64 * j;
+        item[j] = t < k ? topk_idx[q * k + t] : -1;
+        rel[j] = 0.f;
+        slot += __popcll(__ballot(item[j] >= 0));
+    }
     for (int64_t e = e0; e < e1; ++e) {
-        const bool mine = item >= 0 && tgt_idx[e] == item;
-        if (mine) rel = tgt_rel[e];
+        const int64_t id = tgt_idx[e];
+        const float tr = tgt_rel[e];
+        bool mine = false;
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const bool m = item[j] >= 0 && item[j] == id;
+            if (m) rel[j] = tr;
+            mine |= m;
+        }
         if (!__any(mine)) {
-            if (lane == slot && lane < k) rel = tgt_rel[e];
+            if (slot < k) {
+#pragma unroll
+                for (int j = 0; j < R; ++j)
+                    if (slot == lane + 64 * j) rel[j] = tr;
+            }
             ++slot;
         }
     }
@@ -290,15 +282,21 @@ __global__ __launch_bounds__(64) void retrieval_metrics_kernel(const int64_t* __
         }
         if (rank < k) idcg += r / log2f((float)rank + 2.f);
     }
-    float dcg = rel / log2f((float)lane + 2.f);
+    float dcg = 0.f, ap = 0.f;                         // ap: precision at every relevant rank
+    int hits = 0, first = -1;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int t = lane + 64 * j;
+        dcg += rel[j] / log2f((float)t + 2.f);
+        const unsigned long long hit = __ballot(rel[j] > 0.f);
+        if (rel[j] > 0.f) ap += (float)(hits + __popcll(hit & ((2ull << lane) - 1ull))) / (float)(t + 1);
+        if (first < 0 && hit != 0ull) first = 64 * j + __builtin_ctzll(hit);
+        hits += __popcll(hit);
+    }
     dcg = mf_wave_sum(dcg);
     idcg = mf_wave_sum(idcg);
-    npos = mf_wave_sum_int(npos);
-    const unsigned long long hit = __ballot(rel > 0.f);
-    const int hits = __popcll(hit);
-    float ap = 0.f;                                    // precision at every relevant rank
-    if (rel > 0.f) ap = (float)__popcll(hit & ((2ull << lane) - 1ull)) / (float)(lane + 1);
     ap = mf_wave_sum(ap);
+    npos = mf_wave_sum_int(npos);
     if (lane == 0) {
         float* o = out + q * 6;
         const bool any = npos > 0;
@@ -307,21 +305,15 @@ __global__ __launch_bounds__(64) void retrieval_metrics_kernel(const int64_t* __
         o[2] = any ? (float)hits / (float)k : 0.f;
         o[3] = hits > 0 ? ap / (float)hits : 0.f;
         o[4] = hits > 0 ? 1.f : 0.f;
-        o[5] = hits > 0 ? 1.f / (float)(__builtin_ctzll(hit) + 1) : 0.f;
+        o[5] = hits > 0 ? 1.f / (float)(first + 1) : 0.f;
     }
 }
-
-void mf_retrieval_metrics_deep_launch(const int64_t* topk_idx, int64_t Q, int k, const int64_t* tgt_off, const int64_t* tgt_idx,
-                                      const float* tgt_rel, float* out, hipStream_t s);       // mf_topk_deep.hip
 
 extern "C" int mf_retrieval_metrics(const int64_t* topk_idx, int64_t Q, int k, const int64_t* tgt_off,
                                     const int64_t* tgt_idx, const float* tgt_rel, float* out, mf_stream_t stream) {
     if (!topk_idx || !tgt_off || !tgt_idx || !tgt_rel || !out || Q <= 0) return mf_set_error(MF_EINVAL, "mf_retrieval_metrics: bad argument");
     if (k <= 0 || k > MF_TOPK_DEEP_MAX_K) return mf_set_error(MF_ENOTSUP, "mf_retrieval_metrics: k = %d outside 1..%d", k, MF_TOPK_DEEP_MAX_K);
-    if (k > 64) {                 // lane t walks ranks t, t + 64, ...: same definitions, same layout (mf_topk_deep.hip)
-        mf_retrieval_metrics_deep_launch(topk_idx, Q, k, tgt_off, tgt_idx, tgt_rel, out, static_cast<hipStream_t>(stream));
-        return mf_check_launch("mf_retrieval_metrics");
-    }
-    retrieval_metrics_kernel<<<dim3((unsigned)Q), 64, 0, static_cast<hipStream_t>(stream)>>>(topk_idx, k, tgt_off, tgt_idx, tgt_rel, out);
+    auto fn = k <= 64 ? retrieval_metrics_kernel<1> : retrieval_metrics_kernel<MF_TOPK_DEEP_MAX_K / 64>;
+    fn<<<dim3((unsigned)Q), 64, 0, static_cast<hipStream_t>(stream)>>>(topk_idx, k, tgt_off, tgt_idx, tgt_rel, out);
     return mf_check_launch("mf_retrieval_metrics");
 }

@@ -38,6 +38,7 @@
 
 #include "mf_common.h"
 #include "mf_select.h"
+#include "mf_topk_io.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -934,13 +935,8 @@ __global__ __launch_bounds__(64 * BF3_FQ) void bf3_final_kernel(Bf3Final p) {
     }
     BF3_STAMP(5);
     if (lane < p.k) {
-        if (lane < m) {
-            p.out_scores[r * p.k + lane] = mf_key_retrieval_score(sorted[lane]);
-            p.out_idx[r * p.k + lane] = p.idx_base + (int64_t)mf_key_retrieval_col(sorted[lane]);
-        } else {
-            p.out_scores[r * p.k + lane] = -INFINITY;
-            p.out_idx[r * p.k + lane] = -1;
-        }
+        if (lane < m) mf_store_topk_entry(p.out_scores, p.out_idx, r, p.k, lane, sorted[lane], p.idx_base);
+        else mf_store_topk_none(p.out_scores, p.out_idx, r, p.k, lane);
     }
 }
 
@@ -1080,13 +1076,10 @@ static void bf3_launch_final(unsigned grid, const Bf3Final& fp, hipStream_t s) {
 extern "C" int mf_topk_bf3(const float* q, int64_t Q, const float* items, const void* index, int64_t N, int d, int k,
                            const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
                            float* out_scores, int64_t* out_idx, mf_stream_t stream) {
-    if (!q || !items || !index || !out_scores || !out_idx || !ws || Q <= 0 || N <= 0)
-        return mf_set_error(MF_EINVAL, "mf_topk_bf3: bad argument");
-    if (k <= 0 || k > 64) return mf_set_error(MF_ENOTSUP, "mf_topk_bf3: k = %d outside 1..64", k);
-    if (d != 64 && d != 128 && d != 256) return mf_set_error(MF_ENOTSUP, "mf_topk_bf3: embedding width %d not in {64,128,256}", d);
-    if (N >= (1ll << 28) || idx_base < 0 || idx_base + N > (1ll << 32))
-        return mf_set_error(MF_ENOTSUP, "mf_topk_bf3: item indices must fit 32 bits (and a shard 2^28 rows)");
-    if ((excl_off == nullptr) != (excl_idx == nullptr)) return mf_set_error(MF_EINVAL, "mf_topk_bf3: excl_off/excl_idx mismatch");
+    if (!index) return mf_set_error(MF_EINVAL, "mf_topk_bf3: bad argument");
+    if (const int rc = mf_topk_check_args("mf_topk_bf3", {64, 64, 28, 0}, q, Q, items, N, d, k, excl_off, excl_idx, idx_base, ws,
+                                          out_scores, out_idx))
+        return rc;
     // geometry limits first (host arithmetic only: nothing below this point may run for an unsupported shape)
     const Bf3Plan plan = bf3_plan(Q, N, d);
     const uint64_t span_tiles = (uint64_t)plan.bpc * BF3_BLOCK, span_seed = (uint64_t)plan.bpc_seed * plan.bs * BF3_BLOCK;

@@ -24,6 +24,7 @@
 #include "mf_common.h"
 #include "mf_stream.h"
 #include "mf_lists.h"
+#include "mf_topk_io.h"
 
 // a query block's slab is at most this large (the host's preferred block).  Measured at Q = 1024 x N = 62,423 (tools/
 // topk_deep_probe.py, profiles/topk_deep_probe.json): slabs of 16 / 64 / 256 MiB -- 16 / 4 / 1 query blocks -- take the call
@@ -202,6 +203,7 @@ __global__ __launch_bounds__(DEEP_THREADS) void topk_deep_select_kernel(const un
             __syncthreads();
         }
     }
+    // (written out, not mf_store_topk of mf_topk_io.h: through the helper this kernel's registers were allocated differently)
     for (int t = tid; t < k; t += DEEP_THREADS) {
         const unsigned long long key = keys[t];
         if (key != 0ull) {
@@ -261,12 +263,9 @@ extern "C" int mf_topk_deep_plan(int64_t Q, int64_t N, int d, int k, size_t ws_b
 extern "C" int mf_topk_deep(const float* q, int64_t Q, const float* items, int64_t N, int d, int k,
                             const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
                             float* out_scores, int64_t* out_idx, mf_stream_t stream) {
-    if (!q || !items || !out_scores || !out_idx || !ws || Q <= 0 || N <= 0) return mf_set_error(MF_EINVAL, "mf_topk_deep: bad argument");
-    if (k <= 0 || k > MF_TOPK_DEEP_MAX_K) return mf_set_error(MF_ENOTSUP, "mf_topk_deep: k = %d outside 1..%d", k, MF_TOPK_DEEP_MAX_K);
-    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_topk_deep: embedding width %d not in {32,64,128,256}", d);
-    if (N >= (1ll << 31) || idx_base < 0 || idx_base + N > (1ll << 32))
-        return mf_set_error(MF_ENOTSUP, "mf_topk_deep: item indices must fit 32 bits");
-    if ((excl_off == nullptr) != (excl_idx == nullptr)) return mf_set_error(MF_EINVAL, "mf_topk_deep: excl_off/excl_idx mismatch");
+    if (const int rc = mf_topk_check_args("mf_topk_deep", {MF_TOPK_DEEP_MAX_K, 32, 31, 0}, q, Q, items, N, d, k, excl_off, excl_idx, idx_base, ws,
+                                          out_scores, out_idx))
+        return rc;
     const DeepPlan p = deep_plan(Q, N, d, k);
     if (!p.ok) return mf_set_error(MF_ENOTSUP, "mf_topk_deep: a 32-query score slab of %lld columns exceeds the descriptor limit", (long long)N);
     const int64_t qb = deep_qb(p, ws_bytes);
@@ -300,88 +299,4 @@ extern "C" int mf_topk_deep(const float* q, int64_t Q, const float* items, int64
             slab, p.Np, k, idx_base, out_scores + q0 * k, out_idx + q0 * k)));
     }
     return mf_check_launch("mf_topk_deep");
-}
-
-// ------------------------------------------------------------------------------ retrieval metrics, 64 < k <= 1024 ----
-// one wave per query; lane t holds the items retrieved at ranks t, t + 64, ... (register j: rank t + 64 j).  Definitions
-// and output layout: retrieval_metrics_kernel (mf_topk.hip)
-__global__ __launch_bounds__(64) void retrieval_metrics_deep_kernel(const int64_t* __restrict__ topk_idx, int k,
-                                                                    const int64_t* __restrict__ tgt_off, const int64_t* __restrict__ tgt_idx,
-                                                                    const float* __restrict__ tgt_rel, float* __restrict__ out) {
-    constexpr int R = MF_TOPK_DEEP_MAX_K / 64;
-    const int64_t q = blockIdx.x;
-    const int lane = mf_lane();
-    const int64_t e0 = tgt_off[q], e1 = tgt_off[q + 1];
-    int64_t item[R];
-    float rel[R];
-    int slot = 0;                                      // number of retrieved items: where the first missed target ranks
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        const int t = lane + 64 * j;
-        item[j] = t < k ? topk_idx[q * k + t] : -1;
-        rel[j] = 0.f;
-        slot += __popcll(__ballot(item[j] >= 0));
-    }
-    for (int64_t e = e0; e < e1; ++e) {
-        const int64_t id = tgt_idx[e];
-        const float tr = tgt_rel[e];
-        bool mine = false;
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            const bool m = item[j] >= 0 && item[j] == id;
-            if (m) rel[j] = tr;
-            mine |= m;
-        }
-        if (!__any(mine)) {
-            if (slot < k) {
-#pragma unroll
-                for (int j = 0; j < R; ++j)
-                    if (slot == lane + 64 * j) rel[j] = tr;
-            }
-            ++slot;
-        }
-    }
-    float idcg = 0.f;
-    int npos = 0;
-    for (int64_t e = e0 + lane; e < e1; e += 64) {
-        const float r = tgt_rel[e];
-        npos += r > 0.f ? 1 : 0;
-        int rank = 0;
-        for (int64_t f = e0; f < e1; ++f) {
-            const float o = tgt_rel[f];
-            rank += (o > r || (o == r && f < e)) ? 1 : 0;
-        }
-        if (rank < k) idcg += r / log2f((float)rank + 2.f);
-    }
-    float dcg = 0.f, ap = 0.f;
-    int hits = 0, first = -1;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        const int t = lane + 64 * j;
-        dcg += rel[j] / log2f((float)t + 2.f);
-        const unsigned long long hit = __ballot(rel[j] > 0.f);
-        if (rel[j] > 0.f) ap += (float)(hits + __popcll(hit & ((2ull << lane) - 1ull))) / (float)(t + 1);
-        if (first < 0 && hit != 0ull) first = 64 * j + __builtin_ctzll(hit);
-        hits += __popcll(hit);
-    }
-    dcg = mf_wave_sum(dcg);
-    idcg = mf_wave_sum(idcg);
-    ap = mf_wave_sum(ap);
-    npos = mf_wave_sum_int(npos);
-    if (lane == 0) {
-        float* o = out + q * 6;
-        const bool any = npos > 0;
-        o[0] = (any && idcg > 0.f) ? dcg / idcg : 0.f;
-        o[1] = any ? (float)hits / (float)npos : 0.f;
-        o[2] = any ? (float)hits / (float)k : 0.f;
-        o[3] = hits > 0 ? ap / (float)hits : 0.f;
-        o[4] = hits > 0 ? 1.f : 0.f;
-        o[5] = hits > 0 ? 1.f / (float)(first + 1) : 0.f;
-    }
-}
-
-// (called by mf_retrieval_metrics, mf_topk.hip, for 64 < k <= MF_TOPK_DEEP_MAX_K)
-void mf_retrieval_metrics_deep_launch(const int64_t* topk_idx, int64_t Q, int k, const int64_t* tgt_off, const int64_t* tgt_idx,
-                                      const float* tgt_rel, float* out, hipStream_t s) {
-    retrieval_metrics_deep_kernel<<<dim3((unsigned)Q), 64, 0, s>>>(topk_idx, k, tgt_off, tgt_idx, tgt_rel, out);
 }

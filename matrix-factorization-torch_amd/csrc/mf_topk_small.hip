@@ -22,6 +22,7 @@
 // Results are bit-identical to mf_topk (same chain, same 64-bit keys): tests/test_gpu_parity.py.
 #include "mf_common.h"
 #include "mf_select.h"
+#include "mf_topk_io.h"
 
 static constexpr int SQ_MAXQ = 32;       // queries per call
 static constexpr int SQ_NW = 4;          // waves per workgroup (each takes one 64-row block per pass)
@@ -515,6 +516,7 @@ __global__ __launch_bounds__(64 * SQ_SEL_WAVES) void topk_small_select_kernel(co
     int r = 0;
     for (int t = 0; t < m; ++t) r += top[t] > mine ? 1 : 0;
     if (lane < k) {
+        // (written out, not mf_store_topk_entry / _none of mf_topk_io.h: through them this kernel's code came out differently)
         if (lane < m) {
             out_scores[q * k + r] = mf_key_retrieval_score(mine);
             out_idx[q * k + r] = idx_base + (int64_t)mf_key_retrieval_col(mine);
@@ -557,14 +559,9 @@ static void launch_small(const SmallParams& sp, int grid, hipStream_t s) {
 extern "C" int mf_topk_small(const float* q, int64_t Q, const float* blocked, int64_t N, int d, int k,
                              const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws,
                              size_t ws_bytes, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
-    if (!q || !blocked || !out_scores || !out_idx || !ws || Q <= 0 || N <= 0)
-        return mf_set_error(MF_EINVAL, "mf_topk_small: bad argument");
-    if (Q > SQ_MAXQ) return mf_set_error(MF_ENOTSUP, "mf_topk_small: Q = %lld > %d (use mf_topk)", (long long)Q, SQ_MAXQ);
-    if (k <= 0 || k > 64) return mf_set_error(MF_ENOTSUP, "mf_topk_small: k = %d outside 1..64", k);
-    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_topk_small: embedding width %d not in {32,64,128,256}", d);
-    if (N >= (1ll << 31) || idx_base < 0 || idx_base + N > (1ll << 32))
-        return mf_set_error(MF_ENOTSUP, "mf_topk_small: item indices must fit 32 bits");
-    if ((excl_off == nullptr) != (excl_idx == nullptr)) return mf_set_error(MF_EINVAL, "mf_topk_small: excl_off/excl_idx mismatch");
+    if (const int rc = mf_topk_check_args("mf_topk_small", {64, 32, 31, SQ_MAXQ}, q, Q, blocked, N, d, k, excl_off, excl_idx, idx_base, ws,
+                                          out_scores, out_idx))
+        return rc;
     if (ws_bytes < mf_topk_small_ws_bytes(Q, N, d, k)) return mf_set_error(MF_ENOSPC, "mf_topk_small: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t nblocks = (N + 63) / 64;

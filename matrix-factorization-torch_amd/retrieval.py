@@ -117,9 +117,6 @@ class ItemIndex:
             q = torch.nn.functional.pad(q, (0, self.embeddings.shape[1] - self.dim))
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
-        lib = _lib.lib()
-        scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
-        rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
         if path not in self.PATHS:
             msg = f"path must be 'auto', 'scan', 'tiles', 'bf16' or 'deep': {path = }"
             raise ValueError(msg)
@@ -130,11 +127,7 @@ class ItemIndex:
             msg = f"the scan path takes at most {self.SMALL_Q} queries: {nq = }"
             raise ValueError(msg)
         if path == "deep" or (path == "auto" and top_k > self.TILE_MAX_K):
-            ws = self._workspace(("deep", nq, top_k), lib.mf_topk_deep_ws_bytes(nq, n, d, top_k))
-            _lib.check(lib.mf_topk_deep(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, top_k, _lib.ptr(off), _lib.ptr(ids),
-                                        self.idx_base, ws.data_ptr(), ws.numel(), scores.data_ptr(), rows.data_ptr(),
-                                        _lib.stream_ptr()))
-            return scores, rows
+            return self._run("deep", q, top_k, off, ids)
         # the few-query scan matches exclusion entries against every 64-row block: staged in LDS up to SCAN_MAX_EXCL entries
         # (all queries together), a walk over each query's list per block beyond -- measured at N = 62,423: Q = 8 x 2,000 ids
         # 89 us, Q = 32 x 30,000 ids 4 ms, against 46 / 85 us through the prefilter (which builds bit rows once).  So "auto"
@@ -144,25 +137,36 @@ class ItemIndex:
         scan_ok = nq <= self.AUTO_SMALL_Q and (entries <= self.SCAN_MAX_EXCL or not bf16_ok and entries <= 16 * self.SCAN_MAX_EXCL)
         if path == "scan" or (path == "auto" and scan_ok):
             # the reference's own shape: one query (or a handful) per call -- bandwidth-bound scan, two launches
-            ws = self._workspace(("small", nq, top_k), lib.mf_topk_small_ws_bytes(nq, n, d, top_k))
-            _lib.check(lib.mf_topk_small(q.data_ptr(), nq, self.blocked().data_ptr(), n, d, top_k, _lib.ptr(off), _lib.ptr(ids),
-                                         self.idx_base, ws.data_ptr(), ws.numel(), scores.data_ptr(), rows.data_ptr(),
-                                         _lib.stream_ptr()))
-            return scores, rows
+            return self._run("scan", q, top_k, off, ids)
         if path == "bf16" or (path == "auto" and (nq >= self.BF16_MIN_Q or not scan_ok) and bf16_ok):
-            ws = self._workspace(("bf16", nq, top_k), lib.mf_topk_bf3_ws_bytes(nq, n, d, top_k))
-            rc = lib.mf_topk_bf3(q.data_ptr(), nq, self.embeddings.data_ptr(), self.bf16_index().data_ptr(), n, d, top_k,
-                                 _lib.ptr(off), _lib.ptr(ids), self.idx_base, ws.data_ptr(), ws.numel(), scores.data_ptr(),
-                                 rows.data_ptr(), _lib.stream_ptr())
             # a shape outside the prefilter's descriptor limits (MF_ENOTSUP, decided on the host before any launch) goes
             # to the fp32 tile engine when the caller left the choice to us; an explicit path="bf16" raises
-            if not (rc == _lib.MF_ENOTSUP and path == "auto"):
-                _lib.check(rc)
-                return scores, rows
-        ws = self._workspace(("tile", nq, top_k), lib.mf_topk_ws_bytes(nq, n, d, top_k))
-        _lib.check(lib.mf_topk(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, top_k, _lib.ptr(off), _lib.ptr(ids),
-                               self.idx_base, ws.data_ptr(), ws.numel(), scores.data_ptr(), rows.data_ptr(),
-                               _lib.stream_ptr()))
+            out = self._run("bf16", q, top_k, off, ids, refusal_ok=path == "auto")
+            if out is not None:
+                return out
+        return self._run("tiles", q, top_k, off, ids)
+
+    # engine -> (workspace-size export, search export, workspace key, the source tensors behind the queries)
+    _ENGINES = {
+        "deep": ("mf_topk_deep_ws_bytes", "mf_topk_deep", "deep", lambda self: (self.embeddings,)),
+        "scan": ("mf_topk_small_ws_bytes", "mf_topk_small", "small", lambda self: (self.blocked(),)),
+        "bf16": ("mf_topk_bf3_ws_bytes", "mf_topk_bf3", "bf16", lambda self: (self.embeddings, self.bf16_index())),
+        "tiles": ("mf_topk_ws_bytes", "mf_topk", "tile", lambda self: (self.embeddings,)),
+    }
+
+    def _run(self, engine: str, q: torch.Tensor, top_k: int, off, ids, refusal_ok: bool = False):
+        """One engine's search export on its kept workspace: ``(scores, rows)``, or None for MF_ENOTSUP with ``refusal_ok``."""
+        ws_bytes, export, key, sources = self._ENGINES[engine]
+        lib = _lib.lib()
+        nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
+        rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
+        ws = self._workspace((key, nq, top_k), getattr(lib, ws_bytes)(nq, n, d, top_k))
+        rc = getattr(lib, export)(q.data_ptr(), nq, *(t.data_ptr() for t in sources(self)), n, d, top_k, _lib.ptr(off), _lib.ptr(ids),
+                                  self.idx_base, ws.data_ptr(), ws.numel(), scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr())
+        if rc == _lib.MF_ENOTSUP and refusal_ok:
+            return None
+        _lib.check(rc)
         return scores, rows
 
 

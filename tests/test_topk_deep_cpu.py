@@ -117,8 +117,14 @@ def test_new_kernels_do_not_spill():
     spec = importlib.util.spec_from_file_location("kernel_resources", ROOT / "tools" / "kernel_resources.py")
     kr = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(kr)
-    mine = {n: r for n, r in kr.kernel_resources().items() if "topk_deep_" in n or "retrieval_metrics_deep_kernel" in n}
+    deep_r = 1024 // 64                                          # MF_TOPK_DEEP_MAX_K / 64: ranks per lane of the metrics kernel for k > 64
+    table = kr.kernel_resources()
+    mine = {n: r for n, r in table.items() if "topk_deep_" in n or f"retrieval_metrics_kernel<{deep_r}>" in n}
     assert sum("topk_deep_slab_kernel" in n for n in mine) == 4 and len(mine) == 7, sorted(mine)
+    assert sum("topk_deep_excl_kernel" in n for n in mine) == 1 and sum("topk_deep_select_kernel" in n for n in mine) == 1
+    shallow = {n: r for n, r in table.items() if "retrieval_metrics_kernel<1>" in n}
+    assert len(shallow) == 1 and sum("retrieval_metrics_kernel" in n for n in table) == 2, sorted(shallow)
+    mine.update(shallow)
     for name, r in mine.items():
         assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, (name, r)
         assert r["group_segment_fixed_size"] <= 64 * 1024, (name, r)

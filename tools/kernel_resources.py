@@ -89,7 +89,8 @@ def text_digests(lib: pathlib.Path = DEFAULT_LIB) -> dict[str, str]:
     """{demangled function name: sha256 of its disassembled instruction text} for every function of the library's code
     objects.  The text is what ``llvm-objdump -d`` prints without addresses and encodings, comments dropped and the
     function's own symbol replaced by a fixed word: two builds whose kernels differ in name only (a template argument that
-    changed its type) give the same digests.  Whole texts are hashed; nothing is searched for."""
+    changed its type) give the same digests, and so do two builds that lay the same kernel out at another place in the
+    code object (the ``s_nop`` padding behind a function's last instruction is dropped).  Nothing else is searched for."""
     table: dict[str, str] = {}
     for co in code_objects(pathlib.Path(lib)):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
@@ -102,6 +103,8 @@ def text_digests(lib: pathlib.Path = DEFAULT_LIB) -> dict[str, str]:
             label = re.fullmatch(r"(?:[0-9a-f]+ )?<(\S+)>:", line.strip())
             if label:
                 if name is not None:
+                    while lines and lines[-1] in ("", "s_nop 0", "..."):     # padding up to the next function's alignment: layout, not code
+                        lines.pop()
                     text = "\n".join(x for x in lines if x).replace(name, "SELF")
                     table[name] = hashlib.sha256(text.encode()).hexdigest()
                 name, lines = label.group(1), []

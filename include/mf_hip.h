@@ -335,10 +335,15 @@ int mf_topk_small(const float* q, int64_t Q, const float* blocked, int64_t N, in
  * bound on the bf16 error (csrc/mf_topk_bf3.hip) makes the candidate set a superset of the true top k, so scores,
  * order, rows, exclusion semantics and the -inf / -1 tail are IDENTICAL to mf_topk's (finite inputs).  `index`:
  * mf_topk_bf3_index_bytes(N, d) bytes filled once per catalog by mf_topk_bf3_build (bf16 rows + the largest row
- * norm); `items` are the same fp32 rows mf_topk takes. */
+ * norm); `items` are the same fp32 rows mf_topk takes.  mf_topk_bf3_plan is host-only: the geometry a search of this
+ * shape runs with, out16[0..13] = NT (32-row tiles), nblk (4-tile blocks), XT (query tiles per wave), xw (query-tile sets per
+ * workgroup), Qp (padded queries), gy (query workgroups), bs (the seed scan takes one block in every bs), nvb_seed, bpc_seed,
+ * nwg_seed (seed scan: blocks, blocks per workgroup, workgroups), bpc, nwg (full scan), nvals (seed maxima per query),
+ * windows of the exclusion-word prep; out16[14..15] = 0.  MF_EINVAL for a null out16 or a shape mf_topk_bf3_ws_bytes sizes as 0. */
 size_t mf_topk_bf3_index_bytes(int64_t N, int d);
 int mf_topk_bf3_build(const float* items, int64_t N, int d, void* index, size_t index_bytes, mf_stream_t stream);
 size_t mf_topk_bf3_ws_bytes(int64_t Q, int64_t N, int d, int k);
+int mf_topk_bf3_plan(int64_t Q, int64_t N, int d, int64_t* out16);
 int mf_topk_bf3(const float* q, int64_t Q, const float* items, const void* index, int64_t N, int d, int k,
                 const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
                 float* out_scores, int64_t* out_idx, mf_stream_t stream);

@@ -89,6 +89,7 @@ SIGNATURES = {
     "mf_topk_bf3_index_bytes": (c_sz, [c_i64, c_int]),
     "mf_topk_bf3_build": (c_int, [c_vp, c_i64, c_int, c_vp, c_sz, c_vp]),
     "mf_topk_bf3_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
+    "mf_topk_bf3_plan": (c_int, [c_i64, c_i64, c_int, ctypes.POINTER(c_i64)]),
     "mf_topk_bf3": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "mf_topk_deep_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "mf_topk_deep_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),

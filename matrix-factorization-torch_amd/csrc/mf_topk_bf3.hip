@@ -187,6 +187,17 @@ extern "C" size_t mf_topk_bf3_ws_bytes(int64_t Q, int64_t N, int d, int k) {
     return bf3_ws(nullptr, Q, N, d).total;
 }
 
+static constexpr int BF3_PREP_W = 2048;         // words per query in a window of the prep kernel (65,536 catalog rows; longer catalogs: more windows)
+// host-only: the geometry a search of this shape runs with (what the tests assert their cells through)
+extern "C" int mf_topk_bf3_plan(int64_t Q, int64_t N, int d, int64_t* out) {
+    if (!out || mf_topk_bf3_ws_bytes(Q, N, d, 1) == 0) return mf_set_error(MF_EINVAL, "mf_topk_bf3_plan: bad argument");
+    const Bf3Plan p = bf3_plan(Q, N, d);
+    const int64_t v[16] = {p.NT, p.nblk, p.XT, p.xw, p.Qp, p.gy, p.bs, p.nvb_seed, p.bpc_seed, p.nwg_seed, p.bpc, p.nwg, p.nvals,
+                           ((int64_t)(p.nblk + 1) * BF3_BLOCK + BF3_PREP_W - 1) / BF3_PREP_W, 0, 0};
+    for (int i = 0; i < 16; ++i) out[i] = v[i];
+    return MF_OK;
+}
+
 // -------------------------------------------------------------------- scan ----
 struct Bf3Scan {
     int64_t Q, Qp;
@@ -946,8 +957,7 @@ __global__ __launch_bounds__(64 * BF3_FQ) void bf3_final_kernel(Bf3Final p) {
 // row of words per query: that DMA touched 32 cache lines for 512 bytes).  The four lists are one contiguous range of the CSR
 // array: all 256 threads stride over it with their loads in flight together; a workgroup writes 64-byte pieces, its
 // neighbours the rest of the line.
-static constexpr int BF3_PREP_Q = 4;            // queries per workgroup
-static constexpr int BF3_PREP_W = 2048;         // words per query in a window (65,536 catalog rows; longer catalogs: more windows)
+static constexpr int BF3_PREP_Q = 4;            // queries per workgroup (BF3_PREP_W words per query in a window: beside the plan)
 __global__ __launch_bounds__(256) void bf3_prep_kernel(const int64_t* __restrict__ excl_off, const int64_t* __restrict__ excl_idx,
                                                        int64_t idx_base, int64_t Q, int64_t Qp, int64_t N, int nblk,
                                                        uint32_t* __restrict__ exclW, const float* __restrict__ q, int d,

@@ -16,7 +16,7 @@ def test_library_exports_every_declared_symbol(mf):
     header = (ROOT / "include" / "mf_hip.h").read_text()
     declared = set(re.findall(r"\b(mf_[a-z0-9_]+)\s*\(", header))
     assert {"mf_loss_fwd", "mf_loss_bwd", "mf_gather_rows", "mf_update_sgd", "mf_update_adam", "mf_topk",
-            "mf_topk_merge"} <= declared
+            "mf_topk_merge", "mf_topk_bf3_plan"} <= declared
     lib = mf._lib.lib()
     for name in declared:
         assert hasattr(lib, name), f"libmf_hip.so lacks {name}"

@@ -380,6 +380,38 @@ int mf_topk_deep(const float* q, int64_t Q, const float* items, int64_t N, int d
 int mf_retrieval_metrics(const int64_t* topk_idx, int64_t Q, int k, const int64_t* tgt_off,
                          const int64_t* tgt_idx, const float* tgt_rel, float* out, mf_stream_t stream);
 
+/* Positions instead of lists: the exact place of GIVEN rows (a query's targets, CSR tgt_off[Q+1] / tgt_idx[n_targets], global
+ * rows) in the query's order of all admissible rows -- the order the searches above select from: key(y) = the
+ * retrieval key of mf_numerics.h for (chain score, y), row y admissible iff 0 <= y < N and y + idx_base is not on the query's exclusion list.
+ * out_ncand[r] = admissible rows of query r.  For entry e of query r with y = tgt_idx[e] - idx_base: admissible ->
+ * out_pos[e] = number of admissible rows with a larger key (0 = best), out_score[e] = its chain score; otherwise -1 / -inf.
+ * So 0 <= out_pos[e] < k <= 1024 means mf_topk_deep returns that row at column out_pos[e] with the same score bits, and
+ * out_pos[e] >= k that it does not.  Duplicate entries get the same answer, an empty list writes nothing; n_targets (the length
+ * of tgt_idx and of both outputs) is only checked, n_targets == 0 still writes out_ncand.  Runs mf_topk_deep's slab stage per
+ * block of queries, then one workgroup per query counts over its slab row (lists of any length, 1024 entries per sweep of the
+ * row).  Workspace = the slab, sized like mf_topk_deep's: _ws_bytes the preferred size, _min_ws_bytes one block of 32 queries, 0
+ * for invalid shapes.  No host read, no allocation, no float atomics; capturable.  MF_EINVAL: a null pointer (the exclusion pair
+ * may be null together), Q <= 0, N <= 0, n_targets < 0, a width outside {32, 64, 128, 256}; MF_ENOTSUP: N >= 2^31,
+ * idx_base + N > 2^32, a 32-query slab of 4 GiB or more; MF_ENOSPC: a workspace below the minimum; all before any launch. */
+size_t mf_target_positions_ws_bytes(int64_t Q, int64_t N, int d);
+size_t mf_target_positions_min_ws_bytes(int64_t Q, int64_t N, int d);
+int mf_target_positions(const float* q, int64_t Q, const float* items, int64_t N, int d,
+                        const int64_t* tgt_off, const int64_t* tgt_idx, int64_t n_targets,
+                        const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base,
+                        void* ws, size_t ws_bytes, int64_t* out_pos, float* out_score, int64_t* out_ncand, mf_stream_t stream);
+
+/* Retrieval metrics from positions (mf_target_positions): pos / tgt_rel[tgt_off[q] .. tgt_off[q+1]), ncand[Q]; ks = nk cut-offs
+ * in HOST memory (1 <= nk <= 8, each >= 1, no upper limit: a k above N is legal).  out[q][6 nk + 3]: for every k the six values
+ * of mf_retrieval_metrics in its order and with its conventions, "retrieved at column t" read as "position t < k" (a target at
+ * -1 is never retrieved but counts among the relevant targets and in IDCG); then, over the relevant targets with a position
+ * (rating > 0, pos >= 0), MRR = 1 / (smallest position + 1), MeanPosition, and AUC = mean of 1 - (pos - a) / max(ncand -
+ * n, 1) with a = such targets of the query placed above this one and n = their number -- the share of other admissible
+ * rows placed above a relevant one; 0 without such a target.  Differs from mf_retrieval_metrics in one case: fewer than k
+ * admissible rows AND a target that is not admissible, which that kernel places below the short list and this one never
+ * places.  MF_EINVAL: a null pointer, Q <= 0, a k < 1; MF_ENOTSUP: nk outside 1..8. */
+int mf_position_metrics(const int64_t* pos, const int64_t* tgt_off, const float* tgt_rel, const int64_t* ncand, int64_t Q,
+                        const int32_t* ks, int nk, float* out, mf_stream_t stream);
+
 /* The batch producer on the device (replaces the host datapipe of
  * xfmr_rec/data/lightning.py:311-363 + data/load.py:38-141 for id-only towers).  The interaction list
  * pair_*[n_pairs] and the users' positive lists (CSR pos_off[num_users + 1], pos_items) stay in HBM;

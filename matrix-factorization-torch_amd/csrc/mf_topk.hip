@@ -317,3 +317,132 @@ extern "C" int mf_retrieval_metrics(const int64_t* topk_idx, int64_t Q, int k, c
     fn<<<dim3((unsigned)Q), 64, 0, static_cast<hipStream_t>(stream)>>>(topk_idx, k, tgt_off, tgt_idx, tgt_rel, out);
     return mf_check_launch("mf_retrieval_metrics");
 }
+
+// ------------------------------------------------------- metrics from positions ----
+// The same six values at up to POS_METRICS_MAX_K cut-offs at once, and three uncut ones, from every target's exact place
+// among the query's admissible rows (mf_target_positions; -1: not admissible) instead of from a list: "retrieved at
+// column t" reads "position t < k", so k has no upper limit and a target that is not retrieved needs no place.  One wave
+// per query, lane l takes targets l, l + 64, ..; a target's rank among the ratings (IDCG) and the number of relevant
+// targets placed above it (MAP, AUC) are counted over the list, once for all cut-offs.
+static constexpr int POS_METRICS_MAX_K = 8;
+struct PosMetricKs {
+    int32_t k[POS_METRICS_MAX_K];
+};
+
+__device__ __forceinline__ int64_t mf_wave_sum_i64(int64_t x) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) x += __shfl_xor(x, s, 64);
+    return x;
+}
+__device__ __forceinline__ int64_t mf_wave_min_i64(int64_t x) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const int64_t o = __shfl_xor(x, s, 64);
+        x = o < x ? o : x;
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(64) void position_metrics_kernel(const int64_t* __restrict__ pos, const int64_t* __restrict__ tgt_off,
+                                                              const float* __restrict__ tgt_rel, const int64_t* __restrict__ ncand,
+                                                              PosMetricKs ks, int nk, float* __restrict__ out) {
+    const int64_t q = blockIdx.x;
+    const int lane = mf_lane();
+    const int64_t e0 = tgt_off[q], e1 = tgt_off[q + 1];
+    float dcg[POS_METRICS_MAX_K], idcg[POS_METRICS_MAX_K], ap[POS_METRICS_MAX_K];
+    int hits[POS_METRICS_MAX_K];
+#pragma unroll
+    for (int i = 0; i < POS_METRICS_MAX_K; ++i) dcg[i] = idcg[i] = ap[i] = 0.f, hits[i] = 0;
+    int npos = 0, nadm = 0;                            // relevant targets; relevant AND admissible ones
+    int64_t first = INT64_MAX, sum_pos = 0, sum_nonrel_above = 0;
+    // (every lane runs every round: a round's 64 entries are loaded once, one per lane, and handed round by lane number)
+    for (int64_t eb = e0; eb < e1; eb += 64) {
+        const int64_t e = eb + lane;
+        const float r = e < e1 ? tgt_rel[e] : 0.f;
+        const int64_t p = e < e1 ? pos[e] : -1;
+        const bool relevant = r > 0.f, placed = relevant && p >= 0;
+        const int pi = (int)p;                         // (positions are below 2^31: N is)
+        // rank among the ratings, descending, list order among equals: one 64-bit key per entry, larger = earlier
+        const unsigned long long ke = ((unsigned long long)mf_orderable(r) << 32) | (unsigned long long)~(unsigned)(e - e0);
+        int rank = 0, above = 0;
+        for (int64_t fb = e0; fb < e1; fb += 64) {
+            const int64_t f = fb + lane;
+            const float of = f < e1 ? tgt_rel[f] : 0.f;
+            const int64_t pf = f < e1 ? pos[f] : -1;
+            const int k_hi = f < e1 ? (int)mf_orderable(of) : 0, k_lo = f < e1 ? (int)~(unsigned)(f - e0) : 0;      // (0: behind every entry)
+            const int at = (of > 0.f && pf >= 0) ? (int)pf : INT32_MAX;      // where a relevant target stands; never above anyone else
+#pragma unroll 16
+            for (int j = 0; j < 64; ++j) {
+                const unsigned long long kf = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(k_hi, j) << 32) |
+                                              (unsigned long long)(unsigned)__builtin_amdgcn_readlane(k_lo, j);
+                rank += kf > ke ? 1 : 0;
+                above += __builtin_amdgcn_readlane(at, j) < pi ? 1 : 0;
+            }
+        }
+        if (e >= e1) continue;
+        npos += relevant ? 1 : 0;
+        if (placed) {
+            ++nadm;
+            first = p < first ? p : first;
+            sum_pos += p;
+            sum_nonrel_above += p - above;
+        }
+        const float gain_ideal = r / log2f((float)rank + 2.f);
+        const float gain = p >= 0 ? r / log2f((float)p + 2.f) : 0.f;
+        const float prec = placed ? (float)(above + 1) / (float)(p + 1) : 0.f;
+#pragma unroll
+        for (int i = 0; i < POS_METRICS_MAX_K; ++i) {
+            if (i >= nk) continue;
+            const int k = ks.k[i];
+            if (rank < k) idcg[i] += gain_ideal;
+            if (p >= 0 && p < k) {
+                dcg[i] += gain;
+                ap[i] += prec;
+                hits[i] += placed ? 1 : 0;
+            }
+        }
+    }
+    npos = mf_wave_sum_int(npos);
+    nadm = mf_wave_sum_int(nadm);
+    first = mf_wave_min_i64(first);
+    sum_pos = mf_wave_sum_i64(sum_pos);
+    sum_nonrel_above = mf_wave_sum_i64(sum_nonrel_above);
+    float* o = out + q * (6 * nk + 3);
+    const bool any = npos > 0;
+#pragma unroll
+    for (int i = 0; i < POS_METRICS_MAX_K; ++i) {
+        if (i >= nk) continue;
+        const float d = mf_wave_sum(dcg[i]), id = mf_wave_sum(idcg[i]), a = mf_wave_sum(ap[i]);
+        const int h = mf_wave_sum_int(hits[i]);
+        if (lane == 0) {
+            const int k = ks.k[i];
+            o[6 * i + 0] = (any && id > 0.f) ? d / id : 0.f;
+            o[6 * i + 1] = any ? (float)h / (float)npos : 0.f;
+            o[6 * i + 2] = any ? (float)h / (float)k : 0.f;
+            o[6 * i + 3] = h > 0 ? a / (float)h : 0.f;
+            o[6 * i + 4] = h > 0 ? 1.f : 0.f;
+            o[6 * i + 5] = h > 0 ? 1.f / (float)(first + 1) : 0.f;
+        }
+    }
+    if (lane == 0) {
+        const int64_t nonrel = ncand[q] - nadm;                         // admissible rows that are no relevant target
+        const double den = (double)nadm * (double)(nonrel > 1 ? nonrel : 1);
+        o[6 * nk + 0] = nadm > 0 ? 1.f / (float)(first + 1) : 0.f;
+        o[6 * nk + 1] = nadm > 0 ? (float)((double)sum_pos / (double)nadm) : 0.f;
+        o[6 * nk + 2] = nadm > 0 ? (float)(1.0 - (double)sum_nonrel_above / den) : 0.f;
+    }
+}
+
+extern "C" int mf_position_metrics(const int64_t* pos, const int64_t* tgt_off, const float* tgt_rel, const int64_t* ncand, int64_t Q,
+                                   const int32_t* ks, int nk, float* out, mf_stream_t stream) {
+    if (!pos || !tgt_off || !tgt_rel || !ncand || !ks || !out || Q <= 0) return mf_set_error(MF_EINVAL, "mf_position_metrics: bad argument");
+    if (nk < 1 || nk > POS_METRICS_MAX_K)
+        return mf_set_error(MF_ENOTSUP, "mf_position_metrics: %d cut-offs outside 1..%d", nk, POS_METRICS_MAX_K);
+    PosMetricKs k{};
+    for (int i = 0; i < nk; ++i) {
+        if (ks[i] < 1) return mf_set_error(MF_EINVAL, "mf_position_metrics: k = %d < 1", ks[i]);
+        k.k[i] = ks[i];
+    }
+    position_metrics_kernel<<<dim3((unsigned)Q), 64, 0, static_cast<hipStream_t>(stream)>>>(pos, tgt_off, tgt_rel, ncand, k, nk, out);
+    return mf_check_launch("mf_position_metrics");
+}

@@ -18,6 +18,9 @@
 //              chunks; when ALL of them are needed no order has to be decided and they are collected with the rest);
 //              bitonic sort of the <= 1024 unique 64-bit keys, best first, -inf / -1 behind them.
 //
+// The slab is also all it takes to say where GIVEN rows stand in a query's order of the whole catalog (mf_target_positions:
+// stages 1 and 2, then target_positions_kernel, section 4 below) -- evaluation without a list, at any depth.
+//
 // No float atomics, no host read, nothing depends on atomic arrival order.
 #include <cmath>
 
@@ -98,6 +101,25 @@ __global__ __launch_bounds__(256) void topk_deep_excl_kernel(const int64_t* __re
 
 // ------------------------------------------------------------------------------------- 3.-5. select, collect, sort ----
 static constexpr int DEEP_THREADS = 256;
+
+// bitonic sort of keys[0 .. P - 1] in LDS, descending (P a power of two; every thread of the workgroup calls it; ends on a barrier)
+__device__ __forceinline__ void deep_sort_desc(unsigned long long* keys, int P) {
+    const int tid = threadIdx.x;
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < (P >> 1); i += DEEP_THREADS) {
+                const int a = ((i / stride) * 2 * stride) + (i % stride), b = a + stride;
+                const unsigned long long ka = keys[a], kb = keys[b];
+                const bool desc = (a & size) == 0;
+                if (desc ? ka < kb : ka > kb) {
+                    keys[a] = kb;
+                    keys[b] = ka;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
 
 __global__ __launch_bounds__(DEEP_THREADS) void topk_deep_select_kernel(const unsigned* __restrict__ slab, int64_t Np, int k,
                                                                         int64_t idx_base, float* __restrict__ out_scores,
@@ -189,20 +211,7 @@ __global__ __launch_bounds__(DEEP_THREADS) void topk_deep_select_kernel(const un
     // bitonic sort, descending, of the first P = 2^ceil(log2 k) slots (unused ones hold 0 and sink to the end)
     int P = 1;
     while (P < k) P <<= 1;
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < (P >> 1); i += DEEP_THREADS) {
-                const int a = ((i / stride) * 2 * stride) + (i % stride), b = a + stride;
-                const unsigned long long ka = keys[a], kb = keys[b];
-                const bool desc = (a & size) == 0;
-                if (desc ? ka < kb : ka > kb) {
-                    keys[a] = kb;
-                    keys[b] = ka;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    deep_sort_desc(keys, P);
     // (written out, not mf_store_topk of mf_topk_io.h: through the helper this kernel's registers were allocated differently)
     for (int t = tid; t < k; t += DEEP_THREADS) {
         const unsigned long long key = keys[t];
@@ -213,6 +222,209 @@ __global__ __launch_bounds__(DEEP_THREADS) void topk_deep_select_kernel(const un
             out_scores[r * k + t] = -INFINITY;
             out_idx[r * k + t] = -1;
         }
+    }
+}
+
+// ----------------------------------------------------------------------------------- 4. positions of given rows ----
+// Instead of the k best rows of a query, the place of GIVEN rows (its targets) in the order of all admissible ones: the
+// number of slab words whose key (word << 32 | ~column) is larger than the target's.  One workgroup per query, the target
+// list in passes of POS_PASS entries; a pass sweeps the slab row once.  Up to POS_FEW entries are counted by plain compares
+// in registers and reduced once (one or two targets would send nearly every element of the row to the same LDS word); more
+// are sorted, an element finds by binary search how many of the pass's keys are >= its own and adds 1 to that bin (integer
+// LDS atomics: exact, order-free), and a scan over the bins gives every key the number of elements above it.  Elements
+// below the pass's lowest key are above nobody and are not binned.
+static constexpr int POS_PASS = 1024;
+static constexpr int POS_FEW = 16;
+static constexpr int POS_LOADS = 4;        // 16-byte loads a thread has in flight during the sweep
+
+// f(four words, first column) over the slab row, zero words included; POS_LOADS independent loads are issued before the first is used
+template <class F>
+__device__ __forceinline__ void pos_sweep(const uint4* __restrict__ row4, int n4, F&& f) {
+    for (int i0 = 0; i0 < n4; i0 += POS_LOADS * DEEP_THREADS) {
+        uint4 v[POS_LOADS];
+#pragma unroll
+        for (int u = 0; u < POS_LOADS; ++u) {
+            const int i = i0 + u * DEEP_THREADS + (int)threadIdx.x;
+            v[u] = i < n4 ? row4[i] : uint4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int u = 0; u < POS_LOADS; ++u) {
+            const unsigned w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            f(w, 4u * (unsigned)(i0 + u * DEEP_THREADS + (int)threadIdx.x));
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned long long pos_key(unsigned word, unsigned col) {
+    return ((unsigned long long)word << 32) | (unsigned long long)mf_key_retrieval_lo(col);
+}
+
+// a pass of at most M <= POS_FEW entries, keys[0 .. M - 1] in LDS (unused slots hold all ones: nothing is above them);
+// leaves the counts in red[0][0 .. M - 1] and the row's non-zero words in red[0][M].  (A zero word makes a key below every
+// admissible entry's, so it needs no test here.)
+template <int M>
+__device__ __forceinline__ void pos_count_few(const uint4* __restrict__ row4, int n4, const unsigned long long* keys,
+                                              int (*red)[POS_FEW + 1]) {
+    unsigned long long kk[M];
+    int cnt[M], nz = 0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        kk[j] = keys[j];
+        cnt[j] = 0;
+    }
+    pos_sweep(row4, n4, [&](const unsigned (&w)[4], unsigned col) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const unsigned long long ek = pos_key(w[c], col + c);
+            nz += w[c] != 0u ? 1 : 0;
+#pragma unroll
+            for (int j = 0; j < M; ++j) cnt[j] += ek > kk[j] ? 1 : 0;
+        }
+    });
+    const int lane = mf_lane(), wave = (int)threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const int c = mf_wave_sum_int(cnt[j]);
+        if (lane == 0) red[wave][j] = c;
+    }
+    nz = mf_wave_sum_int(nz);
+    if (lane == 0) red[wave][M] = nz;
+    __syncthreads();
+    if ((int)threadIdx.x <= M) {
+        int t = 0;
+        for (int w = 0; w < DEEP_THREADS / 64; ++w) t += red[w][threadIdx.x];
+        red[0][threadIdx.x] = t;                              // (thread j reads and writes column j only)
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(DEEP_THREADS) void target_positions_kernel(const unsigned* __restrict__ slab, int64_t Np, int64_t N, int64_t q0,
+                                                                        int64_t idx_base, const int64_t* __restrict__ tgt_off,
+                                                                        const int64_t* __restrict__ tgt_idx, int64_t* __restrict__ out_pos,
+                                                                        float* __restrict__ out_score, int64_t* __restrict__ out_ncand) {
+    __shared__ unsigned long long keys[POS_PASS];
+    __shared__ unsigned bins[POS_PASS];
+    __shared__ int red[DEEP_THREADS / 64][POS_FEW + 1];
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    const unsigned* row = slab + r * Np;
+    const uint4* row4 = reinterpret_cast<const uint4*>(row);             // Np is a multiple of 32, the slab 256-byte aligned
+    const int n4 = (int)(Np >> 2);
+    const int64_t e0 = tgt_off[q0 + r], e1 = tgt_off[q0 + r + 1];
+
+    for (int64_t p0 = e0; p0 == e0 || p0 < e1; p0 += POS_PASS) {        // (a query without targets: one pass, for its count)
+        const int m = (int)(e1 - p0 < POS_PASS ? (e1 > p0 ? e1 - p0 : 0) : POS_PASS);
+        // entry tid + 256 j of the pass: its key from one slab word (0: excluded, out of range -- not admissible)
+        unsigned long long mine[POS_PASS / DEEP_THREADS];
+#pragma unroll
+        for (int j = 0; j < POS_PASS / DEEP_THREADS; ++j) {
+            const int t = tid + DEEP_THREADS * j;
+            mine[j] = 0ull;
+            if (t < m) {
+                const int64_t y = tgt_idx[p0 + t] - idx_base;
+                if (y >= 0 && y < N) {
+                    const unsigned w = row[y];
+                    if (w != 0u) mine[j] = pos_key(w, (unsigned)y);
+                }
+            }
+        }
+        if (m <= POS_FEW) {
+            if (tid < POS_FEW) keys[tid] = tid < m && mine[0] != 0ull ? mine[0] : ~0ull;
+            __syncthreads();
+            if (m <= 1) pos_count_few<1>(row4, n4, keys, red);
+            else if (m <= 4) pos_count_few<4>(row4, n4, keys, red);
+            else pos_count_few<POS_FEW>(row4, n4, keys, red);
+            if (tid < m) {
+                out_pos[p0 + tid] = mine[0] != 0ull ? (int64_t)red[0][tid] : -1;
+                out_score[p0 + tid] = mine[0] != 0ull ? mf_key_retrieval_score(mine[0]) : -INFINITY;
+            }
+            if (p0 == e0 && tid == 0) out_ncand[q0 + r] = red[0][m <= 1 ? 1 : (m <= 4 ? 4 : POS_FEW)];
+            __syncthreads();                                 // (keys and red are written again by the next pass)
+            continue;
+        }
+        // sort the pass's keys, best first; the inadmissible entries' zeros sink behind the nvalid admissible ones
+        int P = 32;
+        while (P < m) P <<= 1;
+        int64_t nv[1] = {0}, nvt[1];
+#pragma unroll
+        for (int j = 0; j < POS_PASS / DEEP_THREADS; ++j) {
+            const int t = tid + DEEP_THREADS * j;
+            if (t < P) keys[t] = mine[j];
+            bins[t] = 0u;
+            nv[0] += mine[j] != 0ull ? 1 : 0;
+        }
+        block_excl_scan<DEEP_THREADS, 1>(nv, nvt);           // (its barriers also publish keys and bins)
+        const int nvalid = (int)nvt[0];
+        deep_sort_desc(keys, P);
+        const unsigned long long kmin = nvalid > 0 ? keys[nvalid - 1] : ~0ull;
+        int nz = 0;
+        pos_sweep(row4, n4, [&](const unsigned (&w)[4], unsigned col) {
+            unsigned long long ek[4];
+            bool any = false;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                nz += w[c] != 0u ? 1 : 0;
+                ek[c] = pos_key(w[c], col + c);
+                any |= ek[c] > kmin;
+            }
+            if (!any) return;                                // below the pass's lowest key: above nobody
+            // bin = the number of sorted keys >= the element's = the first key below it (0 .. nvalid - 1 for an element above
+            // kmin); a fixed log2 P halvings, the four words' searches side by side: four LDS reads in flight
+            int at[4] = {0, 0, 0, 0};
+            for (int s = P >> 1; s > 0; s >>= 1) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) at[c] += keys[at[c] + s - 1] >= ek[c] ? s : 0;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (ek[c] > kmin) atomicAdd(&bins[at[c]], 1u);
+        });
+        if (p0 == e0) {                                      // (uniform)
+            nz = mf_wave_sum_int(nz);
+            if (mf_lane() == 0) red[tid >> 6][0] = nz;
+        }
+        __syncthreads();
+        // bins -> elements above sorted key i = bins[0] + .. + bins[i]; thread t owns bins 4 t .. 4 t + 3
+        unsigned b4[4];
+        int64_t sc[1] = {0}, tot[1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            b4[j] = bins[4 * tid + j];
+            sc[0] += b4[j];
+        }
+        block_excl_scan<DEEP_THREADS, 1>(sc, tot);
+        unsigned run = (unsigned)sc[0];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            run += b4[j];
+            bins[4 * tid + j] = run;
+        }
+        __syncthreads();
+        // every entry looks its own key up: equal keys (duplicates in the list) meet the same answer
+#pragma unroll
+        for (int j = 0; j < POS_PASS / DEEP_THREADS; ++j) {
+            const int t = tid + DEEP_THREADS * j;
+            if (t >= m) continue;
+            if (mine[j] == 0ull) {
+                out_pos[p0 + t] = -1;
+                out_score[p0 + t] = -INFINITY;
+                continue;
+            }
+            int lo = 0, hi = nvalid - 1;                     // the first sorted key <= mine: one of its copies
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (keys[mid] <= mine[j]) hi = mid;
+                else lo = mid + 1;
+            }
+            out_pos[p0 + t] = (int64_t)bins[lo];
+            out_score[p0 + t] = mf_key_retrieval_score(mine[j]);
+        }
+        if (p0 == e0 && tid == 0) {
+            int t = 0;
+            for (int w = 0; w < DEEP_THREADS / 64; ++w) t += red[w][0];
+            out_ncand[q0 + r] = t;
+        }
+        __syncthreads();
     }
 }
 
@@ -260,6 +472,34 @@ extern "C" int mf_topk_deep_plan(int64_t Q, int64_t N, int d, int k, size_t ws_b
     return MF_OK;
 }
 
+// one query block's slab: scores of queries q0 .. q0 + nq - 1 against the whole catalog, exclusions stored over them.
+// Launch geometry of the scoring pass: ~2048 workgroups, at least 4 catalog tiles each; a workgroup's tiles go through one
+// buffer descriptor based at its first row (mf_stream.h)
+static int deep_fill_slab(const float* q, int64_t q0, int64_t nq, int64_t Q, const float* items, int64_t N, int d, const DeepPlan& p,
+                          const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, unsigned* slab, hipStream_t s) {
+    const int nw = mf_nw(d);
+    const int NT = (int)(p.Np / 32);
+    const int qtiles = (int)((nq + 31) / 32);
+    const int gy = (qtiles + nw - 1) / nw;
+    const int want = (2048 + gy - 1) / gy;
+    int tpc = (NT + want - 1) / want;
+    if (tpc < 4) tpc = 4;
+    if (tpc > DEEP_MAX_TPC) tpc = DEEP_MAX_TPC;
+    const int nchunk = (NT + tpc - 1) / tpc;
+    MF_DISPATCH_D(d, {
+        auto fn = topk_deep_slab_kernel<D>;
+        const int bytes = 2 * TileGeom<D>::TILEB;
+        (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        MF_TIMED("topk_deep_scores", s, (fn<<<dim3((unsigned)nchunk, (unsigned)gy), 64 * mf_nw(D), bytes, s>>>(
+            q, q0, Q, qtiles, items, N, NT, tpc, p.Np, slab)));
+    });
+    if (excl_off) topk_deep_excl_kernel<<<dim3((unsigned)nq), 256, 0, s>>>(excl_off, excl_idx, idx_base, N, p.Np, q0, slab);
+    return MF_OK;
+}
+static bool deep_extent_ok(const DeepPlan& p, int64_t qb, int d) {
+    return (int64_t)DEEP_MAX_TPC * 32 * d * 4 <= (int64_t)MF_SRD_MAX_BYTES && qb * p.row_bytes <= (int64_t)MF_SRD_MAX_BYTES;
+}
+
 extern "C" int mf_topk_deep(const float* q, int64_t Q, const float* items, int64_t N, int d, int k,
                             const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
                             float* out_scores, int64_t* out_idx, mf_stream_t stream) {
@@ -270,33 +510,43 @@ extern "C" int mf_topk_deep(const float* q, int64_t Q, const float* items, int64
     if (!p.ok) return mf_set_error(MF_ENOTSUP, "mf_topk_deep: a 32-query score slab of %lld columns exceeds the descriptor limit", (long long)N);
     const int64_t qb = deep_qb(p, ws_bytes);
     if (qb < 32) return mf_set_error(MF_ENOSPC, "mf_topk_deep: workspace too small");
-    // launch geometry of the scoring pass: ~2048 workgroups, at least 4 catalog tiles each; a workgroup's tiles go through
-    // one buffer descriptor based at its first row (mf_stream.h)
-    const int nw = mf_nw(d);
-    const int NT = (int)(p.Np / 32);
-    if ((int64_t)DEEP_MAX_TPC * 32 * d * 4 > (int64_t)MF_SRD_MAX_BYTES || qb * p.row_bytes > (int64_t)MF_SRD_MAX_BYTES)
-        return mf_set_error(MF_ENOTSUP, "mf_topk_deep: extent beyond the descriptor limit");
+    if (!deep_extent_ok(p, qb, d)) return mf_set_error(MF_ENOTSUP, "mf_topk_deep: extent beyond the descriptor limit");
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned* slab = static_cast<unsigned*>(ws);
     for (int64_t q0 = 0; q0 < Q; q0 += qb) {
         const int64_t nq = Q - q0 < qb ? Q - q0 : qb;
-        const int qtiles = (int)((nq + 31) / 32);
-        const int gy = (qtiles + nw - 1) / nw;
-        const int want = (2048 + gy - 1) / gy;
-        int tpc = (NT + want - 1) / want;
-        if (tpc < 4) tpc = 4;
-        if (tpc > DEEP_MAX_TPC) tpc = DEEP_MAX_TPC;
-        const int nchunk = (NT + tpc - 1) / tpc;
-        MF_DISPATCH_D(d, {
-            auto fn = topk_deep_slab_kernel<D>;
-            const int bytes = 2 * TileGeom<D>::TILEB;
-            (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            MF_TIMED("topk_deep_scores", s, (fn<<<dim3((unsigned)nchunk, (unsigned)gy), 64 * mf_nw(D), bytes, s>>>(
-                q, q0, Q, qtiles, items, N, NT, tpc, p.Np, slab)));
-        });
-        if (excl_off) topk_deep_excl_kernel<<<dim3((unsigned)nq), 256, 0, s>>>(excl_off, excl_idx, idx_base, N, p.Np, q0, slab);
+        if (const int rc = deep_fill_slab(q, q0, nq, Q, items, N, d, p, excl_off, excl_idx, idx_base, slab, s)) return rc;
         MF_TIMED("topk_deep_select", s, (topk_deep_select_kernel<<<dim3((unsigned)nq), DEEP_THREADS, 0, s>>>(
             slab, p.Np, k, idx_base, out_scores + q0 * k, out_idx + q0 * k)));
     }
     return mf_check_launch("mf_topk_deep");
+}
+
+// ---- positions: the same blocks and slabs, k out of the picture
+extern "C" size_t mf_target_positions_ws_bytes(int64_t Q, int64_t N, int d) { return mf_topk_deep_ws_bytes(Q, N, d, 1); }
+extern "C" size_t mf_target_positions_min_ws_bytes(int64_t Q, int64_t N, int d) { return mf_topk_deep_min_ws_bytes(Q, N, d, 1); }
+
+extern "C" int mf_target_positions(const float* q, int64_t Q, const float* items, int64_t N, int d, const int64_t* tgt_off,
+                                   const int64_t* tgt_idx, int64_t n_targets, const int64_t* excl_off, const int64_t* excl_idx,
+                                   int64_t idx_base, void* ws, size_t ws_bytes, int64_t* out_pos, float* out_score, int64_t* out_ncand,
+                                   mf_stream_t stream) {
+    if (!tgt_off || !tgt_idx || !out_ncand || n_targets < 0) return mf_set_error(MF_EINVAL, "mf_target_positions: bad argument");
+    if (const int rc = mf_topk_check_args("mf_target_positions", {1, 32, 31, 0}, q, Q, items, N, d, 1, excl_off, excl_idx, idx_base, ws,
+                                          out_score, out_pos))
+        return rc;
+    const DeepPlan p = deep_plan(Q, N, d, 1);
+    if (!p.ok)
+        return mf_set_error(MF_ENOTSUP, "mf_target_positions: a 32-query score slab of %lld columns exceeds the descriptor limit", (long long)N);
+    const int64_t qb = deep_qb(p, ws_bytes);
+    if (qb < 32) return mf_set_error(MF_ENOSPC, "mf_target_positions: workspace too small");
+    if (!deep_extent_ok(p, qb, d)) return mf_set_error(MF_ENOTSUP, "mf_target_positions: extent beyond the descriptor limit");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned* slab = static_cast<unsigned*>(ws);
+    for (int64_t q0 = 0; q0 < Q; q0 += qb) {
+        const int64_t nq = Q - q0 < qb ? Q - q0 : qb;
+        if (const int rc = deep_fill_slab(q, q0, nq, Q, items, N, d, p, excl_off, excl_idx, idx_base, slab, s)) return rc;
+        MF_TIMED("target_positions", s, (target_positions_kernel<<<dim3((unsigned)nq), DEEP_THREADS, 0, s>>>(
+            slab, p.Np, N, q0, idx_base, tgt_off, tgt_idx, out_pos, out_score, out_ncand)));
+    }
+    return mf_check_launch("mf_target_positions");
 }

@@ -21,12 +21,13 @@ from __future__ import annotations
 
 import contextlib
 
+import pydantic
 import torch
 
 from . import losses as mf_losses
 from . import fused, models, optim
 from .params import INDEX_PATH, PROCESSORS_JSON, TOP_K, TOWERS_PATH
-from .retrieval import RetrievalMetrics, ItemProcessor
+from .retrieval import ItemProcessor, PositionMetrics, RetrievalMetrics
 
 FEATURE_BAGS_PATH = "feature_bags.safetensors"     # the feature towers' registered bags (save / load)
 
@@ -44,6 +45,9 @@ except ImportError:  # noqa: SIM105
             return next(self.parameters()).device
 
 
+METRICS_MODES = ("topk", "positions")
+
+
 class MatrixFactorizationLitConfig(models.ModelConfig):
     hidden_size: int = 32          # xfmr_rec/lightning.py:33
     train_loss: str = "PairwiseHingeLoss"
@@ -55,6 +59,18 @@ class MatrixFactorizationLitConfig(models.ModelConfig):
     optimizer: str = "adam"        # "adam" = row-wise AdamW (the reference's optimiser class), "sgd", "adagrad" = row-wise Adagrad
     fused_losses: bool = True      # all seven losses from one sweep instead of seven sweeps
     use_logq: bool = False         # logQ correction (absent upstream)
+    # "topk": the metrics read a top_k list (top_k <= 1024); "positions": they read every target's exact place in the catalog
+    # (ItemIndex.positions) -- any top_k, further cut-offs eval_ks in the same pass, and uncut MRR / MeanPosition / AUC
+    metrics_mode: str = "topk"
+    eval_ks: list[int] | None = None      # with "positions": cut-offs beside top_k (logged as name@k)
+
+    @pydantic.field_validator("metrics_mode")
+    @classmethod
+    def _known_metrics_mode(cls, v: str) -> str:
+        if v not in METRICS_MODES:
+            msg = f"metrics_mode must be 'topk' or 'positions': {v!r}"
+            raise ValueError(msg)
+        return v
 
 
 HISTORY_TOWERS = ("history", "transformer")      # user towers whose input is the user's history, not its id
@@ -69,7 +85,7 @@ class MatrixFactorizationLitModule(_Base):
         self.item_processor: ItemProcessor | None = None
         self.history: dict[int, list[int]] = {}      # user_rn -> item ids already consumed (recommend excludes them)
         self.logq: torch.Tensor | None = None         # [num_items] log sampling probability, when use_logq
-        self.metrics: dict[str, RetrievalMetrics] | None = None
+        self.metrics: dict[str, RetrievalMetrics | PositionMetrics] | None = None
         self._fused: fused.FusedSmallStep | None = None
 
     # ------------------------------------------------------------------ towers ---
@@ -328,9 +344,13 @@ class MatrixFactorizationLitModule(_Base):
             msg = "`user_processor` and `item_processor` must be initialised first"
             raise ValueError(msg)
         queries = self._queries(batch)
-        _, rows = self.item_processor.index.search(queries, self.config.top_k, exclude_csr=batch.get("history"))
         off, ids, rating = batch["target"]
         metric = self.metrics[step_name]
+        if self.config.metrics_mode == "positions":      # no list: where each target stands among all admissible rows
+            pos, _, ncand = self.item_processor.index.positions(queries, (off, ids), exclude_csr=batch.get("history"))
+            metric.update(pos, off, rating, ncand)
+            return metric.compute()
+        _, rows = self.item_processor.index.search(queries, self.config.top_k, exclude_csr=batch.get("history"))
         metric.update(rows, off, ids, rating)
         return metric.compute()
 
@@ -434,9 +454,13 @@ class MatrixFactorizationLitModule(_Base):
             [cls(num_negatives=cfg.num_negatives, sigma=cfg.sigma, margin=cfg.margin) for cls in loss_classes]
         )
 
-    def get_metrics(self) -> dict[str, RetrievalMetrics]:
-        """NDCG / Recall / Precision / MAP / HitRate / MRR @top_k for "val" and "test" (lightning.py:289-306)."""
-        return {step: RetrievalMetrics(top_k=self.config.top_k, prefix=f"{step}/") for step in ("val", "test")}
+    def get_metrics(self) -> dict[str, RetrievalMetrics | PositionMetrics]:
+        """NDCG / Recall / Precision / MAP / HitRate / MRR @top_k for "val" and "test" (lightning.py:289-306); with
+        ``metrics_mode="positions"`` also @ every ``eval_ks`` and the uncut MRR / MeanPosition / AUC."""
+        cfg = self.config
+        if cfg.metrics_mode == "positions":
+            return {step: PositionMetrics((cfg.top_k, *(cfg.eval_ks or ())), prefix=f"{step}/") for step in ("val", "test")}
+        return {step: RetrievalMetrics(top_k=cfg.top_k, prefix=f"{step}/") for step in ("val", "test")}
 
     def on_validation_start(self) -> None:
         self.item_processor.get_index(self)

@@ -10,6 +10,7 @@ instead of approximate, batched over queries, ties broken by lowest item row.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Sequence
 
 import numpy as np
@@ -99,6 +100,46 @@ class ItemIndex:
     def num_items(self) -> int:
         return self.embeddings.shape[0]
 
+    def _queries(self, queries: torch.Tensor) -> torch.Tensor:
+        """The queries as the engines take them: fp32 on the device, ``[Q, dim]``, padded to the catalog's width."""
+        q = _lib.dev_f32(queries, "queries")
+        if q.dim() != 2 or q.shape[1] != self.dim:
+            msg = f"queries should be (num_queries, {self.dim}): {tuple(q.shape) = }"
+            raise ValueError(msg)
+        if self.embeddings.shape[1] != self.dim:
+            q = torch.nn.functional.pad(q, (0, self.embeddings.shape[1] - self.dim))
+        return q
+
+    def positions(self, queries: torch.Tensor, targets_csr: tuple[torch.Tensor, torch.Tensor], *,
+                  exclude: Sequence[Sequence[int]] | None = None,
+                  exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``(pos int64 [T], score fp32 [T], ncand int64 [Q])``: for every entry of ``targets_csr = (offsets [Q + 1], GLOBAL
+        item rows [T])`` its exact place among the query's admissible rows -- the rows ``search`` selects from, in its order
+        (0 = best) -- and its score; -1 / -inf for a row that is excluded or outside the catalog.  ``ncand`` is the number of
+        admissible rows per query.  A position below ``k`` is the column ``search(..., k, path="deep")`` returns the row at
+        (``mf_target_positions``: no list is built, so there is no deepest k)."""
+        q = self._queries(queries)
+        nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        t_off, t_ids = (_lib.dev_i64(t, name) for t, name in zip(targets_csr, ("target offsets", "target rows")))
+        if t_off.numel() != nq + 1:
+            msg = f"one target list per query expected: {t_off.numel() = }, {nq = }"
+            raise ValueError(msg)
+        off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
+        nt = t_ids.numel()
+        pos = torch.empty(nt, dtype=torch.int64, device=q.device)
+        score = torch.empty(nt, dtype=torch.float32, device=q.device)
+        ncand = torch.empty(nq, dtype=torch.int64, device=q.device)
+        if nt == 0:       # keep the pointers valid
+            t_ids, pos_arg, score_arg = (torch.zeros(1, dtype=dt, device=q.device) for dt in (torch.int64, torch.int64, torch.float32))
+        else:
+            pos_arg, score_arg = pos, score
+        lib = _lib.lib()
+        ws = self._workspace(("positions", nq), lib.mf_target_positions_ws_bytes(nq, n, d))
+        _lib.check(lib.mf_target_positions(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, t_off.data_ptr(), t_ids.data_ptr(), nt,
+                                           _lib.ptr(off), _lib.ptr(ids), self.idx_base, ws.data_ptr(), ws.numel(), pos_arg.data_ptr(),
+                                           score_arg.data_ptr(), ncand.data_ptr(), _lib.stream_ptr()))
+        return pos, score, ncand
+
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None,
                path: str = "auto") -> tuple[torch.Tensor, torch.Tensor]:
@@ -109,12 +150,7 @@ class ItemIndex:
         a radix select per query (``mf_topk_deep``: any ``top_k`` up to ``DEEP_MAX_K``; the other three stop at
         ``TILE_MAX_K``); "auto" takes "deep" exactly when ``top_k > TILE_MAX_K`` and otherwise picks by the number of
         queries; all four give the same bits."""
-        q = _lib.dev_f32(queries, "queries")
-        if q.dim() != 2 or q.shape[1] != self.dim:
-            msg = f"queries should be (num_queries, {self.dim}): {tuple(q.shape) = }"
-            raise ValueError(msg)
-        if self.embeddings.shape[1] != self.dim:
-            q = torch.nn.functional.pad(q, (0, self.embeddings.shape[1] - self.dim))
+        q = self._queries(queries)
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
         if path not in self.PATHS:
@@ -307,3 +343,55 @@ class RetrievalMetrics:
             return {self.prefix + name: torch.tensor(0.0) for name in METRIC_NAMES}
         mean = (self._sum / self._n).to(torch.float32)
         return {self.prefix + name: mean[j] for j, name in enumerate(METRIC_NAMES)}
+
+
+POSITION_METRIC_NAMES = ("MRR", "MeanPosition", "AUC")
+MAX_EVAL_KS = 8       # cut-offs one mf_position_metrics launch serves
+
+
+class PositionMetrics:
+    """The six metrics of ``RetrievalMetrics`` at one or several cut-offs, and three uncut ones, from the targets' exact
+    positions (``ItemIndex.positions``) instead of a top-k list: no deepest k, one launch for all cut-offs.  ``compute()``
+    returns the first k's values under the names ``RetrievalMetrics`` uses, further ks' under ``name@k``, and ``MRR``,
+    ``MeanPosition`` and ``AUC`` over the relevant targets that have a position -- means over all queries seen."""
+
+    def __init__(self, top_k: int | Sequence[int] = TOP_K, prefix: str = "") -> None:
+        ks = (int(top_k),) if isinstance(top_k, (int, np.integer)) else tuple(int(k) for k in top_k)
+        if not 1 <= len(ks) <= MAX_EVAL_KS or min(ks) < 1 or len(set(ks)) != len(ks):
+            msg = f"1 to {MAX_EVAL_KS} distinct cut-offs >= 1 expected: {ks = }"
+            raise ValueError(msg)
+        self.ks, self.top_k, self.prefix = ks, ks[0], prefix
+        self.names = tuple(name if j == 0 else f"{name}@{k}" for j, k in enumerate(ks) for name in METRIC_NAMES) + POSITION_METRIC_NAMES
+        self.reset()
+
+    def reset(self) -> None:
+        self._sum, self._n = None, 0
+
+    @torch.no_grad()
+    def update(self, pos: torch.Tensor, target_offsets: torch.Tensor, target_rating: torch.Tensor, ncand: torch.Tensor) -> torch.Tensor:
+        """``pos`` [T] and ``ncand`` [Q] as ``ItemIndex.positions`` returns them; the targets of query q are entries
+        ``target_offsets[q] : target_offsets[q + 1]`` of ``pos`` / ``target_rating``.  Returns [Q, 6 * len(ks) + 3]."""
+        p = _lib.dev_i64(pos, "pos")
+        off = _lib.dev_i64(target_offsets, "target_offsets")
+        rel = _lib.dev_f32(target_rating, "target_rating")
+        nc = _lib.dev_i64(ncand, "ncand")
+        q = nc.numel()
+        if off.numel() != q + 1 or p.numel() != rel.numel():
+            msg = f"target CSR does not match the queries: {off.numel() = }, {q = }, {p.numel() = }, {rel.numel() = }"
+            raise ValueError(msg)
+        if p.numel() == 0:       # keep the pointers valid
+            p, rel = torch.zeros(1, dtype=torch.int64, device=nc.device), torch.zeros(1, device=nc.device)
+        out = torch.empty(q, len(self.names), dtype=torch.float32, device=nc.device)
+        ks = (ctypes.c_int32 * len(self.ks))(*self.ks)
+        _lib.check(_lib.lib().mf_position_metrics(p.data_ptr(), off.data_ptr(), rel.data_ptr(), nc.data_ptr(), q, ks, len(self.ks),
+                                                  out.data_ptr(), _lib.stream_ptr()))
+        tot = out.sum(dim=0, dtype=torch.float64)
+        self._sum = tot if self._sum is None else self._sum + tot
+        self._n += q
+        return out
+
+    def compute(self) -> dict[str, torch.Tensor]:
+        if not self._n:
+            return {self.prefix + name: torch.tensor(0.0) for name in self.names}
+        mean = (self._sum / self._n).to(torch.float32)
+        return {self.prefix + name: mean[j] for j, name in enumerate(self.names)}

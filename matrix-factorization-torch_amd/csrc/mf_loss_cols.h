@@ -2,7 +2,7 @@
 //
 // A Zipf batch repeats its popular items: of the 16,384 columns of the headline step ~10,700 are distinct.  Copies of a
 // column have the same row bits (the tower gather is deterministic) and the same logQ, hence the same logit for every
-// user; the three sweeps (mf_loss.hip) then stream the N' distinct columns -- v'[k], |v'|^2, -logq', weight w[k] -- instead
+// user; the three sweeps (mf_loss_dense.hip) then stream the N' distinct columns -- v'[k], |v'|^2, -logq', weight w[k] -- instead
 // of all N.  The loss API takes v[N, d] and logq[N] as free inputs, so an id alone proves nothing: column j is a COPY iff
 //     f = colfirst[j] != j,  the d floats of v[j] equal those of v[f] bit for bit,  and  -logq[j] equals -logq[f] bit for bit
 // (the rule of the mining prefilter's rep[], mf_mine_bf.h).  Any other column is KEPT; a column whose id repeats with other

@@ -1,5 +1,5 @@
 // mf_loss_math.h -- per-row arithmetic of the seven losses (statistics, loss values, backward coefficients), shared by the
-// batch kernels of mf_loss.hip and the one-workgroup step of mf_step_small.hip: the same expressions, compiled once each way
+// batch kernels of the loss units (mf_loss*.hip) and the one-workgroup step of mf_step_small.hip: the same expressions, compiled once each way
 // with -ffp-contract=off, give the same bits.
 // Reference restated: alignment/contrastive/infonce/mine xfmr_rec/losses.py:164-246, pairwise :324-359; SURVEY.md Appendix A.
 #pragma once

@@ -90,17 +90,8 @@ static inline MineBfPlan mine_bf_plan(int64_t B, int64_t N, int d, int k) {
     return p;
 }
 
-// run-time switch: 1 = the prefilter where it pays (default), 2 = wherever it can serve (tests and the stress compare the two
-// searches on small shapes), 0 = the fp32 search everywhere; MF_MINE_BF in the environment sets the initial value
-static int g_mine_bf_mode = -1;
-static inline int mine_bf_mode() {
-    if (g_mine_bf_mode < 0) {
-        const char* e = getenv("MF_MINE_BF");
-        g_mine_bf_mode = (e && e[0] == '0') ? 0 : (e && e[0] == '2') ? 2 : 1;
-    }
-    return g_mine_bf_mode;
-}
-static inline bool mine_bf_use(const MineBfPlan& p) { return p.ok && (mine_bf_mode() == 2 || (mine_bf_mode() == 1 && p.pays)); }
+// (the run-time switch between this path and the fp32 search -- mf_set_mining_prefilter, MF_MINE_BF -- is process-wide state
+// and lives in mf_loss_mined.hip; the plan above is host arithmetic and may be included wherever the workspace is laid out)
 
 #ifdef __HIPCC__
 
@@ -668,7 +659,7 @@ __device__ __forceinline__ int mine_copies(const MineRescore& p, int64_t x, unsi
 }
 
 // One wave (= one workgroup) per user (grid: the padded user count).  The wave also FINISHES its user -- Fin::run: the selected
-// columns, their logits, the row's statistics (MinedRowFinish in mf_loss.hip; mined_rows_kernel's second half) --: the row lists
+// columns, their logits, the row's statistics (MinedRowFinish in mf_loss_mined.hip; mined_rows_kernel's second half) --: the row lists
 // of the fp32 search (cand / cand_cnt) are not written on this path at all.
 template <int D, class Fin>
 __global__ __launch_bounds__(64) void mine_rescore_kernel(MineRescore p, typename Fin::Params fp) {

@@ -1,8 +1,8 @@
 """Cases of the dense (unmined) loss at which a workgroup of the three sweeps streams SEVERAL tiles, shared by
 tests/test_dense_sweep_cpu.py (the cases themselves, checked without a GPU) and tests/test_gpu_dense_sweeps.py.
 
-csrc/mf_loss.hip splits the streamed axis of the forward, dU and dV sweeps into ranges of ``tps`` tiles per workgroup
-(split_geometry; a tile is 32 columns).  With four waves per workgroup ``tps`` > 1 needs Bp * Np > 2^21, above every other
+csrc/mf_loss_dense.hip splits the streamed axis of the forward, dU and dV sweeps into ranges of ``tps`` tiles per workgroup
+(split_geometry, csrc/mf_loss_cols.h, applied in csrc/mf_loss_ws.h; a tile is 32 columns).  With four waves per workgroup ``tps`` > 1 needs Bp * Np > 2^21, above every other
 dense case that is compared with a reference.  What a workgroup does depends on its tile count: one tile skips the
 pipelined loop, two take the first iteration and the tail, three or more enter the loop unrolled by two tiles, five wrap
 the forward's 4-deep side-input ring, four wrap the 3-slot ring of the d = 32 backward, and the last split may be shorter

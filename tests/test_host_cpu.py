@@ -94,7 +94,8 @@ def test_mining_prefilter_plan_holds_what_its_kernels_write(mf):
 
 
 def test_loss_plan_tells_how_many_tiles_a_workgroup_streams(mf):
-    """mf_loss_plan is host arithmetic on the launch geometry of the dense sweeps (split_geometry, csrc/mf_loss.hip).
+    """mf_loss_plan is host arithmetic on the launch geometry of the dense sweeps (split_geometry, as csrc/mf_loss_ws.h
+    applies it for the sweeps of csrc/mf_loss_dense.hip).
     What a workgroup does depends on its tile count, so the tests that are about the multi-tile paths
     (tests/test_gpu_dense_sweeps.py) assert through it that they reach them -- and this one, that the dense cases of
     the older tests never did: one tile per workgroup up to Bp * Np = 2^21."""

@@ -400,6 +400,37 @@ int mf_target_positions(const float* q, int64_t Q, const float* items, int64_t N
                         const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base,
                         void* ws, size_t ws_bytes, int64_t* out_pos, float* out_score, int64_t* out_ncand, mf_stream_t stream);
 
+/* Positions over a ROW-SHARDED catalog: every shard holds N rows, local row l = global row g(l) = l * stride + offset
+ * (round-robin: stride = shards, offset = shard; contiguous blocks: stride = 1, offset = first row), and the global order is
+ * mf_target_positions' on the whole catalog: order word (mf_orderable of the chain score) descending, then global row ascending.
+ * Two calls per shard, one exchange between them, one after:
+ *
+ * mf_target_words: out_word[e] (int64, a value in [0, 2^32)) = the order word of entry e's row against its query when this
+ *   shard holds the row -- tgt_idx[e] - offset >= 0, divisible by stride, quotient < N; the bits the slab of the searches
+ *   holds -- and 0 otherwise.  Exclusion lists play no part.  The caller takes the MAXIMUM over the shards: at most one holds a row.
+ *   One launch, no workspace.
+ * mf_key_positions: tgt_word = those maxima.  With L = clamp(ceil((tgt_idx[e] - offset) / stride), 0, N), out_above[e] = this
+ *   shard's admissible rows l with word_l > tgt_word[e], or word_l == tgt_word[e] and l < L (g(l) grows with l, so that is
+ *   "global row below the target's"); -1 when tgt_word[e] == 0 (no shard holds the row) or when this shard holds it and it is
+ *   excluded.  out_score[e] = the score whose order word tgt_word[e] is (mf_unorderable of mf_numerics.h), -inf beside -1.  out_ncand[r] = this shard's admissible rows.
+ *   excl_off / excl_local: per-query lists of LOCAL rows (entries outside [0, N) are ignored; both may be null).
+ * The caller combines: position = sum of out_above over the shards, or -1 / -inf if any shard wrote -1; ncand = sum of
+ * out_ncand.  That equals mf_target_positions on the unsharded catalog: integers equal, scores bit for bit.  mf_key_positions
+ * runs mf_target_positions' stages on its workspace sizes (the _ws_bytes pair below returns the same numbers) with the same
+ * counting code; no host read, no allocation, integer atomics only, capturable.  Refusals, all before any launch: MF_EINVAL a
+ * null pointer (the exclusion pair may be null together), Q <= 0, N <= 0, n_targets < 0, stride < 1, offset < 0, a width outside
+ * {32, 64, 128, 256}; MF_ENOTSUP N >= 2^31, (mf_target_words) Q >= 2^31, (mf_key_positions) a 32-query slab of 4 GiB or more; MF_ENOSPC a workspace below
+ * the minimum -- in mf_target_positions' order. */
+int mf_target_words(const float* q, int64_t Q, const float* items, int64_t N, int d,
+                    const int64_t* tgt_off, const int64_t* tgt_idx, int64_t n_targets, int64_t stride, int64_t offset,
+                    int64_t* out_word, mf_stream_t stream);
+size_t mf_key_positions_ws_bytes(int64_t Q, int64_t N, int d);
+size_t mf_key_positions_min_ws_bytes(int64_t Q, int64_t N, int d);
+int mf_key_positions(const float* q, int64_t Q, const float* items, int64_t N, int d,
+                     const int64_t* tgt_off, const int64_t* tgt_idx, const int64_t* tgt_word, int64_t n_targets,
+                     int64_t stride, int64_t offset, const int64_t* excl_off, const int64_t* excl_local,
+                     void* ws, size_t ws_bytes, int64_t* out_above, float* out_score, int64_t* out_ncand, mf_stream_t stream);
+
 /* Retrieval metrics from positions (mf_target_positions): pos / tgt_rel[tgt_off[q] .. tgt_off[q+1]), ncand[Q]; ks = nk cut-offs
  * in HOST memory (1 <= nk <= 8, each >= 1, no upper limit: a k above N is legal).  out[q][6 nk + 3]: for every k the six values
  * of mf_retrieval_metrics in its order and with its conventions, "retrieved at column t" read as "position t < k" (a target at

@@ -99,6 +99,11 @@ SIGNATURES = {
     "mf_target_positions_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_target_positions": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp,
                                     c_vp]),
+    "mf_target_words": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "mf_key_positions_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
+    "mf_key_positions_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
+    "mf_key_positions": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp,
+                                 c_vp, c_vp]),
     "mf_position_metrics": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(ctypes.c_int32), c_int, c_vp, c_vp]),
     "mf_pool_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "mf_pool_forward": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp,

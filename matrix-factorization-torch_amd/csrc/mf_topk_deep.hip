@@ -19,7 +19,8 @@
 //              bitonic sort of the <= 1024 unique 64-bit keys, best first, -inf / -1 behind them.
 //
 // The slab is also all it takes to say where GIVEN rows stand in a query's order of the whole catalog (mf_target_positions:
-// stages 1 and 2, then target_positions_kernel, section 4 below) -- evaluation without a list, at any depth.
+// stages 1 and 2, then target_positions_kernel, section 4 below) -- evaluation without a list, at any depth.  Over a catalog
+// that is row-sharded the same count runs per shard on keys given from outside (mf_target_words + mf_key_positions, section 5).
 //
 // No float atomics, no host read, nothing depends on atomic arrival order.
 #include <cmath>
@@ -298,10 +299,49 @@ __device__ __forceinline__ void pos_count_few(const uint4* __restrict__ row4, in
     __syncthreads();
 }
 
-__global__ __launch_bounds__(DEEP_THREADS) void target_positions_kernel(const unsigned* __restrict__ slab, int64_t Np, int64_t N, int64_t q0,
-                                                                        int64_t idx_base, const int64_t* __restrict__ tgt_off,
-                                                                        const int64_t* __restrict__ tgt_idx, int64_t* __restrict__ out_pos,
-                                                                        float* __restrict__ out_score, int64_t* __restrict__ out_ncand) {
+// Where an entry's key comes from -- src(row, e, key) sets the key of target entry e against this query's slab row, and leaves
+// the 0 it finds there when the entry is not admissible.
+// PosOwnRow: the catalog is whole, the entry names one of its rows and the key is read off that row's slab word.
+struct PosOwnRow {
+    int64_t N, idx_base;
+    const int64_t* __restrict__ tgt_idx;
+    __device__ __forceinline__ void operator()(const unsigned* row, int64_t e, unsigned long long& key) const {
+        const int64_t y = tgt_idx[e] - idx_base;
+        if (y >= 0 && y < N) {
+            const unsigned w = row[y];
+            if (w != 0u) key = pos_key(w, (unsigned)y);
+        }
+    }
+};
+// PosGivenKey: the catalog is ONE SHARD of N rows, local row l = global row l * stride + offset, and the entry's word was
+// computed by the shard that holds its global row g (mf_target_words, the maximum over the shards; 0: nobody holds it).  Global
+// order = word descending, then global row ascending; g(l) grows with l, so this shard's rows above (word, g) are those with a
+// larger word, or the same word and l < L = clamp(ceil((g - offset) / stride), 0, N) -- the comparison against (word << 32 | ~L),
+// and on the shard that holds g, L is the row itself: there a slab word of 0 (excluded) makes the entry inadmissible.
+struct PosGivenKey {
+    int64_t N, stride, offset;
+    const int64_t* __restrict__ tgt_idx;
+    const int64_t* __restrict__ tgt_word;
+    __device__ __forceinline__ void operator()(const unsigned* row, int64_t e, unsigned long long& key) const {
+        const unsigned w = (unsigned)tgt_word[e];
+        if (w == 0u) return;
+        const int64_t g = tgt_idx[e];
+        int64_t L = 0;
+        if (g >= offset) {                                   // (g - offset cannot overflow: both are >= 0 here)
+            const int64_t dist = g - offset, quo = dist / stride;
+            if (quo >= N) L = N;                             // beyond the last row: every equal word is above
+            else if (quo * stride != dist) L = quo + 1;      // between two rows
+            else if (row[quo] == 0u) return;                 // this shard's row, and it is excluded
+            else L = quo;
+        }
+        key = pos_key(w, (unsigned)L);
+    }
+};
+
+// one query's targets against its slab row (every thread of the workgroup; r = the query's row of the slab, q0 + r its number)
+template <class Src>
+__device__ __forceinline__ void pos_count_row(const unsigned* slab, int64_t Np, int64_t q0, const int64_t* tgt_off, const Src src, int64_t* out_pos,
+                                              float* out_score, int64_t* out_ncand) {
     __shared__ unsigned long long keys[POS_PASS];
     __shared__ unsigned bins[POS_PASS];
     __shared__ int red[DEEP_THREADS / 64][POS_FEW + 1];
@@ -314,19 +354,13 @@ __global__ __launch_bounds__(DEEP_THREADS) void target_positions_kernel(const un
 
     for (int64_t p0 = e0; p0 == e0 || p0 < e1; p0 += POS_PASS) {        // (a query without targets: one pass, for its count)
         const int m = (int)(e1 - p0 < POS_PASS ? (e1 > p0 ? e1 - p0 : 0) : POS_PASS);
-        // entry tid + 256 j of the pass: its key from one slab word (0: excluded, out of range -- not admissible)
+        // entry tid + 256 j of the pass: its key (0: excluded, out of range -- not admissible)
         unsigned long long mine[POS_PASS / DEEP_THREADS];
 #pragma unroll
         for (int j = 0; j < POS_PASS / DEEP_THREADS; ++j) {
             const int t = tid + DEEP_THREADS * j;
             mine[j] = 0ull;
-            if (t < m) {
-                const int64_t y = tgt_idx[p0 + t] - idx_base;
-                if (y >= 0 && y < N) {
-                    const unsigned w = row[y];
-                    if (w != 0u) mine[j] = pos_key(w, (unsigned)y);
-                }
-            }
+            if (t < m) src(row, p0 + t, mine[j]);
         }
         if (m <= POS_FEW) {
             if (tid < POS_FEW) keys[tid] = tid < m && mine[0] != 0ull ? mine[0] : ~0ull;
@@ -425,6 +459,70 @@ __global__ __launch_bounds__(DEEP_THREADS) void target_positions_kernel(const un
             out_ncand[q0 + r] = t;
         }
         __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(DEEP_THREADS) void target_positions_kernel(const unsigned* __restrict__ slab, int64_t Np, int64_t N, int64_t q0,
+                                                                        int64_t idx_base, const int64_t* __restrict__ tgt_off,
+                                                                        const int64_t* __restrict__ tgt_idx, int64_t* __restrict__ out_pos,
+                                                                        float* __restrict__ out_score, int64_t* __restrict__ out_ncand) {
+    pos_count_row(slab, Np, q0, tgt_off, PosOwnRow{N, idx_base, tgt_idx}, out_pos, out_score, out_ncand);
+}
+
+// ------------------------------------------------------------------- 5. positions over a row-sharded catalog ----
+// One shard's share of a position: the same count, the entries' keys given from outside (PosGivenKey above).
+__global__ __launch_bounds__(DEEP_THREADS) void shard_key_count_kernel(const unsigned* __restrict__ slab, int64_t Np, int64_t N, int64_t q0,
+                                                                       int64_t stride, int64_t offset, const int64_t* __restrict__ tgt_off,
+                                                                       const int64_t* __restrict__ tgt_idx, const int64_t* __restrict__ tgt_word,
+                                                                       int64_t* __restrict__ out_above, float* __restrict__ out_score,
+                                                                       int64_t* __restrict__ out_ncand) {
+    pos_count_row(slab, Np, q0, tgt_off, PosGivenKey{N, stride, offset, tgt_idx, tgt_word}, out_above, out_score, out_ncand);
+}
+
+// The words themselves: entry e of query r names global row g; the shard that holds it (local row l = (g - offset) / stride)
+// writes mf_orderable of the canonical chain q_r . items_l -- the bits its MFMA slab holds at [r][l] -- and every other shard 0.
+// One lane per entry (the chain is one accumulator), workgroup (r, c) takes entries c * 256 + tid, + WORDS_SPLIT * 256, .. of
+// query r's list with the query row in LDS (every lane reads the same word: a broadcast) and the item row from memory in
+// 16-byte loads, up to 128 floats in flight.
+static constexpr int WORDS_THREADS = 256;
+static constexpr int WORDS_SPLIT = 4;
+
+template <int D>
+__global__ __launch_bounds__(WORDS_THREADS) void shard_words_kernel(const float* __restrict__ q, const float* __restrict__ items, int64_t N,
+                                                                     const int64_t* __restrict__ tgt_off, const int64_t* __restrict__ tgt_idx,
+                                                                     int64_t stride, int64_t offset, int64_t* __restrict__ out_word) {
+    __shared__ __attribute__((aligned(16))) float xq[D];
+    const int64_t r = blockIdx.x;
+    const int64_t e0 = tgt_off[r] + (int64_t)blockIdx.y * WORDS_THREADS, e1 = tgt_off[r + 1];
+    if (e0 >= e1) return;                                    // (uniform)
+    for (int i = threadIdx.x; i < D; i += WORDS_THREADS) xq[i] = q[r * D + i];
+    __syncthreads();
+    constexpr int B = D < 128 ? D : 128;
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += (int64_t)WORDS_SPLIT * WORDS_THREADS) {
+        const int64_t g = tgt_idx[e];
+        unsigned word = 0u;
+        if (g >= offset) {                                   // (g - offset cannot overflow: both are >= 0 here)
+            const int64_t dist = g - offset, l = dist / stride;
+            if (l * stride == dist && l < N) {
+                const float* __restrict__ row = items + l * D;
+                float acc = 0.f;
+#pragma unroll
+                for (int g0 = 0; g0 < D; g0 += B) {
+                    f32x4 y[B / 4];
+#pragma unroll
+                    for (int j = 0; j < B / 4; ++j) y[j] = *reinterpret_cast<const f32x4*>(row + g0 + 4 * j);
+#pragma unroll
+                    for (int k = 0; k < B; k += 8)           // k order of mf_dot_chain
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            acc = __builtin_fmaf(xq[g0 + k + t], y[k / 4][t], acc);
+                            acc = __builtin_fmaf(xq[g0 + k + 4 + t], y[k / 4 + 1][t], acc);
+                        }
+                }
+                word = mf_orderable(acc);
+            }
+        }
+        out_word[e] = (int64_t)word;
     }
 }
 
@@ -549,4 +647,50 @@ extern "C" int mf_target_positions(const float* q, int64_t Q, const float* items
             slab, p.Np, N, q0, idx_base, tgt_off, tgt_idx, out_pos, out_score, out_ncand)));
     }
     return mf_check_launch("mf_target_positions");
+}
+
+// ---- positions over a row-sharded catalog: every shard runs the two calls below, the caller combines (mf_hip.h)
+extern "C" int mf_target_words(const float* q, int64_t Q, const float* items, int64_t N, int d, const int64_t* tgt_off,
+                               const int64_t* tgt_idx, int64_t n_targets, int64_t stride, int64_t offset, int64_t* out_word,
+                               mf_stream_t stream) {
+    if (!q || !items || !tgt_off || !tgt_idx || !out_word || Q <= 0 || N <= 0 || n_targets < 0 || stride < 1 || offset < 0)
+        return mf_set_error(MF_EINVAL, "mf_target_words: bad argument");
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_target_words: embedding width %d not in {32,64,128,256}", d);
+    if (N >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_target_words: item indices must fit 32 bits");
+    if (Q >= (1ll << 31)) return mf_set_error(MF_ENOTSUP, "mf_target_words: Q = %lld queries exceed one launch", (long long)Q);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MF_DISPATCH_D(d, {
+        MF_TIMED("target_words", s, (shard_words_kernel<D><<<dim3((unsigned)Q, WORDS_SPLIT), WORDS_THREADS, 0, s>>>(
+            q, items, N, tgt_off, tgt_idx, stride, offset, out_word)));
+    });
+    return mf_check_launch("mf_target_words");
+}
+
+extern "C" size_t mf_key_positions_ws_bytes(int64_t Q, int64_t N, int d) { return mf_target_positions_ws_bytes(Q, N, d); }
+extern "C" size_t mf_key_positions_min_ws_bytes(int64_t Q, int64_t N, int d) { return mf_target_positions_min_ws_bytes(Q, N, d); }
+
+extern "C" int mf_key_positions(const float* q, int64_t Q, const float* items, int64_t N, int d, const int64_t* tgt_off,
+                                const int64_t* tgt_idx, const int64_t* tgt_word, int64_t n_targets, int64_t stride, int64_t offset,
+                                const int64_t* excl_off, const int64_t* excl_local, void* ws, size_t ws_bytes, int64_t* out_above,
+                                float* out_score, int64_t* out_ncand, mf_stream_t stream) {
+    if (!tgt_off || !tgt_idx || !tgt_word || !out_ncand || n_targets < 0 || stride < 1 || offset < 0)
+        return mf_set_error(MF_EINVAL, "mf_key_positions: bad argument");
+    if (const int rc = mf_topk_check_args("mf_key_positions", {1, 32, 31, 0}, q, Q, items, N, d, 1, excl_off, excl_local, 0, ws, out_score,
+                                          out_above))
+        return rc;
+    const DeepPlan p = deep_plan(Q, N, d, 1);
+    if (!p.ok)
+        return mf_set_error(MF_ENOTSUP, "mf_key_positions: a 32-query score slab of %lld columns exceeds the descriptor limit", (long long)N);
+    const int64_t qb = deep_qb(p, ws_bytes);
+    if (qb < 32) return mf_set_error(MF_ENOSPC, "mf_key_positions: workspace too small");
+    if (!deep_extent_ok(p, qb, d)) return mf_set_error(MF_ENOTSUP, "mf_key_positions: extent beyond the descriptor limit");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned* slab = static_cast<unsigned*>(ws);
+    for (int64_t q0 = 0; q0 < Q; q0 += qb) {
+        const int64_t nq = Q - q0 < qb ? Q - q0 : qb;
+        if (const int rc = deep_fill_slab(q, q0, nq, Q, items, N, d, p, excl_off, excl_local, 0, slab, s)) return rc;
+        MF_TIMED("key_positions", s, (shard_key_count_kernel<<<dim3((unsigned)nq), DEEP_THREADS, 0, s>>>(
+            slab, p.Np, N, q0, stride, offset, tgt_off, tgt_idx, tgt_word, out_above, out_score, out_ncand)));
+    }
+    return mf_check_launch("mf_key_positions");
 }

@@ -33,7 +33,8 @@ below is the north-star's and our design:
 * **retrieval**: queries are all-gathered, every rank scans ITS shard for all queries
   (``mf_topk`` on local rows, mapped to global rows before they leave), the partial top-k travel back to the query's rank by
   all-to-all and are merged exactly (``mf_topk_merge``): bit-identical to the
-  single-GPU result.
+  single-GPU result.  Evaluation needs no list: the exact place of given target rows over all shards is a sum of per-shard
+  counts once the owner's key of a target has reached every shard (``ShardedIndex.positions``).
 
 Local compute goes through an ``ops`` object (default :class:`HipOps`) and the exchanges through a ``comm``
 object, so that the routing logic can be exercised on CPU with ``gloo`` by injecting the oracle.
@@ -311,10 +312,22 @@ class HipOps:
         # built once.  The entry holds the source tensor itself (so its address cannot be handed to another tensor while
         # the entry lives) and its version counter: an in-place change of the rows rebuilds the index.  Like the
         # reference's index (a table written by get_index) it is a SNAPSHOT of the rows at build time.
+        return self._shard_index(items, idx_base).search(queries, k, exclude_csr=exclude_csr)
+
+    def _shard_index(self, items, idx_base=0):
         hit = self.__dict__.get("_index")
         if hit is None or hit[0] is not items or hit[1] != items._version or hit[2] != int(idx_base):
             hit = self._index = (items, items._version, int(idx_base), self.mf.retrieval.ItemIndex(items, idx_base=idx_base))
-        return hit[3].search(queries, k, exclude_csr=exclude_csr)
+        return hit[3]
+
+    def target_words(self, queries, items, targets_csr, stride, offset):
+        """Order words of the target rows this shard holds, 0 for the others (``ItemIndex.target_words``, on ``topk``'s index)."""
+        return self._shard_index(items).target_words(queries, targets_csr, stride=stride, offset=offset)
+
+    def key_positions(self, queries, items, targets_csr, words, stride, offset, exclude_local_csr):
+        """This shard's rows above every target's key, and its admissible rows (``ItemIndex.key_positions``)."""
+        return self._shard_index(items).key_positions(queries, targets_csr, words, stride=stride, offset=offset,
+                                                      exclude_local_csr=exclude_local_csr)
 
     def drop_indexes(self) -> None:
         self.__dict__.pop("_index", None)
@@ -749,7 +762,8 @@ class ShardedTrainer:
 
 
 class ShardedIndex:
-    """Exact top-k over a row-sharded catalog; bit-identical to the single-GPU result.  Local row l of
+    """Exact top-k (``search``) and exact target positions (``positions``) over a row-sharded catalog; bit-identical to the
+    single-GPU results.  Local row l of
     this rank's shard is global item row ``l * stride + offset`` (round-robin rows: stride = world,
     offset = rank; contiguous blocks: stride = 1, offset = first row)."""
 
@@ -774,6 +788,54 @@ class ShardedIndex:
         ours = (d >= 0) & (torch.remainder(d, self.stride) == 0)
         return torch.where(ours, torch.div(d, self.stride, rounding_mode="floor"), torch.full_like(d, -1))
 
+    def _gather_lists(self, lists_csr, q: int, capacity: int | None, name: str):
+        """Every rank's per-query lists ``(off [q + 1], ids)`` as ONE CSR over all ``world * q`` queries, rank after rank:
+        ``(offsets [world * q + 1], ids, first entry of this rank's block)``.  ``capacity=None``: the lists travel at their exact
+        lengths -- one host read of the other ranks' lengths; ``capacity=C`` (a bound on ``ids.numel()`` the caller knows on the
+        host, the same on every rank): every rank sends a block of C entries padded with -1 and the offsets are rebased onto the
+        blocks on the device -- no host sync; a block's padding rides with its last query."""
+        comm, world = self.comm, self.comm.world
+        off, ids = lists_csr
+        device = off.device
+        if capacity is not None:
+            cap = int(capacity)
+            if ids.numel() > cap or cap < 1:
+                msg = f"{name} = {cap} but this rank's lists hold {ids.numel()} entries"
+                raise ValueError(msg)
+            padded = torch.full((cap,), -1, dtype=torch.int64, device=device)
+            padded[: ids.numel()] = ids
+            all_ids = comm.gather(padded)                                        # [world * cap]
+            all_off = comm.gather(off.contiguous()).reshape(world, q + 1)        # every rank's offsets, from 0
+            base = torch.arange(world, device=device, dtype=torch.int64)[:, None] * cap
+            starts = (all_off[:, :q] + base).reshape(-1)                         # query (r, i) starts inside block r ...
+            end = torch.full((1,), world * cap, dtype=torch.int64, device=device)
+            return torch.cat([starts, end]), all_ids, comm.rank * cap            # ... and a block's padding rides with its last query
+        n_loc = torch.tensor([ids.numel()], dtype=torch.int64, device=device)
+        n_all = [int(x) for x in comm.gather(n_loc).tolist()]       # host sync: list lengths
+        cap = max(max(n_all), 1)
+        padded = torch.zeros(cap, dtype=torch.int64, device=device)
+        padded[: ids.numel()] = ids
+        all_ids = comm.gather(padded)
+        all_off = comm.gather(off.contiguous())
+        pieces, offs, base = [], [torch.zeros(1, dtype=torch.int64, device=device)], 0
+        for r in range(world):
+            pieces.append(all_ids[r * cap: r * cap + n_all[r]])
+            offs.append(all_off[r * (q + 1) + 1: (r + 1) * (q + 1)] + base)
+            base += n_all[r]
+        return torch.cat(offs), torch.cat(pieces), sum(n_all[: comm.rank])
+
+    def _exclusions(self, exclude_csr, q: int, exclude_capacity: int | None):
+        """All ranks' exclusion lists as LOCAL rows of this shard (-1: not ours, ignored by the scan), or None.  The same lists
+        as the last call (same tensors, same capacity) are gathered once."""
+        if exclude_csr is None:
+            return None
+        key = (exclude_csr[0].data_ptr(), exclude_csr[1].data_ptr(), exclude_csr[1].numel(), q, exclude_capacity)
+        if getattr(self, "_csr_key", None) != key:
+            off_all, ids_all, _ = self._gather_lists(exclude_csr, q, exclude_capacity, "exclude_capacity")
+            local = self._localise(ids_all) if ids_all.numel() else torch.full((1,), -1, dtype=torch.int64, device=off_all.device)
+            self._csr_key, self._csr_all, self._csr_src = key, (off_all, local), exclude_csr   # (keeps the source tensors alive)
+        return self._csr_all
+
     def search(self, queries: torch.Tensor, top_k: int, *, exclude_csr=None, exclude_capacity: int | None = None):
         """``exclude_csr = (off [q + 1], ids)``: this rank's queries' exclusion lists (global item rows).  Every rank needs every
         rank's lists (it scans its shard for ALL queries).  Default: the lists travel at their exact lengths, which costs one
@@ -785,42 +847,7 @@ class ShardedIndex:
         world = comm.world
         q, d = queries.shape
         all_q = comm.gather(queries)
-        csr = None
-        key = None if exclude_csr is None else (exclude_csr[0].data_ptr(), exclude_csr[1].data_ptr(), exclude_csr[1].numel(), q, exclude_capacity)
-        if key is not None and getattr(self, "_csr_key", None) == key:
-            csr = self._csr_all                       # same exclusion lists as the last call: gathered once
-        elif exclude_csr is not None and exclude_capacity is not None:
-            off, ids = exclude_csr
-            cap = int(exclude_capacity)
-            if ids.numel() > cap or cap < 1:
-                msg = f"exclude_capacity = {cap} but this rank's lists hold {ids.numel()} entries"
-                raise ValueError(msg)
-            padded = torch.full((cap,), -1, dtype=torch.int64, device=queries.device)
-            padded[: ids.numel()] = ids
-            all_ids = comm.gather(padded)                                        # [world * cap]
-            all_off = comm.gather(off.contiguous()).reshape(world, q + 1)        # every rank's offsets, from 0
-            base = torch.arange(world, device=queries.device, dtype=torch.int64)[:, None] * cap
-            starts = (all_off[:, :q] + base).reshape(-1)                         # query (r, i) starts inside block r ...
-            end = torch.full((1,), world * cap, dtype=torch.int64, device=queries.device)
-            csr = (torch.cat([starts, end]), self._localise(all_ids))            # ... and a block's padding rides with its last query: -1, ignored
-            self._csr_key, self._csr_all, self._csr_src = key, csr, exclude_csr
-        elif exclude_csr is not None:
-            off, ids = exclude_csr
-            n_loc = torch.tensor([ids.numel()], dtype=torch.int64, device=queries.device)
-            n_all = [int(x) for x in comm.gather(n_loc).tolist()]       # host sync: list lengths
-            cap = max(max(n_all), 1)
-            padded = torch.zeros(cap, dtype=torch.int64, device=queries.device)
-            padded[: ids.numel()] = ids
-            all_ids = comm.gather(padded)
-            all_off = comm.gather(off.contiguous())
-            pieces, offs, base = [], [torch.zeros(1, dtype=torch.int64, device=queries.device)], 0
-            for r in range(world):
-                pieces.append(all_ids[r * cap: r * cap + n_all[r]])
-                offs.append(all_off[r * (q + 1) + 1: (r + 1) * (q + 1)] + base)
-                base += n_all[r]
-            ids_all = torch.cat(pieces) if base else torch.zeros(1, dtype=torch.int64, device=queries.device)
-            csr = (torch.cat(offs), self._localise(ids_all) if base else ids_all - 1)
-            self._csr_key, self._csr_all, self._csr_src = key, csr, exclude_csr   # (keeps the source tensors alive)
+        csr = self._exclusions(exclude_csr, q, exclude_capacity)
         ps, pi = self.ops.topk(all_q, self.items, top_k, csr, 0)                 # [world * q, k], local rows
         if hasattr(self.ops, "pack"):
             # scores and global rows as ONE int64 per entry: one launch for the row mapping, one exchange, merged as they are
@@ -830,3 +857,39 @@ class ShardedIndex:
         rs = comm.equal(ps)                                                      # block g -> rank g
         ri = comm.equal(pi)
         return self.ops.merge(rs.reshape(world, q, top_k), ri.reshape(world, q, top_k), top_k)
+
+    def positions(self, queries: torch.Tensor, targets_csr, *, exclude_csr=None, exclude_capacity: int | None = None,
+                  target_capacity: int | None = None):
+        """``(pos int64 [T], score fp32 [T], ncand int64 [q])`` for this rank's queries and the entries of ``targets_csr = (off
+        [q + 1], global item rows [T])``: what ``ItemIndex.positions`` returns on the whole catalog -- the exact place of every
+        target among the query's admissible rows of ALL shards (score descending, then global row ascending), -1 / -inf for a
+        row that is excluded or in no shard.  Positions add over shards: the shard that holds a target's row computes its order
+        word (``target_words``), the maximum over the ranks hands it to everybody, every rank counts its own rows above that key
+        (``key_positions``) and the counts are summed.  Target lists travel like exclusion lists: at exact lengths (one host read
+        of the other ranks' lengths) or, with ``target_capacity``, in padded blocks with no host sync -- the -1 padding rides with
+        a block's last query, is in no shard, and is dropped when the rank takes its own entries."""
+        comm, world = self.comm, self.comm.world
+        q = queries.shape[0]
+        t_off, t_ids = targets_csr
+        if t_off.numel() != q + 1:
+            msg = f"one target list per query expected: {t_off.numel() = }, {q = }"
+            raise ValueError(msg)
+        nt = t_ids.numel()
+        all_q = comm.gather(queries)
+        off_all, ids_all, first = self._gather_lists((t_off, t_ids), q, target_capacity, "target_capacity")
+        excl = self._exclusions(exclude_csr, q, exclude_capacity)
+        targets = (off_all, ids_all)
+        words = self.ops.target_words(all_q, self.items, targets, self.stride, self.offset)       # ours, 0 for the others' rows
+        total = ids_all.numel()
+        if total:
+            words = comm.gather(words).reshape(world, total).max(dim=0).values                     # at most one rank holds a row
+        above, score, ncand = self.ops.key_positions(all_q, self.items, targets, words, self.stride, self.offset, excl)
+        # a few bytes per entry: every rank's counts to everybody, each keeps the sum over its own entries
+        ncand = comm.gather(ncand).reshape(world, world * q).sum(dim=0)[comm.rank * q: (comm.rank + 1) * q]
+        if not total:
+            return above, score, ncand
+        parts = comm.gather(above).reshape(world, total)[:, first: first + nt]
+        none = (parts < 0).any(dim=0)                         # excluded on its own shard, or in no shard (then on every one)
+        pos = torch.where(none, torch.full_like(parts[0], -1), parts.sum(dim=0))
+        mine = score[first: first + nt]
+        return pos, torch.where(none, torch.full_like(mine, float("-inf")), mine), ncand

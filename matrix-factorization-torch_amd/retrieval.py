@@ -140,6 +140,72 @@ class ItemIndex:
                                            score_arg.data_ptr(), ncand.data_ptr(), _lib.stream_ptr()))
         return pos, score, ncand
 
+    def _targets(self, nq: int, targets_csr, device) -> tuple[torch.Tensor, torch.Tensor, int]:
+        """A target CSR as the shard exports take it: ``(offsets, rows -- one valid word when the lists are empty, entries)``."""
+        t_off, t_ids = (_lib.dev_i64(t, name) for t, name in zip(targets_csr, ("target offsets", "target rows")))
+        if t_off.numel() != nq + 1:
+            msg = f"one target list per query expected: {t_off.numel() = }, {nq = }"
+            raise ValueError(msg)
+        nt = t_ids.numel()
+        return t_off, (t_ids if nt else torch.zeros(1, dtype=torch.int64, device=device)), nt
+
+    @staticmethod
+    def _shard_map(stride: int, offset: int) -> tuple[int, int]:
+        stride, offset = int(stride), int(offset)
+        if stride < 1 or offset < 0:
+            msg = f"global row = local row * stride + offset needs stride >= 1 and offset >= 0: {stride = }, {offset = }"
+            raise ValueError(msg)
+        return stride, offset
+
+    def target_words(self, queries: torch.Tensor, targets_csr: tuple[torch.Tensor, torch.Tensor], *, stride: int = 1,
+                     offset: int = 0) -> torch.Tensor:
+        """``int64 [T]``: for every entry of ``targets_csr = (offsets [Q + 1], GLOBAL item rows [T])`` whose row this index
+        holds -- local row l is global row ``l * stride + offset`` -- the 32-bit order word of its score (``mf_orderable`` of
+        the chain score: the word the searches rank by), 0 for a row it does not hold.  Exclusion lists play no part.  The
+        first half of positions over a row-sharded catalog (``mf_target_words``): the maximum over the shards is the word
+        ``key_positions`` takes."""
+        q = self._queries(queries)
+        nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        stride, offset = self._shard_map(stride, offset)
+        t_off, t_ids, nt = self._targets(nq, targets_csr, q.device)
+        words = torch.empty(nt, dtype=torch.int64, device=q.device)
+        out = words if nt else torch.zeros(1, dtype=torch.int64, device=q.device)       # keep the pointer valid
+        _lib.check(_lib.lib().mf_target_words(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, t_off.data_ptr(), t_ids.data_ptr(), nt,
+                                              stride, offset, out.data_ptr(), _lib.stream_ptr()))
+        return words
+
+    def key_positions(self, queries: torch.Tensor, targets_csr: tuple[torch.Tensor, torch.Tensor], words: torch.Tensor, *,
+                      stride: int = 1, offset: int = 0,
+                      exclude_local_csr: tuple[torch.Tensor, torch.Tensor] | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``(above int64 [T], score fp32 [T], ncand int64 [Q])``: this shard's share of every target's position.  ``words``
+        are the targets' order words after the maximum over all shards (``target_words``); ``above[e]`` counts this shard's
+        admissible rows that stand before target e in the GLOBAL order (word descending, then global row ascending), or is
+        -1 when the word is 0 or this shard holds the row and finds it excluded; ``ncand`` counts the shard's admissible
+        rows.  Summed over the shards they are ``positions`` on the whole catalog.  ``exclude_local_csr``: per-query lists of
+        LOCAL rows (entries outside the shard are ignored).  ``mf_key_positions``."""
+        q = self._queries(queries)
+        nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        stride, offset = self._shard_map(stride, offset)
+        t_off, t_ids, nt = self._targets(nq, targets_csr, q.device)
+        w = _lib.dev_i64(words, "words")
+        if w.numel() != nt:
+            msg = f"one word per target entry expected: {w.numel() = }, {nt = }"
+            raise ValueError(msg)
+        off, ids = exclude_local_csr if exclude_local_csr is not None else (None, None)
+        above = torch.empty(nt, dtype=torch.int64, device=q.device)
+        score = torch.empty(nt, dtype=torch.float32, device=q.device)
+        ncand = torch.empty(nq, dtype=torch.int64, device=q.device)
+        if nt == 0:       # keep the pointers valid
+            w, above_arg, score_arg = (torch.zeros(1, dtype=dt, device=q.device) for dt in (torch.int64, torch.int64, torch.float32))
+        else:
+            above_arg, score_arg = above, score
+        lib = _lib.lib()
+        ws = self._workspace(("positions", nq), lib.mf_key_positions_ws_bytes(nq, n, d))
+        _lib.check(lib.mf_key_positions(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, t_off.data_ptr(), t_ids.data_ptr(), w.data_ptr(),
+                                        nt, stride, offset, _lib.ptr(off), _lib.ptr(ids), ws.data_ptr(), ws.numel(), above_arg.data_ptr(),
+                                        score_arg.data_ptr(), ncand.data_ptr(), _lib.stream_ptr()))
+        return above, score, ncand
+
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None,
                path: str = "auto") -> tuple[torch.Tensor, torch.Tensor]:
@@ -299,6 +365,18 @@ METRIC_NAMES = ("RetrievalNormalizedDCG", "RetrievalRecall", "RetrievalPrecision
                 "RetrievalMRR")
 
 
+def _all_ranks(total: torch.Tensor | None, n: int, width: int, comm):
+    """A metric's running ``(sums [width] fp64, queries)``, added over the ranks of ``comm`` (one gather of ``width + 1``
+    numbers); as they are without one.  A rank that has seen no query contributes zeros."""
+    if comm is None:
+        return total, n
+    if total is None:
+        total = torch.zeros(width, dtype=torch.float64)
+    mine = torch.cat([total, torch.tensor([float(n)], dtype=torch.float64, device=total.device)])
+    every = comm.gather(mine).reshape(comm.world, width + 1).sum(dim=0)
+    return every[:width], int(every[width].item())
+
+
 class RetrievalMetrics:
     """The reference's ``MetricCollection`` of six retrieval metrics @top_k
     (xfmr_rec/lightning.py:289-306), fed with whole batches of top-k results instead of one
@@ -338,10 +416,12 @@ class RetrievalMetrics:
         self._n += q
         return out
 
-    def compute(self) -> dict[str, torch.Tensor]:
-        if not self._n:
+    def compute(self, comm=None) -> dict[str, torch.Tensor]:
+        """``comm`` (``distributed.TorchComm`` / ``RcclComm``; every rank calls): the means over ALL ranks' queries."""
+        total, n = _all_ranks(self._sum, self._n, len(METRIC_NAMES), comm)
+        if not n:
             return {self.prefix + name: torch.tensor(0.0) for name in METRIC_NAMES}
-        mean = (self._sum / self._n).to(torch.float32)
+        mean = (total / n).to(torch.float32)
         return {self.prefix + name: mean[j] for j, name in enumerate(METRIC_NAMES)}
 
 
@@ -390,8 +470,10 @@ class PositionMetrics:
         self._n += q
         return out
 
-    def compute(self) -> dict[str, torch.Tensor]:
-        if not self._n:
+    def compute(self, comm=None) -> dict[str, torch.Tensor]:
+        """``comm`` (``distributed.TorchComm`` / ``RcclComm``; every rank calls): the means over ALL ranks' queries."""
+        total, n = _all_ranks(self._sum, self._n, len(self.names), comm)
+        if not n:
             return {self.prefix + name: torch.tensor(0.0) for name in self.names}
-        mean = (self._sum / self._n).to(torch.float32)
+        mean = (total / n).to(torch.float32)
         return {self.prefix + name: mean[j] for j, name in enumerate(self.names)}

@@ -11,6 +11,15 @@ and the spread (max - min) -- of the two calls together, and of each alone (``fi
 default: this build, where the list path's code is the same) and binds only the four exports it calls; the position path
 always runs on this tree's build.  ``positions_over_list`` is
 the measured ratio; ``max_abs_diff`` compares the six values @1000 of the two paths (reported, not asserted).
+
+    MF_HIP_LIB=path/to/parent/libmf_hip.so python tools/position_probe.py --shards 1,2,8 [--out profiles/sharded_position_probe.json]
+
+``--shards``: the sharded position path instead -- per cell and S, device time of ``mf_target_words`` + ``mf_key_positions`` on ONE
+shard of the catalog (shard 0 of S dealt round-robin: N / S rows, the exclusion lists localised, the words those of the whole
+catalog), together and each alone; beside it ``mf_target_positions`` on the whole catalog from this build and, in a child
+process, from ``MF_HIP_LIB`` / ``--list-lib`` (a build of the parent commit).  ``positions_guard`` puts the two side by side: this
+build's median may exceed the parent's by no more than the parent's own spread over its three regions.  The exchange between
+the two calls and after them is not in any of these numbers.
 """
 from __future__ import annotations
 
@@ -117,6 +126,73 @@ def positions_path(lib, items, q, excl, tgt):
     return find, metrics, out
 
 
+def shard_path(lib, items, q, excl, tgt, shards: int):
+    """Shard 0 of ``shards`` (rows 0, S, 2 S, ..): the two calls of the sharded path; the words are the whole catalog's."""
+    nq, nt = q.shape[0], tgt[1].numel()
+    part = items[::shards].contiguous()
+    n = part.shape[0]
+    local = torch.where(excl[1] % shards == 0, excl[1] // shards, torch.full_like(excl[1], -1))
+    nbytes = lib.mf_key_positions_ws_bytes(nq, n, D)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    words = torch.empty(nt, dtype=torch.int64, device=DEV)
+    mine = torch.empty(nt, dtype=torch.int64, device=DEV)
+    above = torch.empty(nt, dtype=torch.int64, device=DEV)
+    score = torch.empty(nt, device=DEV)
+    ncand = torch.empty(nq, dtype=torch.int64, device=DEV)
+    check(lib, lib.mf_target_words(q.data_ptr(), nq, items.data_ptr(), N, D, tgt[0].data_ptr(), tgt[1].data_ptr(), nt, 1, 0, words.data_ptr(),
+                                   stream()))
+
+    def find_words():
+        check(lib, lib.mf_target_words(q.data_ptr(), nq, part.data_ptr(), n, D, tgt[0].data_ptr(), tgt[1].data_ptr(), nt, shards, 0,
+                                       mine.data_ptr(), stream()))
+
+    def count():
+        check(lib, lib.mf_key_positions(q.data_ptr(), nq, part.data_ptr(), n, D, tgt[0].data_ptr(), tgt[1].data_ptr(), words.data_ptr(), nt,
+                                        shards, 0, excl[0].data_ptr(), local.data_ptr(), ws.data_ptr(), nbytes, above.data_ptr(),
+                                        score.data_ptr(), ncand.data_ptr(), stream()))
+    return find_words, count
+
+
+def run_shards(path, shard_counts, with_shards: bool) -> list[dict]:
+    """Per cell: ``mf_target_positions`` on the whole catalog and, on this tree's build, the shard calls for every S."""
+    names = ("mf_last_error", "mf_target_positions_ws_bytes", "mf_target_positions", "mf_position_metrics")
+    lib = bind(path, names + (("mf_target_words", "mf_key_positions_ws_bytes", "mf_key_positions") if with_shards else ()))
+    items = catalog()
+    cells = []
+    for nq in QS:
+        for nt in TS:
+            q, excl, tgt = inputs(nq, nt)
+            find, _, _ = positions_path(lib, items, q, excl, tgt)
+            cell = {"Q": nq, "targets": nt, "positions": measure(find)}
+            for s in shard_counts if with_shards else ():
+                find_words, count = shard_path(lib, items, q, excl, tgt, s)
+                cell[f"shards_{s}"] = {**measure(lambda: (find_words(), count())), "words_ms": measure(find_words)["ms"],
+                                       "count_ms": measure(count)["ms"], "rows": -(-N // s)}
+            cells.append(cell)
+            print(json.dumps(cell), file=sys.stderr, flush=True)
+    return cells
+
+
+def main_shards(args) -> None:
+    shard_counts = [int(x) for x in args.shards.split(",")]
+    child = subprocess.run([sys.executable, __file__, "--child", "positions", "--list-lib", args.list_lib], check=True, stdout=subprocess.PIPE,
+                           text=True)
+    parent = json.loads(child.stdout.strip().splitlines()[-1])
+    res = {"shape": {"N": N, "d": D, "exclusions_per_query": EXCL, "shards": shard_counts, "shard": "0 of S, rows dealt round-robin"},
+           "parent_lib": pathlib.Path(args.list_lib).name if pathlib.Path(args.list_lib) == DEFAULT_LIB else "parent build",
+           "unit": "ms of device time per call: median of three regions; spread_ms = max - min", "exchange": "not measured", "cells": []}
+    for mine, theirs in zip(run_shards(DEFAULT_LIB, shard_counts, True), parent):
+        assert (mine["Q"], mine["targets"]) == (theirs["Q"], theirs["targets"])
+        over = mine["positions"]["ms"] - theirs["positions"]["ms"]
+        cell = {"Q": mine["Q"], "targets": mine["targets"], "parent_positions": theirs["positions"], **{k: v for k, v in mine.items() if k not in ("Q", "targets")},
+                "positions_guard": {"slower_by_ms": over, "allowed_ms": theirs["positions"]["spread_ms"], "ok": over <= theirs["positions"]["spread_ms"]}}
+        res["cells"].append(cell)
+        print(json.dumps(cell), flush=True)
+    out_path = pathlib.Path(args.out if args.out != str(ROOT / "profiles" / "position_probe.json") else ROOT / "profiles" / "sharded_position_probe.json")
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    out_path.write_text(json.dumps(res, indent=1) + "\n")
+
+
 def bind(path, names):
     lib = ctypes.CDLL(str(path))
     sig = {
@@ -127,6 +203,9 @@ def bind(path, names):
         "mf_target_positions_ws_bytes": (sz, [i64, i64, ctypes.c_int]),
         "mf_target_positions": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_int, vp, vp, i64, vp, vp, i64, vp, sz, vp, vp, vp, vp]),
         "mf_position_metrics": (ctypes.c_int, [vp, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, vp, vp]),
+        "mf_target_words": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_int, vp, vp, i64, i64, i64, vp, vp]),
+        "mf_key_positions_ws_bytes": (sz, [i64, i64, ctypes.c_int]),
+        "mf_key_positions": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_int, vp, vp, vp, i64, i64, i64, vp, vp, vp, sz, vp, vp, vp, vp]),
     }
     for name in names:
         fn = getattr(lib, name)
@@ -157,8 +236,15 @@ def main() -> None:
     ap.add_argument("--out", default=str(ROOT / "profiles" / "position_probe.json"))
     ap.add_argument("--list-lib", default=os.environ.get("MF_HIP_LIB", str(DEFAULT_LIB)),
                     help="the library the list path is timed on: a build of the parent commit (default: MF_HIP_LIB, else this build)")
-    ap.add_argument("--child", choices=("list",), help=argparse.SUPPRESS)
+    ap.add_argument("--shards", default=None, help="comma-separated shard counts: time the sharded position path (see above)")
+    ap.add_argument("--child", choices=("list", "positions"), help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.child == "positions":
+        print(json.dumps(run_shards(args.list_lib, (), False)))
+        return
+    if args.shards:
+        main_shards(args)
+        return
     if args.child:
         print(json.dumps(run(args.list_lib, args.child)))
         return

@@ -443,6 +443,36 @@ int mf_key_positions(const float* q, int64_t Q, const float* items, int64_t N, i
 int mf_position_metrics(const int64_t* pos, const int64_t* tgt_off, const float* tgt_rel, const int64_t* ncand, int64_t Q,
                         const int32_t* ks, int nk, float* out, mf_stream_t stream);
 
+/* ------------------------------------------------------------ streaming logQ ---
+ * The table the logQ correction reads, estimated from the batches themselves (Yi et al. 2019, Algorithms 2 and 3; our
+ * spec, DESIGN.md 4 "Streaming logQ", restated in numpy as tests/_logq_spec.py).  State per bucket h: last_seen[h] (the step of
+ * its last sighting, 0 = never) and gap[h] (moving average of the steps between sightings, 0 = never).  One update at
+ * step t (>= 1, strictly increasing from call to call) touches every DISTINCT bucket of ids[n] once:
+ *     old = last_seen[h];  g = (float)(t - old)                    (int -> fp32, round to nearest even)
+ *     gap[h] = old == 0 ? g : fl(fl((1 - alpha) gap[h]) + fl(alpha g))          (1 - alpha computed once in fp32)
+ *     last_seen[h] = t
+ * and logq(id) = -logf(D), the log of the estimated per-step inclusion rate 1 / D.
+ *   direct (num_hashes = 0): arrays [n_buckets], bucket = id, D = gap[id]; ids outside [0, n_buckets) are ignored, read 0.
+ *   hashed (num_hashes = 1..4): arrays [num_hashes][n_buckets], bucket j = mf_numerics.h's mf_hash_bucket of (id, j, seed,
+ *     n_buckets), D = the largest of the id's gaps; ids sharing a bucket are one sighting; negative ids are ignored.
+ *   An id with a bucket never seen (gap == 0) reads 0.0: no estimate, no correction.
+ * A second update with the same t changes nothing.  The step is t, or -- t_dev non-null -- *t_dev read on the device (t
+ * is then ignored; the caller advances the counter, the kernels never write it; a value outside 1 .. 2^31 - 1 updates
+ * nothing): a captured call advances on replay.  logq_table (direct mode, [n_buckets], nullable) receives -logf(gap) of
+ * every updated bucket; out_logq (nullable, [n]) the read-out of ids after the update, by a second launch.
+ * mf_logq_lookup is that read-out alone.  No allocation, no host read, no synchronisation, integer atomics only;
+ * capturable.  Refusals, all before any launch: MF_EINVAL a null last_seen / gap / ids (ids may be null when n == 0) /
+ * out_logq of the lookup, n < 0, n_buckets < 1, num_hashes outside 0..4, alpha outside (0, 1], t < 1 without t_dev, a
+ * logq_table with num_hashes > 0; MF_ENOTSUP t >= 2^31, n_buckets >= 2^31, n >= 2^39.  n == 0: MF_OK, nothing launched.
+ * mf_logq_set_peel: how many of a wave's most repeated buckets are reduced to one lane before the atomic (0..8, default
+ * 4; speed only, tools/logq_probe.py). */
+int mf_logq_update(int32_t* last_seen, float* gap, int64_t n_buckets, int num_hashes, uint64_t seed, const int64_t* ids,
+                   int64_t n, int64_t t, const int64_t* t_dev, float alpha, float* logq_table, float* out_logq,
+                   mf_stream_t stream);
+int mf_logq_lookup(const float* gap, int64_t n_buckets, int num_hashes, uint64_t seed, const int64_t* ids, int64_t n,
+                   float* out_logq, mf_stream_t stream);
+void mf_logq_set_peel(int rounds);
+
 /* The batch producer on the device (replaces the host datapipe of
  * xfmr_rec/data/lightning.py:311-363 + data/load.py:38-141 for id-only towers).  The interaction list
  * pair_*[n_pairs] and the users' positive lists (CSR pos_off[num_users + 1], pos_items) stay in HBM;

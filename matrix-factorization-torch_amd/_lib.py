@@ -141,6 +141,9 @@ SIGNATURES = {
     "mf_xfmr_coalesce_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_xfmr_coalesce": (c_int, [c_i64, c_int, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
                                  c_sz, c_vp]),
+    "mf_logq_update": (c_int, [c_vp, c_vp, c_i64, c_int, c_u64, c_vp, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp, c_vp]),
+    "mf_logq_lookup": (c_int, [c_vp, c_i64, c_int, c_u64, c_vp, c_i64, c_vp, c_vp]),
+    "mf_logq_set_peel": (None, [c_int]),
 }
 
 MF_OK, MF_EINVAL, MF_ENOSPC, MF_ELAUNCH, MF_ENOTSUP = 0, -1, -2, -3, -4       # return codes (include/mf_hip.h)

@@ -26,7 +26,8 @@ import torch
 
 from . import losses as mf_losses
 from . import fused, models, optim
-from .params import INDEX_PATH, PROCESSORS_JSON, TOP_K, TOWERS_PATH
+from .logq import StreamingLogQ
+from .params import INDEX_PATH, LOGQ_PATH, PROCESSORS_JSON, TOP_K, TOWERS_PATH
 from .retrieval import ItemProcessor, PositionMetrics, RetrievalMetrics
 
 FEATURE_BAGS_PATH = "feature_bags.safetensors"     # the feature towers' registered bags (save / load)
@@ -46,6 +47,7 @@ except ImportError:  # noqa: SIM105
 
 
 METRICS_MODES = ("topk", "positions")
+LOGQ_MODES = ("table", "streaming")
 
 
 class MatrixFactorizationLitConfig(models.ModelConfig):
@@ -63,6 +65,31 @@ class MatrixFactorizationLitConfig(models.ModelConfig):
     # (ItemIndex.positions) -- any top_k, further cut-offs eval_ks in the same pass, and uncut MRR / MeanPosition / AUC
     metrics_mode: str = "topk"
     eval_ks: list[int] | None = None      # with "positions": cut-offs beside top_k (logged as name@k)
+    # "table": the module's ``logq`` is assigned by the caller (logq.logq_from_counts); "streaming": logq.StreamingLogQ estimates
+    # it from the training batches' item columns, on the device (needs use_logq)
+    logq_mode: str = "table"
+    logq_alpha: float = 0.01       # the estimator's step size: an error shrinks by 1 - alpha per sighting (a default, not tuned)
+    logq_buckets: int = 0          # 0: direct, one bucket per item row; > 0: hashed into that many buckets per hash
+    logq_hashes: int = 2           # 1..4, read only when logq_buckets > 0
+
+    @pydantic.model_validator(mode="after")
+    def _streaming_logq_fields(self):
+        if self.logq_mode not in LOGQ_MODES:
+            msg = f"logq_mode must be 'table' or 'streaming': {self.logq_mode!r}"
+            raise ValueError(msg)
+        if self.logq_mode == "streaming" and not self.use_logq:
+            msg = "logq_mode='streaming' estimates the table of the logQ correction: it needs use_logq=True"
+            raise ValueError(msg)
+        if not 0.0 < self.logq_alpha <= 1.0:
+            msg = f"logq_alpha must be in (0, 1]: {self.logq_alpha}"
+            raise ValueError(msg)
+        if not 0 <= self.logq_buckets < 2**31:
+            msg = f"logq_buckets must be 0 (direct) or a bucket count below 2^31: {self.logq_buckets}"
+            raise ValueError(msg)
+        if not 1 <= self.logq_hashes <= StreamingLogQ.MAX_HASHES:
+            msg = f"logq_hashes must be in 1..{StreamingLogQ.MAX_HASHES}: {self.logq_hashes}"
+            raise ValueError(msg)
+        return self
 
     @pydantic.field_validator("metrics_mode")
     @classmethod
@@ -85,6 +112,7 @@ class MatrixFactorizationLitModule(_Base):
         self.item_processor: ItemProcessor | None = None
         self.history: dict[int, list[int]] = {}      # user_rn -> item ids already consumed (recommend excludes them)
         self.logq: torch.Tensor | None = None         # [num_items] log sampling probability, when use_logq
+        self.logq_estimator: StreamingLogQ | None = None      # logq_mode="streaming": produces ``logq`` (direct) or the batch's rows (hashed)
         self.metrics: dict[str, RetrievalMetrics | PositionMetrics] | None = None
         self._fused: fused.FusedSmallStep | None = None
 
@@ -265,6 +293,8 @@ class MatrixFactorizationLitModule(_Base):
             idx = self.item_processor.index
             save_file({"embeddings": idx.embeddings[:, : idx.dim].cpu().contiguous(),
                        "item_ids": self.item_processor.item_ids.contiguous()}, str(path / INDEX_PATH))
+        if self.logq_estimator is not None:
+            save_file({k: v.detach().cpu().contiguous() for k, v in self.logq_estimator.state_dict().items()}, str(path / LOGQ_PATH))
 
     @classmethod
     def load(cls, path, device="cuda") -> "MatrixFactorizationLitModule":
@@ -294,6 +324,8 @@ class MatrixFactorizationLitModule(_Base):
             for k, t in module.towers.items():
                 if f"{k}.off" in bags:
                     t.set_bags(FeatureBags(bags[f"{k}.off"], bags[f"{k}.tokens"], bags.get(f"{k}.weights")))
+        if module.logq_estimator is not None and (path / LOGQ_PATH).exists():
+            module.logq_estimator.load_state_dict(load_file(str(path / LOGQ_PATH)))      # (copies into the device buffers)
         module.history = {int(k): v for k, v in proc.get("history", {}).items()}
         if (path / INDEX_PATH).exists():
             idx = load_file(str(path / INDEX_PATH))
@@ -314,20 +346,37 @@ class MatrixFactorizationLitModule(_Base):
         # positives then sampled negatives, as xfmr_rec/lightning.py:133-134
         item_idx = torch.cat([batch["item"]["idx"], batch["neg_item"]["idx"]])
         item_embed = self(item_idx, tower="item")
+        # streaming logQ: a training step's item columns are one more batch the estimator sees, before the loss reads it;
+        # evaluation reads the estimate and advances nothing
+        logq_rows = self._streaming_logq(item_idx, advance=step_name == "train" and self.training)
         # the logQ table is looked up by item_idx inside the kernel (no gather launch)
-        logq_table = self.logq if (self.config.use_logq and self.logq is not None) else None
+        logq_table = self.logq if (self.config.use_logq and self.logq is not None and logq_rows is None) else None
         cfg = self.config
         if cfg.fused_losses:
             vals = mf_losses.fused_losses(user_embed, item_embed, target, item_idx=item_idx, pos_idx=pos_idx,
                                           num_negatives=cfg.num_negatives, sigma=cfg.sigma, margin=cfg.margin,
-                                          logq_table=logq_table, pos_csr=pos_csr,
+                                          logq=logq_rows, logq_table=logq_table, pos_csr=pos_csr,
                                           train_loss=cfg.train_loss if step_name == "train" else None)
             return {f"{step_name}/{name}": v for name, v in vals.items()}
         return {
-            f"{step_name}/{fn.__class__.__name__}": fn(user_embed=user_embed, item_embed=item_embed, target=target,
-                                                       item_idx=item_idx, pos_idx=pos_idx, logq_table=logq_table, pos_csr=pos_csr)
+            f"{step_name}/{fn.__class__.__name__}": fn(user_embed=user_embed, item_embed=item_embed, target=target, item_idx=item_idx,
+                                                       pos_idx=pos_idx, logq=logq_rows, logq_table=logq_table, pos_csr=pos_csr)
             for fn in self.loss_fns
         }
+
+    def _streaming_logq(self, item_idx: torch.Tensor, *, advance: bool) -> torch.Tensor | None:
+        """``logq_mode="streaming"``: feed the estimator the step's item columns (``advance``) and hand the loss its values --
+        direct mode through ``self.logq`` (the estimator's table, updated in place: returns None), hashed mode as the rows of
+        ``item_idx`` (returned).  Without an estimator: None, ``self.logq`` is the caller's."""
+        est = self.logq_estimator
+        if est is None:
+            return None
+        if est.num_hashes == 0:
+            if advance:
+                est.update(item_idx, rows=False)
+            self.logq = est.table
+            return None
+        return est.update(item_idx) if advance else est.lookup(item_idx)
 
     # ------------------------------------------------------------------ metrics ---
     @torch.no_grad()
@@ -394,7 +443,10 @@ class MatrixFactorizationLitModule(_Base):
             msg = "`loss_fns` must be initialised first"
             raise ValueError(msg)
         cfg = self.config
-        if self._fused is None or self._fused.opt is not optimizer:
+        est = self.logq_estimator
+        if est is not None and est.num_hashes > 0:      # hashed rows go to the loss as logq=: the three calls
+            self._fused = None
+        elif self._fused is None or self._fused.opt is not optimizer:
             fn = next(f for f in self.loss_fns if f.__class__.__name__ == cfg.train_loss)
             try:
                 self._fused = fused.FusedSmallStep(self.towers, optimizer, fn, all_losses=True,
@@ -410,6 +462,8 @@ class MatrixFactorizationLitModule(_Base):
             optimizer.zero_grad(set_to_none=True)
             return loss.detach()
         flat = {"user": batch["user"]["idx"], "item": torch.cat([batch["item"]["idx"], batch["neg_item"]["idx"]]), "target": batch["target"]}
+        if est is not None:                          # direct mode: the table the step reads is updated in place, ahead of it
+            self._streaming_logq(flat["item"], advance=self.training)
         if batch["user"].get("pos_csr") is not None:
             flat["pos_csr"] = (flat["user"],) + tuple(batch["user"]["pos_csr"][1:])
         elif batch["user"].get("pos_idx") is not None:
@@ -435,6 +489,14 @@ class MatrixFactorizationLitModule(_Base):
             self.item_processor = ItemProcessor()
         if self.metrics is None:
             self.metrics = self.get_metrics()
+        cfg = self.config
+        if self.logq_estimator is None and cfg.logq_mode == "streaming":
+            where = device if device is not None else next(self.towers.parameters()).device
+            hashed = cfg.logq_buckets > 0
+            self.logq_estimator = StreamingLogQ(cfg.logq_buckets if hashed else cfg.num_items, alpha=cfg.logq_alpha,
+                                                num_hashes=cfg.logq_hashes if hashed else 0, device=where)
+            if not hashed:
+                self.logq = self.logq_estimator.table
 
     def get_model(self, device=None) -> torch.nn.ModuleDict:
         return models.init_towers(self.config, device=device)

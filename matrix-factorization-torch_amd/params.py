@@ -22,3 +22,4 @@ USERS_TABLE_NAME = "users"
 # save() layout (xfmr_rec/params.py:24-29 has transformer/ + processors.json + lance_db/; tables replace both stores)
 TOWERS_PATH = "towers.safetensors"
 INDEX_PATH = "item_index.safetensors"
+LOGQ_PATH = "logq_estimator.safetensors"      # the streaming logQ estimator's buffers (logq_mode="streaming" only)

@@ -303,7 +303,9 @@ int mf_topk(const float* q, int64_t Q, const float* items, int64_t N, int d, int
             size_t ws_bytes, float* out_scores, int64_t* out_idx, mf_stream_t stream);
 
 /* Merge G partial results (e.g. the all-gathered per-shard top-k of a row-sharded
- * catalog) part_*[G,Q,k] into the global top-k with the same order. */
+ * catalog) part_*[G,Q,k] into the global top-k with the same order.  Sized for k <= 64 (k selection rounds over the
+ * G * k keys of a query, which sit in 64 KiB of LDS: G * k <= 8192, MF_ENOTSUP "G * k too large" beyond); deeper lists:
+ * mf_topk_merge_deep below. */
 int mf_topk_merge(const float* part_scores, const int64_t* part_idx, int G, int64_t Q, int k,
                   float* out_scores, int64_t* out_idx, mf_stream_t stream);
 
@@ -315,6 +317,23 @@ int mf_topk_pack(const float* scores, const int64_t* rows, int64_t n, int64_t st
                  mf_stream_t stream);
 int mf_topk_merge_packed(const int64_t* packed, int G, int64_t Q, int k, float* out_scores, int64_t* out_idx,
                          mf_stream_t stream);
+
+/* The same two merges for deep lists, 1 <= k <= MF_TOPK_DEEP_MAX_K (what mf_topk_deep returns per shard).  Input contract as
+ * above: [G][Q][k], GLOBAL rows < 2^32 and distinct across the lists of a query, -1 (all ones in the packed form) for none,
+ * each list ordered as the searches return it (score descending, then row ascending, the none-tail last).  Results: the bits,
+ * order and -inf / -1 tail of mf_topk_merge / mf_topk_merge_packed.  One 256-thread workgroup per query holds the G * k keys
+ * in LDS and gives every entry its place by one binary search per other list (place in its own list + keys above it
+ * elsewhere): no selection rounds, no atomics, no float arithmetic; deterministic and capturable.  A key that arrives in
+ * several lists (outside the contract) counts as standing before its copies in later lists, so every column is still written
+ * exactly once; lists that are not ordered give unspecified results, never an access outside the arrays.  Refused before any
+ * launch, in this order: MF_EINVAL "bad argument" (a null pointer, G, Q or k <= 0); MF_ENOTSUP "k = .. outside 1..1024";
+ * MF_ENOTSUP "G * k too large" above MF_TOPK_MERGE_DEEP_MAX_KEYS keys (128 KiB of LDS: 16 lists at k = 1024, 64 at
+ * k = 256). */
+#define MF_TOPK_MERGE_DEEP_MAX_KEYS 16384
+int mf_topk_merge_deep(const float* part_scores, const int64_t* part_idx, int G, int64_t Q, int k,
+                       float* out_scores, int64_t* out_idx, mf_stream_t stream);
+int mf_topk_merge_packed_deep(const int64_t* packed, int G, int64_t Q, int k, float* out_scores, int64_t* out_idx,
+                              mf_stream_t stream);
 
 /* Small-batch form of mf_topk: Q <= 32 queries (the reference's search takes ONE query per call,
  * xfmr_rec/data/lightning.py:237-259; recommend, xfmr_rec/lightning.py:76-95).  A matrix-vector scan is
@@ -358,7 +377,8 @@ int mf_topk_bf3(const float* q, int64_t Q, const float* items, const void* index
  * queries; both are 0 for invalid shapes (k outside 1..1024 included).  mf_topk_deep_plan is host-only: out[0] = queries per
  * block (a multiple of 32), out[1] = blocks, out[2] = slab bytes per block for a workspace of ws_bytes.  Limits as mf_topk
  * (N < 2^31, idx_base + N <= 2^32, d in {32, 64, 128, 256}), and a 32-query slab must stay below 4 GiB (N <= ~33.5 M):
- * MF_ENOTSUP beyond, as for k outside 1..1024; MF_ENOSPC below the minimum workspace; all decided before any launch. */
+ * MF_ENOTSUP beyond, as for k outside 1..1024; MF_ENOSPC below the minimum workspace; all decided before any launch.
+ * Over a row-sharded catalog the per-shard lists of this engine are joined by mf_topk_merge_deep / mf_topk_merge_packed_deep. */
 #define MF_TOPK_DEEP_MAX_K 1024
 size_t mf_topk_deep_ws_bytes(int64_t Q, int64_t N, int d, int k);
 size_t mf_topk_deep_min_ws_bytes(int64_t Q, int64_t N, int d, int k);

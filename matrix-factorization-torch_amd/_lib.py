@@ -86,6 +86,8 @@ SIGNATURES = {
     "mf_topk_small": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "mf_topk_pack": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "mf_topk_merge_packed": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp]),
+    "mf_topk_merge_deep": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp]),
+    "mf_topk_merge_packed_deep": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp]),
     "mf_topk_bf3_index_bytes": (c_sz, [c_i64, c_int]),
     "mf_topk_bf3_build": (c_int, [c_vp, c_i64, c_int, c_vp, c_sz, c_vp]),
     "mf_topk_bf3_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
@@ -148,7 +150,8 @@ SIGNATURES = {
 
 MF_OK, MF_EINVAL, MF_ENOSPC, MF_ELAUNCH, MF_ENOTSUP = 0, -1, -2, -3, -4       # return codes (include/mf_hip.h)
 MF_TOPK_DEEP_MAX_K = 1024                                 # deepest top-k any engine serves: mf_topk_deep (include/mf_hip.h)
-XFMR_FP32, XFMR_BF16_MIXED = 0, 1                         # precision of the transformer tower's dense layers (include/mf_hip.h)
+MF_TOPK_MERGE_DEEP_MAX_KEYS = 16384                       # G * k keys of a query the deep merges hold in LDS (include/mf_hip.h)
+XFMR_FP32, XFMR_BF16_MIXED = 0, 1                        # precision of the transformer tower's dense layers (include/mf_hip.h)
 LOSS_TARGET_I64, LOSS_ROWC, LOSS_MASKS_READY = 1, 2, 4     # flags of mf_loss_fwd / mf_loss_bwd (include/mf_hip.h)
 
 _lib: ctypes.CDLL | None = None

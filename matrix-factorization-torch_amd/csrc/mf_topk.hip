@@ -5,7 +5,9 @@
 // per-query selection (mf_select.h), exclusion lists scattered once into a
 // bitmask (one coalesced word per query and tile), then an exact ordered merge per query.
 // One merge kernel joins the partial top-k of a row-sharded catalog, from (scores, rows) or from
-// the packed exchange form (mf_topk_merge, mf_topk_merge_packed); one metrics kernel serves every k.
+// the packed exchange form (mf_topk_merge, mf_topk_merge_packed: k <= 64); a second one ranks every entry by binary searches over
+// the other lists instead of selecting k times, for lists up to k = 1024 (mf_topk_merge_deep, mf_topk_merge_packed_deep); one
+// metrics kernel serves every k.
 // Argument checks and the result store are shared with the other engines: mf_topk_io.h.
 #include <cmath>
 
@@ -125,11 +127,24 @@ struct MergeParts {                     // (scores, rows), -1 for none
     const float* ps;
     const int64_t* pi;
     __device__ unsigned long long operator()(int64_t at) const { return pi[at] >= 0 ? mf_key_retrieval(ps[at], (unsigned)pi[at]) : 0ull; }
+    // the same in two steps, for a kernel that keeps several entries' loads in flight before it looks at any (the deep merge:
+    // both words are loaded whatever the row says; operator() stays as topk_merge_kernel was compiled with it)
+    struct Raw {
+        float s;
+        int64_t i;
+    };
+    __device__ Raw raw(int64_t at) const { return Raw{ps[at], pi[at]}; }
+    static __device__ unsigned long long key(const Raw& v) { return v.i >= 0 ? mf_key_retrieval(v.s, (unsigned)v.i) : 0ull; }
 };
 struct MergePacked {                    // what topk_pack_kernel below writes
     const int64_t* packed;
     __device__ unsigned long long operator()(int64_t at) const {
         const int64_t v = packed[at];
+        return v != -1ll ? mf_key_retrieval(__builtin_bit_cast(float, (unsigned)((unsigned long long)v >> 32)), (unsigned)v) : 0ull;
+    }
+    using Raw = int64_t;
+    __device__ Raw raw(int64_t at) const { return packed[at]; }
+    static __device__ unsigned long long key(Raw v) {
         return v != -1ll ? mf_key_retrieval(__builtin_bit_cast(float, (unsigned)((unsigned long long)v >> 32)), (unsigned)v) : 0ull;
     }
 };
@@ -151,6 +166,132 @@ template <class Load>
 static int topk_merge_launch(const char* who, Load load, int G, int64_t Q, int k, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
     if ((size_t)G * k * 8 > 64 * 1024) return mf_set_error(MF_ENOTSUP, "%s: G * k too large", who);       // the keys of a query sit in LDS
     topk_merge_kernel<<<dim3((unsigned)Q), 64, (size_t)G * k * 8, static_cast<hipStream_t>(stream)>>>(load, G, Q, k, out_scores, out_idx);
+    return mf_check_launch(who);
+}
+
+// Deep lists (k up to MF_TOPK_DEEP_MAX_K): the merge above runs k selection rounds over all G k keys; this one uses that every
+// partial list arrives ORDERED by the same 64-bit key.  The place of entry e of list g in the merged list is e plus, for every
+// other list, the number of its keys that stand before x = key(g, e): one binary search per other list over a descending run
+// in LDS.  A key of an earlier list stands before an equal key of a later one (>= x against > x), so the ranks are a
+// permutation of 0 .. m - 1 for ANY ordered lists -- equal keys across lists never meet on contract inputs, whose global rows
+// are distinct -- and every output column is written exactly once: ranks below k by their entries, [min(m, k), k) as the tail.
+// One 256-thread workgroup per query; the keys sit in LDS as [g][e], every list one contiguous run, no padding: a binary
+// search has every lane on an address of its own, which no layout turns into a conflict-free pattern, but the lanes of a wave
+// hold entries of like rank, so their searches of one list share their first probes (one address: a broadcast) and part only
+// near the end.  Integer compares alone: no atomics, no float arithmetic, no selection rounds.  Every probe is clamped to its run, so an
+// input that is not ordered gives unspecified results but no access outside the arrays (a rank is >= 0 by construction and
+// checked against k before the store).
+static constexpr int MERGE_DEEP_THREADS = 256;
+static constexpr int MERGE_DEEP_STAGE = 8;             // keys a thread loads before it stores the first
+static constexpr int MERGE_DEEP_ILP = 4;             // lists searched side by side by one thread: independent LDS read chains
+
+template <class Load>
+__global__ __launch_bounds__(MERGE_DEEP_THREADS) void topk_merge_deep_kernel(Load load, int G, int64_t Q, int k, float* __restrict__ out_scores,
+                                                                              int64_t* __restrict__ out_idx) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long s_keys[];      // [g][e]: list g is the run s_keys + g k
+    __shared__ unsigned long long s_floor[MERGE_DEEP_THREADS / 64];
+    __shared__ int s_valid[MERGE_DEEP_THREADS / 64];
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int total = G * k;
+    // stage the keys (a list is one contiguous piece of the input: coalesced) and count the entries that are there.  m is
+    // the sum of the lists' valid lengths: counted here, where every key passes anyway, instead of searched for per list
+    // (G lengths would want G more words of LDS: 16,384 lists at k = 1)
+    // MERGE_DEEP_STAGE loads per thread are in flight before the first is looked at: a load that is turned into its key under
+    // the bounds check is waited for on the spot, and one load per trip was all latency (62 trips in a row at G k = 16,000).
+    // So the loads carry no branch -- past the end they read the last entry again, inside the arrays -- and the keys are
+    // formed behind them
+    int valid = 0;
+    for (int t0 = 0; t0 < total; t0 += MERGE_DEEP_STAGE * MERGE_DEEP_THREADS) {      // (uniform trip count: the ballot sees the whole wave)
+        typename Load::Raw raw[MERGE_DEEP_STAGE];
+#pragma unroll
+        for (int j = 0; j < MERGE_DEEP_STAGE; ++j) {
+            const int t = min(t0 + j * MERGE_DEEP_THREADS + tid, total - 1);
+            const int g = t / k, e = t - g * k;
+            raw[j] = load.raw(((int64_t)g * Q + r) * k + e);
+        }
+#pragma unroll
+        for (int j = 0; j < MERGE_DEEP_STAGE; ++j) {
+            const int t = t0 + j * MERGE_DEEP_THREADS + tid;
+            const unsigned long long key = t < total ? Load::key(raw[j]) : 0ull;
+            if (t < total) s_keys[t] = key;
+            valid += __popcll(__ballot(key != 0ull));
+        }
+    }
+    if ((tid & 63) == 0) s_valid[tid >> 6] = valid;
+    __syncthreads();
+    int m = 0;
+#pragma unroll
+    for (int w = 0; w < MERGE_DEEP_THREADS / 64; ++w) m += s_valid[w];
+    const int filled = min(m, k);
+
+    // Most entries are out of the first k (all but k of G k), and most of them can be told without a search: with
+    // p = ceil(k / G) - 1, every list holds p + 1 keys >= its own key at p, so G (p + 1) >= k keys are >= the smallest of those
+    // G keys -- whatever is below that floor has k keys before it.  (A list shorter than p + 1 makes the floor 0: nothing is
+    // dropped, nothing is wrong.)  Rows dealt evenly leave a little more than k entries to rank.
+    const int p = (k + G - 1) / G - 1;
+    unsigned long long inv = 0ull;                       // ~key: the smallest key is the largest ~key
+    for (int gg = tid; gg < G; gg += MERGE_DEEP_THREADS) inv = max(inv, ~s_keys[gg * k + p]);
+    inv = mf_wave_max_u64(inv);
+    if ((tid & 63) == 0) s_floor[tid >> 6] = inv;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < MERGE_DEEP_THREADS / 64; ++w) inv = max(inv, s_floor[w]);
+    const unsigned long long floor_key = ~inv;
+
+    int top = 1;
+    while (top * 2 <= k) top *= 2;
+    // entries are dealt position-major (t = e G + g): what is left to rank are the heads of the lists, and a wave whose 64
+    // entries are all dropped moves on after one LDS read -- dealt list-major, every wave would meet a few survivors in many
+    // of its turns and run the searches for them with most lanes idle
+    for (int t = tid; t < total; t += MERGE_DEEP_THREADS) {
+        const int e = t / G, g = t - e * G;
+        const unsigned long long x = s_keys[g * k + e];
+        if (x == 0ull || x < floor_key) continue;
+        int rank = e;
+        // lists before g: keys >= x, i.e. > x - 1 (x != 0); lists behind g: keys > x.  The count c of a run's keys above y grows
+        // by powers of two from `top`, the largest one <= k: floor(log2 k) + 1 probes (11 at k = 1024), each at
+        // min(c + s, k) - 1, inside the run.  MERGE_DEEP_ILP lists per round, and no further round once the entry is out
+        // of the first k
+        for (int g0 = 0; g0 < G && rank < k; g0 += MERGE_DEEP_ILP) {
+            int c[MERGE_DEEP_ILP], run[MERGE_DEEP_ILP];
+            unsigned long long y[MERGE_DEEP_ILP];
+#pragma unroll
+            for (int j = 0; j < MERGE_DEEP_ILP; ++j) {
+                const int gg = min(g0 + j, G - 1);                           // (past the last list: a second search of it, not added)
+                c[j] = 0;
+                run[j] = gg * k;
+                y[j] = gg < g ? x - 1ull : x;
+            }
+            for (int s = top; s > 0; s >>= 1) {
+                unsigned long long v[MERGE_DEEP_ILP];
+#pragma unroll
+                for (int j = 0; j < MERGE_DEEP_ILP; ++j) v[j] = s_keys[run[j] + min(c[j] + s, k) - 1];
+                // all reads of a step are issued before any is looked at (the empty statement pins each value: left alone,
+                // the compiler moves every read behind the test of its own `c + s <= k` and waits for them one by one)
+#pragma unroll
+                for (int j = 0; j < MERGE_DEEP_ILP; ++j) asm volatile("" : "+v"(v[j]));
+#pragma unroll
+                for (int j = 0; j < MERGE_DEEP_ILP; ++j) c[j] = (c[j] + s <= k && v[j] > y[j]) ? c[j] + s : c[j];
+            }
+#pragma unroll
+            for (int j = 0; j < MERGE_DEEP_ILP; ++j) rank += (g0 + j < G && g0 + j != g) ? c[j] : 0;
+        }
+        if (rank < k) mf_store_topk_entry(out_scores, out_idx, r, k, rank, x, 0);
+    }
+    for (int t = filled + tid; t < k; t += MERGE_DEEP_THREADS) mf_store_topk_none(out_scores, out_idx, r, k, t);
+}
+
+// the keys of a query sit in LDS: G k <= MF_TOPK_MERGE_DEEP_MAX_KEYS of 8 bytes = 128 KiB of the CU's 160
+template <class Load>
+static int topk_merge_deep_launch(const char* who, Load load, int G, int64_t Q, int k, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
+    if (k > MF_TOPK_DEEP_MAX_K) return mf_set_error(MF_ENOTSUP, "%s: k = %d outside 1..%d", who, k, MF_TOPK_DEEP_MAX_K);
+    if ((int64_t)G * k > MF_TOPK_MERGE_DEEP_MAX_KEYS) return mf_set_error(MF_ENOTSUP, "%s: G * k too large", who);
+    auto fn = topk_merge_deep_kernel<Load>;
+    static const hipError_t lds_set =                  // once per instantiation: the largest dynamic LDS any launch asks for
+        hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, MF_TOPK_MERGE_DEEP_MAX_KEYS * 8);
+    (void)lds_set;
+    fn<<<dim3((unsigned)Q), MERGE_DEEP_THREADS, (size_t)G * k * 8, static_cast<hipStream_t>(stream)>>>(load, G, Q, k, out_scores, out_idx);
     return mf_check_launch(who);
 }
 
@@ -177,6 +318,11 @@ extern "C" int mf_topk_pack(const float* scores, const int64_t* rows, int64_t n,
 extern "C" int mf_topk_merge_packed(const int64_t* packed, int G, int64_t Q, int k, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
     if (!packed || !out_scores || !out_idx || G <= 0 || Q <= 0 || k <= 0) return mf_set_error(MF_EINVAL, "mf_topk_merge_packed: bad argument");
     return topk_merge_launch("mf_topk_merge_packed", MergePacked{packed}, G, Q, k, out_scores, out_idx, stream);
+}
+
+extern "C" int mf_topk_merge_packed_deep(const int64_t* packed, int G, int64_t Q, int k, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
+    if (!packed || !out_scores || !out_idx || G <= 0 || Q <= 0 || k <= 0) return mf_set_error(MF_EINVAL, "mf_topk_merge_packed_deep: bad argument");
+    return topk_merge_deep_launch("mf_topk_merge_packed_deep", MergePacked{packed}, G, Q, k, out_scores, out_idx, stream);
 }
 
 #ifdef MF_PROBE
@@ -226,6 +372,13 @@ extern "C" int mf_topk_merge(const float* part_scores, const int64_t* part_idx, 
     if (!part_scores || !part_idx || !out_scores || !out_idx || G <= 0 || Q <= 0 || k <= 0)
         return mf_set_error(MF_EINVAL, "mf_topk_merge: bad argument");
     return topk_merge_launch("mf_topk_merge", MergeParts{part_scores, part_idx}, G, Q, k, out_scores, out_idx, stream);
+}
+
+extern "C" int mf_topk_merge_deep(const float* part_scores, const int64_t* part_idx, int G, int64_t Q, int k,
+                                  float* out_scores, int64_t* out_idx, mf_stream_t stream) {
+    if (!part_scores || !part_idx || !out_scores || !out_idx || G <= 0 || Q <= 0 || k <= 0)
+        return mf_set_error(MF_EINVAL, "mf_topk_merge_deep: bad argument");
+    return topk_merge_deep_launch("mf_topk_merge_deep", MergeParts{part_scores, part_idx}, G, Q, k, out_scores, out_idx, stream);
 }
 
 // ------------------------------------------------------------ retrieval metrics ----

@@ -33,7 +33,9 @@ below is the north-star's and our design:
 * **retrieval**: queries are all-gathered, every rank scans ITS shard for all queries
   (``mf_topk`` on local rows, mapped to global rows before they leave), the partial top-k travel back to the query's rank by
   all-to-all and are merged exactly (``mf_topk_merge``): bit-identical to the
-  single-GPU result.  Evaluation needs no list: the exact place of given target rows over all shards is a sum of per-shard
+  single-GPU result.  Lists deeper than 64 (``top_k`` up to 1024, ``world * top_k`` up to 16,384) take the deep engine per
+  shard and a merge that ranks every entry by binary searches over the other shards' ordered lists
+  (``mf_topk_merge_packed_deep``): ``world * q * top_k`` int64 per rank, still one all-to-all.  Evaluation needs no list: the exact place of given target rows over all shards is a sum of per-shard
   counts once the owner's key of a target has reached every shard (``ShardedIndex.positions``).
 
 Local compute goes through an ``ops`` object (default :class:`HipOps`) and the exchanges through a ``comm``
@@ -49,6 +51,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, optim
+from .retrieval import MERGE_DEEP_MAX_KEYS, ItemIndex
 
 # a trainer's per-table state (``ShardedTrainer.state[name]``), in the order ``optim.row_update`` takes the tensors
 STATE_KEYS = {"sgd": (), "adagrad": ("sum",), "adam": ("m", "v")}
@@ -345,7 +348,9 @@ class HipOps:
     def merge_packed(self, packed, world, q, k):
         scores = torch.empty(q, k, dtype=torch.float32, device=packed.device)
         rows = torch.empty(q, k, dtype=torch.int64, device=packed.device)
-        _lib.check(_lib.lib().mf_topk_merge_packed(packed.data_ptr(), world, q, k, scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
+        # deep lists (``mf_topk_deep`` per shard) have a merge of their own; up to TILE_MAX_K the call is the one it always was
+        merge = _lib.lib().mf_topk_merge_packed_deep if k > ItemIndex.TILE_MAX_K else _lib.lib().mf_topk_merge_packed
+        _lib.check(merge(packed.data_ptr(), world, q, k, scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
         return scores, rows
 
 
@@ -842,9 +847,21 @@ class ShardedIndex:
         host read of the other ranks' lengths per NEW set of lists.  ``exclude_capacity = C`` (a bound on ``ids.numel()`` the
         caller knows on the host, the same on every rank): every rank sends a block of C entries padded with -1 and the
         offsets are rebased onto the blocks on the device -- no host sync at all (the padding lands in the last query of each
-        block as ids no shard owns, which the scan ignores)."""
+        block as ids no shard owns, which the scan ignores).
+
+        ``1 <= top_k <= ItemIndex.DEEP_MAX_K``.  Up to ``ItemIndex.TILE_MAX_K`` every shard runs one of the k <= 64 engines
+        and the k <= 64 merge joins the lists; a deeper call runs the deep engine per shard (``mf_topk_deep``), exchanges
+        ``world * q * top_k`` int64 per rank in ONE all-to-all (the packed lists of all ranks' queries) and joins them with
+        ``mf_topk_merge_packed_deep``, which holds a query's ``world * top_k`` keys in LDS: at most ``MERGE_DEEP_MAX_KEYS``
+        (16 ranks at 1024, 64 at 256).  Both limits are checked here, on the host, before the first collective -- every rank
+        sees the same numbers, so all raise ``ValueError`` together."""
         comm = self.comm
         world = comm.world
+        top_k = int(top_k)
+        if not 1 <= top_k <= ItemIndex.DEEP_MAX_K or (top_k > ItemIndex.TILE_MAX_K and world * top_k > MERGE_DEEP_MAX_KEYS):
+            msg = (f"top_k must be in 1..{ItemIndex.DEEP_MAX_K}, and beyond {ItemIndex.TILE_MAX_K} world * top_k at most "
+                   f"{MERGE_DEEP_MAX_KEYS}: {top_k = }, {world = }")
+            raise ValueError(msg)
         q, d = queries.shape
         all_q = comm.gather(queries)
         csr = self._exclusions(exclude_csr, q, exclude_capacity)

@@ -273,7 +273,9 @@ class ItemIndex:
 
 
 def merge_topk(part_scores: torch.Tensor, part_rows: torch.Tensor, top_k: int) -> tuple[torch.Tensor, torch.Tensor]:
-    """Merge per-shard results ``[G, Q, k]`` (global rows) into the global top-k (``mf_topk_merge``)."""
+    """Merge per-shard results ``[G, Q, k]`` (global rows, each list ordered as ``search`` returns it) into the global top-k:
+    ``mf_topk_merge`` up to ``ItemIndex.TILE_MAX_K``, ``mf_topk_merge_deep`` for deeper lists (``top_k`` up to
+    ``ItemIndex.DEEP_MAX_K``, ``G * top_k`` up to ``MERGE_DEEP_MAX_KEYS``) -- the same bits either way."""
     ps = _lib.dev_f32(part_scores, "part_scores")
     pr = _lib.dev_i64(part_rows, "part_rows")
     g, nq, k = ps.shape
@@ -282,9 +284,12 @@ def merge_topk(part_scores: torch.Tensor, part_rows: torch.Tensor, top_k: int) -
         raise ValueError(msg)
     scores = torch.empty(nq, k, dtype=torch.float32, device=ps.device)
     rows = torch.empty(nq, k, dtype=torch.int64, device=ps.device)
-    _lib.check(_lib.lib().mf_topk_merge(ps.data_ptr(), pr.data_ptr(), g, nq, k, scores.data_ptr(), rows.data_ptr(),
-                                        _lib.stream_ptr()))
+    merge = _lib.lib().mf_topk_merge_deep if top_k > ItemIndex.TILE_MAX_K else _lib.lib().mf_topk_merge
+    _lib.check(merge(ps.data_ptr(), pr.data_ptr(), g, nq, k, scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
     return scores, rows
+
+
+MERGE_DEEP_MAX_KEYS = _lib.MF_TOPK_MERGE_DEEP_MAX_KEYS      # ``G * top_k`` the deep merges take: a query's keys sit in 128 KiB of LDS
 
 
 class ItemProcessor:

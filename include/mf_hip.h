@@ -194,6 +194,19 @@ void mf_set_dense_dedup(int mode);
 /* Tests and tools only (a device -> host copy; never inside a step): out[9] = {served, N' (distinct columns), NT' (tiles
  * streamed), forward (splits, tiles per split), dU (the same), dV (the same)} of the last forward on this workspace. */
 int mf_loss_cols_info(const void* ws, int64_t* out);
+/* The two backward sweeps of the dense losses at d = 128 contract on the bf16 matrix cores with fp32-grade results: both
+ * operands are split into three bf16 pieces and the six leading piece products are accumulated in fp32 (csrc/mf_bf_split.h;
+ * dropped terms ~2^-23 of a product).  The gradients hold to the tolerances of the fp32 sweeps, not to their bits; the forward
+ * -- loss value and logit stash -- is untouched.  mode 1 (default): from 8192 columns upward; mode 2: wherever d = 128
+ * (tests); mode 0: never.  Served with and without the distinct-column plan; not served: every other width, the mined
+ * losses.  Read at each backward.  Process-wide. */
+void mf_set_dense_bwd_split(int mode);
+/* Tests and tools only: the path of the last mf_loss_bwd on this workspace -- bit 0: distinct columns, bit 1: split
+ * contraction, bit 2: dV derived G' from the logit stash itself.  0 for a workspace no dense backward has run on. */
+int mf_loss_bwd_path(const void* ws);
+/* Tests only: the slot of (row of a 32-row tile, feature, piece) among the 12,288 bf16 of a tile's operand image
+ * (csrc/mf_bf_split.h); -1 outside 32 x 128 x 3. */
+int mf_bwd_split_image_index(int row, int feature, int piece);
 /* Host-only: the geometry the device derives for `ncols` distinct columns of a shape, with what is launched and allocated
  * around it: out[16] = {can serve, NT', forward (splits, tps), dU (splits, tps), dV (splits, tps), dV X blocks, launched:
  * forward splits, dU splits, dV workgroups, capacity of the partial buffers: forward splits, dU splits, dV X blocks, 0}.

@@ -307,10 +307,15 @@ __global__ __launch_bounds__(256) void mask_export_dense_kernel(const uint32_t* 
 // Block (ti, tj) is 4 KiB: [q = e / 4][lane][e % 4] in the forward's accumulator layout
 // (lane = user), i.e. four whole-KiB coalesced stores per tile and a linear LDS-DMA on the way
 // back.  The dU sweep turns each block into G' = dloss/dL (one exp / step / sigmoid per element,
-// diagonal patched) and writes it to a second stash, so the dV sweep, which runs after it, reads G'
-// and has no per-element arithmetic at all: on gfx950 fp32 MFMA and VALU share the SIMD's FP32
-// lanes (a VALU op costs ~2 cycles of MFMA throughput, a transcendental ~17 -- measured), so
-// every VALU instruction removed from these loops is MFMA time won back.
+// diagonal patched).  What happens to G' next depends on which pipe contracts it:
+//  * fp32 sweeps (v_mfma_f32_32x32x2f32; d = 32, 256, and d = 128 with the split switched off): dU writes G' to a second
+//    stash and dV, which runs after it, reads it and has no per-element arithmetic at all.  The fp32 MFMA and the VALU share
+//    the SIMD's FP32 lanes there (a VALU op costs ~2 cycles of MFMA throughput, a transcendental ~17 -- measured), so every
+//    VALU instruction removed from those loops is MFMA time won back.
+//  * split sweeps (v_mfma_f32_32x32x16_bf16, d = 128; SPLIT below) and d = 64: the matrix time of a tile is short, VALU work
+//    beside a bf16 MFMA costs it nothing while it fits the gaps, and the sweeps are bound by the 4 KiB stash block each
+//    tile brings.  dV derives G' from the logit stash itself and dU writes no second stash (RECOMP in BwdLds): one pass
+//    over the stash per sweep instead of three for the pair.
 // (Folding the split sum into these kernels -- the workgroup that reaches an X block's ticket last adds the
 // partials -- was measured and dropped: 64..128 last workgroups reading 8 x 64 KiB each is far less parallel than
 // the separate sum_parts launch; dU 0.287 -> 0.489 ms.)
@@ -326,18 +331,23 @@ struct BwdParams {
     // distinct-column sweeps (CP): v is the packed v', the streamed / kept extent of the item axis comes from the device words
     const int32_t* geo;
     const float* cw;         // column weights (dU: the MFMA operand and the row sum take G' x w; the stash keeps G' itself)
+    const unsigned short* img;   // split sweeps: the bf16 piece image of the streamed operand, YT tiles (mf_bf_split.h)
 };
 
-template <int D, bool XU>
+#ifndef BWD_SPLIT_VPM
+#define BWD_SPLIT_VPM 7       // A/B knob: VALU / SALU instructions of the next tile's G' placed behind each MFMA of the split contraction
+#endif
+template <int D, bool XU, int SPLIT = 0>
 struct BwdLds {
     using G = TileGeom<D>;
+    static_assert(SPLIT == 0 || D == 128, "the split sweeps are written for d = 128");
     // Two schedules (see the kernel): SPREAD for long tiles (d >= 64) -- 2-slot tile ring, the wave's own
     // 4 KiB stash / G' block comes straight into registers (it is wave-private: routing it through LDS
     // only added 16 KiB of DMA writes and 16 KiB of reads per tile to an LDS port that the MFMA operand
     // reads need); otherwise whole stages two tiles ahead, stash blocks behind the tile in each slot.
     static constexpr bool SPREAD = D >= 64;
     static constexpr int LT = G::TILEB;                  // (not SPREAD) NW x 4 KiB stash blocks behind the tile
-    static constexpr int SLOT = G::TILEB + (SPREAD ? 0 : G::NW * 4096);
+    static constexpr int SLOT = SPLIT ? BSI_TILEB : G::TILEB + (SPREAD ? 0 : G::NW * 4096);
     static constexpr int EXTRA = XU ? 0 : G::NW * 32 * 32 * 4;   // dV: per-wave 32 x 32 transpose scratch (XOR-swizzled)
     // the deepest ring that still puts two waves on every SIMD (two 4-wave workgroups per CU, or one of
     // eight waves); 2 slots cost a second barrier per tile, measured free
@@ -348,9 +358,11 @@ struct BwdLds {
     // MFMAs shrink with d).  There the dV sweep derives G' from the LOGIT stash itself -- the per-element map dU applies, with
     // the users' coefficients loaded per tile (lanes are users BEFORE the block is transposed) -- and dU no longer writes a
     // G' stash: dU moves 0.57 GB instead of 1.07 at C2's shape (round 4; same bits: the same map on the same logits).
-    static constexpr bool RECOMP = D == 64;              // (d = 32 stages two tiles ahead: the coefficients would need a ring of their own)
+    // (The split sweeps at d = 128 are stash-bound in the same way and do the same.)
+    static constexpr bool RECOMP = D == 64 || SPLIT != 0;   // (d = 32 stages two tiles ahead: the coefficients would need a ring of their own)
     static constexpr int NCOEF = (RECOMP && !XU) ? 4 : 0;   // a, b, coefG, gdiag of the tile's users
-    static constexpr int NDMA = G::PPW + 4 + NCOEF;      // memory instructions per wave per stage (4 = the stash block)
+    static constexpr int PPW = SPLIT ? BSI_TILEB / G::NW / 1024 : G::PPW;   // 1-KiB DMA pieces of the streamed tile per wave
+    static constexpr int NDMA = PPW + 4 + NCOEF;         // memory instructions per wave per stage (4 = the stash block)
     static constexpr int NSTORE = (XU && !RECOMP) ? 4 : 0;  // G' stores per tile
 };
 
@@ -360,11 +372,16 @@ struct BwdLds {
 // of v' in the splits the device words name, weights G' by the copy count for the contraction and the row sum, and
 // patches no diagonal (a user's own column is masked by id in every copy: G' = 0 there; the epilogue adds the term).
 // dV is launched as a LINEAR grid for the worst case: workgroup id -> (X block, split) by the device geometry.
-template <int D, bool XU, int GMODE, bool CP>
+// SPLIT (d = 128): the contraction on the bf16 matrix cores, fp32-grade (mf_bf_split.h).  The streamed operand arrives as its
+// image of three bf16 pieces (bwd_split_image_kernel), G' is split in registers -- in accumulator layout it IS the B operand
+// of v_mfma_f32_32x32x16_bf16, two k-steps of 16 rows -- and the six leading piece products go into the same fp32
+// accumulators: 48 MFMAs of 8 passes per tile instead of 64 of 16.  Everything around the contraction -- the G' map, the
+// stash, the transpose, the row sum, the epilogue -- is the fp32 sweep's; dV derives G' itself (RECOMP, see BwdLds).
+template <int D, bool XU, int GMODE, bool CP, int SPLIT>
 __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG : 1) void loss_bwd_dense_kernel(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using L = BwdLds<D, XU>;
-    static_assert(!CP || (L::SPREAD && !L::RECOMP), "the distinct-column sweeps are written for the d = 128 schedule");
+    using L = BwdLds<D, XU, SPLIT>;
+    static_assert(!CP || (L::SPREAD && (!L::RECOMP || SPLIT)), "the distinct-column sweeps are written for the d = 128 schedule");
     const int lane = mf_lane(), c = lane & 31, h = lane >> 5;
     const int wave = mf_wave_id();
     int split = blockIdx.x, tps = p.tps, YT = p.YT;
@@ -405,7 +422,20 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
     float rsum = 0.f;
 
     TileSrc<D> tsrc;
-    mf_tile_src_init<D>(tsrc, Y, nY, (int64_t)t0 * 32);
+    if (!SPLIT) mf_tile_src_init<D>(tsrc, Y, nY, (int64_t)t0 * 32);
+    // SPLIT: the image is copied linearly -- one descriptor over its tiles from t0 (p.YT of them exist), piece q of this
+    // wave's share at lane offset + scalar ((t - t0) tiles + q KiB); a tile past the descriptor's end would arrive as zeros
+    mf_rsrc_t irsrc;
+    const unsigned ioff = (unsigned)(wave * L::PPW * 1024 + lane * 16);
+    if (SPLIT) {
+        int64_t bytes = (int64_t)(p.YT - t0) * BSI_TILEB;
+        bytes = bytes < 0 ? 0 : (bytes > (int64_t)MF_SRD_MAX_BYTES ? (int64_t)MF_SRD_MAX_BYTES : bytes);
+#if defined(__HIP_DEVICE_COMPILE__)
+        irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(p.img + (int64_t)t0 * BSI_TILE_ELEMS), 0, (int)(unsigned)bytes, 0x00020000);
+#else
+        (void)irsrc; (void)ioff;
+#endif
+    }
     auto block_of = [&](int t) { return XU ? ((int64_t)xt * p.NT + t) : ((int64_t)t * p.NT + xt); };
     // piece j of the staging of tile t: 0..3 the wave's 4 KiB stash / G' block (into LDS, or -- SPREAD --
     // straight into the registers Gn), 4.. its share of the Y tile
@@ -423,6 +453,11 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
             const char* lsrc = reinterpret_cast<const char*>(((XU || RECOMP) ? p.stash : p.gstash) + block_of(t) * 1024) + lane * 16;
             if (SPREAD) Gn[j] = *reinterpret_cast<const f32x4*>(lsrc + j * 1024);
             else __builtin_amdgcn_global_load_lds((mf_glb_ptr)(lsrc + j * 1024), (mf_lds_ptr)(slot + L::LT + wave * 4096 + j * 1024), 16, 0, 0);
+        } else if (SPLIT) {
+#if defined(__HIP_DEVICE_COMPILE__)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(irsrc, (mf_lds_ptr)(slot + (wave * L::PPW + (j - 4)) * 1024), 16, (int)ioff,
+                                                     (int)((unsigned)(t - t0) * BSI_TILEB + (j - 4) * 1024), 0, 0);
+#endif
         } else {
             mf_stage_tile_piece<D>(slot, t * 32, j - 4, tsrc);
         }
@@ -431,6 +466,163 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
 #pragma unroll
         for (int j = 0; j < NDMA; ++j) stage_piece(t, slot_idx, j);
     };
+    // A tile's stash block as it arrived (SPREAD: in Gn) with its weights, and -- dV, RECOMP -- its users' coefficients
+    auto take = [&](float (&Gv)[16], float (&Wv)[16], const char* lt) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 t4 = SPREAD ? Gn[q] : *reinterpret_cast<const f32x4*>(lt + q * 1024 + lane * 16);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) { Gv[4 * q + t] = t4[t]; Wv[4 * q + t] = Wn[q][t]; }
+        }
+        if (!XU && RECOMP) {            // this tile's users' coefficients (asked for with the block)
+            xa = cn[0]; xb = cn[1]; xc = gout * cn[2]; xd = gout * cn[3];
+            xb2 = xb * 1.44269504088896341f;
+        }
+    };
+    // The block of tile `tile` -> the B operand of its contraction: G' (unless the stash holds it already), handed to dV,
+    // weighted, transposed for dV; its elements are added to the lane's row sum `rs`
+    auto gprime = [&](float (&Gv)[16], const float (&Wv)[16], int tile, float& rs) {
+        if (XU || RECOMP) {
+            // masked logits -> G' (masked entries are -inf: exp / step / sigmoid give exactly 0)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                if (GMODE == G_EXP) Gv[e] = xc * __builtin_amdgcn_exp2f(__builtin_fmaf(Gv[e] - xa, 1.44269504088896341f, xb2));
+                else Gv[e] = xc * g_of(GMODE, (Gv[e] - xa) + xb);
+            }
+            if (!CP && tile == xt) {    // only the diagonal tile holds the user's own positive
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    if (mf_acc_row(e, h) == c) Gv[e] = xd;
+            }
+        }
+        if (XU && !RECOMP) {
+            float* blk = p.gstash + block_of(tile) * 1024 + lane * 4;   // hand G' to the dV sweep
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                *reinterpret_cast<f32x4*>(blk + q * 256) = f32x4{Gv[4 * q], Gv[4 * q + 1], Gv[4 * q + 2], Gv[4 * q + 3]};
+        }
+        if (XU && CP) {                 // (the stash keeps the per-copy gradient: dV needs it unweighted)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) Gv[e] *= Wv[e];
+        }
+        if (!XU) {
+            // block layout is (lane = user, register = item row): transpose to (lane = item, register = user row)
+            // (SPLIT: the next tile's DMA is in flight here -- stores the compiler sees would drain it, mf_stream.h)
+            float* tr = reinterpret_cast<float*>(smem + L::TR) + wave * (32 * 32);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                if (SPLIT) mf_lds_store_b32(&tr[mf_acc_row(e, h) * 32 + (c ^ mf_acc_row(e, h))], Gv[e]);
+                else tr[mf_acc_row(e, h) * 32 + (c ^ mf_acc_row(e, h))] = Gv[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) Gv[e] = tr[c * 32 + (mf_acc_row(e, h) ^ c)];
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) rs += Gv[e];
+    };
+    if constexpr (SPLIT != 0) {
+        // The split schedule.  The contraction of a tile is 48 short MFMAs, too few to hide what precedes them, so the G' of
+        // tile ty + 1 -- map, transpose, the split into pieces: VALU and LDS work -- is computed beside the MFMAs of tile ty,
+        // and the register loads (stash block, weights, coefficients) run TWO tiles ahead; the image of tile ty + 1 goes into
+        // the slot tile ty - 1 left, as in SPREAD.  One barrier per tile.
+        static_assert(L::RECOMP && SPREAD, "the split sweeps keep no G' stash");
+        typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+        // G' in three bf16 pieces: g[s][q] is piece q of registers 8 s .. 8 s + 7, the B fragment of k-step s
+        auto split_g = [&](const float (&Gv)[16], mbf16x8 (&g)[2][3]) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                u16x8 g3[3];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    unsigned short o[3];
+                    mbf_split3(Gv[8 * s + j], o);
+                    g3[0][j] = o[0]; g3[1][j] = o[1]; g3[2][j] = o[2];
+                }
+#pragma unroll
+                for (int q = 0; q < 3; ++q) g[s][q] = __builtin_bit_cast(mbf16x8, g3[q]);
+            }
+        };
+        auto stage_regs = [&](int t) {
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j)
+                if (j < 4 || j >= 4 + L::PPW) stage_piece(t, 0, j);
+        };
+        auto stage_image = [&](int t, int slot_idx) {
+#pragma unroll
+            for (int j = 4; j < 4 + L::PPW; ++j) stage_piece(t, slot_idx, j);
+        };
+        mbf16x8 gb[2][3];
+        float Gv[16], Wv[16];
+        if (t0 < t1) {
+            stage_image(t0, 0);
+            stage_regs(t0);
+            mf_wait_vmcnt<0>();
+            take(Gv, Wv, nullptr);
+            if (t0 + 1 < t1) stage_regs(t0 + 1);
+            gprime(Gv, Wv, t0, rsum);
+            split_g(Gv, gb);
+        }
+        int cur = 0;
+        for (int ty = t0; ty < t1; ++ty) {
+            mf_wait_vmcnt<0>();           // the image of tile ty and the registers of tile ty + 1: issued one tile ago
+            mf_block_barrier();
+            const bool more = ty + 1 < t1;
+            take(Gv, Wv, nullptr);        // tile ty + 1 as it arrived (none: what the registers held -- finite or -inf, and unused)
+            if (more) {
+                stage_image(ty + 1, cur ^ 1);
+                if (ty + 2 < t1) stage_regs(ty + 2);
+            }
+            float rs = 0.f;
+            gprime(Gv, Wv, ty + 1, rs);
+            rsum += more ? rs : 0.f;
+            mbf16x8 gn[2][3];
+            split_g(Gv, gn);
+            // dX[m][x] += sum_y Y[y][m] * G[y][x], piece products a_i g_j with i + j <= 2, the smallest first.  A step is one
+            // k-step of two accumulator blocks (12 MFMAs, alternating between the two); its six A fragments are read one
+            // step ahead.
+            const mbf16x8* img = reinterpret_cast<const mbf16x8*>(smem + cur * L::SLOT) + lane;
+            auto frags = [&](mbf16x8 (&a)[2][3], int step) {
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) a[b][q] = img[((q * 4 + 2 * (step & 1) + b) * 2 + (step >> 1)) * 64];
+            };
+            mbf16x8 av[2][3];
+            frags(av, 0);
+#pragma unroll
+            for (int step = 0; step < 4; ++step) {
+                mbf16x8 an[2][3];
+                if (step + 1 < 4) frags(an, step + 1);
+                const int s = step >> 1, b0 = 2 * (step & 1);
+#pragma unroll
+                for (int pr = 0; pr < 6; ++pr) {
+                    // (a piece, g piece): (2,0) (1,1) (0,2) | (1,0) (0,1) | (0,0)
+                    const int ai = pr == 0 ? 2 : (pr == 1 || pr == 3) ? 1 : 0;
+                    const int gi = pr == 2 ? 2 : (pr == 1 || pr == 4) ? 1 : 0;
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+                        dacc[b0 + b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[b][ai], gb[s][gi], dacc[b0 + b], 0, 0, 0);
+                }
+                if (step + 1 < 4) {
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) av[b][q] = an[b][q];
+                }
+            }
+            // one MFMA, then a share of the next tile's VALU work, 48 times (hipcc otherwise keeps the two streams apart)
+#pragma unroll
+            for (int m = 0; m < 48; ++m) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x006, BWD_SPLIT_VPM, 0);
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) gb[s][q] = gn[s][q];
+            cur ^= 1;
+        }
+    } else {
     // Two schedules.  SPREAD (2-slot ring, d >= 64): the loads of tile ty+1 are issued ONE PER MFMA STEP
     // inside the contraction of tile ty, the tile pieces into the slot tile ty-1 left; no second barrier.
     // Otherwise (3 slots, short tiles): whole stages, two tiles ahead.
@@ -449,51 +641,9 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
         mf_block_barrier();
         if (!SPREAD && L::NSLOT == 3 && ty + 2 < t1) stage(ty + 2, cur >= 1 ? cur - 1 : 2);
         const char* slot = smem + cur * L::SLOT;
-        const char* lt = slot + L::LT + wave * 4096;
         float Gv[16], Wv[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 t4 = SPREAD ? Gn[q] : *reinterpret_cast<const f32x4*>(lt + q * 1024 + lane * 16);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { Gv[4 * q + t] = t4[t]; Wv[4 * q + t] = Wn[q][t]; }
-        }
-        if (!XU && RECOMP) {            // this tile's users' coefficients (asked for one tile ago)
-            xa = cn[0]; xb = cn[1]; xc = gout * cn[2]; xd = gout * cn[3];
-            xb2 = xb * 1.44269504088896341f;
-        }
-        if (XU || RECOMP) {
-            // masked logits -> G' (masked entries are -inf: exp / step / sigmoid give exactly 0)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                if (GMODE == G_EXP) Gv[e] = xc * __builtin_amdgcn_exp2f(__builtin_fmaf(Gv[e] - xa, 1.44269504088896341f, xb2));
-                else Gv[e] = xc * g_of(GMODE, (Gv[e] - xa) + xb);
-            }
-            if (!CP && ty == xt) {      // only the diagonal tile holds the user's own positive
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (mf_acc_row(e, h) == c) Gv[e] = xd;
-            }
-        }
-        if (XU && !RECOMP) {
-            float* blk = p.gstash + block_of(ty) * 1024 + lane * 4;     // hand G' to the dV sweep
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<f32x4*>(blk + q * 256) = f32x4{Gv[4 * q], Gv[4 * q + 1], Gv[4 * q + 2], Gv[4 * q + 3]};
-            if (CP) {                   // (the stash keeps the per-copy gradient: dV needs it unweighted)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) Gv[e] *= Wv[e];
-            }
-        }
-        if (!XU) {
-            // block layout is (lane = user, register = item row): transpose to (lane = item, register = user row)
-            float* tr = reinterpret_cast<float*>(smem + L::TR) + wave * (32 * 32);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) tr[mf_acc_row(e, h) * 32 + (c ^ mf_acc_row(e, h))] = Gv[e];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) Gv[e] = tr[c * 32 + (mf_acc_row(e, h) ^ c)];
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) rsum += Gv[e];
+        take(Gv, Wv, slot + L::LT + wave * 4096);
+        gprime(Gv, Wv, ty, rsum);
         // dX[m][x] += sum_y Y[y][m] * G[y][x]   (the G tile is already a B operand)
         // (the Y fragment of step t + 1 is read before the MFMAs of step t are issued)
         const bool more = ty + 1 < t1;
@@ -517,6 +667,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
             if (ty + 2 < t1) stage(ty + 2, cur);
         }
         cur = cur + 1 == L::NSLOT ? 0 : cur + 1;
+    }
     }
     mf_wait_vmcnt<0>();                 // nothing of this workgroup may still be on its way into LDS when it ends
     rsum += mf_shfl_xor32(rsum);
@@ -611,21 +762,84 @@ __global__ __launch_bounds__(256) void sum_parts_cols_kernel(SumColsParams p, in
     reinterpret_cast<f32x4*>((first ? p.du : p.dv) + r * d)[cidx] = acc - rs * xr;
 }
 
-template <int D, bool XU, bool CP = false>
-static void launch_bwd(int gmode, dim3 grid, const BwdParams& bp, hipStream_t s);
-
-template <int D, bool XU, int GMODE, bool CP>
+template <int D, bool XU, int GMODE, bool CP, int SPLIT>
 static void launch_bwd_g(dim3 grid, const BwdParams& bp, hipStream_t s) {
-    auto fn = loss_bwd_dense_kernel<D, XU, GMODE, CP>;
-    if (BwdLds<D, XU>::BYTES > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, BwdLds<D, XU>::BYTES);
-    fn<<<grid, 64 * mf_nw(D), BwdLds<D, XU>::BYTES, s>>>(bp);
+    auto fn = loss_bwd_dense_kernel<D, XU, GMODE, CP, SPLIT>;
+    using L = BwdLds<D, XU, SPLIT>;
+    if (L::BYTES > 64 * 1024) (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES);
+    fn<<<grid, 64 * mf_nw(D), L::BYTES, s>>>(bp);
 }
-template <int D, bool XU, bool CP>
+template <int D, bool XU, bool CP = false, int SPLIT = 0>
 static void launch_bwd(int gmode, dim3 grid, const BwdParams& bp, hipStream_t s) {
-    if (gmode == G_EXP) launch_bwd_g<D, XU, G_EXP, CP>(grid, bp, s);
-    else if (gmode == G_STEP) launch_bwd_g<D, XU, G_STEP, CP>(grid, bp, s);
-    else launch_bwd_g<D, XU, G_SIGM, CP>(grid, bp, s);
+    if (gmode == G_EXP) launch_bwd_g<D, XU, G_EXP, CP, SPLIT>(grid, bp, s);
+    else if (gmode == G_STEP) launch_bwd_g<D, XU, G_STEP, CP, SPLIT>(grid, bp, s);
+    else launch_bwd_g<D, XU, G_SIGM, CP, SPLIT>(grid, bp, s);
+}
+
+// ---- the split sweeps' operand images and switch (mf_bf_split.h) ----
+// One launch, inside the backward: the images of u (dV streams it) and of v, or of the packed v' (dU).  A workgroup is one
+// tile; thread (k-step s, lane (r, h)) reads features 4 r .. 4 r + 3 of the 8 rows its fragment holds -- whole 512-byte rows
+// across r -- and writes the 16-byte fragments of 3 pieces x 4 blocks.  Rows from `rows` on are zeros.
+struct SplitImage {
+    const float* src;
+    int64_t rows;
+    int tiles;
+    unsigned short* img;
+};
+__global__ __launch_bounds__(128) void bwd_split_image_kernel(SplitImage ja, SplitImage jb, const int32_t* __restrict__ geo) {
+    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+    const bool first = (int)blockIdx.x < ja.tiles;
+    const SplitImage& job = first ? ja : jb;
+    const int tile = (int)blockIdx.x - (first ? 0 : ja.tiles);
+    if (!first && geo && tile >= geo[CG_NT]) return;          // (packed v': the sweeps stream the tiles of N' only)
+    const int s = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    u16x8 out[3][4];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int64_t y = (int64_t)tile * 32 + (j & 3) + 8 * (2 * s + (j >> 2)) + 4 * h;
+        f32x4 x = {0.f, 0.f, 0.f, 0.f};
+        if (y < job.rows) x = reinterpret_cast<const f32x4*>(job.src + y * 128)[r];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            unsigned short o[3];
+            mbf_split3(x[b], o);
+            out[0][b][j] = o[0]; out[1][b][j] = o[1]; out[2][b][j] = o[2];
+        }
+    }
+    u16x8* dst = reinterpret_cast<u16x8*>(job.img + (int64_t)tile * BSI_TILE_ELEMS);
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) dst[bsi_index(16 * s + 4 * h, 4 * r + b, q) >> 3] = out[q][b];
+}
+// tests only: slot of (row of the tile, feature, piece) in a tile's image
+extern "C" int mf_bwd_split_image_index(int row, int feature, int piece) {
+    if (row < 0 || row >= 32 || feature < 0 || feature >= 128 || piece < 0 || piece >= 3) return -1;
+    return bsi_index(row, feature, piece);
+}
+
+// 0 never, 1 where it pays (default: from SPLIT_MIN_N columns upward), 2 wherever it can serve (tests).  Served: the dense
+// (unmined) backward at d = 128, with or without the column plan.  Below the threshold a sweep's workgroup streams a few tiles
+// and the image launch is not paid back: forward + backward in us, fp32 / split -- (B, N) = (1024, 4096): 123.1 / 124.7,
+// (2048, 4096): 121.9 / 121.5, (4096, 8192): 192.8 / 174.5 (profiles/bwd_split_threshold.json).
+static int g_dense_bwd_split = 1;
+static constexpr int64_t SPLIT_MIN_N = 8192;
+extern "C" void mf_set_dense_bwd_split(int mode) { g_dense_bwd_split = mode <= 0 ? 0 : (mode >= 2 ? 2 : 1); }
+static bool split_serve(const LossWs& w) {
+    if (!w.split_ok || g_dense_bwd_split == 0) return false;
+    return g_dense_bwd_split == 2 || w.N >= SPLIT_MIN_N;
+}
+// which path the last backward on a workspace took (tests and tools): bit 0 distinct columns, 1 split contraction, 2 dV recomputed G'
+static std::mutex g_path_mu;
+static std::unordered_map<const void*, int> g_bwd_path;
+extern "C" int mf_loss_bwd_path(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_path_mu);
+    const auto it = g_bwd_path.find(ws);
+    return it == g_bwd_path.end() ? 0 : it->second;
+}
+static void bwd_path_note(const void* ws, int path) {
+    std::lock_guard<std::mutex> lk(g_path_mu);
+    g_bwd_path[ws] = path;
 }
 
 // ---- the distinct-column sweeps' switch (mf_loss_cols.h) ----
@@ -734,13 +948,23 @@ int dense_bwd(const LossWs& w, const void* ws, int gmode, const float* u, const 
               float* dv, hipStream_t s) {
     const int64_t B = w.B, N = w.N;
     const int d = w.d;
-    if (cols_served(ws)) {
+    const bool cols = cols_served(ws), split = split_serve(w);
+    bwd_path_note(ws, (cols ? 1 : 0) | (split ? 2 | 4 : 0));
+    if (split) {
+        // (tile shares of a split sweep are checked against the descriptor by split_ok: the whole image fits one)
+        const SplitImage ju{u, B, w.BT, w.bimg_u}, jv{cols ? w.cv : v, cols ? w.Np : N, w.NT, w.bimg_v};
+        bwd_split_image_kernel<<<dim3((unsigned)(w.BT + w.NT)), 128, 0, s>>>(ju, jv, cols ? w.geo : nullptr);
+    }
+    if (cols) {
         // the forward on this workspace swept the distinct columns: so do dU and dV (the stashes hold packed columns)
         BwdParams bp{u, w.cv, w.rowc, grad_out, w.stash, w.gstash, w.dpart, w.rpart, B, w.Np, w.Bp, w.Np, w.NT, 0, 0, w.geo, w.cw};
-        bp.YT = w.NT;
-        MF_TIMED("loss_bwd_du", s, (launch_bwd<128, true, true>(gmode, dim3((unsigned)w.cl.grid_u, (unsigned)(w.BT / w.NW)), bp, s)));
-        bp.YT = w.BT; bp.dpart = w.dpart_v; bp.rpart = w.rpart_v;
-        MF_TIMED("loss_bwd_dv", s, (launch_bwd<128, false, true>(G_EXP, dim3((unsigned)w.cl.grid_v), bp, s)));
+        const dim3 grid_u((unsigned)w.cl.grid_u, (unsigned)(w.BT / w.NW)), grid_v((unsigned)w.cl.grid_v);
+        bp.YT = w.NT; bp.img = w.bimg_v;
+        if (split) MF_TIMED("loss_bwd_du", s, (launch_bwd<128, true, true, 1>(gmode, grid_u, bp, s)));
+        else MF_TIMED("loss_bwd_du", s, (launch_bwd<128, true, true>(gmode, grid_u, bp, s)));
+        bp.YT = w.BT; bp.dpart = w.dpart_v; bp.rpart = w.rpart_v; bp.img = w.bimg_u;
+        if (split) MF_TIMED("loss_bwd_dv", s, (launch_bwd<128, false, true, 1>(gmode, grid_v, bp, s)));
+        else MF_TIMED("loss_bwd_dv", s, (launch_bwd<128, false, true>(G_EXP, grid_v, bp, s)));
         const int nb_a = (int)((B * (d / 4) + 255) / 256), nb_b = (int)((N * (d / 4) + 255) / 256);
         const SumColsParams sp{w.dpart, w.rpart, w.dpart_v, w.rpart_v, u, v, w.rowc, grad_out, w.geo, w.crank, B, N, w.Bp, du, dv, nb_a, 32 * w.NW};
         sum_parts_cols_kernel<<<dim3((unsigned)(nb_a + nb_b)), 256, 0, s>>>(sp, d);
@@ -749,6 +973,16 @@ int dense_bwd(const LossWs& w, const void* ws, int gmode, const float* u, const 
     if ((size_t)w.tps_u * 32 * d * 4 > MF_SRD_MAX_BYTES || (size_t)w.tps_v * 32 * d * 4 > MF_SRD_MAX_BYTES)
         return mf_set_error(MF_ENOTSUP, "mf_loss_bwd: a sweep's share of the batch exceeds 4 GiB (buffer descriptor)");
     BwdParams bp{u, v, w.rowc, grad_out, w.stash, w.gstash, w.dpart, w.rpart, B, N, w.Bp, w.Np, w.NT, 0, 0, nullptr, nullptr};
+    if (split) {
+        bp.YT = w.NT; bp.tps = w.tps_u; bp.img = w.bimg_v;
+        MF_TIMED("loss_bwd_du", s, (launch_bwd<128, true, false, 1>(gmode, dim3((unsigned)w.nsplit_u, (unsigned)(w.BT / w.NW)), bp, s)));
+        bp.YT = w.BT; bp.tps = w.tps_v; bp.dpart = w.dpart_v; bp.rpart = w.rpart_v; bp.img = w.bimg_u;
+        MF_TIMED("loss_bwd_dv", s, (launch_bwd<128, false, false, 1>(gmode, dim3((unsigned)w.nsplit_v, (unsigned)(w.NT / w.NW)), bp, s)));
+        const SumJob ja{w.dpart, w.rpart, u, w.nsplit_u, B, w.Bp, du}, jb{w.dpart_v, w.rpart_v, v, w.nsplit_v, N, w.Np, dv};
+        const int nb_a = (int)((B * (128 / 4) + 255) / 256), nb_b = (int)((N * (128 / 4) + 255) / 256);
+        sum_parts_kernel<<<dim3((unsigned)(nb_a + nb_b)), 256, 0, s>>>(ja, jb, 128, nb_a);
+        return MF_OK;
+    }
     MF_DISPATCH_D(d, {
         bp.YT = w.NT; bp.tps = w.tps_u;
         MF_TIMED("loss_bwd_du", s, (launch_bwd<D, true>(gmode, dim3((unsigned)w.nsplit_u, (unsigned)(w.BT / w.NW)), bp, s)));

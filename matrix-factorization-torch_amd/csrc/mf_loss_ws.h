@@ -11,6 +11,7 @@
 // and its per-workspace record in mf_loss_dense.hip): nothing here is a variable.
 #pragma once
 
+#include "mf_bf_split.h"
 #include "mf_common.h"
 #include "mf_loss_cols.h"
 #include "mf_loss_math.h"
@@ -71,6 +72,9 @@ struct LossWs {
     int wgs_f, wgs_b;            // workgroups the forward / the backward sweeps aim at
     int32_t *geo, *ckept, *ccnt, *ctcnt, *crank, *cfirst;
     float *cv, *cnv, *clq, *cw;
+    // the split backward sweeps (mf_bf_split.h; dense path at d = 128): the bf16 piece images of u and of v (or the packed v')
+    bool split_ok;               // the shape can be served by them
+    unsigned short *bimg_u, *bimg_v;
     size_t total;
 };
 
@@ -98,6 +102,8 @@ static inline LossWs loss_ws(void* base, int64_t B, int64_t N, int d, int num_ne
     // (a sweep's buffer descriptor may have to cover the whole streamed operand: tiles per split are only known on the device)
     w.cols_ok = !w.mined && d == 128 && (size_t)w.Np * d * 4 <= MF_SRD_MAX_BYTES;
     w.cl = cols_launch(w.BT, w.NT, w.NW, w.wgs_f, w.wgs_b);
+    // (as above: a sweep's descriptor may have to cover the whole image of its streamed operand, 24 KiB per tile)
+    w.split_ok = !w.mined && d == 128 && (size_t)w.NT * BSI_TILEB <= MF_SRD_MAX_BYTES;
     const int k = num_negatives;
     w.plan = mf_select_plan(B, N, d, k);
     MfArena a(base);
@@ -176,6 +182,19 @@ static inline LossWs loss_ws(void* base, int64_t B, int64_t N, int d, int num_ne
         w.rpart_v = a.take<float>(rows_v);
         w.stash = a.take<float>((size_t)w.Bp * w.Np);
         w.gstash = a.take<float>((size_t)w.Bp * w.Np);
+        if (w.split_ok) {
+            // A backward either runs the split sweeps, which keep no G' stash (dV derives G' itself), or the fp32 sweeps, which
+            // read no image; both are rebuilt by every backward.  So the images live in the G' stash wherever they fit (24 KiB
+            // per tile against 4 KiB per pair of tiles: from a few hundred rows on) and the workspace grows for tiny shapes only.
+            const size_t nu = (size_t)w.BT * BSI_TILE_ELEMS, nv = (size_t)w.NT * BSI_TILE_ELEMS;
+            if ((nu + nv) * sizeof(unsigned short) <= (size_t)w.Bp * w.Np * sizeof(float)) {
+                w.bimg_u = reinterpret_cast<unsigned short*>(w.gstash);
+                w.bimg_v = w.gstash ? w.bimg_u + nu : nullptr;
+            } else {
+                w.bimg_u = a.take<unsigned short>(nu);
+                w.bimg_v = a.take<unsigned short>(nv);
+            }
+        }
     }
     w.total = a.used();
     return w;

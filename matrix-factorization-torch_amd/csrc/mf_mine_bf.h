@@ -33,6 +33,7 @@
 
 #include <cstdlib>
 
+#include "mf_bf_split.h"
 #include "mf_common.h"
 #include "mf_select.h"
 #include "mf_stream.h"
@@ -95,19 +96,7 @@ static inline MineBfPlan mine_bf_plan(int64_t B, int64_t N, int d, int k) {
 
 #ifdef __HIPCC__
 
-__device__ __forceinline__ unsigned short mbf_round(float x) {
-    const __bf16 b = (__bf16)x;
-    return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float mbf_float(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
-// x -> three bf16 pieces whose sum is x to 2^-26 |x| (the subtractions are exact)
-__device__ __forceinline__ void mbf_split3(float x, unsigned short (&o)[3]) {
-    o[0] = mbf_round(x);
-    const float r1 = x - mbf_float(o[0]);
-    o[1] = mbf_round(r1);
-    const float r2 = r1 - mbf_float(o[1]);
-    o[2] = mbf_round(r2);
-}
+// (mbf_round, mbf_float, mbf_split3: mf_bf_split.h)
 
 // ------------------------------------------------------- user fragments ----
 // as u (as = sigma sign(target)) split in two bf16 numbers, in MFMA operand order (hi steps, then lo steps); one thread per

@@ -202,7 +202,8 @@ int mf_loss_cols_info(const void* ws, int64_t* out);
  * losses.  Read at each backward.  Process-wide. */
 void mf_set_dense_bwd_split(int mode);
 /* Tests and tools only: the path of the last mf_loss_bwd on this workspace -- bit 0: distinct columns, bit 1: split
- * contraction, bit 2: dV derived G' from the logit stash itself.  0 for a workspace no dense backward has run on. */
+ * contraction, bit 2: dV derived G' from the logit stash itself.  0 for a workspace no backward has run on, and after a
+ * backward that runs no dense sweep (a mined loss, the alignment loss). */
 int mf_loss_bwd_path(const void* ws);
 /* Tests only: the slot of (row of a 32-row tile, feature, piece) among the 12,288 bf16 of a tile's operand image
  * (csrc/mf_bf_split.h); -1 outside 32 x 128 x 3. */

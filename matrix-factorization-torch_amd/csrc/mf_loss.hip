@@ -371,6 +371,7 @@ extern "C" int mf_loss_bwd(int64_t B, int64_t N, int d, int P, int num_negatives
     if (!(flags & MF_LOSS_ROWC))      // else finish_kernel of the forward already wrote them
         rowc_kernel<<<dim3((unsigned)((w.Bp + 255) / 256)), 256, 0, s>>>(w.stats, w.tgt, w.lii, w.sgn, B, w.Bp, kind, sigma, margin, w.rowc);
     const int gmode = gmode_of(kind);
+    if (kind == MF_ALIGNMENT || w.mined) dense_bwd_none(ws);
     if (kind == MF_ALIGNMENT) {
         MF_DISPATCH_D(d, {
             const int64_t nthreads = N * (D / 4);

@@ -841,6 +841,7 @@ static void bwd_path_note(const void* ws, int path) {
     std::lock_guard<std::mutex> lk(g_path_mu);
     g_bwd_path[ws] = path;
 }
+void dense_bwd_none(const void* ws) { bwd_path_note(ws, 0); }
 
 // ---- the distinct-column sweeps' switch (mf_loss_cols.h) ----
 // 0 never, 1 where it pays (default), 2 wherever it can serve (tests).  Served: the dense (unmined) path at d = 128, all

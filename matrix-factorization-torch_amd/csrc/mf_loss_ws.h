@@ -259,6 +259,8 @@ int dense_fwd(const LossWs& w, bool cols, int planes, const float* u, const floa
 // dU, dV and their split sums, on the path the last forward on `ws` took
 int dense_bwd(const LossWs& w, const void* ws, int gmode, const float* u, const float* v, const float* grad_out, float* du,
               float* dv, hipStream_t s);
+// a backward that runs no dense sweep (mined, alignment): mf_loss_bwd_path answers 0 for it, not what an earlier one left
+void dense_bwd_none(const void* ws);
 // mf_loss_mined.hip: candidate search, row top-k into w.sel / w.sel_L / w.stats, [the mask export]
 int mined_fwd(const LossWs& w, const float* u, const float* v, int num_negatives, int need, float sigma, float margin,
               uint32_t* out_mask_bits, hipStream_t s);

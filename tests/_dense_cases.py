@@ -185,14 +185,16 @@ def grad_excess(got, want, sigma, base=1e-4, per_sigma=5e-6, floor=1e-5):
     return (np.abs(got - want) / allowed).max(axis=1)
 
 
-def assert_grads_close_located(got, want, sigma, what, side, p):
+def assert_grads_close_located(got, want, sigma, what, side, p, floor_scale=1.0):
     """_golden_util.assert_grads_close over ALL rows; a failure names the worst row and where the sweeps hold it.
     ``side``: "du" (a user row: kept by the forward / dU workgroup i // 128, streamed by dV) or "dv" (an item row: kept by
-    the dV workgroup j // 128, streamed by the forward and dU)."""
+    the dV workgroup j // 128, streamed by the forward and dU).  ``floor_scale``: the absolute floor of the bar times this --
+    |g| where ``want`` is g x the gradient (a backward under a non-unit grad_out); the relative part scales by itself."""
+    floor = 1e-5 * floor_scale
     try:
-        gu.assert_grads_close(got, want, sigma, what)
+        gu.assert_grads_close(got, want, sigma, what, floor=floor)
     except AssertionError as e:
-        ex = grad_excess(got, want, sigma)
+        ex = grad_excess(got, want, sigma, floor=floor)
         bad = np.nonzero(ex > 1.0)[0]
         r = int(np.argmax(ex))
         if side == "du":

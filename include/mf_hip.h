@@ -401,6 +401,41 @@ int mf_topk_deep(const float* q, int64_t Q, const float* items, int64_t N, int d
                  const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base,
                  void* ws, size_t ws_bytes, float* out_scores, int64_t* out_idx, mf_stream_t stream);
 
+/* Partitioned (inverted-file) retrieval: a query scans only the cells it probes -- and those exactly.  The catalog is kept a
+ * second time ordered by cell, every cell padded to whole 64-row blocks: `blocked` = mf_topk_blocked_build of that padded
+ * matrix (padding rows zero), cell_blk[C + 1] = the first 64-row block of every cell (cell_blk[c] == cell_blk[c + 1]: an empty
+ * cell), row_of[Npad] = the catalog row at a padded position, -1 for padding, max_cell_blocks = the largest cell's blocks.
+ *
+ * mf_ivf_scan replaces the partition scan of the reference's `search` (xfmr_rec/data/lightning.py:250-259: LanceDB visits
+ * num_probes = 8 partitions and scores their rows through a product quantiser).  probes[Q][nprobe] names the cells of every
+ * query (a cell outside [0, C) contributes nothing).  Every row of a probed cell is scored with the chain of mf_topk and keyed
+ * by its CATALOG row, exclusion lists as for mf_topk (GLOBAL rows, any order); one workgroup per (query, probe, slice of the
+ * cell) leaves its k best as a partial list in ws: [G = nprobe * S][Q][k] packed entries as mf_topk_pack writes them (global
+ * rows, -1 for none), which mf_topk_merge_packed(ws, G, Q, k, ..) turns into the result -- bit for bit mf_topk's over the
+ * union of the probed cells (all cells probed: over the catalog).  S = slices per cell, 0 for the planned number.  One launch,
+ * no atomics, nothing to clear, no host read: capturable.
+ * Refused before any launch, in this order: MF_EINVAL "bad argument" (a null pointer, Q, N, C or max_cell_blocks <= 0, Npad
+ * below N or no multiple of 64, max_cell_blocks > Npad / 64, S < 0); MF_ENOTSUP k outside 1..64; MF_ENOTSUP nprobe outside
+ * 1..min(C, 64); MF_EINVAL a width outside {32, 64, 128, 256}; MF_ENOTSUP "item indices must fit 32 bits" (Npad >= 2^31,
+ * idx_base < 0 or idx_base + N > 2^32); MF_ENOTSUP "nprobe * S * k too large" (above the 8192 keys of mf_topk_merge, or
+ * S > max_cell_blocks); MF_ENOSPC "workspace too small" (below G * Q * k * 8 bytes); MF_EINVAL an exclusion pair of which one
+ * is null.
+ * mf_ivf_plan is host-only: out[0] = S for this shape -- enough workgroups for a single query, at most max_cell_blocks, and
+ * nprobe * S * k <= 8192 --, out[1] = G, out[2] = workgroups, out[3] = bytes of the partial lists.  mf_ivf_ws_bytes: those
+ * bytes rounded up to 256, 0 for a shape mf_ivf_plan refuses (MF_EINVAL).
+ * mf_ivf_cell_mean replaces the centroid update of the k-means behind the reference's `create_index` (:222-229;
+ * LanceDB trains its partitions internally): out[c] = the mean of rows items[order[cell_off[c] .. cell_off[c + 1])], added in
+ * that order by one thread per dimension (no float atomics: the same bits every run), scaled to unit L2 length when
+ * `normalize` (a mean of norm zero stays as it is); an empty cell leaves out[c] untouched. */
+size_t mf_ivf_ws_bytes(int64_t Q, int nprobe, int k, int64_t max_cell_blocks);
+int mf_ivf_plan(int64_t Q, int nprobe, int k, int64_t max_cell_blocks, int64_t* out4);
+int mf_ivf_scan(const float* q, int64_t Q, const float* blocked, const int64_t* cell_blk, const int64_t* row_of, int64_t Npad,
+                int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
+                const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
+                mf_stream_t stream);
+int mf_ivf_cell_mean(const float* items, int64_t N, int d, const int64_t* order, const int64_t* cell_off, int64_t C,
+                     int normalize, float* out, mf_stream_t stream);
+
 /* Retrieval metrics @k on device, straight from the top-k output.  Replaces the
  * per-example torchmetrics updates of `update_metrics` / `get_metrics` (xfmr_rec/lightning.py:149-187,
  * :289-306: RetrievalNormalizedDCG / Recall / Precision / MAP / HitRate / MRR, top_k = 20).

@@ -100,6 +100,11 @@ SIGNATURES = {
     "mf_topk_deep_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "mf_topk_deep_plan": (c_int, [c_i64, c_i64, c_int, c_int, c_sz, ctypes.POINTER(c_i64)]),
     "mf_topk_deep": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "mf_ivf_ws_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
+    "mf_ivf_plan": (c_int, [c_i64, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]),
+    "mf_ivf_scan": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp,
+                            c_i64, c_vp, c_sz, c_vp]),
+    "mf_ivf_cell_mean": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "mf_target_positions_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_target_positions_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_target_positions": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp,

@@ -28,7 +28,7 @@ from . import losses as mf_losses
 from . import fused, models, optim
 from .logq import StreamingLogQ
 from .params import INDEX_PATH, LOGQ_PATH, PROCESSORS_JSON, TOP_K, TOWERS_PATH
-from .retrieval import ItemProcessor, PositionMetrics, RetrievalMetrics
+from .retrieval import ItemProcessor, PartitionedIndex, PositionMetrics, RetrievalMetrics
 
 FEATURE_BAGS_PATH = "feature_bags.safetensors"     # the feature towers' registered bags (save / load)
 
@@ -71,6 +71,29 @@ class MatrixFactorizationLitConfig(models.ModelConfig):
     logq_alpha: float = 0.01       # the estimator's step size: an error shrinks by 1 - alpha per sighting (a default, not tuned)
     logq_buckets: int = 0          # 0: direct, one bucket per item row; > 0: hashed into that many buckets per hash
     logq_hashes: int = 2           # 1..4, read only when logq_buckets > 0
+    # the item index ``ItemProcessor`` builds: "exact" scans the catalog; "partitioned" = retrieval.PartitionedIndex, the
+    # reference's inverted file (data/lightning.py:203, 222-229): num_partitions cells (None: its default for the catalog's
+    # size), num_probes visited per query, k-means seeded with index_seed.  The saved files are the same either way
+    index_type: str = "exact"
+    num_partitions: int | None = None
+    num_probes: int = 8
+    index_seed: int = 0
+
+    @pydantic.model_validator(mode="after")
+    def _index_fields(self):
+        if self.index_type not in ItemProcessor.INDEX_TYPES:
+            msg = f"index_type must be 'exact' or 'partitioned': {self.index_type!r}"
+            raise ValueError(msg)
+        if self.num_partitions is not None and self.num_partitions < 1:
+            msg = f"num_partitions must be None (the default for the catalog's size) or at least 1: {self.num_partitions}"
+            raise ValueError(msg)
+        if not 1 <= self.num_probes <= PartitionedIndex.MAX_PROBES:
+            msg = f"num_probes must be in 1..{PartitionedIndex.MAX_PROBES}: {self.num_probes}"
+            raise ValueError(msg)
+        if self.index_seed < 0:
+            msg = f"index_seed must not be negative: {self.index_seed}"
+            raise ValueError(msg)
+        return self
 
     @pydantic.model_validator(mode="after")
     def _streaming_logq_fields(self):
@@ -255,6 +278,11 @@ class MatrixFactorizationLitModule(_Base):
         """``Service.recommend_with_user_id`` (service.py:286-311): the user's history is excluded."""
         return self.recommend(user_idx, top_k=top_k, exclude_item_ids=exclude_item_ids)
 
+    def _item_processor(self, item_ids=None) -> ItemProcessor:
+        cfg = self.config
+        return ItemProcessor(item_ids, index_type=cfg.index_type, num_partitions=cfg.num_partitions, num_probes=cfg.num_probes,
+                             index_seed=cfg.index_seed)
+
     # ------------------------------------------------------------- save / load (f-3) ---
     def save(self, path) -> None:
         """The counterpart of ``save`` (xfmr_rec/lightning.py:312-328: ``transformer/`` + ``processors.json`` +
@@ -329,7 +357,7 @@ class MatrixFactorizationLitModule(_Base):
         module.history = {int(k): v for k, v in proc.get("history", {}).items()}
         if (path / INDEX_PATH).exists():
             idx = load_file(str(path / INDEX_PATH))
-            module.item_processor = ItemProcessor(idx["item_ids"])
+            module.item_processor = module._item_processor(idx["item_ids"])      # (a partitioned index: the same build, so the same cells)
             module.item_processor.set_index(idx["embeddings"].to(device))
         return module
 
@@ -486,7 +514,7 @@ class MatrixFactorizationLitModule(_Base):
         if self.loss_fns is None:
             self.loss_fns = self.get_loss_fns()
         if self.item_processor is None:
-            self.item_processor = ItemProcessor()
+            self.item_processor = self._item_processor()
         if self.metrics is None:
             self.metrics = self.get_metrics()
         cfg = self.config

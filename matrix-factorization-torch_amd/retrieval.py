@@ -1,4 +1,5 @@
-"""Exact brute-force retrieval over the item table (replaces the LanceDB ANN index).
+"""Exact brute-force retrieval over the item table (replaces the LanceDB ANN index), and the reference's probing of a
+partitioned index on top of it.
 
 Reference: ``ItemProcessor.get_index`` embeds every item and builds an
 ``IVF_HNSW_PQ`` cosine index (xfmr_rec/data/lightning.py:182-235);
@@ -7,10 +8,13 @@ and returns the ``top_k`` rows with ``score = 1 - cosine distance``, best first
 (:237-259).  Here the "index" is the unit-norm item matrix itself, resident in HBM,
 and ``search`` is an exact scan (``mf_topk``): same scores for unit-norm rows, exact
 instead of approximate, batched over queries, ties broken by lowest item row.
+``PartitionedIndex`` adds the inverted-file half of that index (``num_partitions`` cells, ``num_probes`` of them visited
+per query): which rows a query looks at becomes approximate, how they are scored and ordered stays exact.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Sequence
 
 import numpy as np
@@ -272,6 +276,190 @@ class ItemIndex:
         return scores, rows
 
 
+def default_num_partitions(num_items: int) -> int:
+    """The reference's default (``num_partitions = 2 ** int(log2(num_items) / 2)``, data/lightning.py:203), within 1..N."""
+    n = int(num_items)
+    return max(1, min(n, 2 ** int(math.log2(max(n, 1)) / 2)))
+
+
+def partition_layout(assign: torch.Tensor, num_partitions: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Where the rows of a catalog go when it is stored cell by cell: ``(perm [N], cell_blk [C + 1], row_of [Npad])``, all
+    int64 on ``assign``'s device.  ``assign[r]`` in ``[0, C)`` is row r's cell.  ``perm`` lists the rows by cell, inside a cell
+    in ascending row (a stable sort); every cell is padded to a multiple of 64 rows; ``cell_blk[c]`` is the first 64-row block
+    of cell c (``cell_blk[c] == cell_blk[c + 1]``: an empty cell, ``Npad = 64 * cell_blk[C]``); ``row_of[p]`` is the row at
+    padded position p, -1 for padding.  Torch ops only."""
+    c = int(num_partitions)
+    if assign.dim() != 1 or assign.dtype != torch.int64 or assign.numel() == 0 or c < 1:
+        msg = f"assign should be a non-empty int64 vector and num_partitions >= 1: {tuple(assign.shape) = }, {assign.dtype = }, {c = }"
+        raise ValueError(msg)
+    if int(assign.min()) < 0 or int(assign.max()) >= c:
+        msg = f"cells must lie in [0, {c}): {int(assign.min()) = }, {int(assign.max()) = }"
+        raise ValueError(msg)
+    dev = assign.device
+    sorted_cell, perm = torch.sort(assign, stable=True)
+    bounds = torch.searchsorted(sorted_cell, torch.arange(c + 1, dtype=torch.int64, device=dev))      # first sorted place of every cell
+    blocks = (bounds[1:] - bounds[:-1] + 63) // 64
+    cell_blk = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(blocks, 0)])
+    at = cell_blk[sorted_cell] * 64 + (torch.arange(assign.numel(), dtype=torch.int64, device=dev) - bounds[sorted_cell])
+    row_of = torch.full((int(cell_blk[-1]) * 64,), -1, dtype=torch.int64, device=dev)
+    row_of[at] = perm
+    return perm, cell_blk, row_of
+
+
+class PartitionedIndex(ItemIndex):
+    """An ``ItemIndex`` that can also search like the reference's inverted-file index (``get_index`` builds ``num_partitions``
+    cells, ``search`` visits ``num_probes = 8`` of them: data/lightning.py:203, 222-229, 250-259): the catalog is kept a second
+    time ordered by cell, and ``search`` scans the ``nprobe`` cells whose centroids score best against the query.  Which rows are
+    looked at is the only approximation: every row looked at is scored and ordered exactly, so the result is bit for bit the
+    exact engines' answer over the union of the probed cells, and ``nprobe = num_partitions`` gives ``ItemIndex.search``'s.
+    The original matrix stays: ``positions``, ``target_words`` and ``search(path="exact")`` are the parent's, on all rows.
+    The reference's ``refine_factor`` and ``num_sub_vectors`` belong to its product quantiser; scores here are exact, so there
+    is nothing to refine and they are not offered."""
+
+    MAX_PROBES = 64     # cells one query may visit (mf_ivf_scan)
+    ASSIGN_BATCH = 16384       # rows per nearest-centroid search of the build
+
+    def __init__(self, embeddings: torch.Tensor, centroids: torch.Tensor, assign: torch.Tensor, *, idx_base: int = 0,
+                 num_probes: int = 8) -> None:
+        super().__init__(embeddings, idx_base=idx_base)
+        self.num_probes = int(num_probes)
+        self._build_args: dict | None = None             # how ``build`` made this index: ``rebuild`` runs it again
+        self._install(centroids, assign)
+
+    @classmethod
+    def from_assignment(cls, embeddings: torch.Tensor, centroids: torch.Tensor, assign: torch.Tensor, *, idx_base: int = 0,
+                        num_probes: int = 8) -> "PartitionedIndex":
+        """The index over given cells: ``centroids [C, dim]``, ``assign [N]`` int64 in ``[0, C)`` (cells may be empty)."""
+        return cls(embeddings, centroids, assign, idx_base=idx_base, num_probes=num_probes)
+
+    @classmethod
+    def build(cls, embeddings: torch.Tensor, num_partitions: int | None = None, *, iters: int = 10, seed: int = 0,
+              num_probes: int = 8, idx_base: int = 0) -> "PartitionedIndex":
+        """Cells by spherical k-means, the same for the same rows and seed: the first centroids are the rows at the first C
+        places of a permutation drawn on the host; an iteration puts every row in the cell of its best centroid (the exact
+        engines' top-1: chain score, lowest cell on ties) and replaces every centroid by the unit-length mean of its rows,
+        added in row order (``mf_ivf_cell_mean``); an empty cell keeps its centroid.  A last assignment follows the last
+        update, so every row lies in the cell of its best final centroid.  ``num_partitions=None``: the reference's default."""
+        index = cls.__new__(cls)
+        ItemIndex.__init__(index, embeddings, idx_base=idx_base)
+        index.num_probes = int(num_probes)
+        n = index.num_items
+        c = default_num_partitions(n) if num_partitions is None else int(num_partitions)
+        if not 1 <= c <= n or iters < 0:
+            msg = f"num_partitions must be in 1..{n} and iters >= 0: {c = }, {iters = }"
+            raise ValueError(msg)
+        index._build_args = {"num_partitions": c, "iters": int(iters), "seed": int(seed)}
+        index._install(*index._kmeans(c, int(iters), int(seed)))
+        return index
+
+    def _assign(self, centroids: torch.Tensor) -> torch.Tensor:
+        coarse = ItemIndex(centroids)
+        rows = self.embeddings
+        out = [coarse.search(rows[a : a + self.ASSIGN_BATCH], 1)[1][:, 0] for a in range(0, rows.shape[0], self.ASSIGN_BATCH)]
+        return torch.cat(out)
+
+    def _kmeans(self, c: int, iters: int, seed: int) -> tuple[torch.Tensor, torch.Tensor]:
+        emb = self.embeddings
+        n, d = emb.shape
+        first = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:c]
+        centroids = emb[first.to(emb.device)].clone()
+        lib = _lib.lib()
+        edges = torch.arange(c + 1, dtype=torch.int64, device=emb.device)
+        for _ in range(iters):
+            cells, order = torch.sort(self._assign(centroids), stable=True)
+            cell_off = torch.searchsorted(cells, edges)
+            _lib.check(lib.mf_ivf_cell_mean(emb.data_ptr(), n, d, order.data_ptr(), cell_off.data_ptr(), c, 1, centroids.data_ptr(),
+                                            _lib.stream_ptr()))
+        return centroids, self._assign(centroids)
+
+    def _install(self, centroids: torch.Tensor, assign: torch.Tensor) -> None:
+        cen = _lib.dev_f32(centroids.detach(), "centroids")
+        if cen.dim() != 2 or cen.shape[0] < 1 or cen.shape[1] not in (self.dim, self.embeddings.shape[1]):
+            msg = f"centroids should be (num_partitions, {self.dim}): {tuple(cen.shape) = }"
+            raise ValueError(msg)
+        if cen.shape[1] != self.embeddings.shape[1]:
+            cen = torch.nn.functional.pad(cen, (0, self.embeddings.shape[1] - cen.shape[1]))
+        a = _lib.dev_i64(assign, "assign").reshape(-1)
+        if a.numel() != self.num_items:
+            msg = f"one cell per row expected: {a.numel() = }, {self.num_items = }"
+            raise ValueError(msg)
+        self.centroids = cen.contiguous()
+        self.assign = a
+        self.num_partitions = cen.shape[0]
+        self.perm, self.cell_blk, self.row_of = partition_layout(a, self.num_partitions)
+        self.max_cell_blocks = int((self.cell_blk[1:] - self.cell_blk[:-1]).max())
+        self.coarse = ItemIndex(self.centroids)
+        self._cells = None
+
+    def cell_blocked(self) -> torch.Tensor:
+        """The catalog ordered by cell (``row_of``; padding rows zero) in the blocked layout of ``mf_topk_small``
+        (``mf_topk_blocked_build`` on the padded matrix), built once: what the cell search reads where the few-query scan
+        reads ``blocked()``.  (``blocked()`` itself stays the parent's, in row order, and is only built if ``path="scan"`` or an
+        exact search of a few queries asks for it.)"""
+        if self._cells is None:
+            lib = _lib.lib()
+            npad, d = self.row_of.numel(), self.embeddings.shape[1]
+            padded = self.embeddings[self.row_of.clamp(min=0)]
+            padded.masked_fill_((self.row_of < 0).unsqueeze(1), 0.0)
+            out = torch.empty(lib.mf_topk_blocked_bytes(npad, d) // 4, dtype=torch.float32, device=padded.device)
+            _lib.check(lib.mf_topk_blocked_build(padded.data_ptr(), npad, d, out.data_ptr(), _lib.stream_ptr()))
+            self._cells = out
+        return self._cells
+
+    def refresh(self) -> None:
+        """Forget the derived copies (the cell-ordered one too); the cells stay as they are -- ``rebuild()`` for new ones."""
+        super().refresh()
+        self._cells = None
+
+    def rebuild(self) -> None:
+        """Run the build again on the rows as they are now (an index from ``from_assignment`` keeps its cells and only
+        forgets the derived copies)."""
+        self.refresh()
+        if self._build_args is not None:
+            b = self._build_args
+            self._install(*self._kmeans(b["num_partitions"], b["iters"], b["seed"]))
+
+    def plan(self, num_queries: int, top_k: int = TOP_K, nprobe: int | None = None) -> dict[str, int]:
+        """The geometry ``search`` runs with (``mf_ivf_plan``): slices per cell, partial lists per query, workgroups."""
+        out = (ctypes.c_int64 * 4)()
+        nprobe = self.num_probes if nprobe is None else int(nprobe)
+        _lib.check(_lib.lib().mf_ivf_plan(int(num_queries), nprobe, int(top_k), self.max_cell_blocks, out))
+        return {"slices": out[0], "lists": out[1], "workgroups": out[2], "bytes": out[3]}
+
+    def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
+               exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, nprobe: int | None = None,
+               path: str = "cells") -> tuple[torch.Tensor, torch.Tensor]:
+        """``ItemIndex.search``'s inputs and result -- shapes, dtypes, the -inf / -1 tail -- over the rows of the ``nprobe``
+        cells (default ``num_probes``) whose centroids score best against each query (exact, lowest cell on ties).
+        ``path="cells"``: three launches' worth of stages, none with a host read -- the cells (the exact engines on the centroid
+        matrix), the scan (``mf_ivf_scan``), the merge (``mf_topk_merge_packed``).  ``path="exact"`` is the parent's search over
+        the whole catalog ("auto"); any other path is passed to the parent as it is."""
+        if path != "cells":
+            return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, path="auto" if path == "exact" else path)
+        nprobe = self.num_probes if nprobe is None else int(nprobe)
+        top_k = int(top_k)
+        if not 1 <= top_k <= self.TILE_MAX_K:
+            msg = f"the partitioned search returns 1..{self.TILE_MAX_K} rows per query: {top_k = }"
+            raise ValueError(msg)
+        if not 1 <= nprobe <= min(self.num_partitions, self.MAX_PROBES):
+            msg = f"nprobe must be in 1..{min(self.num_partitions, self.MAX_PROBES)}: {nprobe = }"
+            raise ValueError(msg)
+        q = self._queries(queries)
+        nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
+        _, probes = self.coarse.search(q, nprobe)
+        lib = _lib.lib()
+        scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
+        rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
+        ws = self._workspace(("cells", nq, nprobe, top_k), lib.mf_ivf_ws_bytes(nq, nprobe, top_k, self.max_cell_blocks))
+        lists = self.plan(nq, top_k, nprobe)["lists"]
+        _lib.check(lib.mf_ivf_scan(q.data_ptr(), nq, self.cell_blocked().data_ptr(), self.cell_blk.data_ptr(), self.row_of.data_ptr(),
+                                   self.row_of.numel(), n, self.num_partitions, d, self.max_cell_blocks, probes.data_ptr(), nprobe, top_k, 0,
+                                   _lib.ptr(off), _lib.ptr(ids), self.idx_base, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        _lib.check(lib.mf_topk_merge_packed(ws.data_ptr(), lists, nq, top_k, scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
+        return scores, rows
+
+
 def merge_topk(part_scores: torch.Tensor, part_rows: torch.Tensor, top_k: int) -> tuple[torch.Tensor, torch.Tensor]:
     """Merge per-shard results ``[G, Q, k]`` (global rows, each list ordered as ``search`` returns it) into the global top-k:
     ``mf_topk_merge`` up to ``ItemIndex.TILE_MAX_K``, ``mf_topk_merge_deep`` for deeper lists (``top_k`` up to
@@ -300,16 +488,34 @@ class ItemProcessor:
     idx_col: str = ITEM_IDX_COL
     id_col: str = ITEM_ID_COL
 
-    def __init__(self, item_ids: Sequence[int] | torch.Tensor | None = None) -> None:
+    INDEX_TYPES = ("exact", "partitioned")
+
+    def __init__(self, item_ids: Sequence[int] | torch.Tensor | None = None, *, index_type: str = "exact",
+                 num_partitions: int | None = None, num_probes: int = 8, index_seed: int = 0) -> None:
+        """``index_type="partitioned"``: ``get_index`` / ``set_index`` / ``append`` build a ``PartitionedIndex`` --
+        ``num_partitions`` cells (None: the reference's default for the catalog's size), ``num_probes`` of them visited per
+        query, k-means seeded with ``index_seed`` -- and ``search`` probes it.  The reference's ``refine_factor`` and
+        ``num_sub_vectors`` tune its product quantiser; rows are scored exactly here, so they are not offered."""
+        if index_type not in self.INDEX_TYPES:
+            msg = f"index_type must be 'exact' or 'partitioned': {index_type!r}"
+            raise ValueError(msg)
         self.item_ids = None if item_ids is None else torch.as_tensor(item_ids, dtype=torch.int64).cpu()
+        self.index_type, self.num_partitions, self.num_probes, self.index_seed = index_type, num_partitions, int(num_probes), int(index_seed)
         self.index: ItemIndex | None = None
         self._row_of_id: dict[int, int] | None = None
+
+    def _make_index(self, embeddings: torch.Tensor) -> ItemIndex:
+        if self.index_type == "exact":
+            return ItemIndex(embeddings)
+        c = self.num_partitions if self.num_partitions is not None else default_num_partitions(embeddings.shape[0])
+        c = max(1, min(int(c), embeddings.shape[0]))
+        return PartitionedIndex.build(embeddings, c, seed=self.index_seed, num_probes=min(self.num_probes, c, PartitionedIndex.MAX_PROBES))
 
     @torch.inference_mode()
     def get_index(self, model: torch.nn.Module, subset: str = "predict") -> ItemIndex:  # noqa: ARG002
         tower = model.towers["item"] if hasattr(model, "towers") else model
         rows = torch.arange(tower.num_embeddings, device=tower.weight.device)
-        self.index = ItemIndex(tower(rows))
+        self.index = self._make_index(tower(rows))
         if self.item_ids is None:
             self.item_ids = torch.arange(tower.num_embeddings)
         self._row_of_id = {int(i): r for r, i in enumerate(self.item_ids.tolist())}
@@ -317,7 +523,7 @@ class ItemProcessor:
 
     def set_index(self, embeddings: torch.Tensor) -> ItemIndex:
         """Install a prebuilt (loaded) item matrix; row r belongs to ``item_ids[r]``."""
-        self.index = ItemIndex(embeddings)
+        self.index = self._make_index(embeddings)
         if self.item_ids is None:
             self.item_ids = torch.arange(embeddings.shape[0])
         self._row_of_id = {int(i): r for r, i in enumerate(self.item_ids.tolist())}

@@ -436,6 +436,65 @@ int mf_ivf_scan(const float* q, int64_t Q, const float* blocked, const int64_t* 
 int mf_ivf_cell_mean(const float* items, int64_t N, int d, const int64_t* order, const int64_t* cell_off, int64_t C,
                      int normalize, float* out, mf_stream_t stream);
 
+/* Product-quantised cells with an exact refine: the rest of the reference's IVF_PQ index (xfmr_rec/data/lightning.py:162-165,
+ * 203-204: num_sub_vectors = embedding_dim // 8, refine_factor = 4; :222-229 create_index; :250-259
+ * search(..).nprobes(..).refine_factor(..)).  The cells, cell_blk, row_of, Npad and max_cell_blocks are those of mf_ivf_scan;
+ * the cell-ordered fp32 copy is replaced by one byte per dsub channels.  With D = M * dsub (dsub in {4, 8, 16}, M <= 64),
+ * codebooks B[M][256][dsub] fp32 and chain = the mf_dot_chain of mf_numerics.h over a sub-vector -- at dsub = 4 its four products
+ * in ascending channel order, the chain of the sub-vector zero-padded to 8 --:
+ *   residual  r = x - centroids[assign[row]]                               (one fp32 subtraction per channel)
+ *   code[m]   = argmax_j (chain(r[m], B[m][j]) - 0.5f * chain(B[m][j], B[m][j])), the lowest j on ties
+ *   lut[m][j] = chain(q[m], B[m][j])
+ *   approx    = ((base + lut[0][code[0]]) + lut[1][code[1]]) + ..,  base = chain(q, centroid of the cell): plain fp32 adds
+ * Code layout (cell-ordered): U = min(M, 4) code bytes make a unit, a row has M / U units, and
+ *   byte ((blk * (M / U) + u) * 64 + lane) * U + b  is code u * U + b of padded position blk * 64 + lane,
+ * i.e. [64-row block][M / 4][64] 32-bit words with lane = row: a wave loads a unit of a block as one coalesced 256 B; Npad * M
+ * bytes in all; padding positions hold code 0 (the scan masks them by row_of < 0).
+ *
+ * mf_pq_encode replaces the encoding step of LanceDB's create_index.  rows[N][d]; with centroids[C][d] and assign[N] the
+ * residuals are formed in the kernel, with both null `rows` are residuals already.  With row_of[Npad] the codes leave in the
+ * layout above; with row_of null (then Npad must equal N) as plain bytes [N][M] -- the assignment step of the codebook
+ * training.  Refused before any launch, in this order: MF_EINVAL "bad argument" (a null rows / codebooks / codes, N <= 0,
+ * Npad below N or no multiple of 64, or Npad != N without row_of); MF_EINVAL "centroids/assign mismatch"; MF_EINVAL a width
+ * outside {32, 64, 128, 256}; MF_ENOTSUP a sub-vector length outside {4, 8, 16} or more than 64 sub-vectors; MF_ENOTSUP
+ * "too many rows".  The codeword update of the training needs no export of its own: mf_ivf_cell_mean(residuals, T, d, order,
+ * cell_off, 256, 0, out[256][d]) with the training rows listed by code of sub-space m gives the means of all channels, of
+ * which channels m * dsub .. are the new codewords -- added in list order, divided by (float)count, an empty codeword's row
+ * left as it was.
+ * mf_pq_scan replaces the quantised partition scan of the reference's search.  probes / probe_scores [Q][nprobe]: the cells of
+ * every query and chain(q, their centroid) -- what the exact engines return on the centroid matrix.  One workgroup per (query,
+ * probe, slice of the cell) builds the query's M x 256 table in LDS, forms approx for every row of its slice and keeps the R
+ * best keys -- mf_key_retrieval of approx and the GLOBAL row --; only a key that beats the current R-th (nothing to beat until a first sort
+ * has left R keys: more than 512 keys waiting, or the end of the slice) is looked up in the exclusion list
+ * (GLOBAL rows, any order), so an excluded row never takes a place.  It writes an ordered list of R packed entries (approx
+ * bits << 32 | global row, -1 for none): ws = [G = nprobe * S][Q][R], which mf_topk_merge_packed_deep(ws, G, Q, R, ..) joins
+ * into the R candidates of every query.  S = slices per cell, 0 for the planned number.  One launch, no atomics, nothing to
+ * clear, no host read: capturable.  Refused before any launch, in this order: MF_EINVAL "bad argument" (a null pointer, Q, N, C
+ * or max_cell_blocks <= 0, Npad below N or no multiple of 64, max_cell_blocks > Npad / 64, S < 0); MF_ENOTSUP R outside
+ * 1..256; MF_ENOTSUP nprobe outside 1..min(C, 64); MF_EINVAL a width outside {32, 64, 128, 256}; MF_ENOTSUP a sub-vector length
+ * outside {4, 8, 16} or more than 64 sub-vectors; MF_ENOTSUP "item indices must fit 32 bits" (Npad >= 2^31, idx_base < 0 or
+ * idx_base + N > 2^32); MF_ENOTSUP "nprobe * S * R too large" (above the MF_TOPK_MERGE_DEEP_MAX_KEYS = 16,384 keys of the
+ * merge, S > max_cell_blocks, or 2^31 workgroups and more: Q * nprobe * S >= 2^31); MF_ENOSPC "workspace too small" (below G * Q * R * 8 bytes); MF_EINVAL an exclusion pair of
+ * which one is null.
+ * mf_pq_plan is host-only and follows the rule of mf_ivf_plan with R in the place of k and that key budget: out[0] = S,
+ * out[1] = G, out[2] = workgroups, out[3] = bytes of the partial lists; MF_EINVAL for a null out, Q or max_cell_blocks <= 0, R
+ * outside 1..256 or nprobe outside 1..64.  mf_pq_ws_bytes: those bytes rounded up to 256, 0 for a shape mf_pq_plan refuses.
+ * mf_pq_refine replaces refine_factor's rescoring: cand[Q][R] GLOBAL rows (-1, or a row outside [idx_base, idx_base + N): no
+ * candidate) are scored with the chain of mf_topk on items[N][d] -- the original matrix --, keyed by mf_key_retrieval of
+ * that score and the global row, and the k best leave as mf_topk writes them (scores, int64 global rows, the -inf / -1 tail).  One workgroup per
+ * query.  Refused before any launch, in this order: MF_EINVAL "bad argument"; MF_ENOTSUP k outside 1..64; MF_ENOTSUP R outside
+ * k..256; MF_EINVAL a width outside {32, 64, 128, 256}; MF_ENOTSUP "item indices must fit 32 bits". */
+int mf_pq_encode(const float* rows, int64_t N, int d, const float* centroids, const int64_t* assign, const float* codebooks,
+                 int dsub, const int64_t* row_of, int64_t Npad, void* codes, mf_stream_t stream);
+size_t mf_pq_ws_bytes(int64_t Q, int nprobe, int R, int64_t max_cell_blocks);
+int mf_pq_plan(int64_t Q, int nprobe, int R, int64_t max_cell_blocks, int64_t* out4);
+int mf_pq_scan(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+               const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes,
+               const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off, const int64_t* excl_idx,
+               int64_t idx_base, void* ws, size_t ws_bytes, mf_stream_t stream);
+int mf_pq_refine(const float* q, int64_t Q, const float* items, int64_t N, int d, const int64_t* cand, int R, int k,
+                 int64_t idx_base, float* out_scores, int64_t* out_idx, mf_stream_t stream);
+
 /* Retrieval metrics @k on device, straight from the top-k output.  Replaces the
  * per-example torchmetrics updates of `update_metrics` / `get_metrics` (xfmr_rec/lightning.py:149-187,
  * :289-306: RetrievalNormalizedDCG / Recall / Precision / MAP / HitRate / MRR, top_k = 20).

@@ -105,6 +105,12 @@ SIGNATURES = {
     "mf_ivf_scan": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp,
                             c_i64, c_vp, c_sz, c_vp]),
     "mf_ivf_cell_mean": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
+    "mf_pq_encode": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_vp]),
+    "mf_pq_ws_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
+    "mf_pq_plan": (c_int, [c_i64, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]),
+    "mf_pq_scan": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_int,
+                           c_vp, c_vp, c_i64, c_vp, c_sz, c_vp]),
+    "mf_pq_refine": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp]),
     "mf_target_positions_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_target_positions_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_target_positions": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp,

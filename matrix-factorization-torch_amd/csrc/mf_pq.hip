@@ -1,0 +1,438 @@
+// mf_pq.hip -- product-quantised cells with an exact refine: the other half of the reference's IVF_PQ index (gfx950).
+//
+// The reference builds its index with num_sub_vectors = embedding_dim // 8 and searches it with
+// nprobes(num_probes).refine_factor(refine_factor) (xfmr_rec/data/lightning.py:162-165, 203-204, 222-229, 250-259): the rows of
+// the probed partitions are ranked by a score read from per-query tables over one-byte codes, and the refine_factor * top_k
+// best of them are scored again on the stored vectors.  mf_ivf.hip keeps the cells and scores every probed row exactly from a
+// cell-ordered fp32 copy; here that copy is replaced by the codes (one byte per dsub channels), and only R = refine_factor *
+// top_k rows per query are read from the original matrix.  Which rows are returned is approximate; their scores are the
+// canonical chain's (mf_numerics.h), keyed by the catalog row.
+//
+// Arithmetic (D = M * dsub channels, codebooks B[M][256][dsub], chain = mf_dot_chain over a sub-vector; at dsub = 4 the four
+// products in ascending channel order -- the chain of the sub-vector zero-padded to 8):
+//   residual   r = x - centroid[cell]                                      one fp32 subtraction per channel
+//   encode     code[m] = argmax_j (chain(r[m], B[m][j]) - 0.5f * chain(B[m][j], B[m][j])), lowest j on ties
+//   table      lut[m][j] = chain(q[m], B[m][j])
+//   approx     ((base + lut[0][code_0]) + lut[1][code_1]) + ..,  base = chain(q, centroid[cell]) (the coarse search's score)
+//
+// Code layout ("cell-ordered", what pq_encode_kernel writes and pq_scan_kernel reads): positions are those of row_of[Npad]
+// (partition_layout: every cell padded to whole 64-row blocks).  With U = min(M, 4) bytes per unit and M / U units per row,
+//   byte ((blk * (M / U) + u) * 64 + lane) * U + b  =  code u * U + b of position blk * 64 + lane:
+// [64-row block][M / 4][64] 32-bit words, lane = row, so a wave loads a unit of a block as one coalesced 256 B (M = 2: 128 B)
+// and a row costs M bytes -- Npad * M in all.  Padding positions hold code 0 and are masked by row_of < 0.
+//
+//   * pq_encode_kernel: a workgroup per 64 positions, lane = position, a wave per sub-space in turn: the residual sub-vector
+//     in registers, the 256 codewords through scalar loads, their half norms in LDS.
+//   * pq_scan_kernel: a workgroup per (query, probe, slice).  It builds the query's M x 256 table in LDS from the codebooks
+//     (thread = codeword), then walks the slice's blocks, a block per wave and pass, lane = row.  Keys that beat the bound (and
+//     only those are looked up in the exclusion list) are appended behind the R kept ones in a workgroup-wide LDS buffer of
+//     1,024 keys -- the waves' counts are exchanged through LDS, no atomics --, which a bitonic sort orders when another pass
+//     might not fit.  Every workgroup writes all R entries of its ordered list: [nprobe * S][Q][R] packed, the form
+//     mf_topk_merge_packed_deep takes.
+//   * pq_refine_kernel: a workgroup per query, a thread per merged candidate: the chain on the original row, then the
+//     top_k <= 64 by mf_row_topk (as the join of ivf_scan_kernel), stored with the standard tail.
+#include "mf_common.h"
+#include "mf_select.h"
+#include "mf_topk_io.h"
+
+static constexpr int PQ_NW = 4;                // waves per workgroup, each a 64-row block per pass
+static constexpr int PQ_THREADS = 64 * PQ_NW;
+static constexpr int PQ_MAX_K = 64;            // one wavefront holds the result
+static constexpr int PQ_MAX_R = PQ_THREADS;    // candidates per query: a thread each in the refine
+static constexpr int PQ_MAX_PROBE = 64;
+static constexpr int PQ_MAX_M = 64;            // 64 KiB of tables
+static constexpr int PQ_MERGE_KEYS = MF_TOPK_MERGE_DEEP_MAX_KEYS;
+static constexpr int PQ_TARGET_WG = 1024;      // workgroups worth launching: four per CU
+static constexpr int PQ_BUF = 1024;            // keys of the workgroup's buffer: PQ_MAX_R kept, then the waiting ones
+
+typedef const __attribute__((address_space(4))) float* pq_const_f32;
+
+static inline bool pq_dsub_ok(int dsub) { return dsub == 4 || dsub == 8 || dsub == 16; }
+
+#define PQ_DISPATCH_M(DS, d, ...)                                                          \
+    switch (d) {                                                                           \
+        case 32: { constexpr int M = 32 / DS, DSUB = DS; __VA_ARGS__; } break;              \
+        case 64: { constexpr int M = 64 / DS, DSUB = DS; __VA_ARGS__; } break;              \
+        case 128: { constexpr int M = 128 / DS, DSUB = DS; __VA_ARGS__; } break;            \
+        default: { constexpr int M = 256 / DS, DSUB = DS; __VA_ARGS__; } break;             \
+    }
+// (d in {32, 64, 128, 256} and dsub in {4, 8, 16} were checked: twelve pairs, M = 2 .. 64)
+#define PQ_DISPATCH(d, dsub, ...)                                                     \
+    switch (dsub) {                                                                        \
+        case 4: PQ_DISPATCH_M(4, d, __VA_ARGS__) break;                                    \
+        case 8: PQ_DISPATCH_M(8, d, __VA_ARGS__) break;                                    \
+        default: PQ_DISPATCH_M(16, d, __VA_ARGS__) break;                                  \
+    }
+
+// the chain over one sub-vector: mf_dot_chain's order for 8 and 16 channels, ascending for 4
+template <int DSUB, class A, class B>
+__device__ __forceinline__ float pq_chain(const A& a, const B& b) {
+    float acc = 0.f;
+    if constexpr (DSUB == 4) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc = __builtin_fmaf(a[t], b[t], acc);
+    } else {
+#pragma unroll
+        for (int g = 0; g < DSUB; g += 8) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                acc = __builtin_fmaf(a[g + t], b[g + t], acc);
+                acc = __builtin_fmaf(a[g + 4 + t], b[g + 4 + t], acc);
+            }
+        }
+    }
+    return acc;
+}
+
+template <int DSUB>
+__device__ __forceinline__ void pq_load_sub(float (&v)[DSUB], const float* __restrict__ src) {
+#pragma unroll
+    for (int c = 0; c < DSUB / 4; ++c) {
+        const f32x4 x = reinterpret_cast<const f32x4*>(src)[c];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[4 * c + t] = x[t];
+    }
+}
+
+// ---------------------------------------------------------------------- encode ----
+struct PqEncodeParams {
+    const float* rows;          // [N][d]: the stored rows, or residuals when centroids is null
+    const float* centroids;     // [C][d], nullable
+    const int64_t* assign;      // [N], with centroids
+    const float* codebooks;     // [M][256][dsub]
+    const int64_t* row_of;      // [npos]: the row at a position, -1 for padding; null: position = row, codes [N][M]
+    int64_t N, npos;
+    int d, M;
+    unsigned char* codes;
+};
+
+template <int DSUB>
+__global__ __launch_bounds__(PQ_THREADS) void pq_encode_kernel(PqEncodeParams p) {
+    __shared__ float half_norm[PQ_NW][256];
+    const int lane = mf_lane(), wave = mf_wave_id();
+    const int64_t pos = (int64_t)blockIdx.x * 64 + lane;
+    int64_t row = -1;
+    if (pos < p.npos) row = p.row_of ? p.row_of[pos] : pos;
+    if (row >= p.N) row = -1;
+    const int64_t safe = row < 0 ? 0 : row;
+    const float* x = p.rows + safe * p.d;
+    const float* cen = p.centroids ? p.centroids + p.assign[safe] * p.d : nullptr;
+    const int U = p.M < 4 ? p.M : 4;
+    for (int m = wave; m < p.M; m += PQ_NW) {                       // (wave-uniform)
+        const float* book = p.codebooks + (size_t)m * 256 * DSUB;
+        mf_row_topk_sync<true>();                                  // the wave has read the last sub-space's norms
+#pragma unroll
+        for (int j = lane; j < 256; j += 64) {
+            float b[DSUB];
+            pq_load_sub<DSUB>(b, book + j * DSUB);
+            half_norm[wave][j] = 0.5f * pq_chain<DSUB>(b, b);
+        }
+        mf_row_topk_sync<true>();
+        float r[DSUB], c[DSUB];
+        pq_load_sub<DSUB>(r, x + m * DSUB);
+        if (cen) {
+            pq_load_sub<DSUB>(c, cen + m * DSUB);
+#pragma unroll
+            for (int t = 0; t < DSUB; ++t) r[t] = r[t] - c[t];
+        }
+        pq_const_f32 bc = (pq_const_f32)book;                        // wave-uniform addresses: scalar loads
+        float best = -INFINITY;
+        int code = 0;
+        for (int j = 0; j < 256; ++j) {
+            const float s = pq_chain<DSUB>(r, bc + j * DSUB) - half_norm[wave][j];
+            if (s > best) {                                        // strictly: the lowest j of equal scores stays
+                best = s;
+                code = j;
+            }
+        }
+        if (pos < p.npos) {
+            const unsigned char byte = row >= 0 ? (unsigned char)code : (unsigned char)0;
+            if (p.row_of) p.codes[(((int64_t)blockIdx.x * (p.M / U) + m / U) * 64 + lane) * U + m % U] = byte;
+            else if (row >= 0) p.codes[pos * p.M + m] = byte;
+        }
+    }
+}
+
+extern "C" int mf_pq_encode(const float* rows, int64_t N, int d, const float* centroids, const int64_t* assign, const float* codebooks,
+                            int dsub, const int64_t* row_of, int64_t Npad, void* codes, mf_stream_t stream) {
+    if (!rows || !codebooks || !codes || N <= 0 || (row_of ? (Npad < N || (Npad & 63) != 0) : Npad != N))
+        return mf_set_error(MF_EINVAL, "mf_pq_encode: bad argument");
+    if ((centroids == nullptr) != (assign == nullptr)) return mf_set_error(MF_EINVAL, "mf_pq_encode: centroids/assign mismatch");
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_pq_encode: embedding width %d not in {32,64,128,256}", d);
+    if (!pq_dsub_ok(dsub) || d / dsub > PQ_MAX_M)
+        return mf_set_error(MF_ENOTSUP, "mf_pq_encode: sub-vector length %d not in {4,8,16} or more than %d sub-vectors", dsub, PQ_MAX_M);
+    if (Npad >= (1ll << 31) * 64) return mf_set_error(MF_ENOTSUP, "mf_pq_encode: too many rows");
+    PqEncodeParams p{rows, centroids, assign, codebooks, row_of, N, Npad, d, d / dsub, static_cast<unsigned char*>(codes)};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((Npad + 63) / 64));
+    MF_TIMED("pq_encode", s, {
+        if (dsub == 4) pq_encode_kernel<4><<<grid, PQ_THREADS, 0, s>>>(p);
+        else if (dsub == 8) pq_encode_kernel<8><<<grid, PQ_THREADS, 0, s>>>(p);
+        else pq_encode_kernel<16><<<grid, PQ_THREADS, 0, s>>>(p);
+    });
+    return mf_check_launch("mf_pq_encode");
+}
+
+// ------------------------------------------------------------------------ scan ----
+struct PqScanParams {
+    const float* q;             // [Q][D]
+    const float* codebooks;     // [M][256][DSUB]
+    const unsigned char* codes; // the cell-ordered layout above
+    const int64_t* cell_blk;    // [C + 1]
+    const int64_t* row_of;      // [Npad]
+    const int64_t* probes;      // [Q][nprobe]
+    const float* probe_scores;  // [Q][nprobe]: chain(q, centroid of the probe)
+    int64_t Q, C;
+    int nprobe, S, R;
+    const int64_t *excl_off, *excl_idx;     // nullable
+    int64_t idx_base;
+    long long* out;             // [nprobe * S][Q][R] packed entries (approx bits << 32 | global row; -1: none)
+};
+
+// buf[0, n) in descending order, n a power of two <= PQ_BUF; every thread of the workgroup calls it
+__device__ __forceinline__ void pq_sort_desc(unsigned long long* buf, int n) {
+    const int tid = threadIdx.x;
+    for (int k2 = 2; k2 <= n; k2 <<= 1) {
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < n / 2; t += PQ_THREADS) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
+                const unsigned long long a = buf[i], b = buf[l];
+                const bool rising = (i & k2) != 0;                 // (never in the last round: the whole is descending)
+                if (rising ? a > b : a < b) {
+                    buf[i] = b;
+                    buf[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <int M, int DSUB>
+__global__ __launch_bounds__(PQ_THREADS) void pq_scan_kernel(PqScanParams p) {
+    constexpr int D = M * DSUB;
+    constexpr int U = M < 4 ? M : 4;           // code bytes per unit
+    constexpr int NU = M / U;
+    __shared__ float lut[M * 256];
+    __shared__ unsigned long long buf[PQ_BUF];
+    __shared__ int cnt[PQ_NW];
+    const int tid = threadIdx.x, lane = mf_lane(), wave = mf_wave_id();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // blockIdx.x = (q * nprobe + probe) * S + slice: everything here is workgroup-uniform
+    const int64_t wg = blockIdx.x;
+    const int slice = (int)(wg % p.S);
+    const int probe = (int)((wg / p.S) % p.nprobe);
+    const int64_t q = wg / ((int64_t)p.S * p.nprobe);
+    const int64_t cell = p.probes[q * p.nprobe + probe];
+    const float base = p.probe_scores[q * p.nprobe + probe];
+    int64_t b0 = 0, b1 = 0;
+    if (cell >= 0 && cell < p.C) {
+        const int64_t c0 = p.cell_blk[cell], nb = p.cell_blk[cell + 1] - c0;
+        b0 = c0 + nb * slice / p.S;
+        b1 = c0 + nb * (slice + 1) / p.S;
+    }
+    int64_t e0 = 0, e1 = 0;
+    if (p.excl_off) {
+        e0 = p.excl_off[q];
+        e1 = p.excl_off[q + 1];
+    }
+    for (int i = tid; i < PQ_BUF; i += PQ_THREADS) buf[i] = 0ull;
+    if (b0 < b1) {                                                   // the query's tables: thread = codeword
+        pq_const_f32 qc = (pq_const_f32)p.q + (size_t)q * D;
+#pragma unroll 2                                                   // (the query's sub-vectors sit in scalar registers: four at dsub = 16 spill them)
+        for (int m = 0; m < M; ++m) {
+            float b[DSUB];
+            pq_load_sub<DSUB>(b, p.codebooks + ((size_t)m * 256 + tid) * DSUB);
+            lut[m * 256 + tid] = pq_chain<DSUB>(qc + m * DSUB, b);
+        }
+    }
+    __syncthreads();
+    unsigned long long tau = 0ull;             // the R-th best key once the buffer holds R: only a larger key matters
+    int pend = 0;                              // keys waiting behind the kept ones (workgroup-uniform)
+    // the R best of the kept and the waiting keys in descending order at the front, the rest cleared
+    auto settle = [&]() {
+        pq_sort_desc(buf, pend <= PQ_BUF / 2 - PQ_MAX_R ? PQ_BUF / 2 : PQ_BUF);
+        tau = buf[p.R - 1];
+        __syncthreads();
+        for (int i = p.R + tid; i < PQ_BUF; i += PQ_THREADS) buf[i] = 0ull;
+        pend = 0;
+        __syncthreads();
+    };
+
+    for (int64_t blk0 = b0; blk0 < b1; blk0 += PQ_NW) {                // (uniform trip count: barriers inside)
+        const int64_t blk = blk0 + wave;
+        unsigned long long key = 0ull;
+        unsigned grow = 0u;
+        if (blk < b1) {
+            const int64_t orig = p.row_of[blk * 64 + lane];
+            float acc = base;
+            if constexpr (U == 4) {
+                const unsigned* src = reinterpret_cast<const unsigned*>(p.codes) + blk * (int64_t)NU * 64 + lane;
+                unsigned w[NU];
+#pragma unroll
+                for (int u = 0; u < NU; ++u) w[u] = src[u * 64];
+#pragma unroll
+                for (int u = 0; u < NU; ++u) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) acc = acc + lut[(4 * u + b) * 256 + ((w[u] >> (8 * b)) & 255u)];
+                }
+            } else {
+                const unsigned w = reinterpret_cast<const unsigned short*>(p.codes)[blk * 64 + lane];
+                acc = acc + lut[w & 255u];
+                acc = acc + lut[256 + (w >> 8)];
+            }
+            grow = (unsigned)(p.idx_base + orig);                    // the GLOBAL row: ties break by it
+            key = orig >= 0 ? mf_key_retrieval(acc, grow) : 0ull;
+        }
+        bool pass = key > tau;
+        if (p.excl_off) {
+            // only a key that would enter the list is looked up: the wave walks the query's exclusion list (any order) for it
+            unsigned long long todo = __ballot(pass);
+            while (todo) {
+                const int src_lane = __builtin_ctzll(todo);
+                todo &= todo - 1ull;
+                const int64_t want = (int64_t)(unsigned)__shfl((int)grow, src_lane, 64);
+                bool hit = false;
+                for (int64_t e = e0 + lane; e < e1; e += 64) hit |= p.excl_idx[e] == want;
+                if (__ballot(hit) != 0ull && lane == src_lane) pass = false;
+            }
+        }
+        const unsigned long long bal = __ballot(pass);
+        if (lane == 0) cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < PQ_NW; ++w) {
+            const int c = cnt[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (pass) buf[PQ_MAX_R + pend + before + __popcll(bal & below)] = key;
+        pend += total;
+        __syncthreads();
+        if (pend > PQ_BUF - PQ_MAX_R - PQ_THREADS) settle();         // no room for another pass's 256
+    }
+    if (pend > 0) settle();                                          // (else the front is in order already: zeros, or the last settle)
+    if (tid < p.R) {
+        const unsigned long long key = buf[tid];
+        long long v = -1ll;
+        if (key != 0ull)
+            v = (long long)(((unsigned long long)__builtin_bit_cast(unsigned, mf_key_retrieval_score(key)) << 32) |
+                            (unsigned long long)mf_key_retrieval_col(key));
+        const int64_t g = (int64_t)probe * p.S + slice;
+        p.out[(g * p.Q + q) * p.R + tid] = v;
+    }
+}
+
+// ------------------------------------------------------------------ the plan ----
+// The rule of mf_ivf_plan with the candidate depth R in the place of k and the key budget of the deep merge: enough
+// workgroups for a single query (PQ_TARGET_WG over Q * nprobe), never fewer than about a block per wave in a slice of the
+// largest cell, never more partial lists than the merge holds.
+static int pq_plan_slices(int64_t Q, int nprobe, int R, int64_t max_cell_blocks) {
+    const int64_t cap_merge = PQ_MERGE_KEYS / ((int64_t)nprobe * R);
+    const int64_t cap = cap_merge < max_cell_blocks ? cap_merge : max_cell_blocks;
+    const int64_t want = (PQ_TARGET_WG + Q * nprobe - 1) / (Q * nprobe);
+    const int64_t by_work = max_cell_blocks / PQ_NW > 1 ? max_cell_blocks / PQ_NW : 1;
+    int64_t S = want < by_work ? want : by_work;
+    if (S > cap) S = cap;
+    if (S < 1) S = 1;
+    return (int)S;
+}
+static bool pq_plan_args_ok(int64_t Q, int nprobe, int R, int64_t max_cell_blocks) {
+    return Q > 0 && max_cell_blocks > 0 && R >= 1 && R <= PQ_MAX_R && nprobe >= 1 && nprobe <= PQ_MAX_PROBE;
+}
+
+extern "C" int mf_pq_plan(int64_t Q, int nprobe, int R, int64_t max_cell_blocks, int64_t* out4) {
+    if (!out4) return mf_set_error(MF_EINVAL, "mf_pq_plan: out is NULL");
+    if (!pq_plan_args_ok(Q, nprobe, R, max_cell_blocks))
+        return mf_set_error(MF_EINVAL, "mf_pq_plan: need Q > 0, max_cell_blocks > 0, R in 1..%d and nprobe in 1..%d", PQ_MAX_R, PQ_MAX_PROBE);
+    const int S = pq_plan_slices(Q, nprobe, R, max_cell_blocks);
+    out4[0] = S;
+    out4[1] = (int64_t)nprobe * S;
+    out4[2] = Q * nprobe * S;
+    out4[3] = (int64_t)nprobe * S * Q * R * 8;
+    return MF_OK;
+}
+
+extern "C" size_t mf_pq_ws_bytes(int64_t Q, int nprobe, int R, int64_t max_cell_blocks) {
+    if (!pq_plan_args_ok(Q, nprobe, R, max_cell_blocks)) return 0;
+    return mf_align_up((size_t)nprobe * pq_plan_slices(Q, nprobe, R, max_cell_blocks) * Q * R * 8, 256);
+}
+
+extern "C" int mf_pq_scan(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+                          const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes,
+                          const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off, const int64_t* excl_idx,
+                          int64_t idx_base, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    if (!q || !codes || !codebooks || !cell_blk || !row_of || !probes || !probe_scores || !ws || Q <= 0 || N <= 0 || C <= 0 || Npad < N ||
+        (Npad & 63) != 0 || max_cell_blocks <= 0 || max_cell_blocks > Npad / 64 || S < 0)
+        return mf_set_error(MF_EINVAL, "mf_pq_scan: bad argument");
+    if (R <= 0 || R > PQ_MAX_R) return mf_set_error(MF_ENOTSUP, "mf_pq_scan: R = %d outside 1..%d", R, PQ_MAX_R);
+    const int64_t max_probe = C < PQ_MAX_PROBE ? C : PQ_MAX_PROBE;
+    if (nprobe <= 0 || nprobe > max_probe)
+        return mf_set_error(MF_ENOTSUP, "mf_pq_scan: nprobe = %d outside 1..%lld", nprobe, (long long)max_probe);
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_pq_scan: embedding width %d not in {32,64,128,256}", d);
+    if (!pq_dsub_ok(dsub) || d / dsub > PQ_MAX_M)
+        return mf_set_error(MF_ENOTSUP, "mf_pq_scan: sub-vector length %d not in {4,8,16} or more than %d sub-vectors", dsub, PQ_MAX_M);
+    if (Npad >= (1ll << 31) || idx_base < 0 || idx_base + N > (1ll << 32))
+        return mf_set_error(MF_ENOTSUP, "mf_pq_scan: item indices must fit 32 bits");
+    if (S == 0) S = pq_plan_slices(Q, nprobe, R, max_cell_blocks);
+    const int64_t G = (int64_t)nprobe * S;
+    if (G * R > PQ_MERGE_KEYS || S > max_cell_blocks || Q * G >= (1ll << 31))
+        return mf_set_error(MF_ENOTSUP, "mf_pq_scan: nprobe * S * R too large");
+    if (ws_bytes < (size_t)G * Q * R * 8) return mf_set_error(MF_ENOSPC, "mf_pq_scan: workspace too small");
+    if ((excl_off == nullptr) != (excl_idx == nullptr)) return mf_set_error(MF_EINVAL, "mf_pq_scan: excl_off/excl_idx mismatch");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PqScanParams p{q, codebooks, static_cast<const unsigned char*>(codes), cell_blk, row_of, probes, probe_scores, Q, C, nprobe, S, R,
+                   excl_off, excl_idx, idx_base, static_cast<long long*>(ws)};
+    const dim3 grid((unsigned)(Q * G));
+    PQ_DISPATCH(d, dsub, { MF_TIMED("pq_scan", s, { pq_scan_kernel<M, DSUB><<<grid, PQ_THREADS, 0, s>>>(p); }); });
+    return mf_check_launch("mf_pq_scan");
+}
+
+// ---------------------------------------------------------------------- refine ----
+template <int D>
+__global__ __launch_bounds__(PQ_THREADS) void pq_refine_kernel(const float* __restrict__ q, const float* __restrict__ items,
+                                                               const int64_t* __restrict__ cand, int R, int k, int64_t N, int64_t idx_base,
+                                                               float* __restrict__ out_scores, int64_t* __restrict__ out_idx) {
+    __shared__ unsigned long long all[PQ_THREADS], win[64], sorted[64];
+    const int tid = threadIdx.x, lane = mf_lane();
+    const int64_t qi = blockIdx.x;
+    unsigned long long key = 0ull;
+    if (tid < R) {
+        const int64_t grow = cand[qi * R + tid], local = grow - idx_base;
+        if (grow >= 0 && local >= 0 && local < N) {
+            const f32x4* x = reinterpret_cast<const f32x4*>(items + local * D);
+            pq_const_f32 qc = (pq_const_f32)q + (size_t)qi * D;
+            float acc = 0.f;
+#pragma unroll 4
+            for (int g = 0; g < D / 8; ++g) {
+                const f32x4 a = x[2 * g], b = x[2 * g + 1];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {                      // k order of mf_dot_chain
+                    acc = __builtin_fmaf(a[t], qc[8 * g + t], acc);
+                    acc = __builtin_fmaf(b[t], qc[8 * g + 4 + t], acc);
+                }
+            }
+            key = mf_key_retrieval(acc, (unsigned)grow);
+        }
+    }
+    all[tid] = key;
+    __syncthreads();
+    if (mf_wave_id() != 0) return;
+    const int m = mf_row_topk<PQ_NW, true>(all, PQ_THREADS, k, win, sorted);
+    if (lane < k) mf_store_topk(out_scores, out_idx, qi, k, lane, lane < m ? sorted[lane] : 0ull, 0);
+}
+
+extern "C" int mf_pq_refine(const float* q, int64_t Q, const float* items, int64_t N, int d, const int64_t* cand, int R, int k,
+                            int64_t idx_base, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
+    if (!q || !items || !cand || !out_scores || !out_idx || Q <= 0 || N <= 0 || Q >= (1ll << 31))
+        return mf_set_error(MF_EINVAL, "mf_pq_refine: bad argument");
+    if (k <= 0 || k > PQ_MAX_K) return mf_set_error(MF_ENOTSUP, "mf_pq_refine: k = %d outside 1..%d", k, PQ_MAX_K);
+    if (R < k || R > PQ_MAX_R) return mf_set_error(MF_ENOTSUP, "mf_pq_refine: R = %d outside k..%d", R, PQ_MAX_R);
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_pq_refine: embedding width %d not in {32,64,128,256}", d);
+    if (N >= (1ll << 31) || idx_base < 0 || idx_base + N > (1ll << 32))
+        return mf_set_error(MF_ENOTSUP, "mf_pq_refine: item indices must fit 32 bits");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MF_DISPATCH_D(d, { MF_TIMED("pq_refine", s, { pq_refine_kernel<D><<<dim3((unsigned)Q), PQ_THREADS, 0, s>>>(q, items, cand, R, k, N, idx_base, out_scores, out_idx); }); });
+    return mf_check_launch("mf_pq_refine");
+}

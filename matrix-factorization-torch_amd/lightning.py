@@ -28,7 +28,7 @@ from . import losses as mf_losses
 from . import fused, models, optim
 from .logq import StreamingLogQ
 from .params import INDEX_PATH, LOGQ_PATH, PROCESSORS_JSON, TOP_K, TOWERS_PATH
-from .retrieval import ItemProcessor, PartitionedIndex, PositionMetrics, RetrievalMetrics
+from .retrieval import ItemProcessor, PartitionedIndex, PositionMetrics, QuantizedIndex, RetrievalMetrics
 
 FEATURE_BAGS_PATH = "feature_bags.safetensors"     # the feature towers' registered bags (save / load)
 
@@ -73,16 +73,30 @@ class MatrixFactorizationLitConfig(models.ModelConfig):
     logq_hashes: int = 2           # 1..4, read only when logq_buckets > 0
     # the item index ``ItemProcessor`` builds: "exact" scans the catalog; "partitioned" = retrieval.PartitionedIndex, the
     # reference's inverted file (data/lightning.py:203, 222-229): num_partitions cells (None: its default for the catalog's
-    # size), num_probes visited per query, k-means seeded with index_seed.  The saved files are the same either way
+    # size), num_probes visited per query, k-means seeded with index_seed; "quantized" = retrieval.QuantizedIndex, those cells
+    # with the reference's product quantiser and refine (:162-165, 203-204): num_sub_vectors codes per row (None: the stored
+    # width // 8), refine_factor * top_k candidates scored exactly.  The saved files are the same whichever it is
     index_type: str = "exact"
     num_partitions: int | None = None
     num_probes: int = 8
     index_seed: int = 0
+    num_sub_vectors: int | None = None
+    refine_factor: int = 4
 
     @pydantic.model_validator(mode="after")
     def _index_fields(self):
         if self.index_type not in ItemProcessor.INDEX_TYPES:
-            msg = f"index_type must be 'exact' or 'partitioned': {self.index_type!r}"
+            msg = f"index_type must be 'exact', 'partitioned' or 'quantized': {self.index_type!r}"
+            raise ValueError(msg)
+        if self.num_sub_vectors is not None and self.num_sub_vectors < 1:
+            msg = f"num_sub_vectors must be None (the stored width // 8) or at least 1: {self.num_sub_vectors}"
+            raise ValueError(msg)
+        if not 1 <= self.refine_factor <= QuantizedIndex.MAX_CANDIDATES:
+            msg = f"refine_factor must be in 1..{QuantizedIndex.MAX_CANDIDATES}: {self.refine_factor}"
+            raise ValueError(msg)
+        if self.index_type == "quantized" and self.refine_factor * self.top_k > QuantizedIndex.MAX_CANDIDATES:
+            msg = (f"a quantized index refines at most {QuantizedIndex.MAX_CANDIDATES} candidates per query: "
+                   f"refine_factor * top_k = {self.refine_factor * self.top_k}")
             raise ValueError(msg)
         if self.num_partitions is not None and self.num_partitions < 1:
             msg = f"num_partitions must be None (the default for the catalog's size) or at least 1: {self.num_partitions}"
@@ -281,7 +295,7 @@ class MatrixFactorizationLitModule(_Base):
     def _item_processor(self, item_ids=None) -> ItemProcessor:
         cfg = self.config
         return ItemProcessor(item_ids, index_type=cfg.index_type, num_partitions=cfg.num_partitions, num_probes=cfg.num_probes,
-                             index_seed=cfg.index_seed)
+                             index_seed=cfg.index_seed, num_sub_vectors=cfg.num_sub_vectors, refine_factor=cfg.refine_factor)
 
     # ------------------------------------------------------------- save / load (f-3) ---
     def save(self, path) -> None:

@@ -10,6 +10,7 @@ and ``search`` is an exact scan (``mf_topk``): same scores for unit-norm rows, e
 instead of approximate, batched over queries, ties broken by lowest item row.
 ``PartitionedIndex`` adds the inverted-file half of that index (``num_partitions`` cells, ``num_probes`` of them visited
 per query): which rows a query looks at becomes approximate, how they are scored and ordered stays exact.
+``QuantizedIndex`` adds the other half, the product quantiser with its exact refine (``num_sub_vectors``, ``refine_factor``).
 """
 from __future__ import annotations
 
@@ -313,8 +314,8 @@ class PartitionedIndex(ItemIndex):
     looked at is the only approximation: every row looked at is scored and ordered exactly, so the result is bit for bit the
     exact engines' answer over the union of the probed cells, and ``nprobe = num_partitions`` gives ``ItemIndex.search``'s.
     The original matrix stays: ``positions``, ``target_words`` and ``search(path="exact")`` are the parent's, on all rows.
-    The reference's ``refine_factor`` and ``num_sub_vectors`` belong to its product quantiser; scores here are exact, so there
-    is nothing to refine and they are not offered."""
+    The reference's ``refine_factor`` and ``num_sub_vectors`` belong to its product quantiser: ``QuantizedIndex`` below adds
+    it to these cells; here every probed row is scored exactly, so there is nothing to refine."""
 
     MAX_PROBES = 64     # cells one query may visit (mf_ivf_scan)
     ASSIGN_BATCH = 16384       # rows per nearest-centroid search of the build
@@ -460,6 +461,234 @@ class PartitionedIndex(ItemIndex):
         return scores, rows
 
 
+class QuantizedIndex(PartitionedIndex):
+    """A ``PartitionedIndex`` whose cells are searched through a product quantiser and refined exactly -- the reference's
+    ``IVF_PQ`` index with ``num_sub_vectors = embedding_dim // 8`` and ``search(...).nprobes(num_probes).refine_factor(4)``
+    (data/lightning.py:162-165, 203-204, 222-229, 250-259).  Every cell-ordered row keeps ``num_sub_vectors`` one-byte codes of
+    its residual to the cell's centroid (``codes()``: ``Npad * M`` bytes, where the parent's ``cell_blocked()`` holds
+    ``Npad * D * 4``); a query ranks the rows of its probed cells by a score read from its lookup tables, and the
+    ``refine_factor * top_k`` best are scored again on the original matrix with the canonical chain.  The scores returned are
+    exact chain scores of the rows returned; which rows are returned is the approximation (on top of the parent's probing).
+    The arithmetic -- residuals, codes, tables, approximate keys, the seeded codebook build -- is fixed to the bit:
+    csrc/mf_pq.hip, DESIGN.md "Quantised cells".  ``path="cells"`` and ``path="exact"`` stay the parent's."""
+
+    MAX_CANDIDATES = 256       # refine_factor * top_k: a thread each in mf_pq_refine
+    SUB_LENGTHS = (4, 8, 16)   # channels per sub-vector
+    MAX_SUB_VECTORS = 64       # 64 KiB of lookup tables
+    TRAIN_ROWS = 65536         # rows the codebooks are trained on
+
+    def __init__(self, embeddings: torch.Tensor, centroids: torch.Tensor, assign: torch.Tensor, codebooks: torch.Tensor, *,
+                 refine_factor: int = 4, idx_base: int = 0, num_probes: int = 8) -> None:
+        super().__init__(embeddings, centroids, assign, idx_base=idx_base, num_probes=num_probes)
+        self.refine_factor = self._refine_factor(refine_factor)
+        self._pq_args: dict | None = None                # how ``build`` trained the codebooks: ``rebuild`` runs it again
+        books = _lib.dev_f32(codebooks.detach(), "codebooks")
+        d = self.embeddings.shape[1]
+        if books.dim() != 3 or books.shape[1] != 256 or books.shape[0] * books.shape[2] != d:
+            msg = f"codebooks should be (num_sub_vectors, 256, {d} // num_sub_vectors): {tuple(books.shape) = }"
+            raise ValueError(msg)
+        self.num_sub_vectors, self.dsub = self._geometry(d, books.shape[0])
+        self.codebooks = books.contiguous()
+
+    @classmethod
+    def from_codebooks(cls, embeddings: torch.Tensor, centroids: torch.Tensor, assign: torch.Tensor, codebooks: torch.Tensor, *,
+                       refine_factor: int = 4, idx_base: int = 0, num_probes: int = 8) -> "QuantizedIndex":
+        """The index over given cells and ``codebooks [M, 256, D // M]`` (D the stored width): the rows are encoded, nothing
+        is trained."""
+        return cls(embeddings, centroids, assign, codebooks, refine_factor=refine_factor, idx_base=idx_base, num_probes=num_probes)
+
+    @classmethod
+    def build(cls, embeddings: torch.Tensor, num_partitions: int | None = None, *, num_sub_vectors: int | None = None,
+              refine_factor: int = 4, pq_iters: int = 10, iters: int = 10, seed: int = 0, num_probes: int = 8,
+              idx_base: int = 0) -> "QuantizedIndex":
+        """The parent's seeded cells, then seeded codebooks, the same for the same rows and seed.  The training rows are the
+        residuals of all rows up to ``TRAIN_ROWS`` of them, else of the rows at the first ``TRAIN_ROWS`` places of a permutation
+        drawn on the host; codeword j of every sub-space starts as the residual sub-vector of training row ``j mod T``; an
+        iteration encodes the training rows (``mf_pq_encode``) and replaces every codeword by the mean of its sub-vectors,
+        added in training-row order (``mf_ivf_cell_mean``, no normalisation); an empty codeword keeps its value.
+        ``num_sub_vectors=None``: the stored width // 8, as in the reference."""
+        d = _lib.padded_width(embeddings.shape[1])
+        geometry = cls._geometry(d, d // 8 if num_sub_vectors is None else int(num_sub_vectors))
+        refine_factor = cls._refine_factor(refine_factor)
+        if pq_iters < 0:
+            msg = f"pq_iters must not be negative: {pq_iters = }"
+            raise ValueError(msg)
+        index = super().build(embeddings, num_partitions, iters=iters, seed=seed, num_probes=num_probes, idx_base=idx_base)
+        index.refine_factor = refine_factor
+        index.num_sub_vectors, index.dsub = geometry
+        index._pq_args = {"pq_iters": int(pq_iters), "seed": int(seed)}
+        index.codebooks = index._train(int(pq_iters), int(seed))
+        return index
+
+    @classmethod
+    def _geometry(cls, d: int, m: int) -> tuple[int, int]:
+        if m < 1 or d % m or d // m not in cls.SUB_LENGTHS or m > cls.MAX_SUB_VECTORS:
+            msg = (f"num_sub_vectors must divide the stored width {d} into sub-vectors of 4, 8 or 16 channels, "
+                   f"at most {cls.MAX_SUB_VECTORS} of them: {m = }")
+            raise ValueError(msg)
+        return m, d // m
+
+    @classmethod
+    def _refine_factor(cls, refine_factor) -> int:
+        if int(refine_factor) < 1:
+            msg = f"refine_factor must be at least 1: {refine_factor = }"
+            raise ValueError(msg)
+        return int(refine_factor)
+
+    def _train(self, pq_iters: int, seed: int) -> torch.Tensor:
+        emb, dev = self.embeddings, self.embeddings.device
+        n, d = emb.shape
+        m, dsub = self.num_sub_vectors, self.dsub
+        if n <= self.TRAIN_ROWS:
+            train = emb - self.centroids[self.assign]
+        else:
+            picked = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[: self.TRAIN_ROWS].to(dev)
+            train = emb[picked] - self.centroids[self.assign[picked]]
+        train = train.contiguous()
+        t = train.shape[0]
+        books = train[torch.arange(256, device=dev) % t].reshape(256, m, dsub).permute(1, 0, 2).contiguous()
+        lib = _lib.lib()
+        edges = torch.arange(257, dtype=torch.int64, device=dev)
+        codes = torch.empty(t, m, dtype=torch.uint8, device=dev)
+        mean = torch.zeros(256, d, dtype=torch.float32, device=dev)
+        for _ in range(pq_iters):
+            _lib.check(lib.mf_pq_encode(train.data_ptr(), t, d, None, None, books.data_ptr(), dsub, None, t, codes.data_ptr(), _lib.stream_ptr()))
+            for j in range(m):
+                # the rows of codeword c of sub-space j as a "cell": mf_ivf_cell_mean adds them in training-row order and
+                # leaves the row of an empty one as it is -- so it starts as the codebook; only columns j are read back
+                cells, order = torch.sort(codes[:, j].to(torch.int64), stable=True)
+                cell_off = torch.searchsorted(cells, edges)
+                mean[:, j * dsub : (j + 1) * dsub] = books[j]
+                _lib.check(lib.mf_ivf_cell_mean(train.data_ptr(), t, d, order.data_ptr(), cell_off.data_ptr(), 256, 0, mean.data_ptr(),
+                                                _lib.stream_ptr()))
+                books[j] = mean[:, j * dsub : (j + 1) * dsub]
+        return books
+
+    def _install(self, centroids: torch.Tensor, assign: torch.Tensor) -> None:
+        super()._install(centroids, assign)
+        self._codes = None
+
+    def codes(self) -> torch.Tensor:
+        """The rows' codes in cell order, ``Npad * M`` bytes in the layout ``mf_pq_scan`` reads (include/mf_hip.h:
+        ``[64-row block][M / 4][64]`` 32-bit words, lane = row; padding positions hold code 0), built once."""
+        if self._codes is None:
+            npad, (n, d) = self.row_of.numel(), self.embeddings.shape
+            out = torch.empty(npad * self.num_sub_vectors, dtype=torch.uint8, device=self.embeddings.device)
+            _lib.check(_lib.lib().mf_pq_encode(self.embeddings.data_ptr(), n, d, self.centroids.data_ptr(), self.assign.data_ptr(),
+                                               self.codebooks.data_ptr(), self.dsub, self.row_of.data_ptr(), npad, out.data_ptr(),
+                                               _lib.stream_ptr()))
+            self._codes = out
+        return self._codes
+
+    def refresh(self) -> None:
+        """Forget the derived copies, the codes among them (encoded again from the rows as they are then, with the same
+        cells and codebooks); ``rebuild()`` for new cells and codebooks."""
+        super().refresh()
+        self._codes = None
+
+    def rebuild(self) -> None:
+        """Run the build again on the rows as they are now: cells and codebooks (an index from ``from_codebooks`` keeps both
+        and only forgets the derived copies)."""
+        super().rebuild()
+        if self._pq_args is not None:
+            self.codebooks = self._train(self._pq_args["pq_iters"], self._pq_args["seed"])
+
+    def _candidates_of(self, top_k: int, refine_factor: int | None) -> int:
+        top_k = int(top_k)
+        rf = self.refine_factor if refine_factor is None else self._refine_factor(refine_factor)
+        if not 1 <= top_k <= self.TILE_MAX_K:
+            msg = f"the quantised search returns 1..{self.TILE_MAX_K} rows per query: {top_k = }"
+            raise ValueError(msg)
+        if rf * top_k > self.MAX_CANDIDATES:
+            msg = f"refine_factor * top_k must not exceed {self.MAX_CANDIDATES}: {rf = }, {top_k = }"
+            raise ValueError(msg)
+        return rf * top_k
+
+    def _nprobe(self, nprobe: int | None) -> int:
+        nprobe = self.num_probes if nprobe is None else int(nprobe)
+        if not 1 <= nprobe <= min(self.num_partitions, self.MAX_PROBES):
+            msg = f"nprobe must be in 1..{min(self.num_partitions, self.MAX_PROBES)}: {nprobe = }"
+            raise ValueError(msg)
+        return nprobe
+
+    def plan(self, num_queries: int, top_k: int = TOP_K, nprobe: int | None = None, refine_factor: int | None = None,
+             path: str = "pq") -> dict[str, int]:
+        """The geometry ``search`` runs with (``mf_pq_plan`` for ``refine_factor * top_k`` candidates; ``path="cells"``: the
+        parent's): slices per cell, partial lists per query, workgroups."""
+        if path != "pq":
+            return super().plan(num_queries, top_k, nprobe)
+        out = (ctypes.c_int64 * 4)()
+        r, nprobe = self._candidates_of(top_k, refine_factor), self._nprobe(nprobe)
+        if int(num_queries) < 1:
+            msg = f"num_queries must be at least 1: {num_queries = }"
+            raise ValueError(msg)
+        _lib.check(_lib.lib().mf_pq_plan(int(num_queries), nprobe, r, self.max_cell_blocks, out))
+        return {"slices": out[0], "lists": out[1], "workgroups": out[2], "bytes": out[3]}
+
+    def candidates(self, queries: torch.Tensor, num_candidates: int, *, exclude: Sequence[Sequence[int]] | None = None,
+                   exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None,
+                   nprobe: int | None = None, slices: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(approximate scores [Q, R] fp32, GLOBAL rows [Q, R] int64)``: the ``R = num_candidates`` (1..``MAX_CANDIDATES``)
+        admissible rows of the probed cells that the quantiser ranks first -- approximate score descending, row ascending,
+        the -inf / -1 tail --, what ``search`` refines.  Three stages, none with a host read: the cells, ``mf_pq_scan``,
+        ``mf_topk_merge_packed_deep``.  ``slices``: into how many workgroups a probed cell is cut (None: the plan's number;
+        1..the largest cell's blocks, ``nprobe * slices * R`` within the merge's ``MERGE_DEEP_MAX_KEYS``) -- the lists are the
+        same for every value."""
+        r = int(num_candidates)
+        if not 1 <= r <= self.MAX_CANDIDATES:
+            msg = f"num_candidates must be in 1..{self.MAX_CANDIDATES}: {r = }"
+            raise ValueError(msg)
+        nprobe = self._nprobe(nprobe)
+        if slices is not None and (not 1 <= int(slices) <= self.max_cell_blocks or nprobe * int(slices) * r > MERGE_DEEP_MAX_KEYS):
+            msg = (f"slices must be in 1..{self.max_cell_blocks} with nprobe * slices * num_candidates <= {MERGE_DEEP_MAX_KEYS}: "
+                   f"{slices = }, {nprobe = }, {r = }")
+            raise ValueError(msg)
+        q = self._queries(queries)
+        off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, q.shape[0], q.device)
+        return self._candidates(q, r, nprobe, off, ids, 0 if slices is None else int(slices))
+
+    def _candidates(self, q: torch.Tensor, r: int, nprobe: int, off, ids, slices: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        base, probes = self.coarse.search(q, nprobe)
+        lib = _lib.lib()
+        out = (ctypes.c_int64 * 4)()
+        _lib.check(lib.mf_pq_plan(nq, nprobe, r, self.max_cell_blocks, out))
+        lists = nprobe * slices if slices else out[1]
+        ws = self._workspace(("pq", nq, nprobe, r, slices), max(lists * nq * r * 8, lib.mf_pq_ws_bytes(nq, nprobe, r, self.max_cell_blocks)))
+        approx = torch.empty(nq, r, dtype=torch.float32, device=q.device)
+        rows = torch.empty(nq, r, dtype=torch.int64, device=q.device)
+        _lib.check(lib.mf_pq_scan(q.data_ptr(), nq, self.codes().data_ptr(), self.codebooks.data_ptr(), self.dsub, self.cell_blk.data_ptr(),
+                                  self.row_of.data_ptr(), self.row_of.numel(), n, self.num_partitions, d, self.max_cell_blocks,
+                                  probes.data_ptr(), base.data_ptr(), nprobe, r, slices, _lib.ptr(off), _lib.ptr(ids), self.idx_base,
+                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        _lib.check(lib.mf_topk_merge_packed_deep(ws.data_ptr(), lists, nq, r, approx.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
+        return approx, rows
+
+    def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
+               exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, nprobe: int | None = None,
+               refine_factor: int | None = None, path: str = "pq") -> tuple[torch.Tensor, torch.Tensor]:
+        """``ItemIndex.search``'s inputs and result.  ``path="pq"``: the ``refine_factor * top_k`` (default: the index's
+        factor; at most ``MAX_CANDIDATES``) best rows of the ``nprobe`` probed cells by the quantiser's approximate score,
+        scored again with the chain on the original rows and ordered exactly -- four stages, none with a host read: the
+        cells, the scan (``mf_pq_scan``), the merge (``mf_topk_merge_packed_deep``), the refine (``mf_pq_refine``); the
+        cell-ordered fp32 copy is not built.  ``path="cells"`` and ``path="exact"`` (and the exact engines' names) are the
+        parent's."""
+        if path != "pq":
+            return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, nprobe=nprobe, path=path)
+        r = self._candidates_of(top_k, refine_factor)
+        top_k = int(top_k)
+        nprobe = self._nprobe(nprobe)
+        q = self._queries(queries)
+        nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
+        _, cand = self._candidates(q, r, nprobe, off, ids)
+        scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
+        rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
+        _lib.check(_lib.lib().mf_pq_refine(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, cand.data_ptr(), r, top_k, self.idx_base,
+                                           scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
+        return scores, rows
+
+
 def merge_topk(part_scores: torch.Tensor, part_rows: torch.Tensor, top_k: int) -> tuple[torch.Tensor, torch.Tensor]:
     """Merge per-shard results ``[G, Q, k]`` (global rows, each list ordered as ``search`` returns it) into the global top-k:
     ``mf_topk_merge`` up to ``ItemIndex.TILE_MAX_K``, ``mf_topk_merge_deep`` for deeper lists (``top_k`` up to
@@ -488,19 +717,26 @@ class ItemProcessor:
     idx_col: str = ITEM_IDX_COL
     id_col: str = ITEM_ID_COL
 
-    INDEX_TYPES = ("exact", "partitioned")
+    INDEX_TYPES = ("exact", "partitioned", "quantized")
 
     def __init__(self, item_ids: Sequence[int] | torch.Tensor | None = None, *, index_type: str = "exact",
-                 num_partitions: int | None = None, num_probes: int = 8, index_seed: int = 0) -> None:
+                 num_partitions: int | None = None, num_probes: int = 8, index_seed: int = 0, num_sub_vectors: int | None = None,
+                 refine_factor: int = 4) -> None:
         """``index_type="partitioned"``: ``get_index`` / ``set_index`` / ``append`` build a ``PartitionedIndex`` --
         ``num_partitions`` cells (None: the reference's default for the catalog's size), ``num_probes`` of them visited per
-        query, k-means seeded with ``index_seed`` -- and ``search`` probes it.  The reference's ``refine_factor`` and
-        ``num_sub_vectors`` tune its product quantiser; rows are scored exactly here, so they are not offered."""
+        query, k-means seeded with ``index_seed`` -- and ``search`` probes it.  ``index_type="quantized"``: a
+        ``QuantizedIndex`` over the same cells -- the reference's ``num_sub_vectors`` one-byte codes per row (None: the stored
+        width // 8) and its ``refine_factor``: ``refine_factor * top_k`` candidates per query are scored exactly."""
         if index_type not in self.INDEX_TYPES:
-            msg = f"index_type must be 'exact' or 'partitioned': {index_type!r}"
+            msg = f"index_type must be 'exact', 'partitioned' or 'quantized': {index_type!r}"
+            raise ValueError(msg)
+        if num_sub_vectors is not None and int(num_sub_vectors) < 1:
+            msg = f"num_sub_vectors must be None (the stored width // 8) or at least 1: {num_sub_vectors = }"
             raise ValueError(msg)
         self.item_ids = None if item_ids is None else torch.as_tensor(item_ids, dtype=torch.int64).cpu()
         self.index_type, self.num_partitions, self.num_probes, self.index_seed = index_type, num_partitions, int(num_probes), int(index_seed)
+        self.num_sub_vectors = None if num_sub_vectors is None else int(num_sub_vectors)
+        self.refine_factor = QuantizedIndex._refine_factor(refine_factor)
         self.index: ItemIndex | None = None
         self._row_of_id: dict[int, int] | None = None
 
@@ -509,7 +745,11 @@ class ItemProcessor:
             return ItemIndex(embeddings)
         c = self.num_partitions if self.num_partitions is not None else default_num_partitions(embeddings.shape[0])
         c = max(1, min(int(c), embeddings.shape[0]))
-        return PartitionedIndex.build(embeddings, c, seed=self.index_seed, num_probes=min(self.num_probes, c, PartitionedIndex.MAX_PROBES))
+        num_probes = min(self.num_probes, c, PartitionedIndex.MAX_PROBES)
+        if self.index_type == "quantized":
+            return QuantizedIndex.build(embeddings, c, num_sub_vectors=self.num_sub_vectors, refine_factor=self.refine_factor,
+                                        seed=self.index_seed, num_probes=num_probes)
+        return PartitionedIndex.build(embeddings, c, seed=self.index_seed, num_probes=num_probes)
 
     @torch.inference_mode()
     def get_index(self, model: torch.nn.Module, subset: str = "predict") -> ItemIndex:  # noqa: ARG002

@@ -421,8 +421,9 @@ int mf_topk_deep(const float* q, int64_t Q, const float* items, int64_t N, int d
  * S > max_cell_blocks); MF_ENOSPC "workspace too small" (below G * Q * k * 8 bytes); MF_EINVAL an exclusion pair of which one
  * is null.
  * mf_ivf_plan is host-only: out[0] = S for this shape -- enough workgroups for a single query, at most max_cell_blocks, and
- * nprobe * S * k <= 8192 --, out[1] = G, out[2] = workgroups, out[3] = bytes of the partial lists.  mf_ivf_ws_bytes: those
- * bytes rounded up to 256, 0 for a shape mf_ivf_plan refuses (MF_EINVAL).
+ * nprobe * S * k <= 8192 (the rule itself: mf_cells_slices of csrc/mf_cells.h, which mf_pq_plan follows too) --, out[1] = G,
+ * out[2] = workgroups, out[3] = bytes of the partial lists.  mf_ivf_ws_bytes: those bytes rounded up to 256, 0 for a shape
+ * mf_ivf_plan refuses (MF_EINVAL).
  * mf_ivf_cell_mean replaces the centroid update of the k-means behind the reference's `create_index` (:222-229;
  * LanceDB trains its partitions internally): out[c] = the mean of rows items[order[cell_off[c] .. cell_off[c + 1])], added in
  * that order by one thread per dimension (no float atomics: the same bits every run), scaled to unit L2 length when

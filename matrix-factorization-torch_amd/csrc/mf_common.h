@@ -67,6 +67,9 @@ struct MfArena {
 
 __device__ __forceinline__ int mf_lane() { return threadIdx.x & 63; }
 
+// fp32 in the constant address space: read through a wave-uniform address, it comes by scalar loads into scalar registers
+typedef const __attribute__((address_space(4))) float* mf_const_f32;
+
 // Fragment of one row per lane pair: lane (r = lane & 31, h = lane >> 5) holds
 // elements 8g + 4h .. 8g + 4h + 3 of row r for every group g.
 template <int D>

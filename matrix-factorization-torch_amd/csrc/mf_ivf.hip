@@ -16,18 +16,17 @@
 //     such keys are waiting.  The four waves' lists are joined by one more selection and leave as one partial list of the
 //     packed form [G = nprobe * S][Q][k] that mf_topk_merge_packed takes.  No atomics, nothing to clear between calls: every
 //     workgroup writes all k entries of its list, "none" for a probe outside [0, C), an empty cell or an empty slice.
+//     The exclusion look-up, the packed entry, the slice plan and the export's checks are mf_cells.h's, shared with
+//     mf_pq.hip; the scoring and the selection are this kernel's own.
 //   * ivf_cell_mean_kernel: the k-means update of the build -- a cell's rows added in a given order by one thread per
 //     dimension (no float atomics: the same bits every run), then the mean and its L2 normalisation.
-#include "mf_common.h"
+#include "mf_cells.h"
 #include "mf_select.h"
-#include "mf_topk_io.h"
 
-static constexpr int IVF_NW = 4;               // waves per workgroup, each a 64-row block per pass
 static constexpr int IVF_MAX_K = 64;           // one wavefront holds a list
-static constexpr int IVF_MAX_PROBE = 64;
-static constexpr int IVF_MERGE_KEYS = 8192;    // G * k keys of a query mf_topk_merge / mf_topk_merge_packed hold in LDS
-static constexpr int IVF_TARGET_WG = 1024;     // workgroups worth launching: four per CU
 static constexpr int IVF_PEND = 128;           // keys a wave collects between selections (a block adds at most 64)
+// lists of k <= 64 entries, G * k of a query within the 8,192 keys mf_topk_merge / mf_topk_merge_packed hold in LDS
+static constexpr MfCellsLimits IVF_LISTS{IVF_MAX_K, 8192, 'k'};
 
 struct IvfParams {
     const float* blocked;       // [Npad / 64][D / 4][64][4]
@@ -39,21 +38,19 @@ struct IvfParams {
     int nprobe, S, k;
     const int64_t *excl_off, *excl_idx;     // nullable
     int64_t idx_base;
-    long long* out;             // [nprobe * S][Q][k] packed entries (score bits << 32 | global row; -1: none)
+    long long* out;             // [nprobe * S][Q][k] packed entries (mf_topk_io.h)
 };
 
-typedef const __attribute__((address_space(4))) float* ivf_const_f32;
-
 template <int D>
-__global__ __launch_bounds__(64 * IVF_NW) void ivf_scan_kernel(IvfParams p) {
+__global__ __launch_bounds__(64 * MF_CELLS_NW) void ivf_scan_kernel(IvfParams p) {
     constexpr int CPR = D / 4;
     constexpr int HALF = CPR > 32 ? 32 : CPR;                  // chunks held in registers at once
-    __shared__ unsigned long long buf[IVF_NW][64 + IVF_PEND];  // per wave: its best keys so far [0, 64), then the waiting ones
-    __shared__ unsigned long long win[IVF_NW][64], sorted[IVF_NW][64];
-    __shared__ unsigned long long all[IVF_NW * 64];
+    __shared__ unsigned long long buf[MF_CELLS_NW][64 + IVF_PEND];  // per wave: its best keys so far [0, 64), then the waiting ones
+    __shared__ unsigned long long win[MF_CELLS_NW][64], sorted[MF_CELLS_NW][64];
+    __shared__ unsigned long long all[MF_CELLS_NW * 64];
     const int lane = mf_lane(), wave = mf_wave_id();
     const unsigned long long below = (1ull << lane) - 1ull;
-    // blockIdx.x = (q * nprobe + probe) * S + slice: everything here is workgroup-uniform
+    // blockIdx.x = (q * nprobe + probe) * S + slice: everything here is workgroup-uniform (mf_pq.hip has the same lines: mf_cells.h)
     const int64_t wg = blockIdx.x;
     const int slice = (int)(wg % p.S);
     const int probe = (int)((wg / p.S) % p.nprobe);
@@ -65,7 +62,7 @@ __global__ __launch_bounds__(64 * IVF_NW) void ivf_scan_kernel(IvfParams p) {
         b0 = c0 + nb * slice / p.S;
         b1 = c0 + nb * (slice + 1) / p.S;
     }
-    ivf_const_f32 qc = (ivf_const_f32)p.q + (size_t)q * D;
+    mf_const_f32 qc = (mf_const_f32)p.q + (size_t)q * D;
     int64_t e0 = 0, e1 = 0;
     if (p.excl_off) {
         e0 = p.excl_off[q];
@@ -89,7 +86,7 @@ __global__ __launch_bounds__(64 * IVF_NW) void ivf_scan_kernel(IvfParams p) {
         mf_row_topk_sync<true>();
     };
 
-    for (int64_t blk = b0 + wave; blk < b1; blk += IVF_NW) {
+    for (int64_t blk = b0 + wave; blk < b1; blk += MF_CELLS_NW) {
         const f32x4* src = reinterpret_cast<const f32x4*>(p.blocked) + blk * (int64_t)CPR * 64 + lane;
         const int64_t orig = p.row_of[blk * 64 + lane];
         f32x4 rc[HALF];
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(64 * IVF_NW) void ivf_scan_kernel(IvfParams p) {
 #pragma unroll
             for (int g = 0; g < HALF / 2; ++g) {
                 const f32x4 a = rc[2 * g], b = rc[2 * g + 1];
-                ivf_const_f32 qv = qc + 4 * (h0 + 2 * g);         // wave-uniform address: scalar loads
+                mf_const_f32 qv = qc + 4 * (h0 + 2 * g);         // wave-uniform address: scalar loads
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {                      // k order of mf_dot_chain
                     acc = __builtin_fmaf(a[t], qv[t], acc);
@@ -112,18 +109,7 @@ __global__ __launch_bounds__(64 * IVF_NW) void ivf_scan_kernel(IvfParams p) {
         const unsigned grow = (unsigned)(p.idx_base + orig);       // the GLOBAL row: ties break by it whatever the permutation
         const unsigned long long key = orig >= 0 ? mf_key_retrieval(acc, grow) : 0ull;
         bool pass = key > tau;
-        if (p.excl_off) {
-            // only a key that would enter the list is looked up: the wave walks the query's exclusion list (any order) for it
-            unsigned long long todo = __ballot(pass);
-            while (todo) {
-                const int src_lane = __builtin_ctzll(todo);
-                todo &= todo - 1ull;
-                const int64_t want = (int64_t)(unsigned)__shfl((int)grow, src_lane, 64);
-                bool hit = false;
-                for (int64_t e = e0 + lane; e < e1; e += 64) hit |= p.excl_idx[e] == want;
-                if (__ballot(hit) != 0ull && lane == src_lane) pass = false;
-            }
-        }
+        if (p.excl_off) pass = mf_cells_admit(pass, grow, p.excl_idx, e0, e1, lane);
         const unsigned long long bal = __ballot(pass);
         if (bal) {
             if (pass) mine[64 + pend + __popcll(bal & below)] = key;
@@ -136,76 +122,37 @@ __global__ __launch_bounds__(64 * IVF_NW) void ivf_scan_kernel(IvfParams p) {
     all[wave * 64 + lane] = mine[lane];
     __syncthreads();
     if (wave != 0) return;
-    const int m = mf_row_topk<IVF_NW, true>(all, IVF_NW * 64, p.k, win[0], sorted[0]);
+    const int m = mf_row_topk<MF_CELLS_NW, true>(all, MF_CELLS_NW * 64, p.k, win[0], sorted[0]);
     if (lane < p.k) {
-        long long v = -1ll;
-        if (lane < m) {
-            const unsigned long long key = sorted[0][lane];
-            v = (long long)(((unsigned long long)__builtin_bit_cast(unsigned, mf_key_retrieval_score(key)) << 32) |
-                            (unsigned long long)mf_key_retrieval_col(key));
-        }
+        const long long v = lane < m ? mf_cells_entry(sorted[0][lane]) : MF_PACKED_NONE;
         const int64_t g = (int64_t)probe * p.S + slice;
         p.out[(g * p.Q + q) * p.k + lane] = v;
     }
 }
 
 // ------------------------------------------------------------------ the plan ----
-// Slices per probed cell: enough workgroups for a single query (IVF_TARGET_WG over Q * nprobe), never fewer than about a
-// block per wave in a slice of the largest cell, never more partial lists than the merge holds.
-static int ivf_plan_slices(int64_t Q, int nprobe, int k, int64_t max_cell_blocks) {
-    const int64_t cap_merge = IVF_MERGE_KEYS / ((int64_t)nprobe * k);
-    const int64_t cap = cap_merge < max_cell_blocks ? cap_merge : max_cell_blocks;
-    const int64_t want = (IVF_TARGET_WG + Q * nprobe - 1) / (Q * nprobe);
-    const int64_t by_work = max_cell_blocks / IVF_NW > 1 ? max_cell_blocks / IVF_NW : 1;
-    int64_t S = want < by_work ? want : by_work;
-    if (S > cap) S = cap;
-    if (S < 1) S = 1;
-    return (int)S;
-}
-static bool ivf_plan_args_ok(int64_t Q, int nprobe, int k, int64_t max_cell_blocks) {
-    return Q > 0 && max_cell_blocks > 0 && k >= 1 && k <= IVF_MAX_K && nprobe >= 1 && nprobe <= IVF_MAX_PROBE;
-}
-
+// (the rule: mf_cells_slices)
 extern "C" int mf_ivf_plan(int64_t Q, int nprobe, int k, int64_t max_cell_blocks, int64_t* out4) {
-    if (!out4) return mf_set_error(MF_EINVAL, "mf_ivf_plan: out is NULL");
-    if (!ivf_plan_args_ok(Q, nprobe, k, max_cell_blocks))
-        return mf_set_error(MF_EINVAL, "mf_ivf_plan: need Q > 0, max_cell_blocks > 0, k in 1..%d and nprobe in 1..%d", IVF_MAX_K, IVF_MAX_PROBE);
-    const int S = ivf_plan_slices(Q, nprobe, k, max_cell_blocks);
-    out4[0] = S;
-    out4[1] = (int64_t)nprobe * S;
-    out4[2] = Q * nprobe * S;
-    out4[3] = (int64_t)nprobe * S * Q * k * 8;
-    return MF_OK;
+    return mf_cells_plan("mf_ivf_plan", IVF_LISTS, Q, nprobe, k, max_cell_blocks, out4);
 }
 
 extern "C" size_t mf_ivf_ws_bytes(int64_t Q, int nprobe, int k, int64_t max_cell_blocks) {
-    if (!ivf_plan_args_ok(Q, nprobe, k, max_cell_blocks)) return 0;
-    return mf_align_up((size_t)nprobe * ivf_plan_slices(Q, nprobe, k, max_cell_blocks) * Q * k * 8, 256);
+    return mf_cells_ws_bytes(IVF_LISTS, Q, nprobe, k, max_cell_blocks);
 }
 
 extern "C" int mf_ivf_scan(const float* q, int64_t Q, const float* blocked, const int64_t* cell_blk, const int64_t* row_of, int64_t Npad,
                            int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
                            const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
                            mf_stream_t stream) {
-    if (!q || !blocked || !cell_blk || !row_of || !probes || !ws || Q <= 0 || N <= 0 || C <= 0 || Npad < N || (Npad & 63) != 0 ||
-        max_cell_blocks <= 0 || max_cell_blocks > Npad / 64 || S < 0)
-        return mf_set_error(MF_EINVAL, "mf_ivf_scan: bad argument");
-    if (k <= 0 || k > IVF_MAX_K) return mf_set_error(MF_ENOTSUP, "mf_ivf_scan: k = %d outside 1..%d", k, IVF_MAX_K);
-    const int64_t max_probe = C < IVF_MAX_PROBE ? C : IVF_MAX_PROBE;
-    if (nprobe <= 0 || nprobe > max_probe)
-        return mf_set_error(MF_ENOTSUP, "mf_ivf_scan: nprobe = %d outside 1..%lld", nprobe, (long long)max_probe);
-    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_ivf_scan: embedding width %d not in {32,64,128,256}", d);
-    if (Npad >= (1ll << 31) || idx_base < 0 || idx_base + N > (1ll << 32))
-        return mf_set_error(MF_ENOTSUP, "mf_ivf_scan: item indices must fit 32 bits");
-    if (S == 0) S = ivf_plan_slices(Q, nprobe, k, max_cell_blocks);
+    if (const int rc = mf_cells_check_shape("mf_ivf_scan", IVF_LISTS, q && blocked && cell_blk && row_of && probes && ws, Q, Npad, N, C, d,
+                                            max_cell_blocks, nprobe, k, S))
+        return rc;
+    if (const int rc = mf_cells_check_lists("mf_ivf_scan", IVF_LISTS, Q, Npad, N, max_cell_blocks, nprobe, k, S, excl_off, excl_idx, idx_base, ws_bytes))
+        return rc;
     const int64_t G = (int64_t)nprobe * S;
-    if (G * k > IVF_MERGE_KEYS || S > max_cell_blocks || Q * G >= (1ll << 31))
-        return mf_set_error(MF_ENOTSUP, "mf_ivf_scan: nprobe * S * k too large");
-    if (ws_bytes < (size_t)G * Q * k * 8) return mf_set_error(MF_ENOSPC, "mf_ivf_scan: workspace too small");
-    if ((excl_off == nullptr) != (excl_idx == nullptr)) return mf_set_error(MF_EINVAL, "mf_ivf_scan: excl_off/excl_idx mismatch");
     hipStream_t s = static_cast<hipStream_t>(stream);
     IvfParams p{blocked, q, cell_blk, row_of, probes, Q, C, nprobe, S, k, excl_off, excl_idx, idx_base, static_cast<long long*>(ws)};
-    MF_DISPATCH_D(d, { MF_TIMED("ivf_scan", s, { ivf_scan_kernel<D><<<dim3((unsigned)(Q * G)), 64 * IVF_NW, 0, s>>>(p); }); });
+    MF_DISPATCH_D(d, { MF_TIMED("ivf_scan", s, { ivf_scan_kernel<D><<<dim3((unsigned)(Q * G)), 64 * MF_CELLS_NW, 0, s>>>(p); }); });
     return mf_check_launch("mf_ivf_scan");
 }
 

@@ -28,24 +28,20 @@
 //     only those are looked up in the exclusion list) are appended behind the R kept ones in a workgroup-wide LDS buffer of
 //     1,024 keys -- the waves' counts are exchanged through LDS, no atomics --, which a bitonic sort orders when another pass
 //     might not fit.  Every workgroup writes all R entries of its ordered list: [nprobe * S][Q][R] packed, the form
-//     mf_topk_merge_packed_deep takes.
+//     mf_topk_merge_packed_deep takes.  The exclusion look-up, the packed entry, the slice plan and the export's checks
+//     are mf_cells.h's, shared with mf_ivf.hip; the tables and the buffer are this kernel's own.
 //   * pq_refine_kernel: a workgroup per query, a thread per merged candidate: the chain on the original row, then the
 //     top_k <= 64 by mf_row_topk (as the join of ivf_scan_kernel), stored with the standard tail.
-#include "mf_common.h"
+#include "mf_cells.h"
 #include "mf_select.h"
-#include "mf_topk_io.h"
 
-static constexpr int PQ_NW = 4;                // waves per workgroup, each a 64-row block per pass
-static constexpr int PQ_THREADS = 64 * PQ_NW;
+static constexpr int PQ_THREADS = 64 * MF_CELLS_NW;
 static constexpr int PQ_MAX_K = 64;            // one wavefront holds the result
 static constexpr int PQ_MAX_R = PQ_THREADS;    // candidates per query: a thread each in the refine
-static constexpr int PQ_MAX_PROBE = 64;
 static constexpr int PQ_MAX_M = 64;            // 64 KiB of tables
-static constexpr int PQ_MERGE_KEYS = MF_TOPK_MERGE_DEEP_MAX_KEYS;
-static constexpr int PQ_TARGET_WG = 1024;      // workgroups worth launching: four per CU
 static constexpr int PQ_BUF = 1024;            // keys of the workgroup's buffer: PQ_MAX_R kept, then the waiting ones
-
-typedef const __attribute__((address_space(4))) float* pq_const_f32;
+// lists of R <= 256 entries, G * R of a query within the keys mf_topk_merge_packed_deep holds in LDS
+static constexpr MfCellsLimits PQ_LISTS{PQ_MAX_R, MF_TOPK_MERGE_DEEP_MAX_KEYS, 'R'};
 
 static inline bool pq_dsub_ok(int dsub) { return dsub == 4 || dsub == 8 || dsub == 16; }
 
@@ -108,7 +104,7 @@ struct PqEncodeParams {
 
 template <int DSUB>
 __global__ __launch_bounds__(PQ_THREADS) void pq_encode_kernel(PqEncodeParams p) {
-    __shared__ float half_norm[PQ_NW][256];
+    __shared__ float half_norm[PQ_THREADS / 64][256];
     const int lane = mf_lane(), wave = mf_wave_id();
     const int64_t pos = (int64_t)blockIdx.x * 64 + lane;
     int64_t row = -1;
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_encode_kernel(PqEncodeParams p)
     const float* x = p.rows + safe * p.d;
     const float* cen = p.centroids ? p.centroids + p.assign[safe] * p.d : nullptr;
     const int U = p.M < 4 ? p.M : 4;
-    for (int m = wave; m < p.M; m += PQ_NW) {                       // (wave-uniform)
+    for (int m = wave; m < p.M; m += PQ_THREADS / 64) {                // (wave-uniform)
         const float* book = p.codebooks + (size_t)m * 256 * DSUB;
         mf_row_topk_sync<true>();                                  // the wave has read the last sub-space's norms
 #pragma unroll
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_encode_kernel(PqEncodeParams p)
 #pragma unroll
             for (int t = 0; t < DSUB; ++t) r[t] = r[t] - c[t];
         }
-        pq_const_f32 bc = (pq_const_f32)book;                        // wave-uniform addresses: scalar loads
+        mf_const_f32 bc = (mf_const_f32)book;                        // wave-uniform addresses: scalar loads
         float best = -INFINITY;
         int code = 0;
         for (int j = 0; j < 256; ++j) {
@@ -186,7 +182,7 @@ struct PqScanParams {
     int nprobe, S, R;
     const int64_t *excl_off, *excl_idx;     // nullable
     int64_t idx_base;
-    long long* out;             // [nprobe * S][Q][R] packed entries (approx bits << 32 | global row; -1: none)
+    long long* out;             // [nprobe * S][Q][R] packed entries (mf_topk_io.h) of the approximate scores
 };
 
 // buf[0, n) in descending order, n a power of two <= PQ_BUF; every thread of the workgroup calls it
@@ -215,10 +211,10 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_scan_kernel(PqScanParams p) {
     constexpr int NU = M / U;
     __shared__ float lut[M * 256];
     __shared__ unsigned long long buf[PQ_BUF];
-    __shared__ int cnt[PQ_NW];
+    __shared__ int cnt[MF_CELLS_NW];
     const int tid = threadIdx.x, lane = mf_lane(), wave = mf_wave_id();
     const unsigned long long below = (1ull << lane) - 1ull;
-    // blockIdx.x = (q * nprobe + probe) * S + slice: everything here is workgroup-uniform
+    // blockIdx.x = (q * nprobe + probe) * S + slice: everything here is workgroup-uniform (mf_ivf.hip has the same lines: mf_cells.h)
     const int64_t wg = blockIdx.x;
     const int slice = (int)(wg % p.S);
     const int probe = (int)((wg / p.S) % p.nprobe);
@@ -238,7 +234,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_scan_kernel(PqScanParams p) {
     }
     for (int i = tid; i < PQ_BUF; i += PQ_THREADS) buf[i] = 0ull;
     if (b0 < b1) {                                                   // the query's tables: thread = codeword
-        pq_const_f32 qc = (pq_const_f32)p.q + (size_t)q * D;
+        mf_const_f32 qc = (mf_const_f32)p.q + (size_t)q * D;
 #pragma unroll 2                                                   // (the query's sub-vectors sit in scalar registers: four at dsub = 16 spill them)
         for (int m = 0; m < M; ++m) {
             float b[DSUB];
@@ -259,7 +255,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_scan_kernel(PqScanParams p) {
         __syncthreads();
     };
 
-    for (int64_t blk0 = b0; blk0 < b1; blk0 += PQ_NW) {                // (uniform trip count: barriers inside)
+    for (int64_t blk0 = b0; blk0 < b1; blk0 += MF_CELLS_NW) {         // (uniform trip count: barriers inside)
         const int64_t blk = blk0 + wave;
         unsigned long long key = 0ull;
         unsigned grow = 0u;
@@ -285,24 +281,13 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_scan_kernel(PqScanParams p) {
             key = orig >= 0 ? mf_key_retrieval(acc, grow) : 0ull;
         }
         bool pass = key > tau;
-        if (p.excl_off) {
-            // only a key that would enter the list is looked up: the wave walks the query's exclusion list (any order) for it
-            unsigned long long todo = __ballot(pass);
-            while (todo) {
-                const int src_lane = __builtin_ctzll(todo);
-                todo &= todo - 1ull;
-                const int64_t want = (int64_t)(unsigned)__shfl((int)grow, src_lane, 64);
-                bool hit = false;
-                for (int64_t e = e0 + lane; e < e1; e += 64) hit |= p.excl_idx[e] == want;
-                if (__ballot(hit) != 0ull && lane == src_lane) pass = false;
-            }
-        }
+        if (p.excl_off) pass = mf_cells_admit(pass, grow, p.excl_idx, e0, e1, lane);
         const unsigned long long bal = __ballot(pass);
         if (lane == 0) cnt[wave] = __popcll(bal);
         __syncthreads();
         int before = 0, total = 0;
 #pragma unroll
-        for (int w = 0; w < PQ_NW; ++w) {
+        for (int w = 0; w < MF_CELLS_NW; ++w) {
             const int c = cnt[w];
             before += w < wave ? c : 0;
             total += c;
@@ -315,72 +300,33 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_scan_kernel(PqScanParams p) {
     if (pend > 0) settle();                                          // (else the front is in order already: zeros, or the last settle)
     if (tid < p.R) {
         const unsigned long long key = buf[tid];
-        long long v = -1ll;
-        if (key != 0ull)
-            v = (long long)(((unsigned long long)__builtin_bit_cast(unsigned, mf_key_retrieval_score(key)) << 32) |
-                            (unsigned long long)mf_key_retrieval_col(key));
+        const long long v = key != 0ull ? mf_cells_entry(key) : MF_PACKED_NONE;
         const int64_t g = (int64_t)probe * p.S + slice;
         p.out[(g * p.Q + q) * p.R + tid] = v;
     }
 }
 
 // ------------------------------------------------------------------ the plan ----
-// The rule of mf_ivf_plan with the candidate depth R in the place of k and the key budget of the deep merge: enough
-// workgroups for a single query (PQ_TARGET_WG over Q * nprobe), never fewer than about a block per wave in a slice of the
-// largest cell, never more partial lists than the merge holds.
-static int pq_plan_slices(int64_t Q, int nprobe, int R, int64_t max_cell_blocks) {
-    const int64_t cap_merge = PQ_MERGE_KEYS / ((int64_t)nprobe * R);
-    const int64_t cap = cap_merge < max_cell_blocks ? cap_merge : max_cell_blocks;
-    const int64_t want = (PQ_TARGET_WG + Q * nprobe - 1) / (Q * nprobe);
-    const int64_t by_work = max_cell_blocks / PQ_NW > 1 ? max_cell_blocks / PQ_NW : 1;
-    int64_t S = want < by_work ? want : by_work;
-    if (S > cap) S = cap;
-    if (S < 1) S = 1;
-    return (int)S;
-}
-static bool pq_plan_args_ok(int64_t Q, int nprobe, int R, int64_t max_cell_blocks) {
-    return Q > 0 && max_cell_blocks > 0 && R >= 1 && R <= PQ_MAX_R && nprobe >= 1 && nprobe <= PQ_MAX_PROBE;
-}
-
+// (the rule: mf_cells_slices, with the candidate depth R and the key budget of the deep merge)
 extern "C" int mf_pq_plan(int64_t Q, int nprobe, int R, int64_t max_cell_blocks, int64_t* out4) {
-    if (!out4) return mf_set_error(MF_EINVAL, "mf_pq_plan: out is NULL");
-    if (!pq_plan_args_ok(Q, nprobe, R, max_cell_blocks))
-        return mf_set_error(MF_EINVAL, "mf_pq_plan: need Q > 0, max_cell_blocks > 0, R in 1..%d and nprobe in 1..%d", PQ_MAX_R, PQ_MAX_PROBE);
-    const int S = pq_plan_slices(Q, nprobe, R, max_cell_blocks);
-    out4[0] = S;
-    out4[1] = (int64_t)nprobe * S;
-    out4[2] = Q * nprobe * S;
-    out4[3] = (int64_t)nprobe * S * Q * R * 8;
-    return MF_OK;
+    return mf_cells_plan("mf_pq_plan", PQ_LISTS, Q, nprobe, R, max_cell_blocks, out4);
 }
 
 extern "C" size_t mf_pq_ws_bytes(int64_t Q, int nprobe, int R, int64_t max_cell_blocks) {
-    if (!pq_plan_args_ok(Q, nprobe, R, max_cell_blocks)) return 0;
-    return mf_align_up((size_t)nprobe * pq_plan_slices(Q, nprobe, R, max_cell_blocks) * Q * R * 8, 256);
+    return mf_cells_ws_bytes(PQ_LISTS, Q, nprobe, R, max_cell_blocks);
 }
 
 extern "C" int mf_pq_scan(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
                           const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes,
                           const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off, const int64_t* excl_idx,
                           int64_t idx_base, void* ws, size_t ws_bytes, mf_stream_t stream) {
-    if (!q || !codes || !codebooks || !cell_blk || !row_of || !probes || !probe_scores || !ws || Q <= 0 || N <= 0 || C <= 0 || Npad < N ||
-        (Npad & 63) != 0 || max_cell_blocks <= 0 || max_cell_blocks > Npad / 64 || S < 0)
-        return mf_set_error(MF_EINVAL, "mf_pq_scan: bad argument");
-    if (R <= 0 || R > PQ_MAX_R) return mf_set_error(MF_ENOTSUP, "mf_pq_scan: R = %d outside 1..%d", R, PQ_MAX_R);
-    const int64_t max_probe = C < PQ_MAX_PROBE ? C : PQ_MAX_PROBE;
-    if (nprobe <= 0 || nprobe > max_probe)
-        return mf_set_error(MF_ENOTSUP, "mf_pq_scan: nprobe = %d outside 1..%lld", nprobe, (long long)max_probe);
-    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_pq_scan: embedding width %d not in {32,64,128,256}", d);
+    const bool pointers = q && codes && codebooks && cell_blk && row_of && probes && probe_scores && ws;
+    if (const int rc = mf_cells_check_shape("mf_pq_scan", PQ_LISTS, pointers, Q, Npad, N, C, d, max_cell_blocks, nprobe, R, S)) return rc;
     if (!pq_dsub_ok(dsub) || d / dsub > PQ_MAX_M)
         return mf_set_error(MF_ENOTSUP, "mf_pq_scan: sub-vector length %d not in {4,8,16} or more than %d sub-vectors", dsub, PQ_MAX_M);
-    if (Npad >= (1ll << 31) || idx_base < 0 || idx_base + N > (1ll << 32))
-        return mf_set_error(MF_ENOTSUP, "mf_pq_scan: item indices must fit 32 bits");
-    if (S == 0) S = pq_plan_slices(Q, nprobe, R, max_cell_blocks);
+    if (const int rc = mf_cells_check_lists("mf_pq_scan", PQ_LISTS, Q, Npad, N, max_cell_blocks, nprobe, R, S, excl_off, excl_idx, idx_base, ws_bytes))
+        return rc;
     const int64_t G = (int64_t)nprobe * S;
-    if (G * R > PQ_MERGE_KEYS || S > max_cell_blocks || Q * G >= (1ll << 31))
-        return mf_set_error(MF_ENOTSUP, "mf_pq_scan: nprobe * S * R too large");
-    if (ws_bytes < (size_t)G * Q * R * 8) return mf_set_error(MF_ENOSPC, "mf_pq_scan: workspace too small");
-    if ((excl_off == nullptr) != (excl_idx == nullptr)) return mf_set_error(MF_EINVAL, "mf_pq_scan: excl_off/excl_idx mismatch");
     hipStream_t s = static_cast<hipStream_t>(stream);
     PqScanParams p{q, codebooks, static_cast<const unsigned char*>(codes), cell_blk, row_of, probes, probe_scores, Q, C, nprobe, S, R,
                    excl_off, excl_idx, idx_base, static_cast<long long*>(ws)};
@@ -402,7 +348,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_refine_kernel(const float* __re
         const int64_t grow = cand[qi * R + tid], local = grow - idx_base;
         if (grow >= 0 && local >= 0 && local < N) {
             const f32x4* x = reinterpret_cast<const f32x4*>(items + local * D);
-            pq_const_f32 qc = (pq_const_f32)q + (size_t)qi * D;
+            mf_const_f32 qc = (mf_const_f32)q + (size_t)qi * D;
             float acc = 0.f;
 #pragma unroll 4
             for (int g = 0; g < D / 8; ++g) {
@@ -419,7 +365,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_refine_kernel(const float* __re
     all[tid] = key;
     __syncthreads();
     if (mf_wave_id() != 0) return;
-    const int m = mf_row_topk<PQ_NW, true>(all, PQ_THREADS, k, win, sorted);
+    const int m = mf_row_topk<PQ_THREADS / 64, true>(all, PQ_THREADS, k, win, sorted);
     if (lane < k) mf_store_topk(out_scores, out_idx, qi, k, lane, lane < m ? sorted[lane] : 0ull, 0);
 }
 

@@ -136,17 +136,12 @@ struct MergeParts {                     // (scores, rows), -1 for none
     __device__ Raw raw(int64_t at) const { return Raw{ps[at], pi[at]}; }
     static __device__ unsigned long long key(const Raw& v) { return v.i >= 0 ? mf_key_retrieval(v.s, (unsigned)v.i) : 0ull; }
 };
-struct MergePacked {                    // what topk_pack_kernel below writes
+struct MergePacked {                    // the packed form of mf_topk_io.h: what topk_pack_kernel below and the cell scans write
     const int64_t* packed;
-    __device__ unsigned long long operator()(int64_t at) const {
-        const int64_t v = packed[at];
-        return v != -1ll ? mf_key_retrieval(__builtin_bit_cast(float, (unsigned)((unsigned long long)v >> 32)), (unsigned)v) : 0ull;
-    }
+    __device__ unsigned long long operator()(int64_t at) const { return mf_packed_key(packed[at]); }
     using Raw = int64_t;
     __device__ Raw raw(int64_t at) const { return packed[at]; }
-    static __device__ unsigned long long key(Raw v) {
-        return v != -1ll ? mf_key_retrieval(__builtin_bit_cast(float, (unsigned)((unsigned long long)v >> 32)), (unsigned)v) : 0ull;
-    }
+    static __device__ unsigned long long key(Raw v) { return mf_packed_key(v); }
 };
 template <class Load>
 __global__ __launch_bounds__(64) void topk_merge_kernel(Load load, int G, int64_t Q, int k, float* __restrict__ out_scores,
@@ -296,15 +291,14 @@ static int topk_merge_deep_launch(const char* who, Load load, int G, int64_t Q, 
 }
 
 // Sharded retrieval, one exchange instead of two: a rank's partial result (scores, LOCAL rows) becomes one int64 per entry
-// -- score bits << 32 | global row (local * stride + offset; < 2^32), all ones for "none" -- in a single launch (the row
+// -- the packed form of mf_topk_io.h, its global row = local * stride + offset (< 2^32) -- in a single launch (the row
 // mapping alone took four elementwise launches), travels as ONE all-to-all, and is merged straight from that form.
 __global__ __launch_bounds__(256) void topk_pack_kernel(const float* __restrict__ s, const int64_t* __restrict__ rows, int64_t n,
                                                         int64_t stride, int64_t offset, int64_t* __restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
     const int64_t r = rows[t];
-    out[t] = r >= 0 ? (int64_t)(((unsigned long long)__builtin_bit_cast(unsigned, s[t]) << 32) | (unsigned long long)(unsigned)(r * stride + offset))
-                    : -1ll;
+    out[t] = r >= 0 ? mf_packed_entry(s[t], (unsigned)(r * stride + offset)) : MF_PACKED_NONE;
 }
 
 extern "C" int mf_topk_pack(const float* scores, const int64_t* rows, int64_t n, int64_t stride, int64_t offset, int64_t* out_packed,

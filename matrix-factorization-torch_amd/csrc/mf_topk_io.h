@@ -1,6 +1,7 @@
 // mf_topk_io.h -- the two ends the exact top-k engines share (mf_topk.hip, mf_topk_small.hip, mf_topk_bf3.hip,
 // mf_topk_deep.hip): the argument check every search export opens with (host), and how one entry of a result -- a 64-bit
-// retrieval key (mf_numerics.h), or "none" -- is stored (device).
+// retrieval key (mf_numerics.h), or "none" -- is stored (device): in the result arrays, and packed into one int64 for the
+// partial lists that the sharded search and the cell scans (mf_cells.h) hand to the packed merges.
 #pragma once
 
 #include <cmath>
@@ -60,5 +61,18 @@ __device__ __forceinline__ void mf_store_topk(float* __restrict__ out_scores, in
                                               int64_t idx_base) {
     if (key != 0ull) mf_store_topk_entry(out_scores, out_idx, row, k, rank, key, idx_base);
     else mf_store_topk_none(out_scores, out_idx, row, k, rank);
+}
+
+// ---- device: the packed form of an entry, one int64 where the two arrays above take twelve bytes -- what partial lists
+// travel in between a kernel that leaves them and a merge (mf_topk_pack, the cell scans of mf_cells.h -> mf_topk_merge_packed,
+// mf_topk_merge_packed_deep): the score's bits << 32 | the GLOBAL row (< 2^32), all ones (-1) for "none" (as an entry
+// that would be row 2^32 - 1 under one particular NaN: nothing a search writes).
+static constexpr long long MF_PACKED_NONE = -1ll;
+__device__ __forceinline__ long long mf_packed_entry(float score, unsigned grow) {
+    return (long long)(((unsigned long long)__builtin_bit_cast(unsigned, score) << 32) | (unsigned long long)grow);
+}
+// the retrieval key of a packed entry, 0 for "none"
+__device__ __forceinline__ unsigned long long mf_packed_key(long long v) {
+    return v != MF_PACKED_NONE ? mf_key_retrieval(__builtin_bit_cast(float, (unsigned)((unsigned long long)v >> 32)), (unsigned)v) : 0ull;
 }
 #endif

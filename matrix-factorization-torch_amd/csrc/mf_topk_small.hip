@@ -154,11 +154,9 @@ static constexpr unsigned SQ_NOKEY = 0xFFFFFFFFu;
 
 // QG queries at a time (compile-time: the accumulators are registers).  The rows of a block stay in registers
 // across the query groups when they fit (d <= 128), else each group re-reads them (L2 / Infinity Cache).  The
-// queries are wave-uniform: they are read by SCALAR loads (constant address space -> s_load_dwordx8 through the
-// scalar cache) and enter the fma as SGPR operands -- no LDS, no vector registers (read by broadcast from LDS the
-// compiler hoisted every fragment: 256 VGPRs, kilobytes of scratch per lane).
-typedef const __attribute__((address_space(4))) float* mf_const_f32;
-
+// queries are wave-uniform: they are read by SCALAR loads (constant address space, mf_const_f32 of mf_common.h ->
+// s_load_dwordx8 through the scalar cache) and enter the fma as SGPR operands -- no LDS, no vector registers (read by
+// broadcast from LDS the compiler hoisted every fragment: 256 VGPRs, kilobytes of scratch per lane).
 template <int D, int QG>
 __global__ __launch_bounds__(64 * SQ_NW) void topk_small_scan_kernel(SmallParams p) {
     constexpr int CPR = D / 4;

@@ -420,12 +420,29 @@ class PartitionedIndex(ItemIndex):
             b = self._build_args
             self._install(*self._kmeans(b["num_partitions"], b["iters"], b["seed"]))
 
+    def _top_k(self, top_k: int, search: str) -> int:
+        top_k = int(top_k)
+        if not 1 <= top_k <= self.TILE_MAX_K:
+            msg = f"the {search} search returns 1..{self.TILE_MAX_K} rows per query: {top_k = }"
+            raise ValueError(msg)
+        return top_k
+
+    def _nprobe(self, nprobe: int | None) -> int:
+        nprobe = self.num_probes if nprobe is None else int(nprobe)
+        if not 1 <= nprobe <= min(self.num_partitions, self.MAX_PROBES):
+            msg = f"nprobe must be in 1..{min(self.num_partitions, self.MAX_PROBES)}: {nprobe = }"
+            raise ValueError(msg)
+        return nprobe
+
+    def _plan(self, export, num_queries: int, nprobe: int, depth: int) -> dict[str, int]:
+        """The four words of a plan export (``mf_ivf_plan``, ``mf_pq_plan``: one rule, csrc/mf_cells.h) for lists of ``depth``."""
+        out = (ctypes.c_int64 * 4)()
+        _lib.check(export(int(num_queries), nprobe, depth, self.max_cell_blocks, out))
+        return {"slices": out[0], "lists": out[1], "workgroups": out[2], "bytes": out[3]}
+
     def plan(self, num_queries: int, top_k: int = TOP_K, nprobe: int | None = None) -> dict[str, int]:
         """The geometry ``search`` runs with (``mf_ivf_plan``): slices per cell, partial lists per query, workgroups."""
-        out = (ctypes.c_int64 * 4)()
-        nprobe = self.num_probes if nprobe is None else int(nprobe)
-        _lib.check(_lib.lib().mf_ivf_plan(int(num_queries), nprobe, int(top_k), self.max_cell_blocks, out))
-        return {"slices": out[0], "lists": out[1], "workgroups": out[2], "bytes": out[3]}
+        return self._plan(_lib.lib().mf_ivf_plan, num_queries, self.num_probes if nprobe is None else int(nprobe), int(top_k))
 
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, nprobe: int | None = None,
@@ -437,14 +454,7 @@ class PartitionedIndex(ItemIndex):
         the whole catalog ("auto"); any other path is passed to the parent as it is."""
         if path != "cells":
             return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, path="auto" if path == "exact" else path)
-        nprobe = self.num_probes if nprobe is None else int(nprobe)
-        top_k = int(top_k)
-        if not 1 <= top_k <= self.TILE_MAX_K:
-            msg = f"the partitioned search returns 1..{self.TILE_MAX_K} rows per query: {top_k = }"
-            raise ValueError(msg)
-        if not 1 <= nprobe <= min(self.num_partitions, self.MAX_PROBES):
-            msg = f"nprobe must be in 1..{min(self.num_partitions, self.MAX_PROBES)}: {nprobe = }"
-            raise ValueError(msg)
+        top_k, nprobe = self._top_k(top_k, "partitioned"), self._nprobe(nprobe)
         q = self._queries(queries)
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
@@ -594,22 +604,12 @@ class QuantizedIndex(PartitionedIndex):
             self.codebooks = self._train(self._pq_args["pq_iters"], self._pq_args["seed"])
 
     def _candidates_of(self, top_k: int, refine_factor: int | None) -> int:
-        top_k = int(top_k)
         rf = self.refine_factor if refine_factor is None else self._refine_factor(refine_factor)
-        if not 1 <= top_k <= self.TILE_MAX_K:
-            msg = f"the quantised search returns 1..{self.TILE_MAX_K} rows per query: {top_k = }"
-            raise ValueError(msg)
+        top_k = self._top_k(top_k, "quantised")
         if rf * top_k > self.MAX_CANDIDATES:
             msg = f"refine_factor * top_k must not exceed {self.MAX_CANDIDATES}: {rf = }, {top_k = }"
             raise ValueError(msg)
         return rf * top_k
-
-    def _nprobe(self, nprobe: int | None) -> int:
-        nprobe = self.num_probes if nprobe is None else int(nprobe)
-        if not 1 <= nprobe <= min(self.num_partitions, self.MAX_PROBES):
-            msg = f"nprobe must be in 1..{min(self.num_partitions, self.MAX_PROBES)}: {nprobe = }"
-            raise ValueError(msg)
-        return nprobe
 
     def plan(self, num_queries: int, top_k: int = TOP_K, nprobe: int | None = None, refine_factor: int | None = None,
              path: str = "pq") -> dict[str, int]:
@@ -617,13 +617,11 @@ class QuantizedIndex(PartitionedIndex):
         parent's): slices per cell, partial lists per query, workgroups."""
         if path != "pq":
             return super().plan(num_queries, top_k, nprobe)
-        out = (ctypes.c_int64 * 4)()
         r, nprobe = self._candidates_of(top_k, refine_factor), self._nprobe(nprobe)
         if int(num_queries) < 1:
             msg = f"num_queries must be at least 1: {num_queries = }"
             raise ValueError(msg)
-        _lib.check(_lib.lib().mf_pq_plan(int(num_queries), nprobe, r, self.max_cell_blocks, out))
-        return {"slices": out[0], "lists": out[1], "workgroups": out[2], "bytes": out[3]}
+        return self._plan(_lib.lib().mf_pq_plan, num_queries, nprobe, r)
 
     def candidates(self, queries: torch.Tensor, num_candidates: int, *, exclude: Sequence[Sequence[int]] | None = None,
                    exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None,
@@ -651,9 +649,8 @@ class QuantizedIndex(PartitionedIndex):
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         base, probes = self.coarse.search(q, nprobe)
         lib = _lib.lib()
-        out = (ctypes.c_int64 * 4)()
-        _lib.check(lib.mf_pq_plan(nq, nprobe, r, self.max_cell_blocks, out))
-        lists = nprobe * slices if slices else out[1]
+        planned = self._plan(lib.mf_pq_plan, nq, nprobe, r)["lists"]
+        lists = nprobe * slices if slices else planned
         ws = self._workspace(("pq", nq, nprobe, r, slices), max(lists * nq * r * 8, lib.mf_pq_ws_bytes(nq, nprobe, r, self.max_cell_blocks)))
         approx = torch.empty(nq, r, dtype=torch.float32, device=q.device)
         rows = torch.empty(nq, r, dtype=torch.int64, device=q.device)

@@ -169,9 +169,7 @@ def device_codes(codes: np.ndarray, row_of: np.ndarray) -> np.ndarray:
 
 def plan_slices(nq: int, nprobe: int, r: int, max_cell_blocks: int) -> int:
     """The documented rule of ``mf_pq_plan``: that of ``mf_ivf_plan`` with R for k and the 16,384 keys of the deep merge."""
-    want = -(-1024 // (nq * nprobe))
-    s = min(want, max(1, max_cell_blocks // 4), 16384 // (nprobe * r), max_cell_blocks)
-    return max(1, s)
+    return ivf.plan_slices(nq, nprobe, r, max_cell_blocks, merge_keys=16384)
 
 
 # ----------------------------------------------------------------------------------------------------- the cases ----

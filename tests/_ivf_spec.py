@@ -149,9 +149,10 @@ def cases() -> dict[str, Case]:
     return {c.name: c for c in out}
 
 
-def plan_slices(nq: int, nprobe: int, k: int, max_cell_blocks: int) -> int:
-    """The documented rule of ``mf_ivf_plan`` (include/mf_hip.h): about 1,024 workgroups, a block per wave in a slice of the
-    largest cell at least, ``nprobe * S * k`` within the merge's 8,192 keys, ``1 <= S <= max_cell_blocks``."""
+def plan_slices(nq: int, nprobe: int, k: int, max_cell_blocks: int, merge_keys: int = 8192) -> int:
+    """The documented rule of ``mf_ivf_plan`` and ``mf_pq_plan`` (include/mf_hip.h): about 1,024 workgroups, a block per wave in
+    a slice of the largest cell at least, ``nprobe * S * k`` within the merge's keys (8,192 for ``mf_topk_merge_packed``),
+    ``1 <= S <= max_cell_blocks``."""
     want = -(-1024 // (nq * nprobe))
-    s = min(want, max(1, max_cell_blocks // 4), 8192 // (nprobe * k), max_cell_blocks)
+    s = min(want, max(1, max_cell_blocks // 4), merge_keys // (nprobe * k), max_cell_blocks)
     return max(1, s)

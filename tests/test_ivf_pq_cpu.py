@@ -159,6 +159,23 @@ def test_plan_over_its_domain(mf):
         assert lib.mf_pq_plan(*bad, out) == E.MF_EINVAL and lib.mf_pq_ws_bytes(*bad) == 0, bad
 
 
+def test_the_two_plans_are_one_rule(mf):
+    """``mf_ivf_plan`` and ``mf_pq_plan`` differ in the merge's key budget (8,192 / 16,384) and the largest depth (64 / 256)
+    alone: over the grid above at the depths both take, wherever neither budget binds -- the slices the larger budget gives
+    keep ``nprobe * S * depth`` within 8,192 -- they return the same four words.  That is most of the grid."""
+    lib, E = mf._lib.lib(), mf._lib
+    a, b = (ctypes.c_int64 * 4)(), (ctypes.c_int64 * 4)()
+    grid = list(itertools.product((1, 2, 8, 32, 33, 1024, 100_000), (1, 3, 8, 32, 64), (1, 20, 64), (1, 3, 4, 40, 96, 5000, 200_000)))
+    free = 0
+    for nq, nprobe, depth, mcb in grid:
+        assert lib.mf_ivf_plan(nq, nprobe, depth, mcb, a) == E.MF_OK and lib.mf_pq_plan(nq, nprobe, depth, mcb, b) == E.MF_OK
+        assert b[0] == spec.ivf.plan_slices(nq, nprobe, depth, mcb, merge_keys=16384) >= a[0]
+        if nprobe * b[0] * depth <= 8192:
+            assert list(a) == list(b), (nq, nprobe, depth, mcb, list(a), list(b))
+            free += 1
+    assert 2 * free >= len(grid), (free, len(grid))
+
+
 # ----------------------------------------------------------------------------------------------------- resources ----
 def test_the_new_kernels_have_no_spill_no_scratch_and_the_lds_they_document():
     s = importlib.util.spec_from_file_location("kernel_resources", ROOT / "tools" / "kernel_resources.py")

@@ -196,11 +196,24 @@ void mf_set_dense_dedup(int mode);
 int mf_loss_cols_info(const void* ws, int64_t* out);
 /* The two backward sweeps of the dense losses at d = 128 contract on the bf16 matrix cores with fp32-grade results: both
  * operands are split into three bf16 pieces and the six leading piece products are accumulated in fp32 (csrc/mf_bf_split.h;
- * dropped terms ~2^-23 of a product).  The gradients hold to the tolerances of the fp32 sweeps, not to their bits; the forward
- * -- loss value and logit stash -- is untouched.  mode 1 (default): from 8192 columns upward; mode 2: wherever d = 128
+ * dropped terms ~2^-23 of a product).  The gradients hold to the tolerances of the fp32 sweeps, not to their bits; this
+ * switch does not reach the forward, which has its own (mf_set_dense_fwd_split), and a backward reads the logit stash
+ * whichever way its forward filled it.  mode 1 (default): from 8192 columns upward; mode 2: wherever d = 128
  * (tests); mode 0: never.  Served with and without the distinct-column plan; not served: every other width, the mined
  * losses.  Read at each backward.  Process-wide. */
 void mf_set_dense_bwd_split(int mode);
+/* The forward sweep of the dense losses at d = 128 computes its score tiles the same way (three bf16 pieces of both operands,
+ * six piece products, fp32 accumulation): loss, logit stash and everything downstream hold to the tolerances of the fp32
+ * forward, not to its bits.  mode 1 (default): from 2048 x 4096 scores (B x N) upward; mode 2: wherever d = 128 and the loss is dense
+ * (tests); mode 0: never.  Not served, and bit for bit as before: every other width, the mined losses, the one-launch small
+ * step.  Read at each forward.  Process-wide. */
+void mf_set_dense_fwd_split(int mode);
+/* Tests and tools only: the path of the last mf_loss_fwd on this workspace -- bit 0: distinct columns, bit 1: split scores.
+ * 0 for a workspace no forward has run on, and after a forward that runs no dense sweep. */
+int mf_loss_fwd_path(const void* ws);
+/* Tests only: the slot of (row of a 32-row tile, feature, piece) among the 12,288 bf16 of a tile's FORWARD operand image
+ * (csrc/mf_bf_split.h); -1 outside 32 x 128 x 3. */
+int mf_fwd_split_image_index(int row, int feature, int piece);
 /* Tests and tools only: the path of the last mf_loss_bwd on this workspace -- bit 0: distinct columns, bit 1: split
  * contraction, bit 2: dV derived G' from the logit stash itself.  0 for a workspace no backward has run on, and after a
  * backward that runs no dense sweep (a mined loss, the alignment loss). */

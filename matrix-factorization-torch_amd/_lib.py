@@ -53,6 +53,9 @@ SIGNATURES = {
     "mf_set_dense_bwd_split": (None, [c_int]),
     "mf_loss_bwd_path": (c_int, [c_vp]),
     "mf_bwd_split_image_index": (c_int, [c_int, c_int, c_int]),
+    "mf_set_dense_fwd_split": (None, [c_int]),
+    "mf_loss_fwd_path": (c_int, [c_vp]),
+    "mf_fwd_split_image_index": (c_int, [c_int, c_int, c_int]),
     "mf_mining_prefilter_plan": (c_int, [c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64)]),
     "mf_mine_logits": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp]),
     "mf_update_ws_bytes": (c_sz, [c_i64, c_int]),

@@ -326,7 +326,7 @@ static int loss_fwd_impl(const char* what, int64_t B, int64_t N, int d, const Po
     // 2. hit masks (unless they were built ahead); 3. the scores of every valid negative, dense or mined; 4. the tail
     int planes = 0, merge_splits = 0;
     if (build) planes = loss_build_masks(w, item_idx, src, s, !cols);
-    if (scores_needed && !w.mined) rc = dense_fwd(w, cols, planes, u, v, need, sigma, margin, out_mask_bits, s, &merge_splits);
+    if (scores_needed && !w.mined) rc = dense_fwd(w, ws, cols, planes, u, v, need, sigma, margin, out_mask_bits, s, &merge_splits);
     else if (scores_needed) rc = mined_fwd(w, u, v, num_negatives, need, sigma, margin, out_mask_bits, s);
     else mf_zero_async(w.stats, (size_t)NSTAT * w.Bp * 4, s);
     if (rc) return rc;

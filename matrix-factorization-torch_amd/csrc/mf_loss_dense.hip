@@ -24,6 +24,8 @@ struct FwdParams {
     // the device words, the column weights ride in lanes 24..31 of the side-input DMA
     const int32_t* geo;
     uint32_t aux_w;
+    // split scores (SPLIT): the bf16 piece image of the streamed item tiles (fsi_index, mf_bf_split.h), NT tiles
+    const unsigned short* img;
 };
 
 // The side inputs -- fp's mask words, norms and -logQ, and the column weights `cw` of a distinct-column sweep -- live in
@@ -53,22 +55,37 @@ static bool fwd_aux_span(FwdParams& fp, const LossWs& w, const float* cw) {
 // matrix pipe, the VALU and the memory instructions overlap without relying on a second wave.  The tile loop is
 // unrolled by the two slots: every LDS address is lane base + immediate, and the two accumulator sets swap roles
 // by name (no register copies at the loop edge).
-template <int D>
+// SPLIT (d = 128): the score tile on the bf16 matrix cores, fp32-grade (mf_bf_split.h).  The item tile arrives as its image of
+// three bf16 pieces (fwd_split_image_kernel: 24 KiB per tile, six 1-KiB DMA pieces per wave), the user fragment is split in
+// registers once per workgroup, and a tile's scores are 8 k-steps x 6 piece products into the same fp32 accumulators: 48 MFMAs
+// of 8 passes instead of 64 of 16.  An MFMA group is then a k-step; the statistics go four slices to a group and the stage's
+// seven memory instructions DPG = 3 to a group, so that the last of them is issued in group 2 of 8 and has most of a tile's
+// matrix time to land.
+template <int D, bool SPLIT = false>
 struct FwdLds {
     using G = TileGeom<D>;
+    static_assert(!SPLIT || D == 128, "the split forward is written for d = 128");
     // side inputs: one 1-KiB DMA per wave and tile -- lanes 0..7 the wave's 32 mask words, 8..15 the tile's item
     // norms, 16..23 its -logq (every wave keeps its own copy: no cross-wave dependency), the other lanes zeros
     static constexpr int AUX_NV = 128, AUX_LQ = 256, AUX_CW = 384, AUXW = 1024, AUXB = G::NW * AUXW;
-    static constexpr int AUX0 = 2 * G::TILEB;           // 4 side-input slots after the 2 tile slots
+    static constexpr int SLOTB = SPLIT ? FSI_TILEB : G::TILEB;   // bytes of a tile slot
+    static constexpr int AUX0 = 2 * SLOTB;              // 4 side-input slots after the 2 tile slots
     static constexpr int BYTES = AUX0 + 4 * AUXB;
-    static constexpr int NG = D / 8;                    // MFMA groups per tile
-    static constexpr int LASTG = G::PPW;                // group of a stage's last DMA (tile pieces, then the side inputs)
+    static constexpr int NG = SPLIT ? 8 : D / 8;        // MFMA groups per tile (SPLIT: the k-steps, six MFMAs each)
+    static constexpr int PPW = SPLIT ? FSI_TILEB / G::NW / 1024 : G::PPW;   // 1-KiB DMA pieces of a tile per wave
+    static constexpr int NDMA = PPW + 1;                // memory instructions of a stage: the tile pieces, then the side inputs
+    static constexpr int DPG = SPLIT ? 3 : 1;           // of them per MFMA group
+    static constexpr int LASTG = (NDMA - 1) / DPG;      // group of a stage's last DMA
     // stash stores of a tile (issued behind logit slices 3, 7, 11, 15 of 32) that are YOUNGER than the stage's last
     // DMA: `s_waitcnt vmcnt(KEEP)` at the next tile's top then proves every DMA of the stage has landed
-    // (a group issues its DMA before its slices, so a store of group LASTG itself is already younger)
+    // (a group issues its DMA before its slices, so a store of group LASTG itself is already younger; SPLIT counts only
+    // the stores of LATER groups -- it waits for one store more than it must and needs no order inside a group)
     static constexpr int store_group(int s) { return s * NG / 32; }
-    static constexpr int KEEP = (store_group(3) >= LASTG) + (store_group(7) >= LASTG) + (store_group(11) >= LASTG) + (store_group(15) >= LASTG);
+    static constexpr bool younger(int s) { return SPLIT ? store_group(s) > LASTG : store_group(s) >= LASTG; }
+    static constexpr int KEEP = younger(3) + younger(7) + younger(11) + younger(15);
     static_assert(LASTG < NG, "a stage's DMAs must fit the tile's MFMA groups");
+    static_assert(SPLIT || (LASTG == G::PPW && NDMA == LASTG + 1), "fp32 scores: one DMA per group, the side inputs last");
+    static_assert(!SPLIT || (PPW == 6 && LASTG == 2 && KEEP == 1 && BYTES == 64 * 1024), "split scores: 7 DMAs in groups 0..2, the store of group 3 is younger");
 };
 
 template <int NEED>
@@ -108,11 +125,86 @@ __device__ __forceinline__ void stats_add_masked_w(RowStats& s, float Lm, float 
     }
 }
 
-template <int D, int NEED, bool CP>
+// The user row of lane (c, h) as the B fragments of the split score tile: x[s][q] is piece q of features 16 s + 8 h .. + 7
+// (the order the image keeps the item rows in, fsi_index); rows past the end are zeros, as in mf_load_frag.
+struct RowFragSplit {
+    mbf16x8 x[8][3];
+};
+__device__ __forceinline__ void mf_load_frag_split(RowFragSplit& f, const float* __restrict__ base, int64_t row, bool valid) {
+    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+    const int h = mf_lane() >> 5;
+    const f32x4* p = reinterpret_cast<const f32x4*>(base + (valid ? row : 0) * 128 + 8 * h);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const f32x4 lo = p[4 * s], hi = p[4 * s + 1];
+        u16x8 g3[3];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            unsigned short o[3];
+            mbf_split3(valid ? (j < 4 ? lo[j] : hi[j - 4]) : 0.f, o);
+            g3[0][j] = o[0]; g3[1][j] = o[1]; g3[2][j] = o[2];
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) f.x[s][q] = __builtin_bit_cast(mbf16x8, g3[q]);
+    }
+}
+
+#ifndef FWD_SPLIT_DROP
+#define FWD_SPLIT_DROP -1     // A/B knob (wrong results): leave out piece product 0..5 -- the build the precision test must fail on
+#endif
+// The split score tile of the staged image with the previous tile's VALU work between the MFMAs, as
+// mf_tile_scores_interleaved (mf_stream.h) does for the fp32 tile: a group is one k-step -- its three A fragments are read
+// one k-step ahead, `hook(g)` issues the group's memory instructions, then the six piece products a_i x_j, i + j <= 2, the
+// smallest first, and the group's share of the slices; VPM VALU / SALU instructions are placed behind each MFMA.
+template <int NSLICE, int VPM, class Slice, class Hook>
+__device__ __forceinline__ f32x16 mf_tile_scores_split_interleaved(const char* lds_tile, const RowFragSplit& x, Slice&& slice, Hook&& hook) {
+    constexpr int NG = 8;
+    static_assert(NSLICE % NG == 0, "slices and k-steps must nest");
+    const mbf16x8* img = reinterpret_cast<const mbf16x8*>(lds_tile) + mf_lane();
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    mbf16x8 a_next[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) a_next[q] = img[(q * 8) * 64];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        mbf16x8 a[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a[q] = a_next[q];
+        if (g + 1 < NG) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) a_next[q] = img[(q * 8 + g + 1) * 64];
+        }
+        hook(g);
+#pragma unroll
+        for (int pr = 0; pr < 6; ++pr) {
+            // (a piece, x piece): (2,0) (1,1) (0,2) | (1,0) (0,1) | (0,0)
+            const int ai = pr == 0 ? 2 : (pr == 1 || pr == 3) ? 1 : 0;
+            const int xi = pr == 2 ? 2 : (pr == 1 || pr == 4) ? 1 : 0;
+            if (pr == FWD_SPLIT_DROP) continue;
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ai], x.x[g][xi], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int sidx = g * NSLICE / NG; sidx < (g + 1) * NSLICE / NG; ++sidx) slice(sidx);
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x006, VPM, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return acc;
+}
+
+#ifndef FWD_SPLIT_VPM
+#define FWD_SPLIT_VPM 14      // A/B knob: VALU / SALU instructions of the previous tile's statistics behind each MFMA of the split score tile
+#endif
+template <int D, int NEED, bool CP, bool SPLIT>
 __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense_kernel(FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using G = TileGeom<D>;
-    using L = FwdLds<D>;
+    using L = FwdLds<D, SPLIT>;
     const int lane = mf_lane(), c = lane & 31, h = lane >> 5;
     const int wave = mf_wave_id();
     // grid = (item-range split, user block): consecutive workgroup ids -- dealt round-robin to the 8 XCDs --
@@ -123,14 +215,29 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
     const int nt_e = CP ? p.geo[CG_NT] : p.NT, tps_e = CP ? p.geo[CG_TPSF] : p.tps;
     const int t0 = blockIdx.x * tps_e, t1 = min(nt_e, t0 + tps_e);
     RowFrag<D> xf;
-    mf_load_frag<D>(xf, p.u, i, i < p.B);
+    RowFragSplit xs;
+    if constexpr (SPLIT) mf_load_frag_split(xs, p.u, i, i < p.B);
+    else mf_load_frag<D>(xf, p.u, i, i < p.B);
     const float nu_i = p.nu[i], s_i = p.sgn[i], lii = p.lii[i];
     const float sm = s_i * p.margin;
     RowStats st;
     stats_init(st);
 
     TileSrc<D> tsrc;
-    mf_tile_src_init<D>(tsrc, p.v, p.N, (int64_t)t0 * 32);
+    if constexpr (!SPLIT) mf_tile_src_init<D>(tsrc, p.v, p.N, (int64_t)t0 * 32);
+    // SPLIT: the image is copied linearly -- one descriptor over its tiles [t0, nt_e) (the image kernel wrote exactly those of
+    // the streamed range), piece j of this wave's share at lane offset + scalar ((t - t0) tiles + j KiB)
+    mf_rsrc_t irsrc;
+    const unsigned ioff = (unsigned)(wave * L::PPW * 1024 + lane * 16);
+    if constexpr (SPLIT) {
+        int64_t bytes = (int64_t)(nt_e - t0) * FSI_TILEB;
+        bytes = bytes < 0 ? 0 : (bytes > (int64_t)MF_SRD_MAX_BYTES ? (int64_t)MF_SRD_MAX_BYTES : bytes);
+#if defined(__HIP_DEVICE_COMPILE__)
+        irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(p.img + (int64_t)t0 * FSI_TILE_ELEMS), 0, (int)(unsigned)bytes, 0x00020000);
+#else
+        (void)irsrc; (void)ioff;
+#endif
+    }
     // side inputs: per-lane byte offset into the aux buffer, advanced by a per-lane stride from stage to stage
     // (stages are issued in tile order t0, t0 + 1, ...); lanes 24.. stay out of range and bring zeros
     mf_rsrc_t arsrc;
@@ -150,7 +257,12 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
     }
     // one memory instruction of the stage of tile t (into tile slot `slot`): j < PPW a tile piece, j = PPW the side inputs
     auto stage_piece = [&](int t, int slot, int j, bool live) {
-        if (j < G::PPW) {
+        if (SPLIT && j < L::PPW) {
+#if defined(__HIP_DEVICE_COMPILE__)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(irsrc, (mf_lds_ptr)(smem + slot * L::SLOTB + (wave * L::PPW + j) * 1024), 16, (int)ioff,
+                                                     live ? (int)((unsigned)(t - t0) * FSI_TILEB + j * 1024) : (int)MF_SRD_DEAD, 0, 0);
+#endif
+        } else if (j < L::PPW) {
             mf_stage_tile_piece<D>(smem + slot * G::TILEB, t * 32, j, tsrc, live);
         } else {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -162,7 +274,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
     };
     auto stage = [&](int t, int slot) {
 #pragma unroll
-        for (int j = 0; j <= L::LASTG; ++j) stage_piece(t, slot, j, true);
+        for (int j = 0; j < L::NDMA; ++j) stage_piece(t, slot, j, true);
     };
     // The statistics of one tile, cut in 32 slices so they can be threaded between the MFMAs of
     // the next tile: slices 0..15 turn score e into logit e (and stash it), slices 16..31 fold
@@ -225,9 +337,20 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
         if (tj == t0) mf_wait_vmcnt<0>(); else mf_wait_vmcnt<L::KEEP>();
         mf_block_barrier();
         const bool live = MODE == 1 || tj + 2 < t1;
+        if constexpr (SPLIT) {
+            nxt = mf_tile_scores_split_interleaved<32, FWD_SPLIT_VPM>(
+                smem + NS * L::SLOTB, xs, [&](int sidx) { slice(sidx, tj, cur); },
+                [&](int g) {
+                    if (MODE != 0 && g <= L::LASTG) {
+#pragma unroll
+                        for (int j = g * L::DPG; j < (g + 1) * L::DPG && j < L::NDMA; ++j) stage_piece(tj + 2, CS, j, live);
+                    }
+                });
+        } else {
         nxt = mf_tile_scores_interleaved<D, 32, (40 * 32 / D)>(
             smem + NS * G::TILEB, xf, [&](int sidx) { slice(sidx, tj, cur); },
             [&](int g) { if (MODE != 0 && g <= L::LASTG) stage_piece(tj + 2, CS, g, live); });
+        }
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -237,9 +360,11 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
         stage(t0, 0);
         if (t0 + 1 < t1) stage(t0 + 1, 1);
         // tile t0: its stage's DMAs are the older ones
-        if (t0 + 1 < t1) mf_wait_vmcnt<L::LASTG + 1>(); else mf_wait_vmcnt<0>();
+        if (t0 + 1 < t1) mf_wait_vmcnt<L::NDMA>(); else mf_wait_vmcnt<0>();
         mf_block_barrier();
-        f32x16 accA = mf_tile_scores_interleaved<D, 32, (40 * 32 / D)>(smem, xf, [](int) {}), accB;
+        f32x16 accA, accB;
+        if constexpr (SPLIT) accA = mf_tile_scores_split_interleaved<32, FWD_SPLIT_VPM>(smem, xs, [](int) {}, [](int) {});
+        else accA = mf_tile_scores_interleaved<D, 32, (40 * 32 / D)>(smem, xf, [](int) {});
         int tj = t0;
         for (; tj + 2 < t1; tj += 2) {      // two tiles per trip: slots and accumulators swap roles by name
             iterate(tj, I0{}, I1{}, accA, accB);
@@ -270,22 +395,59 @@ __global__ __launch_bounds__(64 * mf_nw(D), mf_wg_per_cu(D)) void loss_fwd_dense
     }
 }
 
-template <int D, int NEED, bool CP>
+template <int D, int NEED, bool CP, bool SPLIT>
 static void launch_fwd_n(dim3 grid, const FwdParams& fp, hipStream_t s) {
-    auto fn = loss_fwd_dense_kernel<D, NEED, CP>;
-    if (FwdLds<D>::BYTES > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, FwdLds<D>::BYTES);
-    fn<<<grid, 64 * mf_nw(D), FwdLds<D>::BYTES, s>>>(fp);
+    auto fn = loss_fwd_dense_kernel<D, NEED, CP, SPLIT>;
+    using L = FwdLds<D, SPLIT>;
+    if (L::BYTES > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES);
+    fn<<<grid, 64 * mf_nw(D), L::BYTES, s>>>(fp);
 }
-template <int D, bool CP = false>
+template <int D, bool CP = false, bool SPLIT = false>
 static void launch_fwd(int need, dim3 grid, const FwdParams& fp, hipStream_t s) {
     switch (need) {   // single-loss calls get a specialised epilogue; anything else computes every statistic
-        case NEED_CONTR: launch_fwd_n<D, NEED_CONTR, CP>(grid, fp, s); break;
-        case NEED_LSE: launch_fwd_n<D, NEED_LSE, CP>(grid, fp, s); break;
-        case NEED_HINGE: launch_fwd_n<D, NEED_HINGE, CP>(grid, fp, s); break;
-        case NEED_LOGI: launch_fwd_n<D, NEED_LOGI, CP>(grid, fp, s); break;
-        default: launch_fwd_n<D, 15, CP>(grid, fp, s); break;
+        case NEED_CONTR: launch_fwd_n<D, NEED_CONTR, CP, SPLIT>(grid, fp, s); break;
+        case NEED_LSE: launch_fwd_n<D, NEED_LSE, CP, SPLIT>(grid, fp, s); break;
+        case NEED_HINGE: launch_fwd_n<D, NEED_HINGE, CP, SPLIT>(grid, fp, s); break;
+        case NEED_LOGI: launch_fwd_n<D, NEED_LOGI, CP, SPLIT>(grid, fp, s); break;
+        default: launch_fwd_n<D, 15, CP, SPLIT>(grid, fp, s); break;
     }
+}
+
+// The image of the streamed item tiles for the split forward (fsi_index, mf_bf_split.h): a workgroup is one tile, thread
+// (k-step s, lane (c, h)) reads features 16 s + 8 h .. + 7 of tile row c and writes the 16-byte fragments of its three pieces
+// -- whole KiB per wave and piece.  Rows from `rows` on (geo: from the N' distinct columns on) are written as zeros; of a
+// packed v' only the tiles the sweep streams are written.
+__global__ __launch_bounds__(512) void fwd_split_image_kernel(const float* __restrict__ src, int64_t rows, unsigned short* __restrict__ img,
+                                                              const int32_t* __restrict__ geo) {
+    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+    const int tile = (int)blockIdx.x;
+    if (geo) {
+        if (tile >= geo[CG_NT]) return;
+        rows = geo[CG_NCOLS];
+    }
+    const int s = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+    const int64_t y = (int64_t)tile * 32 + c;
+    f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
+    if (y < rows) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(src + y * 128 + 16 * s + 8 * h);
+        lo = p[0]; hi = p[1];
+    }
+    u16x8 out[3];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        unsigned short o[3];
+        mbf_split3(j < 4 ? lo[j] : hi[j - 4], o);
+        out[0][j] = o[0]; out[1][j] = o[1]; out[2][j] = o[2];
+    }
+    u16x8* dst = reinterpret_cast<u16x8*>(img + (int64_t)tile * FSI_TILE_ELEMS);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) dst[fsi_index(c, 16 * s + 8 * h, q) >> 3] = out[q];
+}
+// tests only: slot of (row of the tile, feature, piece) in a tile's forward image
+extern "C" int mf_fwd_split_image_index(int row, int feature, int piece) {
+    if (row < 0 || row >= 32 || feature < 0 || feature >= 128 || piece < 0 || piece >= 3) return -1;
+    return fsi_index(row, feature, piece);
 }
 
 __global__ __launch_bounds__(256) void mask_export_dense_kernel(const uint32_t* __restrict__ maskW, int64_t B,
@@ -843,6 +1005,31 @@ static void bwd_path_note(const void* ws, int path) {
 }
 void dense_bwd_none(const void* ws) { bwd_path_note(ws, 0); }
 
+// The forward's own switch: 0 never, 1 where it pays (default: from FWD_SPLIT_MIN_BN scores upward), 2 wherever d = 128 and
+// the loss is dense (tests).  Separate from the backward's: a backward reads the logit stash whichever way the forward filled
+// it.  The image launch is paid back once the sweep has enough tiles: forward + backward in us, fp32 forward / split forward
+// -- (B, N) = (1024, 4096): 139.9 / 139.4 (inside the spread), (2048, 4096): 154.8 / 150.6, (4096, 8192): 279.7 / 251.5,
+// (8192, 16384): 844.1 / 726.2 (profiles/fwd_split_threshold.json).
+static int g_dense_fwd_split = 1;
+static constexpr int64_t FWD_SPLIT_MIN_BN = (int64_t)2048 * 4096;
+extern "C" void mf_set_dense_fwd_split(int mode) { g_dense_fwd_split = mode <= 0 ? 0 : (mode >= 2 ? 2 : 1); }
+static bool fwd_split_serve(const LossWs& w) {
+    if (!w.split_ok || g_dense_fwd_split == 0) return false;
+    return g_dense_fwd_split == 2 || w.B * w.N >= FWD_SPLIT_MIN_BN;
+}
+// which path the last forward on a workspace took (tests and tools): bit 0 distinct columns, bit 1 split scores; 0 for a
+// forward that ran no dense sweep
+static std::unordered_map<const void*, int> g_fwd_path;
+extern "C" int mf_loss_fwd_path(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_path_mu);
+    const auto it = g_fwd_path.find(ws);
+    return it == g_fwd_path.end() ? 0 : it->second;
+}
+static void fwd_path_note(const void* ws, int path) {
+    std::lock_guard<std::mutex> lk(g_path_mu);
+    g_fwd_path[ws] = path;
+}
+
 // ---- the distinct-column sweeps' switch (mf_loss_cols.h) ----
 // 0 never, 1 where it pays (default), 2 wherever it can serve (tests).  Served: the dense (unmined) path at d = 128, all
 // seven kinds, masks built inside the forward, no mask export; mode 1 from COLS_MIN_N columns upward.
@@ -914,10 +1101,11 @@ static void cols_plan_launch(const LossWs& w, const float* v, int planes, hipStr
 bool dense_fwd_cols(const LossWs& w, const void* ws, bool scores_needed, bool masks_ready, bool export_masks) {
     const bool cols = scores_needed && cols_serve(w, masks_ready, export_masks);
     cols_note(ws, cols);
+    fwd_path_note(ws, 0);               // (dense_fwd, if this forward reaches it, records what it launched)
     return cols;
 }
 
-int dense_fwd(const LossWs& w, bool cols, int planes, const float* u, const float* v, int need, float sigma, float margin,
+int dense_fwd(const LossWs& w, const void* ws, bool cols, int planes, const float* u, const float* v, int need, float sigma, float margin,
               uint32_t* out_mask_bits, hipStream_t s, int* merge_splits) {
     const int64_t B = w.B, N = w.N;
     const int d = w.d;
@@ -928,11 +1116,24 @@ int dense_fwd(const LossWs& w, bool cols, int planes, const float* u, const floa
     if (cols) { fp.v = w.cv; fp.nv = w.cnv; fp.logq = w.clq; fp.N = w.Np; fp.geo = w.geo; }
     if (!fwd_aux_span(fp, w, cols ? w.cw : nullptr))
         return mf_set_error(MF_EINVAL, "mf_loss_fwd: batch x catalog too large for one sweep (mask words beyond 4 GiB)");
+    const bool split = fwd_split_serve(w);
+    fwd_path_note(ws, (cols ? 1 : 0) | (split ? 2 : 0));
+    if (split) {
+        // The image of the streamed tiles, once per forward, where the backward's image of the same operand will go (inside the
+        // G' stash wherever that fits: nothing uses those bytes until the backward, whose own image launch may overwrite it).
+        fp.img = w.bimg_v;
+        fwd_split_image_kernel<<<dim3((unsigned)w.NT), 512, 0, s>>>(fp.v, cols ? w.Np : N, w.bimg_v, cols ? w.geo : nullptr);
+    }
     if (cols) {
         // launched for the most splits any N' can ask for; a split beyond N''s writes the empty statistics, which merge as nothing
         dim3 grid((unsigned)w.cl.grid_f, (unsigned)(w.BT / w.NW));
-        MF_TIMED("loss_fwd_dense", s, (launch_fwd<128, true>(need, grid, fp, s)));
+        if (split) MF_TIMED("loss_fwd_dense", s, (launch_fwd<128, true, true>(need, grid, fp, s)));
+        else MF_TIMED("loss_fwd_dense", s, (launch_fwd<128, true>(need, grid, fp, s)));
         *merge_splits = w.cl.grid_f;
+    } else if (split) {
+        dim3 grid((unsigned)w.nsplit_f, (unsigned)(w.BT / w.NW));
+        MF_TIMED("loss_fwd_dense", s, (launch_fwd<128, false, true>(need, grid, fp, s)));
+        *merge_splits = w.nsplit_f;
     } else {
         MF_DISPATCH_D(d, {
             dim3 grid((unsigned)w.nsplit_f, (unsigned)(w.BT / w.NW));

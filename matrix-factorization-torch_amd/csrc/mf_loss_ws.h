@@ -254,7 +254,7 @@ void loss_sweep_masks(const LossWs& w, const int32_t* first, int planes, hipStre
 // mf_loss_dense.hip: does this forward sweep the distinct columns?  Recorded for the backward on the same workspace.
 bool dense_fwd_cols(const LossWs& w, const void* ws, bool scores_needed, bool masks_ready, bool export_masks);
 // [the column plan,] the score sweep into w.part / w.stash, [the mask export]; *merge_splits: partial sets the tail merges
-int dense_fwd(const LossWs& w, bool cols, int planes, const float* u, const float* v, int need, float sigma, float margin,
+int dense_fwd(const LossWs& w, const void* ws, bool cols, int planes, const float* u, const float* v, int need, float sigma, float margin,
               uint32_t* out_mask_bits, hipStream_t s, int* merge_splits);
 // dU, dV and their split sums, on the path the last forward on `ws` took
 int dense_bwd(const LossWs& w, const void* ws, int gmode, const float* u, const float* v, const float* grad_out, float* du,

@@ -585,6 +585,42 @@ int mf_key_positions(const float* q, int64_t Q, const float* items, int64_t N, i
 int mf_position_metrics(const int64_t* pos, const int64_t* tgt_off, const float* tgt_rel, const int64_t* ncand, int64_t Q,
                         const int32_t* ks, int nk, float* out, mf_stream_t stream);
 
+/* Filtered search over item tags: `lance_table.search(embedding).where(exclude_filter, prefilter=True)` (xfmr_rec/data/lightning.py:
+ * 247-259) for predicates beyond `movie_id NOT IN (...)` -- rows that fail the predicate are never candidates.  tags [N]: one
+ * int64 per row, 64 boolean attributes; a filter is three 64-bit masks, and row r with tag word t is admissible iff
+ *   (t & all_of) == all_of  &&  (any_of == 0 || (t & any_of) != 0)  &&  (t & none_of) == 0.
+ * The view of a filter: its admissible rows in ascending row order, gathered (mf_gather_rows, a bit copy) into a dense sub-catalog
+ * that the engines above search as they are; the calls below build the view's two index vectors and carry lists into it and
+ * results out of it.  Ascending compaction keeps "score descending, row ascending", and copied rows give the same chain scores: a
+ * search of the view equals, bit for bit, the search of the catalog with every inadmissible row on every query's exclusion list.
+ *
+ * mf_filter_rows: out_rows[0 .. M) = the admissible LOCAL rows, ascending (entries from M on are not written); out_rank[r] = row
+ *   r's slot in out_rows or -1, every r < N written (8-byte aligned); out_count[0] = M, on the device.  Two launches: flags by
+ *   ballot with a count per 2048 rows, then every workgroup takes its base from those counts and a block scan gives each kept row
+ *   its slot.  No atomics: a pure function of the inputs.
+ * mf_filter_remap: out[e] = out_rank[ids[e] - idx_base] when that row lies in [0, N), else -1 -- target lists: an inadmissible
+ *   target stays in place and reads "not in the catalog".  In place (out == ids) is allowed.
+ * mf_filter_lists: an exclusion CSR (off [Q + 1], ids [n_entries], GLOBAL rows) mapped into the view: per query the entries whose
+ *   row the view holds, in their order (sorted lists stay sorted), as slots; the others are dropped.  out_off [Q + 1] is rebuilt on
+ *   the device -- a count per query, a scan over the queries, the write --, out_ids has room for n_entries.  One workgroup per
+ *   query, 1024 entries in flight.  Offsets are clamped to [0, n_entries]; n_entries == 0 still writes out_off.
+ * mf_filter_unmap: out[e] = idx[e] < 0 ? -1 : idx_base + rows[idx[e]] (rows [M] = out_rows; an idx[e] >= M reads -1) -- result
+ *   rows.  In place is allowed.
+ * No allocation, no synchronisation, no host read; capturable.  Refusals, all before any launch: MF_EINVAL a null pointer (rows
+ * may be null when M == 0), a negative count, N <= 0 (mf_filter_rows: N < 0); MF_ENOTSUP N (or M, or Q) >= 2^31; MF_ENOSPC a
+ * short workspace.  A zero count (N, n, Q) is MF_OK with nothing launched.  The _ws_bytes queries return 0 for a size outside
+ * [1, 2^31). */
+size_t mf_filter_ws_bytes(int64_t N);
+int mf_filter_rows(const int64_t* tags, int64_t N, uint64_t any_of, uint64_t all_of, uint64_t none_of, void* ws, size_t ws_bytes,
+                   int64_t* out_rows, int32_t* out_rank, int64_t* out_count, mf_stream_t stream);
+int mf_filter_remap(const int64_t* ids, int64_t n, int64_t idx_base, const int32_t* rank, int64_t N, int64_t* out,
+                    mf_stream_t stream);
+size_t mf_filter_lists_ws_bytes(int64_t Q);
+int mf_filter_lists(const int64_t* off, const int64_t* ids, int64_t n_entries, int64_t Q, int64_t idx_base, const int32_t* rank,
+                    int64_t N, void* ws, size_t ws_bytes, int64_t* out_off, int64_t* out_ids, mf_stream_t stream);
+int mf_filter_unmap(const int64_t* idx, int64_t n, const int64_t* rows, int64_t M, int64_t idx_base, int64_t* out,
+                    mf_stream_t stream);
+
 /* ------------------------------------------------------------ streaming logQ ---
  * The table the logQ correction reads, estimated from the batches themselves (Yi et al. 2019, Algorithms 2 and 3; our
  * spec, DESIGN.md 4 "Streaming logQ", restated in numpy as tests/_logq_spec.py).  State per bucket h: last_seen[h] (the step of

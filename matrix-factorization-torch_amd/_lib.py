@@ -124,6 +124,12 @@ SIGNATURES = {
     "mf_key_positions": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp,
                                  c_vp, c_vp]),
     "mf_position_metrics": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(ctypes.c_int32), c_int, c_vp, c_vp]),
+    "mf_filter_ws_bytes": (c_sz, [c_i64]),
+    "mf_filter_rows": (c_int, [c_vp, c_i64, c_u64, c_u64, c_u64, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    "mf_filter_remap": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "mf_filter_lists_ws_bytes": (c_sz, [c_i64]),
+    "mf_filter_lists": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "mf_filter_unmap": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "mf_pool_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "mf_pool_forward": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

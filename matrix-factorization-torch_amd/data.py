@@ -652,3 +652,31 @@ def synthetic_item_features(num_items: int, num_genres: int = 20, vocab: int = 5
         words = " ".join(f"w{int(w)}" for w in rng.integers(0, vocab, int(rng.integers(1, 13))))
         texts.append(_json_text({"title": f"{words} ({int(rng.integers(1920, 2020))})", "genres": [f"g{g}" for g in gs]}))
     return texts, torch.from_numpy(genre)
+
+
+def item_tag_bits(item_texts, field: str = "genres"):
+    """``(tags int64 [rows], vocabulary list[str])``: the values of ``field`` in the items' JSON texts
+    (:func:`read_movielens_features`, :func:`synthetic_item_features`) as 64 boolean attributes per row -- what
+    ``retrieval.ItemIndex.set_tags`` takes and a ``retrieval.TagFilter`` is evaluated on.  The names are sorted; bit i of row
+    r is set iff the row carries name i (a list value: each element; any other value: itself).  ``None`` / ``""`` (row 0, the
+    padding row) and a row without the field give 0.  More than 64 names: ``ValueError``."""
+    import json
+
+    import numpy as np
+
+    rows = []
+    for text in item_texts:
+        entity = json.loads(text) if isinstance(text, str) and text else (text or {})
+        value = entity.get(field)
+        values = value if isinstance(value, (list, tuple)) else ([] if value is None else [value])
+        rows.append([str(v) for v in values if v is not None])
+    vocabulary = sorted({v for r in rows for v in r})
+    if len(vocabulary) > 64:  # noqa: PLR2004
+        msg = f"at most 64 attributes fit a tag word: {field!r} has {len(vocabulary)} values"
+        raise ValueError(msg)
+    bit = {name: i for i, name in enumerate(vocabulary)}
+    tags = np.zeros(len(rows), dtype=np.uint64)
+    for r, names in enumerate(rows):
+        for name in names:
+            tags[r] |= np.uint64(1) << np.uint64(bit[name])
+    return torch.from_numpy(tags.view(np.int64)), vocabulary

@@ -31,6 +31,7 @@ from .params import INDEX_PATH, LOGQ_PATH, PROCESSORS_JSON, TOP_K, TOWERS_PATH
 from .retrieval import ItemProcessor, PartitionedIndex, PositionMetrics, QuantizedIndex, RetrievalMetrics
 
 FEATURE_BAGS_PATH = "feature_bags.safetensors"     # the feature towers' registered bags (save / load)
+ITEM_TAGS_PATH = "item_tags.safetensors"           # the items' tag words, written only when tags are set
 
 try:  # pragma: no cover - Lightning is absent from the build image
     from lightning import LightningModule as _Base
@@ -161,7 +162,7 @@ class MatrixFactorizationLitModule(_Base):
         return self.towers[tower](idx)
 
     @torch.inference_mode()
-    def recommend(self, user_idx: int, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
+    def recommend(self, user_idx: int, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None, where=None):
         if self.towers is None or self.item_processor is None or self.item_processor.index is None:
             msg = "`user_processor` and `item_processor` must be initialised first"
             raise ValueError(msg)
@@ -172,7 +173,15 @@ class MatrixFactorizationLitModule(_Base):
         else:
             with self._user_tower_eval():
                 embed = self(torch.tensor([int(user_idx)], device=device)).cpu().numpy()
-        return self.item_processor.search(embed, exclude_item_ids=exclude_item_ids, top_k=top_k)
+        return self.item_processor.search(embed, exclude_item_ids=exclude_item_ids, top_k=top_k, where=where)
+
+    def set_item_tags(self, tags, vocabulary=None) -> None:
+        """The items' tag words and the names of their bits (``data.item_tag_bits``), for ``recommend*(where=...)``: a
+        ``retrieval.TagFilter``, or a dict of name lists ``{"any_of": [...], "all_of": [...], "none_of": [...]}``.  Saved with
+        the module."""
+        if self.item_processor is None:
+            self.item_processor = self._item_processor()
+        self.item_processor.set_tags(tags, vocabulary)
 
     @contextlib.contextmanager
     def _user_tower_eval(self):
@@ -198,7 +207,8 @@ class MatrixFactorizationLitModule(_Base):
             return tower(history)
 
     @torch.inference_mode()
-    def recommend_with_history(self, item_ids: list[int], *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
+    def recommend_with_history(self, item_ids: list[int], *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None,
+                               where=None):
         """Serve a user who is in no table from the items they consumed (history tower only): the query is the pooled
         history and the history itself is excluded (xfmr_rec/lightning.py:89-90)."""
         if self.config.user_tower not in HISTORY_TOWERS:
@@ -210,7 +220,7 @@ class MatrixFactorizationLitModule(_Base):
             raise ValueError(msg)
         embed = self._pool_item_ids(list(item_ids)).cpu().numpy()
         exclude = [*(exclude_item_ids or []), *map(int, item_ids)]
-        return self.item_processor.search(embed, exclude_item_ids=exclude, top_k=top_k)
+        return self.item_processor.search(embed, exclude_item_ids=exclude, top_k=top_k, where=where)
 
     # ------------------------------------------------------------ feature towers ---
     def feature_hasher(self):
@@ -243,9 +253,10 @@ class MatrixFactorizationLitModule(_Base):
                 self._feature_tower(name, "set_features").set_bags(self._bags(x))
 
     @torch.no_grad()
-    def add_items(self, item_ids, item_texts) -> None:
+    def add_items(self, item_ids, item_texts, tags=None) -> None:
         """Cold start: embed items that were not in the catalogue from their attributes (the reference's item JSON text)
-        and append their rows and ids to the item index -- and to the item tower's bags, so a rebuilt index keeps them."""
+        and append their rows and ids to the item index -- and to the item tower's bags, so a rebuilt index keeps them.
+        ``tags``: their tag words (0 when the items have tags and none are given)."""
         from .data import FeatureBags
 
         tower = self._feature_tower("item", "add_items")
@@ -256,7 +267,7 @@ class MatrixFactorizationLitModule(_Base):
         if len(bags) != len(item_ids):
             msg = f"one text per item id: {len(item_ids)} != {len(bags)}"
             raise ValueError(msg)
-        self.item_processor.append(item_ids, tower.embed(bags))
+        self.item_processor.append(item_ids, tower.embed(bags), tags=tags)
         if tower.bags is not None:
             old = tower.bags
             w = None
@@ -267,7 +278,7 @@ class MatrixFactorizationLitModule(_Base):
             tower.set_bags(FeatureBags(off, torch.cat([old.tokens.cpu(), bags.tokens.cpu()]), w))
 
     @torch.inference_mode()
-    def recommend_with_text(self, user_text, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
+    def recommend_with_text(self, user_text, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None, where=None):
         """Serve a user from their attributes alone (the reference's user JSON text, or a dict): the counterpart of
         ``recommend(text, ...)`` (xfmr_rec/lightning.py:76-95)."""
         tower = self._feature_tower("user", "recommend_with_text")
@@ -275,10 +286,10 @@ class MatrixFactorizationLitModule(_Base):
             msg = "`user_processor` and `item_processor` must be initialised first"
             raise ValueError(msg)
         embed = tower.embed(self._bags([user_text])).cpu().numpy()
-        return self.item_processor.search(embed, exclude_item_ids=exclude_item_ids, top_k=top_k)
+        return self.item_processor.search(embed, exclude_item_ids=exclude_item_ids, top_k=top_k, where=where)
 
     @torch.inference_mode()
-    def recommend_with_item_id(self, item_id: int, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
+    def recommend_with_item_id(self, item_id: int, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None, where=None):
         """Items closest to item ``item_id`` -- the query is the item's own embedding and the item itself is
         excluded (``Service.recommend_with_item_id`` -> ``recommend_with_item``, xfmr_rec/bentoml/service.py:220-247)."""
         if self.item_processor is None or self.item_processor.index is None:
@@ -286,11 +297,11 @@ class MatrixFactorizationLitModule(_Base):
             raise ValueError(msg)
         row = self.item_processor.row_of(item_id)
         embed = self.item_processor.index.embeddings[row: row + 1, : self.config.hidden_size].cpu().numpy()
-        return self.item_processor.search(embed, exclude_item_ids=[*(exclude_item_ids or []), int(item_id)], top_k=top_k)
+        return self.item_processor.search(embed, exclude_item_ids=[*(exclude_item_ids or []), int(item_id)], top_k=top_k, where=where)
 
-    def recommend_with_user_id(self, user_idx: int, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None):
+    def recommend_with_user_id(self, user_idx: int, *, top_k: int = TOP_K, exclude_item_ids: list[int] | None = None, where=None):
         """``Service.recommend_with_user_id`` (service.py:286-311): the user's history is excluded."""
-        return self.recommend(user_idx, top_k=top_k, exclude_item_ids=exclude_item_ids)
+        return self.recommend(user_idx, top_k=top_k, exclude_item_ids=exclude_item_ids, where=where)
 
     def _item_processor(self, item_ids=None) -> ItemProcessor:
         cfg = self.config
@@ -330,6 +341,9 @@ class MatrixFactorizationLitModule(_Base):
         if bags:
             save_file(bags, str(path / FEATURE_BAGS_PATH))
         proc = {"config": self.config.model_dump(), "history": {str(k): list(map(int, v)) for k, v in self.history.items()}}
+        if self.item_processor is not None and self.item_processor.tags is not None:      # (no tags: no file, no key)
+            save_file({"tags": self.item_processor.tags.contiguous()}, str(path / ITEM_TAGS_PATH))
+            proc["item_tag_vocabulary"] = self.item_processor.tag_vocabulary
         (path / PROCESSORS_JSON).write_text(json.dumps(proc, indent=2))
         if self.item_processor is not None and self.item_processor.index is not None:
             idx = self.item_processor.index
@@ -373,6 +387,8 @@ class MatrixFactorizationLitModule(_Base):
             idx = load_file(str(path / INDEX_PATH))
             module.item_processor = module._item_processor(idx["item_ids"])      # (a partitioned index: the same build, so the same cells)
             module.item_processor.set_index(idx["embeddings"].to(device))
+        if (path / ITEM_TAGS_PATH).exists():
+            module.set_item_tags(load_file(str(path / ITEM_TAGS_PATH))["tags"], proc.get("item_tag_vocabulary"))
         return module
 
     # ------------------------------------------------------------------ losses ---

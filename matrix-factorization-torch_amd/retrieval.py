@@ -15,7 +15,9 @@ per query): which rows a query looks at becomes approximate, how they are scored
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
+from collections import OrderedDict
 from typing import Sequence
 
 import numpy as np
@@ -39,6 +41,36 @@ def _csr(exclude: Sequence[Sequence[int]] | None, q: int, device):
     return torch.from_numpy(off).to(device), torch.from_numpy(flat).to(device)
 
 
+_U64 = 1 << 64
+
+
+@dataclasses.dataclass(frozen=True)
+class TagFilter:
+    """A predicate over the items' tag words (``ItemIndex.set_tags``: 64 boolean attributes per row), three 64-bit masks: a row
+    with tag word t is admissible iff ``(t & all_of) == all_of and (any_of == 0 or t & any_of) and not t & none_of`` -- the
+    ``where`` of the reference's ``search(...).where(filter, prefilter=True)`` (data/lightning.py:247-259) for attribute
+    predicates.  Hashable: the key of an index's cached views."""
+
+    any_of: int = 0
+    all_of: int = 0
+    none_of: int = 0
+
+    def __post_init__(self) -> None:
+        for name in ("any_of", "all_of", "none_of"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < _U64:
+                msg = f"{name} must be an int in [0, 2**64): {v!r}"
+                raise ValueError(msg)
+            object.__setattr__(self, name, int(v))
+        if self.all_of & self.none_of:
+            msg = f"all_of and none_of share bits, so no row is admissible: {self.all_of & self.none_of:#x}"
+            raise ValueError(msg)
+
+
+def _is_filter_sequence(where) -> bool:
+    return isinstance(where, (list, tuple))
+
+
 class ItemIndex:
     """Item embeddings ``[N, d]`` (row r = global item row ``idx_base + r``) on one GPU.  A snapshot, like the table the
     reference's ``get_index`` writes: the derived copies (``blocked()``, ``bf16_index()``) are built on first use from the
@@ -55,6 +87,10 @@ class ItemIndex:
         self._blocked: torch.Tensor | None = None      # second copy for the small-batch scan, built on first use
         self._bf16: torch.Tensor | None = None         # bf16 copy + largest row norm for the prefilter path, built on first use
         self._ws: dict = {}                              # search workspaces, kept between calls
+        self.tags: torch.Tensor | None = None            # int64 [N]: 64 boolean attributes per row (set_tags)
+        self._views: OrderedDict = OrderedDict()         # TagFilter -> FilteredView, least recently used first
+
+    MAX_VIEWS = 8      # cached views per index: each is a second copy of its rows
 
     SMALL_Q = 32       # at most this many queries can take the bandwidth-bound matrix-vector path (mf_topk_small)
     # "auto" (measured at N = 62,423, d = 128, us of device time per call): scan 15 at Q = 1 (FMA chains, HBM-bound), and for
@@ -92,8 +128,92 @@ class ItemIndex:
         return self._bf16
 
     def refresh(self) -> None:
-        """Forget the derived copies: they are rebuilt from the current rows at the next search."""
+        """Forget the derived copies: they are rebuilt from the current rows at the next search.  The cached views of
+        ``filtered`` are copies of rows too, and go with them."""
         self._blocked = self._bf16 = None
+        self._views.clear()
+
+    def set_tags(self, tags: torch.Tensor) -> None:
+        """The rows' tag words, ``int64 [num_items]`` (bit i of row r: the row has attribute i), moved to the index's device:
+        what a ``TagFilter`` is evaluated on.  Drops the cached views."""
+        if not isinstance(tags, torch.Tensor) or tags.dtype != torch.int64 or tags.shape != (self.num_items,):
+            msg = f"tags should be an int64 tensor of shape ({self.num_items},): {getattr(tags, 'dtype', type(tags))}, {tuple(getattr(tags, 'shape', ()))}"
+            raise ValueError(msg)
+        self.tags = tags.detach().to(self.embeddings.device).contiguous()
+        self._views.clear()
+
+    def filtered(self, where, *, cache: bool = True) -> "FilteredView":
+        """The view of the rows ``where`` admits: a ``TagFilter`` over ``tags``, or a ``bool [num_items]`` allow-mask (the same
+        kernel with the mask as the tag word and ``all_of = 1``; never cached).  Built once per filter -- the predicate over
+        the catalog, the admissible rows compacted in ascending order, gathered into a dense sub-catalog -- with the one host
+        read of the view's size; a search of the view reads nothing back.  The last ``MAX_VIEWS`` filters' views are kept
+        (``cache=False``: neither looked up nor kept) until ``refresh()``, ``rebuild()`` or ``set_tags()``."""
+        if isinstance(where, TagFilter):
+            if self.tags is None:
+                msg = "a TagFilter needs the rows' tags: call set_tags first"
+                raise ValueError(msg)
+            if cache and where in self._views:
+                self._views.move_to_end(where)
+                return self._views[where]
+            view = FilteredView(self, self.tags, where)
+            if cache:
+                self._views[where] = view
+                while len(self._views) > self.MAX_VIEWS:
+                    self._views.popitem(last=False)
+            return view
+        if isinstance(where, torch.Tensor) and where.dtype == torch.bool and where.shape == (self.num_items,):
+            return FilteredView(self, where.to(self.embeddings.device).to(torch.int64), TagFilter(all_of=1))
+        msg = f"where should be a TagFilter or a bool tensor of shape ({self.num_items},): {where!r}"
+        raise ValueError(msg)
+
+    def _sub_index(self, embeddings: torch.Tensor, rows: torch.Tensor) -> "ItemIndex":  # noqa: ARG002
+        """An index of this class over gathered rows, local rows from 0: what a view searches.  Its width is the STORED one
+        (the view hands it queries padded like the rows)."""
+        return ItemIndex(embeddings)
+
+    def _where_groups(self, where, nq: int):
+        """A sequence of per-query filters -> ``[(filter, query numbers int64 on the host)]``, one entry per distinct filter in
+        the order of first appearance."""
+        if len(where) != nq:
+            msg = f"one filter per query expected: {len(where) = }, {nq = }"
+            raise ValueError(msg)
+        groups: dict = {}
+        for i, f in enumerate(where):
+            if not isinstance(f, TagFilter):
+                msg = f"a sequence of filters holds TagFilters: {f!r}"
+                raise ValueError(msg)
+            groups.setdefault(f, []).append(i)
+        return [(f, torch.tensor(qs, dtype=torch.int64)) for f, qs in groups.items()]
+
+    @staticmethod
+    def _sub_csr(csr, exclude, qs: torch.Tensor, device):
+        """The lists of the queries ``qs`` (host int64), from a device CSR (sizing the result is a host read) or host lists: a
+        device CSR ``(offsets, entries -- exactly as many as the lists hold)`` or None."""
+        if csr is not None:
+            off, ids = csr
+            sel = qs.to(device)
+            lens = off[sel + 1] - off[sel]
+            sub_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(lens, 0)])
+            owner = torch.repeat_interleave(torch.arange(sel.numel(), device=device), lens)
+            at = off[sel][owner] + torch.arange(owner.numel(), device=device) - sub_off[owner]
+            return sub_off, ids[at]
+        if exclude is not None:
+            return _csr([exclude[i] for i in qs.tolist()], qs.numel(), device)
+        return None
+
+    def _search_groups(self, q: torch.Tensor, top_k: int, where, exclude, exclude_csr, kw) -> tuple[torch.Tensor, torch.Tensor]:
+        nq = q.shape[0]
+        if exclude is not None and len(exclude) != nq:
+            msg = f"one exclusion list per query expected: {len(exclude) = }, {nq = }"
+            raise ValueError(msg)
+        scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
+        rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
+        for f, qs in self._where_groups(where, nq):
+            sel = qs.to(q.device)
+            sub = self._sub_csr(exclude_csr, exclude, qs, q.device)
+            s, r = self.filtered(f).search(q[sel], top_k, exclude_csr=sub, **kw)
+            scores[sel], rows[sel] = s, r
+        return scores, rows
 
     def _workspace(self, key, nbytes: int) -> torch.Tensor:
         ws = self._ws.get(key)
@@ -117,12 +237,16 @@ class ItemIndex:
 
     def positions(self, queries: torch.Tensor, targets_csr: tuple[torch.Tensor, torch.Tensor], *,
                   exclude: Sequence[Sequence[int]] | None = None,
-                  exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                  exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None,
+                  where=None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """``(pos int64 [T], score fp32 [T], ncand int64 [Q])``: for every entry of ``targets_csr = (offsets [Q + 1], GLOBAL
         item rows [T])`` its exact place among the query's admissible rows -- the rows ``search`` selects from, in its order
         (0 = best) -- and its score; -1 / -inf for a row that is excluded or outside the catalog.  ``ncand`` is the number of
         admissible rows per query.  A position below ``k`` is the column ``search(..., k, path="deep")`` returns the row at
-        (``mf_target_positions``: no list is built, so there is no deepest k)."""
+        (``mf_target_positions``: no list is built, so there is no deepest k).  ``where`` (a ``TagFilter``, an allow-mask or one
+        ``TagFilter`` per query): the rows it does not admit count as excluded (``filtered``)."""
+        if where is not None:
+            return self._positions_where(queries, targets_csr, where, exclude, exclude_csr)
         q = self._queries(queries)
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         t_off, t_ids = (_lib.dev_i64(t, name) for t, name in zip(targets_csr, ("target offsets", "target rows")))
@@ -143,6 +267,26 @@ class ItemIndex:
         _lib.check(lib.mf_target_positions(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, t_off.data_ptr(), t_ids.data_ptr(), nt,
                                            _lib.ptr(off), _lib.ptr(ids), self.idx_base, ws.data_ptr(), ws.numel(), pos_arg.data_ptr(),
                                            score_arg.data_ptr(), ncand.data_ptr(), _lib.stream_ptr()))
+        return pos, score, ncand
+
+    def _positions_where(self, queries, targets_csr, where, exclude, exclude_csr):
+        if not _is_filter_sequence(where):
+            return self.filtered(where).positions(queries, targets_csr, exclude=exclude, exclude_csr=exclude_csr)
+        q = self._queries(queries)
+        nq = q.shape[0]
+        t_off, t_ids, nt = self._targets(nq, targets_csr, q.device)
+        if exclude is not None and len(exclude) != nq:
+            msg = f"one exclusion list per query expected: {len(exclude) = }, {nq = }"
+            raise ValueError(msg)
+        pos = torch.empty(nt, dtype=torch.int64, device=q.device)
+        score = torch.empty(nt, dtype=torch.float32, device=q.device)
+        ncand = torch.empty(nq, dtype=torch.int64, device=q.device)
+        entry = torch.arange(nt, dtype=torch.int64, device=q.device)
+        for f, qs in self._where_groups(where, nq):
+            sel = qs.to(q.device)
+            sub_off, sub_at = self._sub_csr((t_off, entry), None, qs, q.device)      # (the entries' numbers: where the answers go)
+            p, s, c = self.filtered(f).positions(q[sel], (sub_off, t_ids[sub_at]), exclude_csr=self._sub_csr(exclude_csr, exclude, qs, q.device))
+            pos[sub_at], score[sub_at], ncand[sel] = p, s, c
         return pos, score, ncand
 
     def _targets(self, nq: int, targets_csr, device) -> tuple[torch.Tensor, torch.Tensor, int]:
@@ -213,14 +357,20 @@ class ItemIndex:
 
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None,
-               path: str = "auto") -> tuple[torch.Tensor, torch.Tensor]:
+               path: str = "auto", where=None) -> tuple[torch.Tensor, torch.Tensor]:
         """``(scores [Q, k] fp32, rows [Q, k] int64)``, best first; ``exclude`` holds GLOBAL
         item rows per query (or pass a prebuilt device CSR with sorted ids).  ``path``: "scan" = the
         matrix-vector kernel (at most ``SMALL_Q`` queries), "tiles" = the fp32 MFMA tile engine, "bf16" = two bf16
         MFMA scans that pick the few dozen rows per query worth an exact fp32 score (d >= 64), "deep" = score once, then
         a radix select per query (``mf_topk_deep``: any ``top_k`` up to ``DEEP_MAX_K``; the other three stop at
         ``TILE_MAX_K``); "auto" takes "deep" exactly when ``top_k > TILE_MAX_K`` and otherwise picks by the number of
-        queries; all four give the same bits."""
+        queries; all four give the same bits.  ``where`` (a ``TagFilter``, a ``bool [num_items]`` allow-mask, or a sequence of
+        one ``TagFilter`` per query): only the rows it admits are candidates -- the same search through ``filtered(where)``, bit
+        for bit what this search returns with every other row on every query's exclusion list."""
+        if where is not None:
+            if _is_filter_sequence(where):
+                return self._search_groups(self._queries(queries), int(top_k), where, exclude, exclude_csr, {"path": path})
+            return self.filtered(where).search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, path=path)
         q = self._queries(queries)
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
@@ -391,6 +541,11 @@ class PartitionedIndex(ItemIndex):
         self.max_cell_blocks = int((self.cell_blk[1:] - self.cell_blk[:-1]).max())
         self.coarse = ItemIndex(self.centroids)
         self._cells = None
+        self._views.clear()                              # (a view keeps the cells of its build)
+
+    def _sub_index(self, embeddings: torch.Tensor, rows: torch.Tensor) -> "PartitionedIndex":
+        """The view's index keeps the cells: the same centroids, every gathered row in the cell it had -- so the same probes."""
+        return PartitionedIndex.from_assignment(embeddings, self.centroids, self.assign[rows], num_probes=self.num_probes)
 
     def cell_blocked(self) -> torch.Tensor:
         """The catalog ordered by cell (``row_of``; padding rows zero) in the blocked layout of ``mf_topk_small``
@@ -446,12 +601,18 @@ class PartitionedIndex(ItemIndex):
 
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, nprobe: int | None = None,
-               path: str = "cells") -> tuple[torch.Tensor, torch.Tensor]:
+               path: str = "cells", where=None) -> tuple[torch.Tensor, torch.Tensor]:
         """``ItemIndex.search``'s inputs and result -- shapes, dtypes, the -inf / -1 tail -- over the rows of the ``nprobe``
         cells (default ``num_probes``) whose centroids score best against each query (exact, lowest cell on ties).
         ``path="cells"``: three launches' worth of stages, none with a host read -- the cells (the exact engines on the centroid
         matrix), the scan (``mf_ivf_scan``), the merge (``mf_topk_merge_packed``).  ``path="exact"`` is the parent's search over
-        the whole catalog ("auto"); any other path is passed to the parent as it is."""
+        the whole catalog ("auto"); any other path is passed to the parent as it is.  ``where``: as in the parent -- the view
+        keeps the cells, so the probes are the same and the result is this search's with the inadmissible rows excluded."""
+        if where is not None:
+            kw = {"nprobe": nprobe, "path": path}
+            if _is_filter_sequence(where):
+                return self._search_groups(self._queries(queries), int(top_k), where, exclude, exclude_csr, kw)
+            return self.filtered(where).search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, **kw)
         if path != "cells":
             return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, path="auto" if path == "exact" else path)
         top_k, nprobe = self._top_k(top_k, "partitioned"), self._nprobe(nprobe)
@@ -578,6 +739,12 @@ class QuantizedIndex(PartitionedIndex):
         super()._install(centroids, assign)
         self._codes = None
 
+    def filtered(self, where, *, cache: bool = True) -> "FilteredView":  # noqa: ARG002
+        """Not implemented: the candidate stage ranks by approximate scores, and that "a view's search equals the search with
+        the other rows excluded" has only been argued for exact scores."""
+        msg = f"{type(self).__name__} takes no filter: its candidates are ranked by approximate scores"
+        raise NotImplementedError(msg)
+
     def codes(self) -> torch.Tensor:
         """The rows' codes in cell order, ``Npad * M`` bytes in the layout ``mf_pq_scan`` reads (include/mf_hip.h:
         ``[64-row block][M / 4][64]`` 32-bit words, lane = row; padding positions hold code 0), built once."""
@@ -663,13 +830,15 @@ class QuantizedIndex(PartitionedIndex):
 
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, nprobe: int | None = None,
-               refine_factor: int | None = None, path: str = "pq") -> tuple[torch.Tensor, torch.Tensor]:
+               refine_factor: int | None = None, path: str = "pq", where=None) -> tuple[torch.Tensor, torch.Tensor]:
         """``ItemIndex.search``'s inputs and result.  ``path="pq"``: the ``refine_factor * top_k`` (default: the index's
         factor; at most ``MAX_CANDIDATES``) best rows of the ``nprobe`` probed cells by the quantiser's approximate score,
         scored again with the chain on the original rows and ordered exactly -- four stages, none with a host read: the
         cells, the scan (``mf_pq_scan``), the merge (``mf_topk_merge_packed_deep``), the refine (``mf_pq_refine``); the
         cell-ordered fp32 copy is not built.  ``path="cells"`` and ``path="exact"`` (and the exact engines' names) are the
-        parent's."""
+        parent's.  ``where``: refused (``filtered``)."""
+        if where is not None:
+            self.filtered(where)
         if path != "pq":
             return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, nprobe=nprobe, path=path)
         r = self._candidates_of(top_k, refine_factor)
@@ -684,6 +853,105 @@ class QuantizedIndex(PartitionedIndex):
         _lib.check(_lib.lib().mf_pq_refine(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, cand.data_ptr(), r, top_k, self.idx_base,
                                            scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
         return scores, rows
+
+
+class FilteredView:
+    """The rows of an index that a filter admits, as an index of their own (``ItemIndex.filtered``): ``rows`` (``int64 [M]``, the
+    admissible local rows in ascending order -- ``mf_filter_rows``), and ``index``, an index of the parent's class over a bit copy
+    of those rows (``mf_gather_rows`` at the stored width) with ``idx_base = 0``; None when ``M == 0``.  ``search`` and
+    ``positions`` take the parent's arguments and return GLOBAL rows: exclusion lists are mapped into the view on the device
+    (``mf_filter_lists``), targets likewise (``mf_filter_remap``), result rows back (``mf_filter_unmap``), and the engines run
+    untouched on ``M`` rows -- ``path=`` and the ``top_k`` limits are theirs.  Ascending compaction keeps "score descending, row
+    ascending" and the copied rows give the same chain scores, so the result is, bit for bit, the parent's search with every
+    inadmissible row on every query's exclusion list.  A snapshot of the rows and tags at its build, like the index itself."""
+
+    def __init__(self, parent: ItemIndex, words: torch.Tensor, where: TagFilter) -> None:
+        lib = _lib.lib()
+        emb = parent.embeddings
+        n, d = emb.shape
+        dev = emb.device
+        if words.data_ptr() % 16:
+            words = words.clone()
+        rows = torch.empty(n, dtype=torch.int64, device=dev)
+        self.rank = torch.empty(n, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = _lib.workspace(lib.mf_filter_ws_bytes(n), dev)
+        _lib.check(lib.mf_filter_rows(words.data_ptr(), n, where.any_of, where.all_of, where.none_of, ws.data_ptr(), ws.numel(),
+                                      rows.data_ptr(), self.rank.data_ptr(), count.data_ptr(), _lib.stream_ptr()))
+        m = int(count.item())                       # the one host read: it sizes the copy
+        self.parent, self.where = parent, where
+        self.rows = rows[:m].clone()
+        self.index: ItemIndex | None = None
+        self._ws: dict = {}
+        if m:
+            sub = torch.empty(m, d, dtype=torch.float32, device=dev)
+            _lib.check(lib.mf_gather_rows(emb.data_ptr(), n, d, self.rows.data_ptr(), m, 0, sub.data_ptr(), None, _lib.stream_ptr()))
+            self.index = parent._sub_index(sub, self.rows)
+
+    @property
+    def num_items(self) -> int:
+        return self.rows.numel()
+
+    def _lists(self, nq: int, exclude, exclude_csr, device):
+        """The exclusion lists inside the view: a device CSR of slots (``mf_filter_lists``), or None without lists."""
+        off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, device)
+        if off is None:
+            return None
+        off, ids = _lib.dev_i64(off, "exclusion offsets"), _lib.dev_i64(ids, "exclusion rows")
+        if off.numel() != nq + 1:
+            msg = f"one exclusion list per query expected: {off.numel() = }, {nq = }"
+            raise ValueError(msg)
+        lib = _lib.lib()
+        entries = ids.numel()
+        if entries == 0:       # keep the pointer valid
+            ids = torch.zeros(1, dtype=torch.int64, device=device)
+        need = lib.mf_filter_lists_ws_bytes(nq)
+        ws = self._ws.get("lists")
+        if ws is None or ws.numel() < need:
+            ws = self._ws["lists"] = _lib.workspace(need, device)
+        out_off = torch.empty(nq + 1, dtype=torch.int64, device=device)
+        out_ids = torch.empty(max(entries, 1), dtype=torch.int64, device=device)
+        _lib.check(lib.mf_filter_lists(off.data_ptr(), ids.data_ptr(), entries, nq, self.parent.idx_base, self.rank.data_ptr(),
+                                       self.parent.num_items, ws.data_ptr(), ws.numel(), out_off.data_ptr(), out_ids.data_ptr(),
+                                       _lib.stream_ptr()))
+        return out_off, out_ids
+
+    def _unmap(self, rows: torch.Tensor) -> torch.Tensor:
+        _lib.check(_lib.lib().mf_filter_unmap(rows.data_ptr(), rows.numel(), self.rows.data_ptr(), self.num_items, self.parent.idx_base,
+                                              rows.data_ptr(), _lib.stream_ptr()))
+        return rows
+
+    def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
+               exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, **kw) -> tuple[torch.Tensor, torch.Tensor]:
+        """The parent's ``search`` over the admissible rows: its arguments (``path=``, ``nprobe=`` as the parent takes them), its
+        result with GLOBAL rows.  An empty view answers -inf / -1 without an engine."""
+        q = self.parent._queries(queries)
+        nq = q.shape[0]
+        if self.index is None:
+            if exclude is not None and len(exclude) != nq:
+                msg = f"one exclusion list per query expected: {len(exclude) = }, {nq = }"
+                raise ValueError(msg)
+            return (torch.full((nq, int(top_k)), -math.inf, dtype=torch.float32, device=q.device),
+                    torch.full((nq, int(top_k)), -1, dtype=torch.int64, device=q.device))
+        scores, rows = self.index.search(q, top_k, exclude_csr=self._lists(nq, exclude, exclude_csr, q.device), **kw)
+        return scores, self._unmap(rows)
+
+    def positions(self, queries: torch.Tensor, targets_csr: tuple[torch.Tensor, torch.Tensor], *,
+                  exclude: Sequence[Sequence[int]] | None = None,
+                  exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The parent's ``positions`` among the admissible rows: a target the filter does not admit reads -1 / -inf, like one
+        that is excluded or outside the catalog."""
+        q = self.parent._queries(queries)
+        nq = q.shape[0]
+        t_off, t_ids, nt = self.parent._targets(nq, targets_csr, q.device)
+        if self.index is None:
+            return (torch.full((nt,), -1, dtype=torch.int64, device=q.device),
+                    torch.full((nt,), -math.inf, dtype=torch.float32, device=q.device),
+                    torch.zeros(nq, dtype=torch.int64, device=q.device))
+        slots = torch.empty(max(nt, 1), dtype=torch.int64, device=q.device)
+        _lib.check(_lib.lib().mf_filter_remap(t_ids.data_ptr(), nt, self.parent.idx_base, self.rank.data_ptr(), self.parent.num_items,
+                                              slots.data_ptr(), _lib.stream_ptr()))
+        return self.index.positions(q, (t_off, slots[:nt]), exclude_csr=self._lists(nq, exclude, exclude_csr, q.device))
 
 
 def merge_topk(part_scores: torch.Tensor, part_rows: torch.Tensor, top_k: int) -> tuple[torch.Tensor, torch.Tensor]:
@@ -736,6 +1004,55 @@ class ItemProcessor:
         self.refine_factor = QuantizedIndex._refine_factor(refine_factor)
         self.index: ItemIndex | None = None
         self._row_of_id: dict[int, int] | None = None
+        self.tags: torch.Tensor | None = None            # int64 [rows] on the host: the items' tag words (set_tags)
+        self.tag_vocabulary: list[str] | None = None     # name of bit i
+
+    def set_tags(self, tags, vocabulary: Sequence[str] | None = None) -> None:
+        """The items' tag words (``data.item_tag_bits``: ``int64 [rows]``, one per item row) and the names of their bits: what
+        ``search(where=...)`` filters on.  Kept here and handed to every index this processor builds."""
+        t = torch.as_tensor(tags)
+        if t.dtype != torch.int64 or t.dim() != 1:
+            msg = f"tags should be an int64 vector, one word per item row: {t.dtype}, {tuple(t.shape)}"
+            raise ValueError(msg)
+        if self.index is not None and t.numel() != self.index.num_items:
+            msg = f"one tag word per item row: {t.numel()} != {self.index.num_items}"
+            raise ValueError(msg)
+        if vocabulary is not None and (len(vocabulary) > 64 or len(set(vocabulary)) != len(vocabulary)):  # noqa: PLR2004
+            msg = f"a vocabulary names at most 64 distinct bits: {len(vocabulary)} names"
+            raise ValueError(msg)
+        self.tags = t.detach().cpu().contiguous()
+        self.tag_vocabulary = None if vocabulary is None else [str(v) for v in vocabulary]
+        if self.index is not None:
+            self.index.set_tags(self.tags)
+
+    def tag_filter(self, any_of: Sequence[str] = (), all_of: Sequence[str] = (), none_of: Sequence[str] = ()) -> TagFilter:
+        """A ``TagFilter`` from names of the vocabulary (``KeyError`` for a name it does not hold)."""
+        if self.tag_vocabulary is None:
+            msg = "tag names need a vocabulary: set_tags(tags, vocabulary)"
+            raise ValueError(msg)
+        bit = {name: i for i, name in enumerate(self.tag_vocabulary)}
+
+        def mask(names) -> int:
+            names = [names] if isinstance(names, str) else list(names)
+            unknown = [n for n in names if n not in bit]
+            if unknown:
+                msg = f"unknown tag names: {unknown}"
+                raise KeyError(msg)
+            return sum({1 << bit[n] for n in names})
+
+        return TagFilter(any_of=mask(any_of), all_of=mask(all_of), none_of=mask(none_of))
+
+    def _where(self, where):
+        """``where`` as the index takes it: a ``TagFilter`` / allow-mask as it is, a dict of name lists through ``tag_filter``."""
+        return self.tag_filter(**where) if isinstance(where, dict) else where
+
+    def _install_tags(self) -> None:
+        """Hand the tags to a newly built index when they still have one word per row; forget them otherwise."""
+        if self.tags is not None and self.index is not None:
+            if self.tags.numel() == self.index.num_items:
+                self.index.set_tags(self.tags)
+            else:
+                self.tags = None
 
     def _make_index(self, embeddings: torch.Tensor) -> ItemIndex:
         if self.index_type == "exact":
@@ -756,6 +1073,7 @@ class ItemProcessor:
         if self.item_ids is None:
             self.item_ids = torch.arange(tower.num_embeddings)
         self._row_of_id = {int(i): r for r, i in enumerate(self.item_ids.tolist())}
+        self._install_tags()
         return self.index
 
     def set_index(self, embeddings: torch.Tensor) -> ItemIndex:
@@ -764,10 +1082,12 @@ class ItemProcessor:
         if self.item_ids is None:
             self.item_ids = torch.arange(embeddings.shape[0])
         self._row_of_id = {int(i): r for r, i in enumerate(self.item_ids.tolist())}
+        self._install_tags()
         return self.index
 
-    def append(self, item_ids, embeddings: torch.Tensor) -> ItemIndex:
-        """Add items to a built index: their rows follow the existing ones (the index is rebuilt, the id map extended)."""
+    def append(self, item_ids, embeddings: torch.Tensor, tags=None) -> ItemIndex:
+        """Add items to a built index: their rows follow the existing ones (the index is rebuilt, the id map extended).
+        ``tags``: the new rows' tag words (0 when tags are set and none are given)."""
         if self.index is None or self.item_ids is None:
             msg = "`index` must be intialised first"
             raise ValueError(msg)
@@ -778,6 +1098,13 @@ class ItemProcessor:
         if set(ids.tolist()) & set(self._row_of_id or {}) or len(set(ids.tolist())) != ids.numel():
             msg = "item ids must be new and distinct"
             raise ValueError(msg)
+        if tags is not None:
+            new_tags = torch.as_tensor(tags)
+            if self.tags is None or new_tags.dtype != torch.int64 or new_tags.shape != (ids.numel(),):
+                msg = "tags of appended items: one int64 word per new item, on a processor whose tags are set"
+                raise ValueError(msg)
+        if self.tags is not None:
+            self.tags = torch.cat([self.tags, torch.zeros(ids.numel(), dtype=torch.int64) if tags is None else new_tags.cpu()])
         old = self.index.embeddings[:, : self.index.dim]
         self.item_ids = torch.cat([self.item_ids, ids])
         return self.set_index(torch.cat([old, embeddings.to(old.device, torch.float32)]))
@@ -788,7 +1115,9 @@ class ItemProcessor:
             raise KeyError(msg)
         return self._row_of_id[int(item_id)]
 
-    def search(self, embedding, exclude_item_ids: list[int] | None = None, top_k: int = TOP_K):
+    def search(self, embedding, exclude_item_ids: list[int] | None = None, top_k: int = TOP_K, where=None):
+        """``where``: only items it admits are returned -- a ``TagFilter``, a ``bool [rows]`` allow-mask, or a dict of name
+        lists (``tag_filter``'s arguments); the reference's ``.where(filter, prefilter=True)``."""
         import pandas as pd
 
         if self.index is None:
@@ -796,7 +1125,8 @@ class ItemProcessor:
             raise ValueError(msg)
         q = torch.as_tensor(np.asarray(embedding), dtype=torch.float32).reshape(1, -1).to(self.index.embeddings.device)
         rows = [self._row_of_id[i] for i in (exclude_item_ids or []) if i in self._row_of_id]
-        scores, idx = self.index.search(q, top_k, exclude=[rows])
+        scores, idx = self.index.search(q, top_k, exclude=[rows]) if where is None else \
+            self.index.search(q, top_k, exclude=[rows], where=self._where(where))
         idx = idx[0].cpu()
         keep = idx >= 0
         idx = idx[keep]

@@ -449,6 +449,20 @@ int mf_ivf_scan(const float* q, int64_t Q, const float* blocked, const int64_t* 
                 mf_stream_t stream);
 int mf_ivf_cell_mean(const float* items, int64_t N, int d, const int64_t* order, const int64_t* cell_off, int64_t C,
                      int normalize, float* out, mf_stream_t stream);
+/* mf_ivf_scan_allow: mf_ivf_scan filtered in place -- the reference's `.where(filter, prefilter=True)` (:250-259) without a
+ * second copy of the admissible rows.  Every argument of mf_ivf_scan in its order, and before ws the allow bitmap: allow
+ * [n_masks][Npad / 64] 64-bit words as mf_filter_cell_bits writes them (bit `lane` of word `blk`: the row at cell-ordered
+ * position blk * 64 + lane may enter a list); query q reads mask allow_of[q] (allow_of null: mask 0, which needs n_masks == 1);
+ * an allow_of[q] outside [0, n_masks) admits nothing -- that query's lists are all -1.  A row whose bit is clear has key 0
+ * before it can compete, as an excluded row's key never enters: the lists -- and after mf_topk_merge_packed the result -- are bit
+ * for bit mf_ivf_scan's with every such row on the query's exclusion list.  A wave loads its block's word once (a scalar load)
+ * and skips a block whose word is 0: no row, no row_of load.  One launch, no atomics, no host read: capturable.  Refusals:
+ * mf_ivf_scan's in its order, then MF_EINVAL "bad allow argument" (allow null, n_masks <= 0, or allow_of null with n_masks
+ * != 1); MF_ENOTSUP n_masks * (Npad / 64) >= 2^31. */
+int mf_ivf_scan_allow(const float* q, int64_t Q, const float* blocked, const int64_t* cell_blk, const int64_t* row_of, int64_t Npad,
+                      int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
+                      const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, const uint64_t* allow, int64_t n_masks,
+                      const int64_t* allow_of, void* ws, size_t ws_bytes, mf_stream_t stream);
 
 /* Product-quantised cells with an exact refine: the rest of the reference's IVF_PQ index (xfmr_rec/data/lightning.py:162-165,
  * 203-204: num_sub_vectors = embedding_dim // 8, refine_factor = 4; :222-229 create_index; :250-259
@@ -508,6 +522,20 @@ int mf_pq_scan(const float* q, int64_t Q, const void* codes, const float* codebo
                int64_t idx_base, void* ws, size_t ws_bytes, mf_stream_t stream);
 int mf_pq_refine(const float* q, int64_t Q, const float* items, int64_t N, int d, const int64_t* cand, int R, int k,
                  int64_t idx_base, float* out_scores, int64_t* out_idx, mf_stream_t stream);
+/* mf_pq_scan_allow: mf_pq_scan filtered in place -- what the reference's IVF_PQ search runs with `.where(filter,
+ * prefilter=True)`.  Every argument of mf_pq_scan in its order, and before ws the allow bitmap of mf_ivf_scan_allow (allow
+ * [n_masks][Npad / 64], n_masks, allow_of [Q] nullable; an allow_of[q] outside [0, n_masks) admits nothing).  A row whose bit
+ * is clear has key 0 before it meets the bound, so the kept keys, the bound and the lists of approximate scores are bit for
+ * bit mf_pq_scan's with every such row on the query's exclusion list -- the argument does not ask whether the scores are exact.
+ * A wave takes the words of 64 blocks by one vector load (lane = block) and reads each pass's word out of that strip; a wave whose
+ * word is 0 loads neither codes nor row_of and still takes every barrier of the pass.  mf_pq_refine needs no mask:
+ * it only sees candidates the scan admitted.  Refusals: mf_pq_scan's in its order, then MF_EINVAL "bad allow argument" (allow
+ * null, n_masks <= 0, or allow_of null with n_masks != 1); MF_ENOTSUP n_masks * (Npad / 64) >= 2^31. */
+int mf_pq_scan_allow(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+                     const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes,
+                     const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off, const int64_t* excl_idx,
+                     int64_t idx_base, const uint64_t* allow, int64_t n_masks, const int64_t* allow_of, void* ws, size_t ws_bytes,
+                     mf_stream_t stream);
 
 /* Retrieval metrics @k on device, straight from the top-k output.  Replaces the
  * per-example torchmetrics updates of `update_metrics` / `get_metrics` (xfmr_rec/lightning.py:149-187,
@@ -620,6 +648,14 @@ int mf_filter_lists(const int64_t* off, const int64_t* ids, int64_t n_entries, i
                     int64_t N, void* ws, size_t ws_bytes, int64_t* out_off, int64_t* out_ids, mf_stream_t stream);
 int mf_filter_unmap(const int64_t* idx, int64_t n, const int64_t* rows, int64_t M, int64_t idx_base, int64_t* out,
                     mf_stream_t stream);
+/* mf_filter_cell_bits: the same predicate as a bitmap over a cell-ordered catalog (row_of [Npad], Npad a multiple of 64: the
+ * layout of mf_ivf_scan), for the scans that filter in place: bit `lane` of out_words[blk] is set iff r = row_of[blk * 64 + lane]
+ * >= 0 and tags[r] is admissible -- Npad / 8 bytes per filter where a view copies its rows; padding positions are never set.
+ * One launch, a wave per block, the word is the wave's ballot; no atomics, no workspace, no host read, every word written: a
+ * pure function of the inputs, capturable.  Refusals before any launch, in this order: MF_EINVAL a null pointer, N <= 0, Npad
+ * < N or no multiple of 64; MF_ENOTSUP Npad >= 2^31. */
+int mf_filter_cell_bits(const int64_t* tags, int64_t N, uint64_t any_of, uint64_t all_of, uint64_t none_of, const int64_t* row_of,
+                        int64_t Npad, uint64_t* out_words, mf_stream_t stream);
 
 /* ------------------------------------------------------------ streaming logQ ---
  * The table the logQ correction reads, estimated from the batches themselves (Yi et al. 2019, Algorithms 2 and 3; our

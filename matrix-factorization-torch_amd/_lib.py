@@ -107,12 +107,16 @@ SIGNATURES = {
     "mf_ivf_plan": (c_int, [c_i64, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]),
     "mf_ivf_scan": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp,
                             c_i64, c_vp, c_sz, c_vp]),
+    "mf_ivf_scan_allow": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp,
+                                  c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "mf_ivf_cell_mean": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "mf_pq_encode": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_vp]),
     "mf_pq_ws_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
     "mf_pq_plan": (c_int, [c_i64, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]),
     "mf_pq_scan": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_int,
                            c_vp, c_vp, c_i64, c_vp, c_sz, c_vp]),
+    "mf_pq_scan_allow": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_int,
+                                 c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "mf_pq_refine": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp]),
     "mf_target_positions_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_target_positions_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
@@ -130,6 +134,7 @@ SIGNATURES = {
     "mf_filter_lists_ws_bytes": (c_sz, [c_i64]),
     "mf_filter_lists": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "mf_filter_unmap": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "mf_filter_cell_bits": (c_int, [c_vp, c_i64, c_u64, c_u64, c_u64, c_vp, c_i64, c_vp, c_vp]),
     "mf_pool_ws_bytes": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "mf_pool_forward": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -1,7 +1,7 @@
 // mf_cells.h -- what the two searches over probed cells share (mf_ivf.hip: exact fp32 rows; mf_pq.hip: one-byte codes): "a
 // 256-thread workgroup scans one slice of one probed cell of one query, a 64-row block per wave and pass, lane = row, and
 // leaves one ordered list of packed entries (mf_topk_io.h)".  Here: into how many slices a cell is cut and what the scan
-// exports refuse (host); the look-up in the query's exclusion list and the entry a workgroup writes (device).  How a row is
+// exports refuse (host); the look-up in the query's exclusion list, the allow bitmap's word test and the entry a workgroup writes (device).  How a row is
 // scored and how the best keys are kept is each scan's own -- DESIGN.md "Cell scans: what is shared".
 #pragma once
 
@@ -80,6 +80,22 @@ static inline int mf_cells_check_lists(const char* who, const MfCellsLimits& lim
     return MF_OK;
 }
 
+// ---- the allow bitmap of mf_ivf_scan_allow / mf_pq_scan_allow: `allow` [n_masks][Npad / 64] 64-bit words, bit `lane` of word
+// `blk` of a mask = the row at cell-ordered position blk * 64 + lane may enter a list (mf_filter_cell_bits writes them); query q
+// reads mask allow_of[q], mask 0 without allow_of.  What the kernels carry of it:
+struct MfCellsAllow {
+    const unsigned long long* words;
+    const int64_t* of;          // [Q], nullable
+    int64_t n_masks, stride;    // stride = Npad / 64 words per mask
+};
+// The checks the two exports add behind their scans' own (mf_cells_check_lists has seen Npad < 2^31).
+static inline int mf_cells_check_allow(const char* who, const void* allow, int64_t n_masks, const void* allow_of, int64_t Npad) {
+    if (!allow || n_masks <= 0 || (!allow_of && n_masks != 1)) return mf_set_error(MF_EINVAL, "%s: bad allow argument", who);
+    if (n_masks >= (1ll << 31) || n_masks * (Npad / 64) >= (1ll << 31))
+        return mf_set_error(MF_ENOTSUP, "%s: n_masks * (Npad / 64) = %lld * %lld words exceed 2^31", who, (long long)n_masks, (long long)(Npad / 64));
+    return MF_OK;
+}
+
 #ifdef __HIPCC__
 // ---- device.  (Which blocks a workgroup walks -- blockIdx.x = (q * nprobe + probe) * S + slice, then the slice's share
 // [b0, b1) of the probed cell's blocks -- stands in both kernels, the same lines: as a function here it cost the scans up to
@@ -99,6 +115,34 @@ __device__ __forceinline__ bool mf_cells_admit(bool pass, unsigned grow, const i
     }
     return pass;
 }
+
+// The words of query q's mask; null where allow_of[q] names no mask: that query admits nothing.  (workgroup-uniform)
+__device__ __forceinline__ const unsigned long long* mf_cells_allow_mask(const MfCellsAllow& a, int64_t q) {
+    const int64_t m = a.of ? a.of[q] : 0;
+    return m >= 0 && m < a.n_masks ? a.words + m * a.stride : nullptr;
+}
+// The word of block `blk` (wave-uniform: one scalar load a wave), 0 for a query without a mask.  A wave whose word is 0 has
+// nothing to read in the block; a lane's key counts only where mf_cells_allowed says so.
+typedef const __attribute__((address_space(4))) unsigned long long* mf_const_u64;
+__device__ __forceinline__ unsigned long long mf_cells_allow_word(const unsigned long long* mask, int64_t blk) {
+    return mask ? ((mf_const_u64)mask)[blk] : 0ull;
+}
+// The same words for a scan whose pass waits on LDS reads (mf_pq_scan.inc): a scalar load shares their counter, which is waited
+// to zero at every barrier, so a word asked for by scalar load costs its whole latency once a pass wherever it is asked for
+// (measured: 3 ... 5 % of the all-ones scan at 1024 queries, at the top of the pass, ahead of the table reads and behind them
+// alike).  Instead lane l takes the word of block `first + l` -- one coalesced vector load for the next 64 blocks, 16 passes of
+// four waves, on the counter of the code loads, which a barrier does not wait for -- and a pass reads its word out of the strip.
+// 0 from `end` on and for a query without a mask.
+__device__ __forceinline__ unsigned long long mf_cells_allow_strip(const unsigned long long* mask, int64_t first, int64_t end, int lane) {
+    return mask && first + lane < end ? mask[first + lane] : 0ull;
+}
+// the word lane `at` of the strip holds; `at` wave-uniform in [0, 64)
+__device__ __forceinline__ unsigned long long mf_cells_strip_word(unsigned long long strip, int at) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)strip, at);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(strip >> 32), at);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ bool mf_cells_allowed(unsigned long long word, int lane) { return (word >> lane) & 1ull; }
 
 // the packed entry of a key that is there (a kernel writes MF_PACKED_NONE from its own branch where there is none)
 __device__ __forceinline__ long long mf_cells_entry(unsigned long long key) {

@@ -18,6 +18,8 @@
 //     workgroup writes all k entries of its list, "none" for a probe outside [0, C), an empty cell or an empty slice.
 //     The exclusion look-up, the packed entry, the slice plan and the export's checks are mf_cells.h's, shared with
 //     mf_pq.hip; the scoring and the selection are this kernel's own.
+//   * ivf_scan_allow_kernel: the same kernel text (mf_ivf_scan.inc) reading an allow bitmap, one 64-bit word per 64-row block
+//     (mf_filter_cell_bits): a row whose bit is clear has key 0, a block whose word is 0 is skipped -- mf_ivf_scan_allow.
 //   * ivf_cell_mean_kernel: the k-means update of the build -- a cell's rows added in a given order by one thread per
 //     dimension (no float atomics: the same bits every run), then the mean and its L2 normalisation.
 #include "mf_cells.h"
@@ -39,96 +41,20 @@ struct IvfParams {
     const int64_t *excl_off, *excl_idx;     // nullable
     int64_t idx_base;
     long long* out;             // [nprobe * S][Q][k] packed entries (mf_topk_io.h)
+    MfCellsAllow allow;         // the ALLOW kernels' bitmap (mf_cells.h); the others never look at it
 };
 
-template <int D>
-__global__ __launch_bounds__(64 * MF_CELLS_NW) void ivf_scan_kernel(IvfParams p) {
-    constexpr int CPR = D / 4;
-    constexpr int HALF = CPR > 32 ? 32 : CPR;                  // chunks held in registers at once
-    __shared__ unsigned long long buf[MF_CELLS_NW][64 + IVF_PEND];  // per wave: its best keys so far [0, 64), then the waiting ones
-    __shared__ unsigned long long win[MF_CELLS_NW][64], sorted[MF_CELLS_NW][64];
-    __shared__ unsigned long long all[MF_CELLS_NW * 64];
-    const int lane = mf_lane(), wave = mf_wave_id();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    // blockIdx.x = (q * nprobe + probe) * S + slice: everything here is workgroup-uniform (mf_pq.hip has the same lines: mf_cells.h)
-    const int64_t wg = blockIdx.x;
-    const int slice = (int)(wg % p.S);
-    const int probe = (int)((wg / p.S) % p.nprobe);
-    const int64_t q = wg / ((int64_t)p.S * p.nprobe);
-    const int64_t cell = p.probes[q * p.nprobe + probe];
-    int64_t b0 = 0, b1 = 0;
-    if (cell >= 0 && cell < p.C) {
-        const int64_t c0 = p.cell_blk[cell], nb = p.cell_blk[cell + 1] - c0;
-        b0 = c0 + nb * slice / p.S;
-        b1 = c0 + nb * (slice + 1) / p.S;
-    }
-    mf_const_f32 qc = (mf_const_f32)p.q + (size_t)q * D;
-    int64_t e0 = 0, e1 = 0;
-    if (p.excl_off) {
-        e0 = p.excl_off[q];
-        e1 = p.excl_off[q + 1];
-    }
-    unsigned long long* mine = buf[wave];
-#pragma unroll
-    for (int j = 0; j < (64 + IVF_PEND) / 64; ++j) mine[lane + 64 * j] = 0ull;
-    unsigned long long tau = 0ull;             // the wave's k-th best key once it holds k: only a larger key matters
-    int pend = 0;
-    // the k best of the wave's list and what waits behind it, in descending order at the front; the rest cleared
-    auto settle = [&]() {
-        mf_row_topk_sync<true>();
-        const int m = mf_row_topk<(64 + IVF_PEND) / 64, true>(mine, 64 + IVF_PEND, p.k, win[wave], sorted[wave]);
-        const unsigned long long keep = lane < m ? sorted[wave][lane] : 0ull;
-        tau = m >= p.k ? sorted[wave][p.k - 1] : 0ull;
-        mf_row_topk_sync<true>();
-#pragma unroll
-        for (int j = 0; j < (64 + IVF_PEND) / 64; ++j) mine[lane + 64 * j] = j == 0 ? keep : 0ull;
-        pend = 0;
-        mf_row_topk_sync<true>();
-    };
-
-    for (int64_t blk = b0 + wave; blk < b1; blk += MF_CELLS_NW) {
-        const f32x4* src = reinterpret_cast<const f32x4*>(p.blocked) + blk * (int64_t)CPR * 64 + lane;
-        const int64_t orig = p.row_of[blk * 64 + lane];
-        f32x4 rc[HALF];
-        float acc = 0.f;
-#pragma unroll
-        for (int h0 = 0; h0 < CPR; h0 += HALF) {
-#pragma unroll
-            for (int j = 0; j < HALF; ++j) rc[j] = src[(int64_t)(h0 + j) * 64];
-#pragma unroll
-            for (int g = 0; g < HALF / 2; ++g) {
-                const f32x4 a = rc[2 * g], b = rc[2 * g + 1];
-                mf_const_f32 qv = qc + 4 * (h0 + 2 * g);         // wave-uniform address: scalar loads
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {                      // k order of mf_dot_chain
-                    acc = __builtin_fmaf(a[t], qv[t], acc);
-                    acc = __builtin_fmaf(b[t], qv[4 + t], acc);
-                }
-            }
-        }
-        const unsigned grow = (unsigned)(p.idx_base + orig);       // the GLOBAL row: ties break by it whatever the permutation
-        const unsigned long long key = orig >= 0 ? mf_key_retrieval(acc, grow) : 0ull;
-        bool pass = key > tau;
-        if (p.excl_off) pass = mf_cells_admit(pass, grow, p.excl_idx, e0, e1, lane);
-        const unsigned long long bal = __ballot(pass);
-        if (bal) {
-            if (pass) mine[64 + pend + __popcll(bal & below)] = key;
-            pend += __popcll(bal);
-            if (pend > IVF_PEND - 64) settle();                    // no room for another block's 64
-        }
-    }
-    if (pend > 0) settle();                                        // (else the front is in order already: zeros, or the last settle)
-    mf_row_topk_sync<true>();
-    all[wave * 64 + lane] = mine[lane];
-    __syncthreads();
-    if (wave != 0) return;
-    const int m = mf_row_topk<MF_CELLS_NW, true>(all, MF_CELLS_NW * 64, p.k, win[0], sorted[0]);
-    if (lane < p.k) {
-        const long long v = lane < m ? mf_cells_entry(sorted[0][lane]) : MF_PACKED_NONE;
-        const int64_t g = (int64_t)probe * p.S + slice;
-        p.out[(g * p.Q + q) * p.k + lane] = v;
-    }
-}
+// The scan kernel in its two forms (mf_ivf_scan.inc): as it was, and reading the allow bitmap of mf_ivf_scan_allow.
+#define MF_SCAN_KERNEL ivf_scan_kernel
+#define MF_SCAN_ALLOW false
+#include "mf_ivf_scan.inc"
+#undef MF_SCAN_KERNEL
+#undef MF_SCAN_ALLOW
+#define MF_SCAN_KERNEL ivf_scan_allow_kernel
+#define MF_SCAN_ALLOW true
+#include "mf_ivf_scan.inc"
+#undef MF_SCAN_KERNEL
+#undef MF_SCAN_ALLOW
 
 // ------------------------------------------------------------------ the plan ----
 // (the rule: mf_cells_slices)
@@ -140,20 +66,45 @@ extern "C" size_t mf_ivf_ws_bytes(int64_t Q, int nprobe, int k, int64_t max_cell
     return mf_cells_ws_bytes(IVF_LISTS, Q, nprobe, k, max_cell_blocks);
 }
 
+// Both exports: the scan's checks in the order their callers rely on, then -- with a bitmap -- the bitmap's (mf_cells_check_allow).
+static int ivf_scan_run(const char* who, const float* q, int64_t Q, const float* blocked, const int64_t* cell_blk, const int64_t* row_of,
+                        int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
+                        const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, bool with_allow, const uint64_t* allow,
+                        int64_t n_masks, const int64_t* allow_of, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    if (const int rc = mf_cells_check_shape(who, IVF_LISTS, q && blocked && cell_blk && row_of && probes && ws, Q, Npad, N, C, d, max_cell_blocks,
+                                            nprobe, k, S))
+        return rc;
+    if (const int rc = mf_cells_check_lists(who, IVF_LISTS, Q, Npad, N, max_cell_blocks, nprobe, k, S, excl_off, excl_idx, idx_base, ws_bytes))
+        return rc;
+    if (with_allow)
+        if (const int rc = mf_cells_check_allow(who, allow, n_masks, allow_of, Npad)) return rc;
+    const int64_t G = (int64_t)nprobe * S;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    IvfParams p{blocked, q, cell_blk, row_of, probes, Q, C, nprobe, S, k, excl_off, excl_idx, idx_base, static_cast<long long*>(ws),
+                {reinterpret_cast<const unsigned long long*>(allow), allow_of, n_masks, Npad / 64}};
+    const dim3 grid((unsigned)(Q * G));
+    if (with_allow) {
+        MF_DISPATCH_D(d, { MF_TIMED("ivf_scan_allow", s, { ivf_scan_allow_kernel<D><<<grid, 64 * MF_CELLS_NW, 0, s>>>(p); }); });
+    } else {
+        MF_DISPATCH_D(d, { MF_TIMED("ivf_scan", s, { ivf_scan_kernel<D><<<grid, 64 * MF_CELLS_NW, 0, s>>>(p); }); });
+    }
+    return mf_check_launch(who);
+}
+
 extern "C" int mf_ivf_scan(const float* q, int64_t Q, const float* blocked, const int64_t* cell_blk, const int64_t* row_of, int64_t Npad,
                            int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
                            const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
                            mf_stream_t stream) {
-    if (const int rc = mf_cells_check_shape("mf_ivf_scan", IVF_LISTS, q && blocked && cell_blk && row_of && probes && ws, Q, Npad, N, C, d,
-                                            max_cell_blocks, nprobe, k, S))
-        return rc;
-    if (const int rc = mf_cells_check_lists("mf_ivf_scan", IVF_LISTS, Q, Npad, N, max_cell_blocks, nprobe, k, S, excl_off, excl_idx, idx_base, ws_bytes))
-        return rc;
-    const int64_t G = (int64_t)nprobe * S;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    IvfParams p{blocked, q, cell_blk, row_of, probes, Q, C, nprobe, S, k, excl_off, excl_idx, idx_base, static_cast<long long*>(ws)};
-    MF_DISPATCH_D(d, { MF_TIMED("ivf_scan", s, { ivf_scan_kernel<D><<<dim3((unsigned)(Q * G)), 64 * MF_CELLS_NW, 0, s>>>(p); }); });
-    return mf_check_launch("mf_ivf_scan");
+    return ivf_scan_run("mf_ivf_scan", q, Q, blocked, cell_blk, row_of, Npad, N, C, d, max_cell_blocks, probes, nprobe, k, S, excl_off, excl_idx,
+                        idx_base, false, nullptr, 0, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int mf_ivf_scan_allow(const float* q, int64_t Q, const float* blocked, const int64_t* cell_blk, const int64_t* row_of, int64_t Npad,
+                                 int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
+                                 const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, const uint64_t* allow, int64_t n_masks,
+                                 const int64_t* allow_of, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    return ivf_scan_run("mf_ivf_scan_allow", q, Q, blocked, cell_blk, row_of, Npad, N, C, d, max_cell_blocks, probes, nprobe, k, S, excl_off,
+                        excl_idx, idx_base, true, allow, n_masks, allow_of, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------- k-means update ----

@@ -30,6 +30,8 @@
 //     might not fit.  Every workgroup writes all R entries of its ordered list: [nprobe * S][Q][R] packed, the form
 //     mf_topk_merge_packed_deep takes.  The exclusion look-up, the packed entry, the slice plan and the export's checks
 //     are mf_cells.h's, shared with mf_ivf.hip; the tables and the buffer are this kernel's own.
+//   * pq_scan_allow_kernel: the same kernel text (mf_pq_scan.inc) reading an allow bitmap, one 64-bit word per 64-row block
+//     (mf_filter_cell_bits): a row whose bit is clear has key 0 before it meets the bound -- mf_pq_scan_allow.
 //   * pq_refine_kernel: a workgroup per query, a thread per merged candidate: the chain on the original row, then the
 //     top_k <= 64 by mf_row_topk (as the join of ivf_scan_kernel), stored with the standard tail.
 #include "mf_cells.h"
@@ -183,6 +185,7 @@ struct PqScanParams {
     const int64_t *excl_off, *excl_idx;     // nullable
     int64_t idx_base;
     long long* out;             // [nprobe * S][Q][R] packed entries (mf_topk_io.h) of the approximate scores
+    MfCellsAllow allow;         // the ALLOW kernels' bitmap (mf_cells.h); the others never look at it
 };
 
 // buf[0, n) in descending order, n a power of two <= PQ_BUF; every thread of the workgroup calls it
@@ -204,107 +207,17 @@ __device__ __forceinline__ void pq_sort_desc(unsigned long long* buf, int n) {
     }
 }
 
-template <int M, int DSUB>
-__global__ __launch_bounds__(PQ_THREADS) void pq_scan_kernel(PqScanParams p) {
-    constexpr int D = M * DSUB;
-    constexpr int U = M < 4 ? M : 4;           // code bytes per unit
-    constexpr int NU = M / U;
-    __shared__ float lut[M * 256];
-    __shared__ unsigned long long buf[PQ_BUF];
-    __shared__ int cnt[MF_CELLS_NW];
-    const int tid = threadIdx.x, lane = mf_lane(), wave = mf_wave_id();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    // blockIdx.x = (q * nprobe + probe) * S + slice: everything here is workgroup-uniform (mf_ivf.hip has the same lines: mf_cells.h)
-    const int64_t wg = blockIdx.x;
-    const int slice = (int)(wg % p.S);
-    const int probe = (int)((wg / p.S) % p.nprobe);
-    const int64_t q = wg / ((int64_t)p.S * p.nprobe);
-    const int64_t cell = p.probes[q * p.nprobe + probe];
-    const float base = p.probe_scores[q * p.nprobe + probe];
-    int64_t b0 = 0, b1 = 0;
-    if (cell >= 0 && cell < p.C) {
-        const int64_t c0 = p.cell_blk[cell], nb = p.cell_blk[cell + 1] - c0;
-        b0 = c0 + nb * slice / p.S;
-        b1 = c0 + nb * (slice + 1) / p.S;
-    }
-    int64_t e0 = 0, e1 = 0;
-    if (p.excl_off) {
-        e0 = p.excl_off[q];
-        e1 = p.excl_off[q + 1];
-    }
-    for (int i = tid; i < PQ_BUF; i += PQ_THREADS) buf[i] = 0ull;
-    if (b0 < b1) {                                                   // the query's tables: thread = codeword
-        mf_const_f32 qc = (mf_const_f32)p.q + (size_t)q * D;
-#pragma unroll 2                                                   // (the query's sub-vectors sit in scalar registers: four at dsub = 16 spill them)
-        for (int m = 0; m < M; ++m) {
-            float b[DSUB];
-            pq_load_sub<DSUB>(b, p.codebooks + ((size_t)m * 256 + tid) * DSUB);
-            lut[m * 256 + tid] = pq_chain<DSUB>(qc + m * DSUB, b);
-        }
-    }
-    __syncthreads();
-    unsigned long long tau = 0ull;             // the R-th best key once the buffer holds R: only a larger key matters
-    int pend = 0;                              // keys waiting behind the kept ones (workgroup-uniform)
-    // the R best of the kept and the waiting keys in descending order at the front, the rest cleared
-    auto settle = [&]() {
-        pq_sort_desc(buf, pend <= PQ_BUF / 2 - PQ_MAX_R ? PQ_BUF / 2 : PQ_BUF);
-        tau = buf[p.R - 1];
-        __syncthreads();
-        for (int i = p.R + tid; i < PQ_BUF; i += PQ_THREADS) buf[i] = 0ull;
-        pend = 0;
-        __syncthreads();
-    };
-
-    for (int64_t blk0 = b0; blk0 < b1; blk0 += MF_CELLS_NW) {         // (uniform trip count: barriers inside)
-        const int64_t blk = blk0 + wave;
-        unsigned long long key = 0ull;
-        unsigned grow = 0u;
-        if (blk < b1) {
-            const int64_t orig = p.row_of[blk * 64 + lane];
-            float acc = base;
-            if constexpr (U == 4) {
-                const unsigned* src = reinterpret_cast<const unsigned*>(p.codes) + blk * (int64_t)NU * 64 + lane;
-                unsigned w[NU];
-#pragma unroll
-                for (int u = 0; u < NU; ++u) w[u] = src[u * 64];
-#pragma unroll
-                for (int u = 0; u < NU; ++u) {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) acc = acc + lut[(4 * u + b) * 256 + ((w[u] >> (8 * b)) & 255u)];
-                }
-            } else {
-                const unsigned w = reinterpret_cast<const unsigned short*>(p.codes)[blk * 64 + lane];
-                acc = acc + lut[w & 255u];
-                acc = acc + lut[256 + (w >> 8)];
-            }
-            grow = (unsigned)(p.idx_base + orig);                    // the GLOBAL row: ties break by it
-            key = orig >= 0 ? mf_key_retrieval(acc, grow) : 0ull;
-        }
-        bool pass = key > tau;
-        if (p.excl_off) pass = mf_cells_admit(pass, grow, p.excl_idx, e0, e1, lane);
-        const unsigned long long bal = __ballot(pass);
-        if (lane == 0) cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < MF_CELLS_NW; ++w) {
-            const int c = cnt[w];
-            before += w < wave ? c : 0;
-            total += c;
-        }
-        if (pass) buf[PQ_MAX_R + pend + before + __popcll(bal & below)] = key;
-        pend += total;
-        __syncthreads();
-        if (pend > PQ_BUF - PQ_MAX_R - PQ_THREADS) settle();         // no room for another pass's 256
-    }
-    if (pend > 0) settle();                                          // (else the front is in order already: zeros, or the last settle)
-    if (tid < p.R) {
-        const unsigned long long key = buf[tid];
-        const long long v = key != 0ull ? mf_cells_entry(key) : MF_PACKED_NONE;
-        const int64_t g = (int64_t)probe * p.S + slice;
-        p.out[(g * p.Q + q) * p.R + tid] = v;
-    }
-}
+// The scan kernel in its two forms (mf_pq_scan.inc): as it was, and reading the allow bitmap of mf_pq_scan_allow.
+#define MF_SCAN_KERNEL pq_scan_kernel
+#define MF_SCAN_ALLOW false
+#include "mf_pq_scan.inc"
+#undef MF_SCAN_KERNEL
+#undef MF_SCAN_ALLOW
+#define MF_SCAN_KERNEL pq_scan_allow_kernel
+#define MF_SCAN_ALLOW true
+#include "mf_pq_scan.inc"
+#undef MF_SCAN_KERNEL
+#undef MF_SCAN_ALLOW
 
 // ------------------------------------------------------------------ the plan ----
 // (the rule: mf_cells_slices, with the candidate depth R and the key budget of the deep merge)
@@ -316,23 +229,49 @@ extern "C" size_t mf_pq_ws_bytes(int64_t Q, int nprobe, int R, int64_t max_cell_
     return mf_cells_ws_bytes(PQ_LISTS, Q, nprobe, R, max_cell_blocks);
 }
 
+// Both exports: the scan's checks in the order their callers rely on, then -- with a bitmap -- the bitmap's (mf_cells_check_allow).
+static int pq_scan_run(const char* who, const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+                       const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes,
+                       const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base,
+                       bool with_allow, const uint64_t* allow, int64_t n_masks, const int64_t* allow_of, void* ws, size_t ws_bytes,
+                       mf_stream_t stream) {
+    const bool pointers = q && codes && codebooks && cell_blk && row_of && probes && probe_scores && ws;
+    if (const int rc = mf_cells_check_shape(who, PQ_LISTS, pointers, Q, Npad, N, C, d, max_cell_blocks, nprobe, R, S)) return rc;
+    if (!pq_dsub_ok(dsub) || d / dsub > PQ_MAX_M)
+        return mf_set_error(MF_ENOTSUP, "%s: sub-vector length %d not in {4,8,16} or more than %d sub-vectors", who, dsub, PQ_MAX_M);
+    if (const int rc = mf_cells_check_lists(who, PQ_LISTS, Q, Npad, N, max_cell_blocks, nprobe, R, S, excl_off, excl_idx, idx_base, ws_bytes))
+        return rc;
+    if (with_allow)
+        if (const int rc = mf_cells_check_allow(who, allow, n_masks, allow_of, Npad)) return rc;
+    const int64_t G = (int64_t)nprobe * S;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PqScanParams p{q, codebooks, static_cast<const unsigned char*>(codes), cell_blk, row_of, probes, probe_scores, Q, C, nprobe, S, R,
+                   excl_off, excl_idx, idx_base, static_cast<long long*>(ws),
+                   {reinterpret_cast<const unsigned long long*>(allow), allow_of, n_masks, Npad / 64}};
+    const dim3 grid((unsigned)(Q * G));
+    if (with_allow) {
+        PQ_DISPATCH(d, dsub, { MF_TIMED("pq_scan_allow", s, { pq_scan_allow_kernel<M, DSUB><<<grid, PQ_THREADS, 0, s>>>(p); }); });
+    } else {
+        PQ_DISPATCH(d, dsub, { MF_TIMED("pq_scan", s, { pq_scan_kernel<M, DSUB><<<grid, PQ_THREADS, 0, s>>>(p); }); });
+    }
+    return mf_check_launch(who);
+}
+
 extern "C" int mf_pq_scan(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
                           const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes,
                           const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off, const int64_t* excl_idx,
                           int64_t idx_base, void* ws, size_t ws_bytes, mf_stream_t stream) {
-    const bool pointers = q && codes && codebooks && cell_blk && row_of && probes && probe_scores && ws;
-    if (const int rc = mf_cells_check_shape("mf_pq_scan", PQ_LISTS, pointers, Q, Npad, N, C, d, max_cell_blocks, nprobe, R, S)) return rc;
-    if (!pq_dsub_ok(dsub) || d / dsub > PQ_MAX_M)
-        return mf_set_error(MF_ENOTSUP, "mf_pq_scan: sub-vector length %d not in {4,8,16} or more than %d sub-vectors", dsub, PQ_MAX_M);
-    if (const int rc = mf_cells_check_lists("mf_pq_scan", PQ_LISTS, Q, Npad, N, max_cell_blocks, nprobe, R, S, excl_off, excl_idx, idx_base, ws_bytes))
-        return rc;
-    const int64_t G = (int64_t)nprobe * S;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PqScanParams p{q, codebooks, static_cast<const unsigned char*>(codes), cell_blk, row_of, probes, probe_scores, Q, C, nprobe, S, R,
-                   excl_off, excl_idx, idx_base, static_cast<long long*>(ws)};
-    const dim3 grid((unsigned)(Q * G));
-    PQ_DISPATCH(d, dsub, { MF_TIMED("pq_scan", s, { pq_scan_kernel<M, DSUB><<<grid, PQ_THREADS, 0, s>>>(p); }); });
-    return mf_check_launch("mf_pq_scan");
+    return pq_scan_run("mf_pq_scan", q, Q, codes, codebooks, dsub, cell_blk, row_of, Npad, N, C, d, max_cell_blocks, probes, probe_scores, nprobe,
+                       R, S, excl_off, excl_idx, idx_base, false, nullptr, 0, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int mf_pq_scan_allow(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+                                const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks,
+                                const int64_t* probes, const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off,
+                                const int64_t* excl_idx, int64_t idx_base, const uint64_t* allow, int64_t n_masks, const int64_t* allow_of,
+                                void* ws, size_t ws_bytes, mf_stream_t stream) {
+    return pq_scan_run("mf_pq_scan_allow", q, Q, codes, codebooks, dsub, cell_blk, row_of, Npad, N, C, d, max_cell_blocks, probes, probe_scores,
+                       nprobe, R, S, excl_off, excl_idx, idx_base, true, allow, n_masks, allow_of, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------- refine ----

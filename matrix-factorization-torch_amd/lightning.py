@@ -83,12 +83,16 @@ class MatrixFactorizationLitConfig(models.ModelConfig):
     index_seed: int = 0
     num_sub_vectors: int | None = None
     refine_factor: int = 4
+    # how recommend*(where=...) filters: "view" = a cached copy of the admissible rows (a quantised index refuses it), "mask" = an
+    # allow bitmap the cell scans read in place (partitioned and quantised indexes)
+    filter_mode: str = "view"
 
     @pydantic.model_validator(mode="after")
     def _index_fields(self):
         if self.index_type not in ItemProcessor.INDEX_TYPES:
             msg = f"index_type must be 'exact', 'partitioned' or 'quantized': {self.index_type!r}"
             raise ValueError(msg)
+        ItemProcessor.check_filter_mode(self.filter_mode, self.index_type)
         if self.num_sub_vectors is not None and self.num_sub_vectors < 1:
             msg = f"num_sub_vectors must be None (the stored width // 8) or at least 1: {self.num_sub_vectors}"
             raise ValueError(msg)
@@ -306,7 +310,8 @@ class MatrixFactorizationLitModule(_Base):
     def _item_processor(self, item_ids=None) -> ItemProcessor:
         cfg = self.config
         return ItemProcessor(item_ids, index_type=cfg.index_type, num_partitions=cfg.num_partitions, num_probes=cfg.num_probes,
-                             index_seed=cfg.index_seed, num_sub_vectors=cfg.num_sub_vectors, refine_factor=cfg.refine_factor)
+                             index_seed=cfg.index_seed, num_sub_vectors=cfg.num_sub_vectors, refine_factor=cfg.refine_factor,
+                             filter_mode=cfg.filter_mode)
 
     # ------------------------------------------------------------- save / load (f-3) ---
     def save(self, path) -> None:

@@ -457,6 +457,21 @@ def partition_layout(assign: torch.Tensor, num_partitions: int) -> tuple[torch.T
     return perm, cell_blk, row_of
 
 
+class CellMask:
+    """Allow bitmaps over a partitioned index's cell order (``PartitionedIndex.cell_mask``): ``words``, ``int64 [F, Npad // 64]`` on
+    the device -- the bit patterns of ``F`` masks' 64-bit words, bit ``lane`` of word ``blk`` set iff the row at cell-ordered
+    position ``blk * 64 + lane`` is admissible (``mf_filter_cell_bits``) -- and ``row_of``, the layout they were built for: a
+    search takes a mask only on the index whose ``row_of`` is that very tensor, so a mask from before ``rebuild()`` is refused.
+    ``Npad / 8`` bytes per mask, where a view (``filtered``) copies its rows."""
+
+    def __init__(self, words: torch.Tensor, row_of: torch.Tensor) -> None:
+        self.words, self.row_of = words, row_of
+
+    @property
+    def num_masks(self) -> int:
+        return self.words.shape[0]
+
+
 class PartitionedIndex(ItemIndex):
     """An ``ItemIndex`` that can also search like the reference's inverted-file index (``get_index`` builds ``num_partitions``
     cells, ``search`` visits ``num_probes = 8`` of them: data/lightning.py:203, 222-229, 250-259): the catalog is kept a second
@@ -542,10 +557,92 @@ class PartitionedIndex(ItemIndex):
         self.coarse = ItemIndex(self.centroids)
         self._cells = None
         self._views.clear()                              # (a view keeps the cells of its build)
+        self._masks: dict = {}                           # TagFilter -> CellMask of these cells (cell_mask)
 
     def _sub_index(self, embeddings: torch.Tensor, rows: torch.Tensor) -> "PartitionedIndex":
         """The view's index keeps the cells: the same centroids, every gathered row in the cell it had -- so the same probes."""
         return PartitionedIndex.from_assignment(embeddings, self.centroids, self.assign[rows], num_probes=self.num_probes)
+
+    def set_tags(self, tags: torch.Tensor) -> None:
+        """The parent's; the cached masks of ``cell_mask`` were evaluated on the old tags and go with the views."""
+        super().set_tags(tags)
+        self._masks.clear()
+
+    def cell_mask(self, where, *, cache: bool = True) -> CellMask:
+        """The allow bitmap(s) of ``where`` over this index's cells, for ``search(allow=...)``: a ``TagFilter`` over ``tags``, a
+        ``bool [num_items]`` tensor (the same kernel with the mask as the tag word and ``all_of = 1``), or a sequence of these
+        (``F`` masks in one tensor, one ``mf_filter_cell_bits`` launch each; a search names each query's mask by ``allow_of``).
+        No host read and no copy of rows: ``Npad / 8`` bytes per mask.  The mask of a single ``TagFilter`` is kept per index
+        (``cache=False``: neither looked up nor kept) until ``set_tags()``, ``rebuild()`` or a new assignment -- and, unlike a
+        view, through ``refresh()``: a mask depends on the tags and the cells, not on the rows' values."""
+        if isinstance(where, CellMask):
+            return where
+        single = not _is_filter_sequence(where)
+        filters = [where] if single else list(where)
+        if not filters:
+            msg = "a sequence of filters must not be empty"
+            raise ValueError(msg)
+        n, dev = self.num_items, self.embeddings.device
+        for f in filters:
+            if isinstance(f, TagFilter):
+                if self.tags is None:
+                    msg = "a TagFilter needs the rows' tags: call set_tags first"
+                    raise ValueError(msg)
+            elif not (isinstance(f, torch.Tensor) and f.dtype == torch.bool and f.shape == (n,)):
+                msg = f"a filter should be a TagFilter or a bool tensor of shape ({n},): {f!r}"
+                raise ValueError(msg)
+        keyed = single and cache and isinstance(where, TagFilter)
+        if keyed and where in self._masks:
+            return self._masks[where]
+        lib = _lib.lib()
+        npad = self.row_of.numel()
+        words = torch.empty(len(filters), npad // 64, dtype=torch.int64, device=dev)
+        for i, f in enumerate(filters):
+            tag_words, f = (self.tags, f) if isinstance(f, TagFilter) else (f.to(dev).to(torch.int64), TagFilter(all_of=1))
+            _lib.check(lib.mf_filter_cell_bits(tag_words.data_ptr(), n, f.any_of, f.all_of, f.none_of, self.row_of.data_ptr(), npad,
+                                               words[i].data_ptr(), _lib.stream_ptr()))
+        mask = CellMask(words, self.row_of)
+        if keyed:
+            self._masks[where] = mask
+        return mask
+
+    def _allow_route(self, allow, allow_of, where, path: str, paths: tuple) -> None:
+        """What ``search`` can refuse about ``allow`` / ``allow_of`` before it has looked at the queries: nothing is launched."""
+        if allow is None:
+            if allow_of is not None:
+                msg = "allow_of names the masks of allow=: it needs one"
+                raise ValueError(msg)
+            return
+        if where is not None:
+            msg = "allow= and where= are two routes for one filter: give one of them"
+            raise ValueError(msg)
+        if path not in paths:
+            msg = f"allow= filters the cell scans in place (path in {paths}); the exact engines have no bitmap route: {path = }"
+            raise ValueError(msg)
+        if isinstance(allow, CellMask) and allow.row_of is not self.row_of:
+            msg = "this CellMask was built for another cell layout (before rebuild(), or on another index): build it again"
+            raise ValueError(msg)
+
+    def _allow_masks(self, allow, allow_of, nq: int):
+        """``allow`` / ``allow_of`` (``_allow_route`` has passed them) for ``nq`` checked queries -> ``(CellMask, allow_of int64 [Q]
+        on the device or None)``, ``(None, None)`` without ``allow``.  A mask given as a filter is built here, after every
+        refusal."""
+        if allow is None:
+            return None, None
+        if type(allow) is CellMask and allow_of is None and allow.words.shape[0] == 1:      # (the common call, kept short: it is timed
+            return allow, None                                                               #  beside the unfiltered search)
+        num_masks = allow.num_masks if isinstance(allow, CellMask) else len(allow) if _is_filter_sequence(allow) else 1
+        if allow_of is None:
+            if num_masks != 1:
+                msg = f"{num_masks} masks need allow_of: one mask number per query"
+                raise ValueError(msg)
+        else:
+            allow_of = torch.as_tensor(allow_of)
+            if allow_of.dtype != torch.int64 or allow_of.shape != (nq,):
+                msg = f"allow_of should be an int64 vector with one mask number per query ({nq}): {allow_of.dtype}, {tuple(allow_of.shape)}"
+                raise ValueError(msg)
+            allow_of = allow_of.to(self.embeddings.device).contiguous()
+        return self.cell_mask(allow), allow_of
 
     def cell_blocked(self) -> torch.Tensor:
         """The catalog ordered by cell (``row_of``; padding rows zero) in the blocked layout of ``mf_topk_small``
@@ -571,6 +668,7 @@ class PartitionedIndex(ItemIndex):
         """Run the build again on the rows as they are now (an index from ``from_assignment`` keeps its cells and only
         forgets the derived copies)."""
         self.refresh()
+        self._masks.clear()
         if self._build_args is not None:
             b = self._build_args
             self._install(*self._kmeans(b["num_partitions"], b["iters"], b["seed"]))
@@ -601,13 +699,18 @@ class PartitionedIndex(ItemIndex):
 
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, nprobe: int | None = None,
-               path: str = "cells", where=None) -> tuple[torch.Tensor, torch.Tensor]:
+               path: str = "cells", where=None, allow=None, allow_of=None) -> tuple[torch.Tensor, torch.Tensor]:
         """``ItemIndex.search``'s inputs and result -- shapes, dtypes, the -inf / -1 tail -- over the rows of the ``nprobe``
         cells (default ``num_probes``) whose centroids score best against each query (exact, lowest cell on ties).
         ``path="cells"``: three launches' worth of stages, none with a host read -- the cells (the exact engines on the centroid
         matrix), the scan (``mf_ivf_scan``), the merge (``mf_topk_merge_packed``).  ``path="exact"`` is the parent's search over
         the whole catalog ("auto"); any other path is passed to the parent as it is.  ``where``: as in the parent -- the view
-        keeps the cells, so the probes are the same and the result is this search's with the inadmissible rows excluded."""
+        keeps the cells, so the probes are the same and the result is this search's with the inadmissible rows excluded; for a
+        filter without the view's copy, its host read and its per-filter grouping, see ``allow``.  ``allow`` (``path="cells"``
+        only): a ``CellMask`` or anything ``cell_mask`` takes -- the scan filters in place (``mf_ivf_scan_allow``), the same
+        result bit for bit; with several masks ``allow_of`` (``int64 [Q]``, host or device) names each query's, and a number
+        outside ``[0, F)`` admits nothing for that query."""
+        self._allow_route(allow, allow_of, where, path, ("cells",))
         if where is not None:
             kw = {"nprobe": nprobe, "path": path}
             if _is_filter_sequence(where):
@@ -618,6 +721,7 @@ class PartitionedIndex(ItemIndex):
         top_k, nprobe = self._top_k(top_k, "partitioned"), self._nprobe(nprobe)
         q = self._queries(queries)
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        mask, allow_of = self._allow_masks(allow, allow_of, nq)
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
         _, probes = self.coarse.search(q, nprobe)
         lib = _lib.lib()
@@ -625,9 +729,13 @@ class PartitionedIndex(ItemIndex):
         rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
         ws = self._workspace(("cells", nq, nprobe, top_k), lib.mf_ivf_ws_bytes(nq, nprobe, top_k, self.max_cell_blocks))
         lists = self.plan(nq, top_k, nprobe)["lists"]
-        _lib.check(lib.mf_ivf_scan(q.data_ptr(), nq, self.cell_blocked().data_ptr(), self.cell_blk.data_ptr(), self.row_of.data_ptr(),
-                                   self.row_of.numel(), n, self.num_partitions, d, self.max_cell_blocks, probes.data_ptr(), nprobe, top_k, 0,
-                                   _lib.ptr(off), _lib.ptr(ids), self.idx_base, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        scan = (q.data_ptr(), nq, self.cell_blocked().data_ptr(), self.cell_blk.data_ptr(), self.row_of.data_ptr(), self.row_of.numel(), n,
+                self.num_partitions, d, self.max_cell_blocks, probes.data_ptr(), nprobe, top_k, 0, _lib.ptr(off), _lib.ptr(ids), self.idx_base)
+        if mask is None:
+            _lib.check(lib.mf_ivf_scan(*scan, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        else:
+            _lib.check(lib.mf_ivf_scan_allow(*scan, mask.words.data_ptr(), mask.num_masks, _lib.ptr(allow_of), ws.data_ptr(), ws.numel(),
+                                             _lib.stream_ptr()))
         _lib.check(lib.mf_topk_merge_packed(ws.data_ptr(), lists, nq, top_k, scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
         return scores, rows
 
@@ -792,13 +900,15 @@ class QuantizedIndex(PartitionedIndex):
 
     def candidates(self, queries: torch.Tensor, num_candidates: int, *, exclude: Sequence[Sequence[int]] | None = None,
                    exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None,
-                   nprobe: int | None = None, slices: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+                   nprobe: int | None = None, slices: int | None = None, allow=None,
+                   allow_of=None) -> tuple[torch.Tensor, torch.Tensor]:
         """``(approximate scores [Q, R] fp32, GLOBAL rows [Q, R] int64)``: the ``R = num_candidates`` (1..``MAX_CANDIDATES``)
         admissible rows of the probed cells that the quantiser ranks first -- approximate score descending, row ascending,
         the -inf / -1 tail --, what ``search`` refines.  Three stages, none with a host read: the cells, ``mf_pq_scan``,
         ``mf_topk_merge_packed_deep``.  ``slices``: into how many workgroups a probed cell is cut (None: the plan's number;
         1..the largest cell's blocks, ``nprobe * slices * R`` within the merge's ``MERGE_DEEP_MAX_KEYS``) -- the lists are the
-        same for every value."""
+        same for every value.  ``allow`` / ``allow_of``: as in ``search`` (``mf_pq_scan_allow``) -- the candidates of the same call
+        with every inadmissible row on every query's exclusion list."""
         r = int(num_candidates)
         if not 1 <= r <= self.MAX_CANDIDATES:
             msg = f"num_candidates must be in 1..{self.MAX_CANDIDATES}: {r = }"
@@ -809,10 +919,13 @@ class QuantizedIndex(PartitionedIndex):
                    f"{slices = }, {nprobe = }, {r = }")
             raise ValueError(msg)
         q = self._queries(queries)
+        self._allow_route(allow, allow_of, None, "pq", ("pq",))
+        mask, allow_of = self._allow_masks(allow, allow_of, q.shape[0])
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, q.shape[0], q.device)
-        return self._candidates(q, r, nprobe, off, ids, 0 if slices is None else int(slices))
+        return self._candidates(q, r, nprobe, off, ids, 0 if slices is None else int(slices), mask, allow_of)
 
-    def _candidates(self, q: torch.Tensor, r: int, nprobe: int, off, ids, slices: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    def _candidates(self, q: torch.Tensor, r: int, nprobe: int, off, ids, slices: int = 0, mask: CellMask | None = None,
+                    allow_of: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         base, probes = self.coarse.search(q, nprobe)
         lib = _lib.lib()
@@ -821,33 +934,44 @@ class QuantizedIndex(PartitionedIndex):
         ws = self._workspace(("pq", nq, nprobe, r, slices), max(lists * nq * r * 8, lib.mf_pq_ws_bytes(nq, nprobe, r, self.max_cell_blocks)))
         approx = torch.empty(nq, r, dtype=torch.float32, device=q.device)
         rows = torch.empty(nq, r, dtype=torch.int64, device=q.device)
-        _lib.check(lib.mf_pq_scan(q.data_ptr(), nq, self.codes().data_ptr(), self.codebooks.data_ptr(), self.dsub, self.cell_blk.data_ptr(),
-                                  self.row_of.data_ptr(), self.row_of.numel(), n, self.num_partitions, d, self.max_cell_blocks,
-                                  probes.data_ptr(), base.data_ptr(), nprobe, r, slices, _lib.ptr(off), _lib.ptr(ids), self.idx_base,
-                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        scan = (q.data_ptr(), nq, self.codes().data_ptr(), self.codebooks.data_ptr(), self.dsub, self.cell_blk.data_ptr(), self.row_of.data_ptr(),
+                self.row_of.numel(), n, self.num_partitions, d, self.max_cell_blocks, probes.data_ptr(), base.data_ptr(), nprobe, r, slices,
+                _lib.ptr(off), _lib.ptr(ids), self.idx_base)
+        if mask is None:
+            _lib.check(lib.mf_pq_scan(*scan, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        else:
+            _lib.check(lib.mf_pq_scan_allow(*scan, mask.words.data_ptr(), mask.num_masks, _lib.ptr(allow_of), ws.data_ptr(), ws.numel(),
+                                            _lib.stream_ptr()))
         _lib.check(lib.mf_topk_merge_packed_deep(ws.data_ptr(), lists, nq, r, approx.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
         return approx, rows
 
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, nprobe: int | None = None,
-               refine_factor: int | None = None, path: str = "pq", where=None) -> tuple[torch.Tensor, torch.Tensor]:
+               refine_factor: int | None = None, path: str = "pq", where=None, allow=None,
+               allow_of=None) -> tuple[torch.Tensor, torch.Tensor]:
         """``ItemIndex.search``'s inputs and result.  ``path="pq"``: the ``refine_factor * top_k`` (default: the index's
         factor; at most ``MAX_CANDIDATES``) best rows of the ``nprobe`` probed cells by the quantiser's approximate score,
         scored again with the chain on the original rows and ordered exactly -- four stages, none with a host read: the
         cells, the scan (``mf_pq_scan``), the merge (``mf_topk_merge_packed_deep``), the refine (``mf_pq_refine``); the
         cell-ordered fp32 copy is not built.  ``path="cells"`` and ``path="exact"`` (and the exact engines' names) are the
-        parent's.  ``where``: refused (``filtered``)."""
+        parent's.  ``where``: refused (``filtered``) -- the filter this index takes is ``allow``: a ``CellMask`` or anything
+        ``cell_mask`` takes (``allow_of``: each query's mask among several), on ``path="pq"`` (``mf_pq_scan_allow``: a row the
+        mask does not admit never becomes a candidate, so the refine only sees admitted rows) and on the parent's
+        ``path="cells"`` -- bit for bit the same search with the inadmissible rows on every query's exclusion list."""
+        self._allow_route(allow, allow_of, where, path, ("pq", "cells"))
         if where is not None:
             self.filtered(where)
         if path != "pq":
-            return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, nprobe=nprobe, path=path)
+            return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, nprobe=nprobe, path=path, allow=allow,
+                                  allow_of=allow_of)
         r = self._candidates_of(top_k, refine_factor)
         top_k = int(top_k)
         nprobe = self._nprobe(nprobe)
         q = self._queries(queries)
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
+        mask, allow_of = self._allow_masks(allow, allow_of, nq)
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
-        _, cand = self._candidates(q, r, nprobe, off, ids)
+        _, cand = self._candidates(q, r, nprobe, off, ids, 0, mask, allow_of)
         scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
         rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
         _lib.check(_lib.lib().mf_pq_refine(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, cand.data_ptr(), r, top_k, self.idx_base,
@@ -983,18 +1107,33 @@ class ItemProcessor:
     id_col: str = ITEM_ID_COL
 
     INDEX_TYPES = ("exact", "partitioned", "quantized")
+    FILTER_MODES = ("view", "mask")
+
+    @classmethod
+    def check_filter_mode(cls, filter_mode: str, index_type: str) -> None:
+        if filter_mode not in cls.FILTER_MODES:
+            msg = f"filter_mode must be 'view' or 'mask': {filter_mode!r}"
+            raise ValueError(msg)
+        if filter_mode == "mask" and index_type not in ("partitioned", "quantized"):
+            msg = f"filter_mode='mask' filters the cell scans: index_type must be 'partitioned' or 'quantized', not {index_type!r}"
+            raise ValueError(msg)
 
     def __init__(self, item_ids: Sequence[int] | torch.Tensor | None = None, *, index_type: str = "exact",
                  num_partitions: int | None = None, num_probes: int = 8, index_seed: int = 0, num_sub_vectors: int | None = None,
-                 refine_factor: int = 4) -> None:
+                 refine_factor: int = 4, filter_mode: str = "view") -> None:
         """``index_type="partitioned"``: ``get_index`` / ``set_index`` / ``append`` build a ``PartitionedIndex`` --
         ``num_partitions`` cells (None: the reference's default for the catalog's size), ``num_probes`` of them visited per
         query, k-means seeded with ``index_seed`` -- and ``search`` probes it.  ``index_type="quantized"``: a
         ``QuantizedIndex`` over the same cells -- the reference's ``num_sub_vectors`` one-byte codes per row (None: the stored
-        width // 8) and its ``refine_factor``: ``refine_factor * top_k`` candidates per query are scored exactly."""
+        width // 8) and its ``refine_factor``: ``refine_factor * top_k`` candidates per query are scored exactly.
+        ``filter_mode``: how ``search(where=...)`` filters -- "view": through the index's ``where=`` (a cached copy of the
+        admissible rows; a quantised index refuses it); "mask": through its ``allow=`` (an allow bitmap over the cells, no
+        copy; partitioned and quantised indexes only)."""
         if index_type not in self.INDEX_TYPES:
             msg = f"index_type must be 'exact', 'partitioned' or 'quantized': {index_type!r}"
             raise ValueError(msg)
+        self.check_filter_mode(filter_mode, index_type)
+        self.filter_mode = filter_mode
         if num_sub_vectors is not None and int(num_sub_vectors) < 1:
             msg = f"num_sub_vectors must be None (the stored width // 8) or at least 1: {num_sub_vectors = }"
             raise ValueError(msg)
@@ -1117,7 +1256,8 @@ class ItemProcessor:
 
     def search(self, embedding, exclude_item_ids: list[int] | None = None, top_k: int = TOP_K, where=None):
         """``where``: only items it admits are returned -- a ``TagFilter``, a ``bool [rows]`` allow-mask, or a dict of name
-        lists (``tag_filter``'s arguments); the reference's ``.where(filter, prefilter=True)``."""
+        lists (``tag_filter``'s arguments); the reference's ``.where(filter, prefilter=True)``.  It reaches the index as
+        ``where=`` or, with ``filter_mode="mask"``, as ``allow=``."""
         import pandas as pd
 
         if self.index is None:
@@ -1125,8 +1265,12 @@ class ItemProcessor:
             raise ValueError(msg)
         q = torch.as_tensor(np.asarray(embedding), dtype=torch.float32).reshape(1, -1).to(self.index.embeddings.device)
         rows = [self._row_of_id[i] for i in (exclude_item_ids or []) if i in self._row_of_id]
-        scores, idx = self.index.search(q, top_k, exclude=[rows]) if where is None else \
-            self.index.search(q, top_k, exclude=[rows], where=self._where(where))
+        if where is None:
+            scores, idx = self.index.search(q, top_k, exclude=[rows])
+        elif self.filter_mode == "mask":
+            scores, idx = self.index.search(q, top_k, exclude=[rows], allow=self._where(where))
+        else:
+            scores, idx = self.index.search(q, top_k, exclude=[rows], where=self._where(where))
         idx = idx[0].cpu()
         keep = idx >= 0
         idx = idx[keep]

@@ -11,7 +11,8 @@ of the product paths spills.
     python tools/kernel_resources.py [path/to/libmf_hip.so] --text-digest [--only=update_fused,update_rows]   # JSON
 
 ``--text-digest``: beside the figures, one sha256 of each kernel's disassembled instruction text -- to show that a refactor
-left the generated code of a kernel as it was (compare two builds' outputs).
+left the generated code of a kernel as it was (compare two builds' outputs).  ``--names-of=record.json`` keeps only the kernels
+an earlier record names: a branch that adds kernels beside the old ones gives a record to compare with the parent's as it is.
 """
 from __future__ import annotations
 
@@ -119,9 +120,10 @@ def main() -> None:
     if "--text-digest" in sys.argv:     # JSON: {kernel: {"text_sha256": ..., the resource figures}}, kernels whose name has one of --only=a,b,..
         lib = pathlib.Path(args[0]) if args else DEFAULT_LIB
         only = next((a.split("=", 1)[1].split(",") for a in sys.argv if a.startswith("--only=")), [""])
+        names = next((set(json.loads(pathlib.Path(a.split("=", 1)[1]).read_text())) for a in sys.argv if a.startswith("--names-of=")), None)
         res, dig = kernel_resources(lib), text_digests(lib)
         print(json.dumps({k: {"text_sha256": dig.get(k), **{f: v for f, v in r.items() if f != "max_flat_workgroup_size"}}
-                          for k, r in sorted(res.items()) if any(o in k for o in only)}, indent=1))
+                          for k, r in sorted(res.items()) if any(o in k for o in only) and (names is None or k in names)}, indent=1))
         return
     res = kernel_resources(pathlib.Path(args[0]) if args else DEFAULT_LIB)
     only_spills = "--spills" in sys.argv

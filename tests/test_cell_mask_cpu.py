@@ -148,6 +148,114 @@ def test_the_spec_on_hand_worked_rows():
     assert spec.extended_lists([[5], []], 2, ok, 100) == [[5, 105, 106], [105, 106]]
 
 
+# ------------------------------------------------------------------------------- the long cell and its strips ----
+GEOMETRIES = [(64, 8), (32, 16), (256, 4)]
+
+
+def _slice_bits(cell_blk, cell, S, i, words):  # noqa: N803
+    """The positions of the set bits of ``words`` inside slice ``i`` of ``S`` of ``cell``."""
+    c0, nb = int(cell_blk[cell]), int(cell_blk[cell + 1] - cell_blk[cell])
+    u = np.asarray(words, dtype=np.int64).view(np.uint64)
+    return {blk * 64 + lane for blk in range(c0 + nb * i // S, c0 + nb * (i + 1) // S) for lane in range(64) if int(u[blk]) >> lane & 1}
+
+
+def test_strip_walk_on_hand_worked_words():
+    # one cell of 70 blocks from block 2 on; bits at blocks 2 (first of strip 0), 65 (last of strip 0), 66 (first of strip 1), 71 (the last)
+    cell_blk = [0, 2, 72]
+    words = np.zeros(72, dtype=np.int64)
+    words[[2, 65, 66, 71]] = [0b1, -2**63, 0b110, 0b1000]
+    words[0] = -1                                                                   # another cell's: never seen
+    t = spec.strip_walk(cell_blk, 1, 1, 0, words)
+    assert t["seen"] == {2 * 64, 65 * 64 + 63, 66 * 64 + 1, 66 * 64 + 2, 71 * 64 + 3}
+    assert (t["passes"], t["rotations"], t["blocks_read"], t["blocks_skipped"], t["blocks_in_last_strip"]) == (18, 1, 4, 66, 6)
+    # passes 0, 15 (block 65), 16 (block 66) and 17 (block 71; two waves past the end) have a reader beside an idle wave
+    assert t["mixed_passes"] == 4 and t["passes_without_a_reader"] == 14
+    stale = spec.strip_walk(cell_blk, 1, 1, 0, words, rotate=False)                 # blocks 66 .. 71 read lanes 0 .. 5 of the first strip
+    assert stale["seen"] == {2 * 64, 65 * 64 + 63, 66 * 64} and stale["rotations"] == 0 and stale["passes"] == 18
+    # two slices of 35 blocks: no rotation, a word past b1 reads 0 even where the mask has one
+    t = spec.strip_walk(cell_blk, 1, 2, 0, words)
+    assert t["seen"] == {2 * 64} and (t["passes"], t["rotations"], t["blocks_in_last_strip"]) == (9, 0, 35)
+    t = spec.strip_walk(cell_blk, 1, 2, 1, words)
+    assert t["seen"] == {65 * 64 + 63, 66 * 64 + 1, 66 * 64 + 2, 71 * 64 + 3} and t["rotations"] == 0
+    full = np.full(72, -1, dtype=np.int64)
+    t = spec.strip_walk(cell_blk, 1, 1, 0, full)
+    assert len(t["seen"]) == 70 * 64 and min(t["seen"]) == 128 and (t["blocks_read"], t["mixed_passes"]) == (70, 1)
+
+
+@pytest.mark.parametrize("d,dsub", GEOMETRIES)
+def test_the_long_cell_case_is_what_the_gpu_tests_lean_on(d, dsub):
+    """tests/test_gpu_cell_mask_strips.py: a cell of 129 blocks that starts at block 1, probed by every query at nprobe = 1."""
+    c = spec.long_cell_case(d, dsub)
+    b = c.base
+    assert (b.items.shape, b.q.shape, b.idx_base, b.nprobe, b.exclude) == ((8440, d), (5, d), 30, 1, None) and c.m == d // dsub
+    cell_blk, row_of = spec.long_cell_layout(d)
+    assert cell_blk.tolist() == [0, 1, 130, 132, 134] and b.max_cell_blocks == 129
+    assert int((row_of[129 * 64: 130 * 64] >= 0).sum()) == 38 and (row_of[64: 129 * 64] >= 0).all()
+    assert (spec.ivf.probes(b.q, b.centroids, 1) == 1).all()
+    if d == 64:
+        many = spec.long_cell_queries(64, 1024)
+        assert many.shape == (1024, 64) and (spec.ivf.probes(many, b.centroids, 1) == 1).all()
+        assert spec.pq.plan_slices(1024, 1, 80, 129) == 1 and spec.pq.plan_slices(256, 1, 80, 129) == 4
+        # the scan itself: 33 passes, settles inside the loop
+        t = spec.pq.scan_trace(*c._args(), 80, None, b.idx_base)
+        assert t["passes"] == 33 and t["settles_in_loop"] >= 2
+
+
+def test_the_slicings_reach_the_rotation():
+    cell_blk, row_of = spec.long_cell_layout(64)
+    full = spec.words(np.ones(8440, bool), row_of)
+    t = spec.strip_walk(cell_blk, 1, 1, 0, full)
+    assert (t["passes"], t["rotations"], t["blocks_in_last_strip"], t["blocks_read"]) == (33, 2, 1, 129)
+    first, second = (spec.strip_walk(cell_blk, 1, 2, i, full) for i in (0, 1))
+    assert (first["blocks_read"], first["rotations"], first["blocks_in_last_strip"]) == (64, 0, 64)
+    assert (second["blocks_read"], second["rotations"], second["blocks_in_last_strip"]) == (65, 1, 1)
+    for i in range(3):
+        t = spec.strip_walk(cell_blk, 1, 3, i, full)
+        assert t["rotations"] == 0 and t["blocks_read"] == 43
+    # the largest slicings the GPU tests force: never more than three blocks a slice, one pass
+    for S in (129, 64):  # noqa: N806
+        assert all(spec.strip_walk(cell_blk, 1, S, i, full)["passes"] == 1 for i in range(S))
+
+
+@pytest.mark.parametrize("d", [64, 32, 256])
+def test_the_mask_families_reach_what_they_are_chosen_for(d):
+    cell_blk, row_of = spec.long_cell_layout(d)
+    assert list(spec.MASK_FAMILIES) == ["third_strip", "second_strip", "not_first_strip", "strip_edges", "two_bits", "alternate_blocks",
+                                        "sparse_blocks", "half"]
+    inside = lambda ok, j0, j1: int(ok[row_of[(1 + j0) * 64: (1 + j1) * 64].clip(0)][row_of[(1 + j0) * 64: (1 + j1) * 64] >= 0].sum())  # noqa: E731
+    for name in spec.MASK_FAMILIES:
+        ok = spec.family_ok(name, d)
+        assert ok.shape == (8440,) and 1 <= int(ok.sum()) <= 8440 - 1, name
+        small = np.concatenate([row_of[:64], row_of[130 * 64:]])
+        small = small[small >= 0]
+        assert 0 < int(ok[small].sum()) < small.size, name                          # about half of the three small cells
+        words = spec.words(ok, row_of)
+        for S in (1, 2, 3):  # noqa: N806
+            for i in range(S):
+                t = spec.strip_walk(cell_blk, 1, S, i, words)
+                assert t["seen"] == _slice_bits(cell_blk, 1, S, i, words), (name, S, i)
+                assert t["blocks_read"] + t["blocks_skipped"] == 129 * (i + 1) // S - 129 * i // S
+        one = spec.strip_walk(cell_blk, 1, 1, 0, words)
+        assert len(one["seen"]) == inside(ok, 0, 129), name
+        if name in ("third_strip", "second_strip", "not_first_strip", "strip_edges", "two_bits"):
+            # a kernel that never rotates sees other bits: at one slice, and in the second of two
+            assert spec.strip_walk(cell_blk, 1, 1, 0, words, rotate=False)["seen"] != one["seen"], name
+            assert spec.strip_walk(cell_blk, 1, 2, 1, words, rotate=False)["seen"] != spec.strip_walk(cell_blk, 1, 2, 1, words)["seen"], name
+    ok = {name: spec.family_ok(name, d) for name in spec.MASK_FAMILIES}
+    assert inside(ok["third_strip"], 0, 129) == inside(ok["third_strip"], 128, 129) == 38
+    assert inside(ok["second_strip"], 0, 129) == inside(ok["second_strip"], 64, 128) == 64 * 64
+    assert inside(ok["not_first_strip"], 0, 64) == 0 and inside(ok["not_first_strip"], 64, 129) == 64 * 64 + 38
+    assert inside(ok["strip_edges"], 0, 129) == 3 * 64 + 38 and inside(ok["strip_edges"], 63, 65) == 128 and inside(ok["strip_edges"], 127, 129) == 102
+    assert inside(ok["two_bits"], 0, 129) == 2
+    two = spec.words(ok["two_bits"], row_of)
+    assert int(two[1 + 64]) == -2**63 and int(two[1 + 128]) == 1 and int((two[1:130] != 0).sum()) == 2
+    alt = spec.strip_walk(cell_blk, 1, 1, 0, spec.words(ok["alternate_blocks"], row_of))
+    assert alt["mixed_passes"] == alt["passes"] == 33 and (alt["blocks_read"], alt["blocks_skipped"]) == (65, 64)
+    sparse = spec.strip_walk(cell_blk, 1, 1, 0, spec.words(ok["sparse_blocks"], row_of))
+    assert sparse["passes_without_a_reader"] >= 1 and sparse["mixed_passes"] >= 1 and sparse["blocks_read"] >= 10
+    assert 0.4 * 8230 < inside(ok["half"], 0, 129) < 0.6 * 8230
+
+
 # --------------------------------------------------------------------------------------------------- filter_mode ----
 def test_filter_mode_of_the_processor_and_the_config(mf):
     P = mf.retrieval.ItemProcessor

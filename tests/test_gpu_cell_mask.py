@@ -233,7 +233,8 @@ def test_the_scan_export_on_one_large_cell(mf):
 
 # ------------------------------------------------------------------------------------------------ the quantised index ----
 def _quantized(mf, d, m, n, nq, base=0):
-    """Seeded random codebooks; at n = 2500 cell 0 holds 2,100 rows (33 blocks) and three small cells follow, else 8 random cells."""
+    """Seeded random codebooks; at n = 2500 cell 0 holds 2,100 rows (33 blocks: one strip of mask words -- slices of 64, 65 and 129
+    blocks are in tests/test_gpu_cell_mask_strips.py) and three small cells follow, else 8 random cells."""
     items, q, lists, tags = _world(d, n, nq, base)
     gen = torch.Generator().manual_seed(d + m)
     if n >= 2500:
@@ -261,7 +262,9 @@ def test_quantised_candidates_and_search_with_a_mask(mf, d, m, n, nq):
         ok = _ok_of(where, tags)
         assert 1 <= int(ok.sum()) <= n - 1
         if n >= 2500 and what == "half":
-            assert int(ok[:2100].sum()) > 512                 # cell 0 at slices=1: the workgroup sorts mid-slice
+            # cell 0 at slices=1: the workgroup sorts mid-slice.  Its 33 blocks stay inside the first strip of mask words (64 blocks,
+            # from block 0 of the mask): the second strip and the rotation are tests/test_gpu_cell_mask_strips.py's
+            assert int(ok[:2100].sum()) > 512
         mask = index.cell_mask(where)
         for user in (None, lists):
             every = spec.extended_lists(user, nq, ok, base)

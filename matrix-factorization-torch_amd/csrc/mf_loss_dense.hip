@@ -499,6 +499,9 @@ struct BwdParams {
 #ifndef BWD_SPLIT_VPM
 #define BWD_SPLIT_VPM 7       // A/B knob: VALU / SALU instructions of the next tile's G' placed behind each MFMA of the split contraction
 #endif
+#ifndef BWD_SPLIT_DPG
+#define BWD_SPLIT_DPG 4       // A/B knob: memory instructions of the next stage per step (12 MFMAs) of the split contraction (12: all in the first)
+#endif
 template <int D, bool XU, int SPLIT = 0>
 struct BwdLds {
     using G = TileGeom<D>;
@@ -641,16 +644,17 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
             xb2 = xb * 1.44269504088896341f;
         }
     };
+    // a masked logit -> G' (masked entries are -inf: exp / step / sigmoid give exactly 0)
+    auto gmap = [&](float Lm) {
+        if (GMODE == G_EXP) return xc * __builtin_amdgcn_exp2f(__builtin_fmaf(Lm - xa, 1.44269504088896341f, xb2));
+        return xc * g_of(GMODE, (Lm - xa) + xb);
+    };
     // The block of tile `tile` -> the B operand of its contraction: G' (unless the stash holds it already), handed to dV,
     // weighted, transposed for dV; its elements are added to the lane's row sum `rs`
     auto gprime = [&](float (&Gv)[16], const float (&Wv)[16], int tile, float& rs) {
         if (XU || RECOMP) {
-            // masked logits -> G' (masked entries are -inf: exp / step / sigmoid give exactly 0)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                if (GMODE == G_EXP) Gv[e] = xc * __builtin_amdgcn_exp2f(__builtin_fmaf(Gv[e] - xa, 1.44269504088896341f, xb2));
-                else Gv[e] = xc * g_of(GMODE, (Gv[e] - xa) + xb);
-            }
+            for (int e = 0; e < 16; ++e) Gv[e] = gmap(Gv[e]);
             if (!CP && tile == xt) {    // only the diagonal tile holds the user's own positive
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
@@ -669,13 +673,9 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
         }
         if (!XU) {
             // block layout is (lane = user, register = item row): transpose to (lane = item, register = user row)
-            // (SPLIT: the next tile's DMA is in flight here -- stores the compiler sees would drain it, mf_stream.h)
             float* tr = reinterpret_cast<float*>(smem + L::TR) + wave * (32 * 32);
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                if (SPLIT) mf_lds_store_b32(&tr[mf_acc_row(e, h) * 32 + (c ^ mf_acc_row(e, h))], Gv[e]);
-                else tr[mf_acc_row(e, h) * 32 + (c ^ mf_acc_row(e, h))] = Gv[e];
-            }
+            for (int e = 0; e < 16; ++e) tr[mf_acc_row(e, h) * 32 + (c ^ mf_acc_row(e, h))] = Gv[e];
 #pragma unroll
             for (int e = 0; e < 16; ++e) Gv[e] = tr[c * 32 + (mf_acc_row(e, h) ^ c)];
         }
@@ -690,28 +690,90 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
         static_assert(L::RECOMP && SPREAD, "the split sweeps keep no G' stash");
         typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
         // G' in three bf16 pieces: g[s][q] is piece q of registers 8 s .. 8 s + 7, the B fragment of k-step s
-        auto split_g = [&](const float (&Gv)[16], mbf16x8 (&g)[2][3]) {
+        auto split_g = [&](const float (&Gv)[16], mbf16x8 (&g)[2][3], int s) {
+            u16x8 g3[3];
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                u16x8 g3[3];
+            for (int j = 0; j < 8; ++j) {
+                unsigned short o[3];
+                mbf_split3(Gv[8 * s + j], o);
+                g3[0][j] = o[0]; g3[1][j] = o[1]; g3[2][j] = o[2];
+            }
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    unsigned short o[3];
-                    mbf_split3(Gv[8 * s + j], o);
-                    g3[0][j] = o[0]; g3[1][j] = o[1]; g3[2][j] = o[2];
-                }
-#pragma unroll
-                for (int q = 0; q < 3; ++q) g[s][q] = __builtin_bit_cast(mbf16x8, g3[q]);
+            for (int q = 0; q < 3; ++q) g[s][q] = __builtin_bit_cast(mbf16x8, g3[q]);
+        };
+        // The memory instructions of a stage, in issue order: the four register loads of tile `tr`'s stash block (they come
+        // from HBM: the longest way), the four per-lane loads of its side inputs (dU under the column plan: the lane's 16 column
+        // weights; dV: its user's four coefficients), then the PPW image pieces of tile `ti` (not live: a dead scalar offset,
+        // the piece fetches nothing).
+        constexpr int NSIDE = XU ? (CP ? 4 : 0) : L::NCOEF;
+        constexpr int NMEM = 4 + NSIDE + L::PPW;
+        constexpr int DPG = BWD_SPLIT_DPG;
+        static_assert(NMEM == NDMA, "the stage of the split loops is the stage BwdLds counts");
+        static_assert(DPG >= 1 && DPG <= 12, "one to twelve memory instructions to a step");
+        static_assert(4 * DPG >= NMEM, "a stage's memory instructions must fit the four steps of the contraction");
+        // where a stage reads: the lane's 16 bytes of tile tr's stash block, its per-lane side inputs, the scalar offset of
+        // tile ti's image (dead: past the descriptor's end, + 5 KiB and a lane offset do not wrap) -- computed ahead of the
+        // contraction, so that no memory instruction inside it waits for address arithmetic
+        struct StageSrc {
+            const char* g;
+            const float* side;
+            unsigned img;
+        };
+        auto stage_src = [&](int ti, bool live, int tr) {
+            StageSrc a;
+            a.g = reinterpret_cast<const char*>(p.stash + block_of(tr) * 1024) + lane * 16;
+            a.side = XU ? p.cw + (int64_t)tr * 32 + 4 * h : p.rowc + (int64_t)tr * 32 + c;
+            a.img = live ? (unsigned)(ti - t0) * BSI_TILEB : MF_SRD_DEAD;
+            return a;
+        };
+        auto mem_piece = [&](int i, int slot_idx, const StageSrc& a) {
+            if (i < 4) {
+                Gn[i] = *reinterpret_cast<const f32x4*>(a.g + i * 1024);
+            } else if (i < 4 + NSIDE) {
+                const int j = i - 4;
+                if (XU) Wn[j] = *reinterpret_cast<const f32x4*>(a.side + 8 * j);     // rows 8 j + 4 h .. + 3 of the tile
+                else cn[j] = a.side[(int64_t)j * p.Bp];
+            } else {
+#if defined(__HIP_DEVICE_COMPILE__)
+                const int j = i - 4 - NSIDE;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(irsrc, (mf_lds_ptr)(smem + slot_idx * L::SLOT + (wave * L::PPW + j) * 1024), 16, (int)ioff,
+                                                         (int)(a.img + j * 1024), 0, 0);
+#endif
             }
         };
         auto stage_regs = [&](int t) {
+            const StageSrc a = stage_src(t0, false, t);
 #pragma unroll
-            for (int j = 0; j < NDMA; ++j)
-                if (j < 4 || j >= 4 + L::PPW) stage_piece(t, 0, j);
+            for (int i = 0; i < 4 + NSIDE; ++i) mem_piece(i, 0, a);
         };
         auto stage_image = [&](int t, int slot_idx) {
+            const StageSrc a = stage_src(t, true, t);
 #pragma unroll
-            for (int j = 4; j < 4 + L::PPW; ++j) stage_piece(t, slot_idx, j);
+            for (int i = 4 + NSIDE; i < NMEM; ++i) mem_piece(i, slot_idx, a);
+        };
+        // The G' of a tile in four slices, one beside each step of the previous tile's contraction; the arithmetic and its
+        // order are gprime's.  0, 1: the map of registers 8 sl .. 8 sl + 7, the diagonal, the weights and (dV) their way into the
+        // transpose scratch; 2: (dV) the transposed block back, the row sum, the pieces of k-step 0; 3: the pieces of k-step 1.
+        // (dV: the image pieces in flight would make hipcc drain them before a store it sees: mf_lds_store_b32, mf_stream.h.)
+        auto gslice = [&](int sl, float (&Gv)[16], const float (&Wv)[16], int tile, float& rs, mbf16x8 (&g)[2][3]) {
+            float* tr = reinterpret_cast<float*>(smem + L::TR) + wave * (32 * 32);
+            if (sl < 2) {
+#pragma unroll
+                for (int e = 8 * sl; e < 8 * sl + 8; ++e) {
+                    Gv[e] = gmap(Gv[e]);
+                    if (!CP && tile == xt && mf_acc_row(e, h) == c) Gv[e] = xd;
+                    if (XU && CP) Gv[e] *= Wv[e];
+                    if (!XU) mf_lds_store_b32(&tr[mf_acc_row(e, h) * 32 + (c ^ mf_acc_row(e, h))], Gv[e]);
+                }
+            } else if (sl == 2) {
+                if (!XU) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) Gv[e] = tr[c * 32 + (mf_acc_row(e, h) ^ c)];
+                }
+#pragma unroll
+                for (int e = 0; e < 16; ++e) rs += Gv[e];
+            }
+            if (sl >= 2) split_g(Gv, g, sl - 2);
         };
         mbf16x8 gb[2][3];
         float Gv[16], Wv[16];
@@ -721,24 +783,32 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
             mf_wait_vmcnt<0>();
             take(Gv, Wv, nullptr);
             if (t0 + 1 < t1) stage_regs(t0 + 1);
-            gprime(Gv, Wv, t0, rsum);
-            split_g(Gv, gb);
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl) gslice(sl, Gv, Wv, t0, rsum, gb);
         }
+        // In the loop, tile ty's contraction carries the stage behind it: BWD_SPLIT_DPG memory instructions to each of its four
+        // steps (fenced: a step's instructions stay in it), the register loads of tile ty + 2 first (they come from HBM),
+        // then the image pieces of tile ty + 1.  What keeps this right:
+        //  * slot reuse -- the image of tile ty + 1 lands in the slot tile ty - 1 left; every piece is issued behind the barrier
+        //    at the top of tile ty, which proves that every wave has finished tile ty - 1 (and the fences between the steps keep
+        //    the compiler from moving one above it);
+        //  * registers -- take() at the top has copied Gn / Wn / cn (tile ty + 1) out before any load of tile ty + 2
+        //    is issued into them, and nothing reads them again before the next top;
+        //  * the wait -- everything outstanding at a top was issued during the previous tile, the image of tile ty among it:
+        //    vmcnt(0), no count to derive;
+        //  * no branch around a load: stage and MFMAs share one basic block.  A piece of a tile that does not exist carries
+        //    the dead offset, and the register loads name the split's last tile again (in bounds, copied out, never used).
         int cur = 0;
         for (int ty = t0; ty < t1; ++ty) {
             mf_wait_vmcnt<0>();           // the image of tile ty and the registers of tile ty + 1: issued one tile ago
             mf_block_barrier();
             const bool more = ty + 1 < t1;
-            take(Gv, Wv, nullptr);        // tile ty + 1 as it arrived (none: what the registers held -- finite or -inf, and unused)
-            if (more) {
-                stage_image(ty + 1, cur ^ 1);
-                if (ty + 2 < t1) stage_regs(ty + 2);
-            }
+            take(Gv, Wv, nullptr);        // tile ty + 1 as it arrived (none: the last tile's block again, unused)
+            const int tr = min(ty + 2, t1 - 1);
+            const StageSrc src = stage_src(ty + 1, more, tr);
+            __builtin_amdgcn_sched_barrier(0);   // what the top of a tile does stays ahead of its first step
             float rs = 0.f;
-            gprime(Gv, Wv, ty + 1, rs);
-            rsum += more ? rs : 0.f;
             mbf16x8 gn[2][3];
-            split_g(Gv, gn);
             // dX[m][x] += sum_y Y[y][m] * G[y][x], piece products a_i g_j with i + j <= 2, the smallest first.  A step is one
             // k-step of two accumulator blocks (12 MFMAs, alternating between the two); its six A fragments are read one
             // step ahead.
@@ -755,6 +825,9 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
             for (int step = 0; step < 4; ++step) {
                 mbf16x8 an[2][3];
                 if (step + 1 < 4) frags(an, step + 1);
+#pragma unroll
+                for (int i = step * DPG; i < (step + 1) * DPG && i < NMEM; ++i) mem_piece(i, cur ^ 1, src);
+                gslice(step, Gv, Wv, ty + 1, rs, gn);
                 const int s = step >> 1, b0 = 2 * (step & 1);
 #pragma unroll
                 for (int pr = 0; pr < 6; ++pr) {
@@ -765,6 +838,14 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
                     for (int b = 0; b < 2; ++b)
                         dacc[b0 + b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[b][ai], gb[s][gi], dacc[b0 + b], 0, 0, 0);
                 }
+                // one MFMA, then a share of the slice's VALU work, twelve times (hipcc otherwise keeps the streams apart); the
+                // fence pins the step's memory instructions and its slice to the step
+#pragma unroll
+                for (int m = 0; m < 12; ++m) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x006, BWD_SPLIT_VPM, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
                 if (step + 1 < 4) {
 #pragma unroll
                     for (int b = 0; b < 2; ++b)
@@ -772,12 +853,7 @@ __global__ __launch_bounds__(64 * mf_nw(D), (D == 128 || D == 64) ? BWD_MIN_WG :
                         for (int q = 0; q < 3; ++q) av[b][q] = an[b][q];
                 }
             }
-            // one MFMA, then a share of the next tile's VALU work, 48 times (hipcc otherwise keeps the two streams apart)
-#pragma unroll
-            for (int m = 0; m < 48; ++m) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x006, BWD_SPLIT_VPM, 0);
-            }
+            rsum += more ? rs : 0.f;
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll

@@ -463,6 +463,26 @@ int mf_ivf_scan_allow(const float* q, int64_t Q, const float* blocked, const int
                       int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
                       const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, const uint64_t* allow, int64_t n_masks,
                       const int64_t* allow_of, void* ws, size_t ws_bytes, mf_stream_t stream);
+/* Deep lists from the cells: mf_ivf_scan and mf_ivf_scan_allow for 1 <= k <= MF_TOPK_DEEP_MAX_K (the reference's
+ * `.limit(top_k)` has no cap; the two scans above stop at 64, a list per wavefront).  The argument lists are exactly theirs,
+ * the geometry, the chain, the keys by CATALOG row, the exclusion lists, the allow bitmap and the packed lists [G = nprobe * S]
+ * [Q][k] too; the workgroup keeps its best keys in one LDS buffer (csrc/mf_ivf_deep.hip) instead of a list per wave.  The lists
+ * go to mf_topk_merge_packed_deep(ws, G, Q, k, ..) -- so nprobe * S * k <= MF_TOPK_MERGE_DEEP_MAX_KEYS = 16,384 -- and the
+ * result is bit for bit mf_topk_deep's over the union of the probed cells (rows the mask admits).  One launch, no atomics,
+ * nothing to clear, no host read: capturable.  Refusals: those of mf_ivf_scan / mf_ivf_scan_allow in their order and words,
+ * with "k = .. outside 1..1024" and the 16,384 keys of the deep merge behind "nprobe * S * k too large".
+ * mf_ivf_deep_plan / mf_ivf_deep_ws_bytes: the rule of mf_ivf_plan / mf_ivf_ws_bytes with k <= 1024 and nprobe * S * k <=
+ * 16,384 (S never below 1: a shape with nprobe * k above 16,384 is planned with S = 1 and refused by the scan). */
+size_t mf_ivf_deep_ws_bytes(int64_t Q, int nprobe, int k, int64_t max_cell_blocks);
+int mf_ivf_deep_plan(int64_t Q, int nprobe, int k, int64_t max_cell_blocks, int64_t* out4);
+int mf_ivf_scan_deep(const float* q, int64_t Q, const float* blocked, const int64_t* cell_blk, const int64_t* row_of, int64_t Npad,
+                     int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
+                     const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes,
+                     mf_stream_t stream);
+int mf_ivf_scan_deep_allow(const float* q, int64_t Q, const float* blocked, const int64_t* cell_blk, const int64_t* row_of, int64_t Npad,
+                           int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes, int nprobe, int k, int S,
+                           const int64_t* excl_off, const int64_t* excl_idx, int64_t idx_base, const uint64_t* allow, int64_t n_masks,
+                           const int64_t* allow_of, void* ws, size_t ws_bytes, mf_stream_t stream);
 
 /* Product-quantised cells with an exact refine: the rest of the reference's IVF_PQ index (xfmr_rec/data/lightning.py:162-165,
  * 203-204: num_sub_vectors = embedding_dim // 8, refine_factor = 4; :222-229 create_index; :250-259

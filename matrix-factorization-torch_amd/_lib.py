@@ -109,6 +109,12 @@ SIGNATURES = {
                             c_i64, c_vp, c_sz, c_vp]),
     "mf_ivf_scan_allow": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp,
                                   c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "mf_ivf_deep_ws_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
+    "mf_ivf_deep_plan": (c_int, [c_i64, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]),
+    "mf_ivf_scan_deep": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp,
+                                 c_i64, c_vp, c_sz, c_vp]),
+    "mf_ivf_scan_deep_allow": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_int, c_int, c_int, c_vp,
+                                       c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "mf_ivf_cell_mean": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "mf_pq_encode": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_vp]),
     "mf_pq_ws_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),

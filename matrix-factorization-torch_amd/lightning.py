@@ -462,7 +462,8 @@ class MatrixFactorizationLitModule(_Base):
             pos, _, ncand = self.item_processor.index.positions(queries, (off, ids), exclude_csr=batch.get("history"))
             metric.update(pos, off, rating, ncand)
             return metric.compute()
-        _, rows = self.item_processor.index.search(queries, self.config.top_k, exclude_csr=batch.get("history"))
+        index = self.item_processor.index
+        _, rows = index.search(queries, self.config.top_k, exclude_csr=batch.get("history"), path=index.default_path(self.config.top_k))
         metric.update(rows, off, ids, rating)
         return metric.compute()
 
@@ -488,7 +489,8 @@ class MatrixFactorizationLitModule(_Base):
     def predict_step(self, batch, _: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
         """``(scores, item rows)`` [Q, top_k] of the batch's users, histories excluded."""
         queries = self._queries(batch)
-        return self.item_processor.index.search(queries, self.config.top_k, exclude_csr=batch.get("history"))
+        index = self.item_processor.index
+        return index.search(queries, self.config.top_k, exclude_csr=batch.get("history"), path=index.default_path(self.config.top_k))
 
     def training_step(self, batch, _: int = 0) -> torch.Tensor:
         losses = self.compute_losses(batch, step_name="train")

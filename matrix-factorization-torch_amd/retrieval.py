@@ -403,6 +403,11 @@ class ItemIndex:
                 return out
         return self._run("tiles", q, top_k, off, ids)
 
+    def default_path(self, top_k: int) -> str:  # noqa: ARG002
+        """The ``path`` a caller that only knows ``top_k`` should pass to ``search`` (``ItemProcessor``, the module's metrics and
+        predictions): ``"auto"`` here, the cell scan that serves the depth on a ``PartitionedIndex``, ``"pq"`` on a quantised one."""
+        return "auto"
+
     # engine -> (workspace-size export, search export, workspace key, the source tensors behind the queries)
     _ENGINES = {
         "deep": ("mf_topk_deep_ws_bytes", "mf_topk_deep", "deep", lambda self: (self.embeddings,)),
@@ -693,9 +698,26 @@ class PartitionedIndex(ItemIndex):
         _lib.check(export(int(num_queries), nprobe, depth, self.max_cell_blocks, out))
         return {"slices": out[0], "lists": out[1], "workgroups": out[2], "bytes": out[3]}
 
-    def plan(self, num_queries: int, top_k: int = TOP_K, nprobe: int | None = None) -> dict[str, int]:
-        """The geometry ``search`` runs with (``mf_ivf_plan``): slices per cell, partial lists per query, workgroups."""
-        return self._plan(_lib.lib().mf_ivf_plan, num_queries, self.num_probes if nprobe is None else int(nprobe), int(top_k))
+    def plan(self, num_queries: int, top_k: int = TOP_K, nprobe: int | None = None, path: str = "cells") -> dict[str, int]:
+        """The geometry ``search`` runs with (``mf_ivf_plan``; ``path="cells_deep"``: ``mf_ivf_deep_plan``): slices per cell, partial
+        lists per query, workgroups."""
+        export = _lib.lib().mf_ivf_deep_plan if path == "cells_deep" else _lib.lib().mf_ivf_plan
+        return self._plan(export, num_queries, self.num_probes if nprobe is None else int(nprobe), int(top_k))
+
+    def default_path(self, top_k: int) -> str:
+        """The cell scan that serves ``top_k``: a list per wavefront up to ``TILE_MAX_K`` rows, the deep scan beyond."""
+        return "cells" if int(top_k) <= self.TILE_MAX_K else "cells_deep"
+
+    def _deep_top_k(self, top_k: int, nprobe: int) -> int:
+        """``path="cells_deep"``'s depth: 1..``DEEP_MAX_K``, and a list per probe at least within the deep merge's keys."""
+        top_k = int(top_k)
+        if not 1 <= top_k <= self.DEEP_MAX_K:
+            msg = f"the deep partitioned search returns 1..{self.DEEP_MAX_K} rows per query: {top_k = }"
+            raise ValueError(msg)
+        if nprobe * top_k > MERGE_DEEP_MAX_KEYS:
+            msg = f"nprobe * top_k must not exceed {MERGE_DEEP_MAX_KEYS} (the keys the merge of the lists holds): {nprobe = }, {top_k = }"
+            raise ValueError(msg)
+        return top_k
 
     def search(self, queries: torch.Tensor, top_k: int = TOP_K, *, exclude: Sequence[Sequence[int]] | None = None,
                exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None, nprobe: int | None = None,
@@ -706,19 +728,24 @@ class PartitionedIndex(ItemIndex):
         matrix), the scan (``mf_ivf_scan``), the merge (``mf_topk_merge_packed``).  ``path="exact"`` is the parent's search over
         the whole catalog ("auto"); any other path is passed to the parent as it is.  ``where``: as in the parent -- the view
         keeps the cells, so the probes are the same and the result is this search's with the inadmissible rows excluded; for a
-        filter without the view's copy, its host read and its per-filter grouping, see ``allow``.  ``allow`` (``path="cells"``
+        filter without the view's copy, its host read and its per-filter grouping, see ``allow``.  ``path="cells_deep"``: the same
+        contract and the same three stages for ``1 <= top_k <= DEEP_MAX_K`` (``mf_ivf_scan_deep``, ``mf_topk_merge_packed_deep``;
+        ``"cells"`` stops at ``TILE_MAX_K``, a list per wavefront) with ``nprobe * top_k`` within ``MERGE_DEEP_MAX_KEYS`` -- bit for
+        bit ``ItemIndex.search(path="deep")`` with the rows outside the probed cells excluded.  ``allow`` (the two cell paths
         only): a ``CellMask`` or anything ``cell_mask`` takes -- the scan filters in place (``mf_ivf_scan_allow``), the same
         result bit for bit; with several masks ``allow_of`` (``int64 [Q]``, host or device) names each query's, and a number
         outside ``[0, F)`` admits nothing for that query."""
-        self._allow_route(allow, allow_of, where, path, ("cells",))
+        self._allow_route(allow, allow_of, where, path, ("cells", "cells_deep"))
         if where is not None:
             kw = {"nprobe": nprobe, "path": path}
             if _is_filter_sequence(where):
                 return self._search_groups(self._queries(queries), int(top_k), where, exclude, exclude_csr, kw)
             return self.filtered(where).search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, **kw)
-        if path != "cells":
+        if path not in ("cells", "cells_deep"):
             return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, path="auto" if path == "exact" else path)
-        top_k, nprobe = self._top_k(top_k, "partitioned"), self._nprobe(nprobe)
+        deep = path == "cells_deep"
+        nprobe = self._nprobe(nprobe)
+        top_k = self._deep_top_k(top_k, nprobe) if deep else self._top_k(top_k, "partitioned")
         q = self._queries(queries)
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         mask, allow_of = self._allow_masks(allow, allow_of, nq)
@@ -727,16 +754,18 @@ class PartitionedIndex(ItemIndex):
         lib = _lib.lib()
         scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
         rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
-        ws = self._workspace(("cells", nq, nprobe, top_k), lib.mf_ivf_ws_bytes(nq, nprobe, top_k, self.max_cell_blocks))
-        lists = self.plan(nq, top_k, nprobe)["lists"]
+        ws_bytes, scan_plain, scan_allow, merge = (
+            (lib.mf_ivf_deep_ws_bytes, lib.mf_ivf_scan_deep, lib.mf_ivf_scan_deep_allow, lib.mf_topk_merge_packed_deep) if deep else
+            (lib.mf_ivf_ws_bytes, lib.mf_ivf_scan, lib.mf_ivf_scan_allow, lib.mf_topk_merge_packed))
+        ws = self._workspace((path, nq, nprobe, top_k), ws_bytes(nq, nprobe, top_k, self.max_cell_blocks))
+        lists = PartitionedIndex.plan(self, nq, top_k, nprobe, path)["lists"]      # (this scan's plan, whatever a subclass plans by default)
         scan = (q.data_ptr(), nq, self.cell_blocked().data_ptr(), self.cell_blk.data_ptr(), self.row_of.data_ptr(), self.row_of.numel(), n,
                 self.num_partitions, d, self.max_cell_blocks, probes.data_ptr(), nprobe, top_k, 0, _lib.ptr(off), _lib.ptr(ids), self.idx_base)
         if mask is None:
-            _lib.check(lib.mf_ivf_scan(*scan, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+            _lib.check(scan_plain(*scan, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
         else:
-            _lib.check(lib.mf_ivf_scan_allow(*scan, mask.words.data_ptr(), mask.num_masks, _lib.ptr(allow_of), ws.data_ptr(), ws.numel(),
-                                             _lib.stream_ptr()))
-        _lib.check(lib.mf_topk_merge_packed(ws.data_ptr(), lists, nq, top_k, scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
+            _lib.check(scan_allow(*scan, mask.words.data_ptr(), mask.num_masks, _lib.ptr(allow_of), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        _lib.check(merge(ws.data_ptr(), lists, nq, top_k, scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
         return scores, rows
 
 
@@ -798,6 +827,10 @@ class QuantizedIndex(PartitionedIndex):
         index._pq_args = {"pq_iters": int(pq_iters), "seed": int(seed)}
         index.codebooks = index._train(int(pq_iters), int(seed))
         return index
+
+    def default_path(self, top_k: int) -> str:  # noqa: ARG002
+        """``"pq"``: the quantiser's own search at every depth it serves (``refine_factor * top_k <= MAX_CANDIDATES``)."""
+        return "pq"
 
     @classmethod
     def _geometry(cls, d: int, m: int) -> tuple[int, int]:
@@ -891,7 +924,7 @@ class QuantizedIndex(PartitionedIndex):
         """The geometry ``search`` runs with (``mf_pq_plan`` for ``refine_factor * top_k`` candidates; ``path="cells"``: the
         parent's): slices per cell, partial lists per query, workgroups."""
         if path != "pq":
-            return super().plan(num_queries, top_k, nprobe)
+            return super().plan(num_queries, top_k, nprobe, "cells_deep" if path == "cells_deep" else "cells")
         r, nprobe = self._candidates_of(top_k, refine_factor), self._nprobe(nprobe)
         if int(num_queries) < 1:
             msg = f"num_queries must be at least 1: {num_queries = }"
@@ -958,7 +991,7 @@ class QuantizedIndex(PartitionedIndex):
         ``cell_mask`` takes (``allow_of``: each query's mask among several), on ``path="pq"`` (``mf_pq_scan_allow``: a row the
         mask does not admit never becomes a candidate, so the refine only sees admitted rows) and on the parent's
         ``path="cells"`` -- bit for bit the same search with the inadmissible rows on every query's exclusion list."""
-        self._allow_route(allow, allow_of, where, path, ("pq", "cells"))
+        self._allow_route(allow, allow_of, where, path, ("pq", "cells", "cells_deep"))
         if where is not None:
             self.filtered(where)
         if path != "pq":
@@ -1265,12 +1298,13 @@ class ItemProcessor:
             raise ValueError(msg)
         q = torch.as_tensor(np.asarray(embedding), dtype=torch.float32).reshape(1, -1).to(self.index.embeddings.device)
         rows = [self._row_of_id[i] for i in (exclude_item_ids or []) if i in self._row_of_id]
+        path = self.index.default_path(top_k)          # (a partitioned index: the deep cell scan beyond 64 rows)
         if where is None:
-            scores, idx = self.index.search(q, top_k, exclude=[rows])
+            scores, idx = self.index.search(q, top_k, exclude=[rows], path=path)
         elif self.filter_mode == "mask":
-            scores, idx = self.index.search(q, top_k, exclude=[rows], allow=self._where(where))
+            scores, idx = self.index.search(q, top_k, exclude=[rows], path=path, allow=self._where(where))
         else:
-            scores, idx = self.index.search(q, top_k, exclude=[rows], where=self._where(where))
+            scores, idx = self.index.search(q, top_k, exclude=[rows], path=path, where=self._where(where))
         idx = idx[0].cpu()
         keep = idx >= 0
         idx = idx[keep]

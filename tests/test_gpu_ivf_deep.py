@@ -99,6 +99,7 @@ def test_shallow_depths_equal_the_wavefront_scan(mf, name):
 
 
 # ------------------------------------------------------------------------------------------- 4: several settles ----
+# (the plain kernel on scores s * e0; masks, lists, ties and every kept class on real dot products: tests/test_gpu_ivf_deep_settles.py)
 @pytest.fixture(scope="module")
 def long_cell(mf):
     """One cell of ``settle_rows()`` rows, the row at cell position i = (its score) * e0; the query is e0."""

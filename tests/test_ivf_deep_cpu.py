@@ -1,8 +1,9 @@
 """CPU: the host side of the deep cell scan (csrc/mf_ivf_deep.hip, ``PartitionedIndex.search(path="cells_deep")``) -- the four
 exports, every refusal of the two scans and of the plan with their order (all decided before any launch: never-dereferenced fake
 pointers do), the plan over its domain, the kernels' resources from the code objects' notes, the buffer's constants read from
-the source with what the GPU test of several settles leans on, ``default_path``, the Python refusals, the deep case set, and the
-digest record."""
+the source with what the GPU test of several settles leans on, the long cell under masks, lists and ties (what
+tests/test_gpu_ivf_deep_settles.py leans on: its inputs reach the settles they are chosen for and tell wrong kernels apart),
+``default_path``, the Python refusals, the deep case set, and the digest record."""
 from __future__ import annotations
 
 import ctypes
@@ -15,6 +16,9 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import chain
+from tests import _cell_mask_spec as cell_mask_spec
+from tests import _filter_spec
 from tests import _ivf_deep_spec as deep
 from tests import _ivf_spec as spec
 
@@ -185,6 +189,242 @@ def test_the_constants_and_the_cell_of_several_settles():
                 assert len(live) >= 1 and 0 < sum(live) < n - k, (order, k, w["settles"])
     # a slice of the cell at the planned geometry settles too: 52 slices of four blocks at k = 100 do not, S = 1 does
     assert len(deep.walk(deep.settle_scores("ascending")[:256], 100)["settles"]) == 1
+
+
+# ------------------------------------------------------- the long cell under masks, lists and ties: the inputs ----
+# What tests/test_gpu_ivf_deep_settles.py leans on, from the walk with admission (``deep.walk(scores, k, admitted, rows)``): its
+# inputs drive the buffer where they are meant to, and they tell a subtly wrong kernel from the right one.
+WIDTHS = (64, 256)
+GPU_MASKS = {64: tuple(deep.SETTLE_MASKS), 256: ("half", "every other block")}      # the masks the GPU file runs at each width
+
+
+def _walk(d, i, k, mask="all", lists=None, lo=0, hi=None, **kw):
+    """The walk of query i over positions ``[lo, hi)`` of the long cell of width d."""
+    hi = deep.settle_rows() if hi is None else hi
+    admitted = deep.settle_admitted(d, mask, lists)[i]
+    return deep.walk(deep.long_scores(d)[i][lo:hi], k, admitted[lo:hi], deep.long_rows(d)[lo:hi], **kw)
+
+
+def _in_loop_live(w):
+    return sum(live and inside for _, live, inside, _ in w["settles"])
+
+
+def test_the_walk_without_admission_is_the_walk_of_before():
+    scores = deep.settle_scores("shuffled")
+    n = scores.size
+    plain = deep.walk(scores, 100)
+    assert set(plain) == {"settles", "best"} and all(len(s) == 2 for s in plain["settles"])
+    full = deep.walk(scores, 100, np.ones(n, dtype=bool), np.arange(n))
+    assert [s[:2] for s in full["settles"]] == plain["settles"] and full["best"] == plain["best"] == full["rows"]
+    for waiting, _, inside, length in full["settles"]:
+        assert inside == (waiting > deep.room_of(100)) and length >= max(512, 128 + waiting) and (length == 512 or length // 2 < 128 + waiting)
+    assert [deep.room_of(k) for k in deep.SETTLE_DEPTHS] == [1664, 1536, 1280, 2816]
+    assert [deep.kept(k) for k in deep.SETTLE_DEPTHS] == [128, 256, 512, 1024]
+
+
+@pytest.mark.parametrize("d", WIDTHS)
+def test_the_settle_catalog_is_what_the_gpu_file_takes_it_for(d):
+    c = deep.settle_catalog(d)
+    n = deep.settle_rows()
+    rows, scores = deep.long_rows(d), deep.long_scores(d)
+    assert c.sizes.tolist() == [150, n, 70] == list(deep.settle_sizes()) and n == 13288 and -(-n // 64) == 208 and n % 64 == 40
+    assert c.idx_base == deep.SETTLE_BASE == 30 and c.max_cell_blocks == 208 and c.items.shape == (13508, d)
+    # position is not row: the long cell begins at block 3 of the mask, and its rows are no shifted range
+    assert -(-150 // 64) == deep.SETTLE_FIRST_BLOCK == 3
+    assert np.unique(rows - np.arange(n)).size > 100 and (np.diff(rows) > 0).all()
+    # query 0 ascends along the cell, query 1 is its negation to the bit, query 2 neither ascends nor descends
+    assert (np.diff(scores[0]) >= 0).all() and (np.diff(scores[0]) > 0).sum() > n - 50
+    assert np.array_equal((-scores[0]).view(np.uint32), scores[1].view(np.uint32)) and not (scores == 0).any()
+    up = (np.diff(scores[2]) > 0).mean()
+    assert 0.4 < up < 0.6
+    # queries 0 and 2 probe the long cell at nprobe = 1; query 1 cannot (its score with centroid 1 is -1)
+    probed = spec.probes(c.q, c.centroids, 1)[:, 0].tolist()
+    assert probed[0] == probed[2] == deep.SETTLE_CELL != probed[1]
+    # the in-cell oracle is the spec at nprobe = 1 for the queries that probe the cell, and numpy's selection is the oracle's
+    lists = deep.settle_lists("long and scattered", d, 100, "half")
+    every = _filter_spec.extended_lists(lists, 3, deep.settle_ok("half", d), c.idx_base)
+    ws, wr = spec.expected(c.q, c.items, c.centroids, c.assign, 100, 1, every, c.idx_base)
+    gs, gr = deep.settle_expected(d, 100, "half", lists)
+    admitted = deep.settle_admitted(d, "half", lists)
+    for i in range(3):
+        if i != 1:
+            assert np.array_equal(gr[i], wr[i]) and np.array_equal(gs[i].view(np.uint32), ws[i].view(np.uint32)), i
+        best = deep.best_first(scores[i], rows, admitted[i], 0, n)[:100]
+        assert np.array_equal(rows[best] + c.idx_base, gr[i]) and np.array_equal(scores[i][best].view(np.uint32), gs[i].view(np.uint32)), i
+        assert _walk(d, i, 100, "half", lists)["rows"] == rows[best].tolist(), i
+
+
+def test_the_masks_and_the_lists_are_what_their_names_say():
+    n = deep.settle_rows()
+    count = {name: int(deep.settle_mask(name).sum()) for name in deep.SETTLE_MASKS}
+    assert count["all"] == n and count["none"] == 0 and count["last block only"] == 40 and count["late"] == n - 3000
+    assert 0.48 * n < count["half"] < 0.52 * n and count["every other block"] == 104 * 64 and count["one block in five"] == n - 41 * 64
+    # tails: the last block alone leaves fewer than k rows at every depth
+    assert count["last block only"] < min(deep.SETTLE_DEPTHS)
+    # zero words in a pass of four waves: none, one beside three live waves, two, all four
+    live_word = {name: np.pad(deep.settle_mask(name), (0, 24)).reshape(52, 4, 64).any(axis=2) for name in deep.SETTLE_MASKS}
+    zero_words = {name: set((4 - w.sum(axis=1)).tolist()) for name, w in live_word.items()}
+    assert zero_words["one block in five"] == {0, 1} and zero_words["every other block"] == {2} and zero_words["late"] == {4, 2, 0}
+    assert zero_words["last block only"] == {4, 3} and zero_words["none"] == {4} and zero_words["all"] == zero_words["half"] == {0}
+    ok = deep.settle_ok("half", 64)
+    c = deep.settle_catalog(64)
+    assert ok[c.assign != deep.SETTLE_CELL].all() and np.array_equal(ok[deep.long_rows(64)], deep.settle_mask("half"))
+    for d in WIDTHS:
+        c = deep.settle_catalog(d)
+        inside = set((deep.long_rows(d) + c.idx_base).tolist())
+        for k in (100, 1000):
+            for mask in ("all", "half"):
+                admitted = deep.settle_mask(mask)
+                best, scattered, three = (deep.settle_lists(f, d, k, mask) for f in deep.SETTLE_LISTS)
+                for i in range(3):
+                    assert len(set(best[i])) == len(best[i]) == 2 * k and set(best[i]) <= inside
+                    assert len(scattered[i]) == 1025 + 40 + 2 and c.idx_base - 1 in scattered[i] and c.idx_base + 13508 in scattered[i]
+                    assert len(set(scattered[i]) & inside) == 1025 and len(set(scattered[i]) - inside) == 42
+                    assert len(three[i]) == int(admitted.sum()) - 3 and int(deep.settle_admitted(d, mask, three)[i].sum()) == 3
+                assert list(best[0]) != sorted(best[0]) and best[0] != best[2]
+
+
+@pytest.mark.parametrize("d", WIDTHS)
+def test_the_ascending_query_settles_inside_the_loop_under_a_live_bound(d):
+    """A condition on the inputs: another seed or a longer cell if it fails, never a weaker condition."""
+    live = []
+    for k in deep.SETTLE_DEPTHS:
+        w = _walk(d, 0, k)
+        live.append(sum(s[1] for s in w["settles"]))
+        assert _in_loop_live(w) >= 2, (k, w["settles"])
+        for mask, lists in (("half", None), ("every other block", None), ("half", deep.settle_lists("long and scattered", d, k, "half"))):
+            w = _walk(d, 0, k, mask, lists)
+            assert _in_loop_live(w) >= 1, (k, mask, lists is not None, w["settles"])
+        for family in deep.SETTLE_LISTS[:2]:                # the lists meet a live bound in the plain kernel too
+            assert _in_loop_live(_walk(d, 0, k, "all", deep.settle_lists(family, d, k))) >= 1, (k, family)
+    assert live == [7, 7, 8, 4]                             # every key beats the bound: 13,288 rows in settles of 1792 / 1792 / 1536 / 3072
+    # the descending query: one settle inside the loop, then nothing beats the bound; the third: live settles, not all keys
+    for k in deep.SETTLE_DEPTHS:
+        assert [s[1:3] for s in _walk(d, 1, k)["settles"]] == [(False, True)], k
+        w = _walk(d, 2, k)
+        assert _in_loop_live(w) >= 1 and sum(s[0] for s in w["settles"]) < deep.settle_rows() - k, (k, w["settles"])
+
+
+def test_every_sort_length_runs_and_each_under_a_live_bound():
+    n = deep.settle_rows()
+    lengths, live = set(), set()
+    for d in WIDTHS:
+        for mask in GPU_MASKS[d]:
+            for k in deep.SETTLE_DEPTHS:
+                for i in range(3):
+                    for slices in (1, 3):
+                        for s in range(slices):
+                            w = _walk(d, i, k, mask, lo=min(n, 64 * (208 * s // slices)), hi=min(n, 64 * (208 * (s + 1) // slices)))
+                            lengths |= {length for _, _, _, length in w["settles"]}
+                            live |= {length for _, was_live, _, length in w["settles"] if was_live}
+    assert lengths == live == {512, 1024, 2048, 4096}
+
+
+@pytest.mark.parametrize("d", WIDTHS)
+def test_depths_200_and_500_settle_by_their_own_class(d):
+    """Class 512 is the boundary of ``ivfd_capacity`` (4 * 512 == IVFD_BUF_MIN): room 1280, where class 256 has 1536.  The cases
+    tell the two rules apart: a walk with the other class's room settles at other passes."""
+    for k, room, other in ((500, 1280, 1536), (200, 1536, 1280)):
+        assert deep.room_of(k) == room
+        for i, mask in ((0, "all"), (0, "half"), (2, "all")):
+            right, wrong = _walk(d, i, k, mask), _walk(d, i, k, mask, room=other)
+            inside = [waiting for waiting, _, begun, _ in right["settles"] if begun]
+            assert len(inside) >= 2 and all(room < waiting <= room + 256 for waiting in inside), (k, i, mask, right["settles"])
+            assert [s[0] for s in wrong["settles"]] != [s[0] for s in right["settles"]], (k, i, mask)
+            assert wrong["best"] == right["best"]          # (the rule decides when the buffer is sorted and whether it overflows, not the list)
+    assert 512 + 1536 + 256 > deep.capacity(512)            # class 256's room at kept part 512: a full pass more would not fit
+
+
+def test_the_slicings_of_the_long_cell(mf):
+    """Three queries on one probe: the plan cuts the 208 blocks into 52 / 52 / 32 / 16 slices; the deepest slicing the merge holds
+    is a list per 1.3 ... 13 blocks.  Slices of four blocks exactly at k = 100 and 200 -- the slicings of 3 and the deepest have
+    the ragged last passes."""
+    lib = mf._lib.lib()
+    out = (ctypes.c_int64 * 4)()
+    planned = []
+    for k in deep.SETTLE_DEPTHS:
+        assert lib.mf_ivf_deep_plan(3, 1, k, 208, out) == 0
+        planned.append(out[0])
+    assert planned == [52, 52, 32, 16] and [min(208, deep.MERGE_KEYS // k) for k in deep.SETTLE_DEPTHS] == [163, 81, 32, 16]
+    assert [208 * (s + 1) // 3 - 208 * s // 3 for s in range(3)] == [69, 69, 70]
+
+
+# ---- the inputs tell wrong kernels apart: each restated in a few lines, each differs from the spec on a case of the set
+def test_a_mask_applied_by_row_gives_another_list():
+    d, k = 64, 100
+    c = deep.settle_catalog(d)
+    rows, n = deep.long_rows(d), deep.settle_rows()
+    cell_blk, row_of = cell_mask_spec.layout(c.assign, 3)
+    assert cell_blk.tolist() == [0, 3, 211, 213] and np.array_equal(row_of[192: 192 + n], rows)
+    for mask in ("half", "every other block", "late"):
+        ok = deep.settle_ok(mask, d)
+        bits = (row_of >= 0) & ok[np.clip(row_of, 0, None)]                      # the words, a bit per padded position
+        assert np.array_equal(bits[192: 192 + n], deep.settle_mask(mask))
+        by_row = bits[rows]                                                      # the wrong kernel: bit number `row`, not `position`
+        want = deep.settle_expected(d, k, mask)[1]
+        for i in range(3):
+            wrong = rows[deep.best_first(deep.long_scores(d)[i], rows, by_row, 0, n)[:k]] + c.idx_base
+            assert not np.array_equal(wrong, want[i]), (mask, i)
+
+
+def test_ties_broken_by_position_give_another_list():
+    n, row_of = deep.settle_rows(), deep.tie_row_of()
+    c = deep.tie_catalog()
+    assert sorted(row_of[:n].tolist()) == list(range(n)) and (row_of[n:] == -1).all() and row_of.size == 208 * 64
+    assert 0.2 < (np.diff(row_of[:n]) > 0).mean() < 0.8                     # neither ascending nor descending from one position to the next
+    assert (c.items == c.items[0]).all() and np.array_equal(c.q, c.items[:1]) and c.idx_base == 30
+    scores = np.full(n, chain.scores(c.q, c.items[:1])[0, 0], dtype=np.float32)
+    for mask in ("all", "half"):
+        admitted = deep.settle_mask(mask)
+        for k in deep.TIE_DEPTHS:
+            for slices in (1, 3):
+                for s in range(slices):
+                    lo, hi = min(n, 64 * (208 * s // slices)), min(n, 64 * (208 * (s + 1) // slices))
+                    right = deep.walk(scores[lo:hi], k, admitted[lo:hi], row_of[lo:hi])
+                    want = np.sort(row_of[lo:hi][admitted[lo:hi]])[:k].tolist()
+                    assert right["rows"] == want, (mask, k, slices, s)
+                    # a later pass holds better tied keys: the bound is live and still moves (half a slice of three at k = 1000
+                    # is 2,200 keys, fewer than a first settle's 2,816: the whole cell below does it)
+                    assert mask == "half" or sum(live for _, live, _, _ in right["settles"]) >= 1, (mask, k, slices, s)
+                    by_position = deep.walk(scores[lo:hi], k, admitted[lo:hi])      # the wrong kernel: the key holds the position
+                    assert row_of[lo:hi][by_position["best"]].tolist() != want, (mask, k, slices, s)
+            assert _in_loop_live(deep.walk(scores, k, admitted, row_of[:n])) >= 1, (mask, k)
+
+
+def test_excluded_keys_that_enter_the_bound_give_a_short_list():
+    d = 64
+    c = deep.settle_catalog(d)
+    rows, n = deep.long_rows(d), deep.settle_rows()
+    for k in (100, 1000):
+        for mask in ("all", "half"):
+            lists = deep.settle_lists("the best 2k", d, k, mask)
+            want = deep.settle_expected(d, k, mask, lists)[1]
+            assert (want >= 0).all()                                             # the right kernel fills its list
+            for i in range(3):
+                # the wrong kernel: a listed key waits and is kept like any other, and is dropped when the list is written
+                held = deep.walk(deep.long_scores(d)[i], k, deep.settle_mask(mask), rows)["rows"]
+                left = [r + c.idx_base for r in held if r + c.idx_base not in set(lists[i])]
+                assert left == [] and left != want[i].tolist(), (k, mask, i)
+
+
+def test_a_word_read_past_the_slices_end_gives_another_list():
+    """A wave past ``b1`` that took its block's word would admit rows of the next slice.  The slices of 3 and of the deepest
+    slicing are no multiples of four blocks, so the last pass of a slice has such waves."""
+    d, n = 64, deep.settle_rows()
+    rows = deep.long_rows(d)
+    for k in deep.SETTLE_DEPTHS:
+        for slices in (3, min(208, deep.MERGE_KEYS // k)):
+            ragged = differs = 0
+            for s in range(slices):
+                b0, b1 = 208 * s // slices, 208 * (s + 1) // slices
+                over = min(208, b0 + -(-(b1 - b0) // 4) * 4)                     # the blocks the slice's last pass covers
+                ragged += over > b1
+                for i, mask in ((0, "all"), (2, "half")):
+                    admitted = deep.settle_mask(mask)
+                    right = deep.best_first(deep.long_scores(d)[i], rows, admitted, 64 * b0, min(n, 64 * b1))[:k]
+                    wrong = deep.best_first(deep.long_scores(d)[i], rows, admitted, 64 * b0, min(n, 64 * over))[:k]
+                    differs += not np.array_equal(right, wrong)
+            assert ragged >= 2 and differs >= 2, (k, slices, ragged, differs)
 
 
 # -------------------------------------------------------------------------------------------------------- python ----

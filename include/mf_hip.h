@@ -556,6 +556,36 @@ int mf_pq_scan_allow(const float* q, int64_t Q, const void* codes, const float* 
                      const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off, const int64_t* excl_idx,
                      int64_t idx_base, const uint64_t* allow, int64_t n_masks, const int64_t* allow_of, void* ws, size_t ws_bytes,
                      mf_stream_t stream);
+/* Deep lists from the quantised cells: the same search where R = refine_factor * k exceeds 256 or k exceeds 64 -- the
+ * reference's `.refine_factor(4).limit(top_k)` has no cap.  mf_pq_scan_deep / mf_pq_scan_deep_allow take every argument of
+ * mf_pq_scan / mf_pq_scan_allow in its order and score to the bit as they do (tables, plain fp32 adds, the key by the global
+ * row); the workgroup keeps its best keys as mf_ivf_scan_deep does -- one LDS buffer of 4,096 keys, the kept part in classes
+ * 128 / 256 / 512 / 1024, a bitonic settle -- and every workgroup writes all R entries of its list, "none" where it has fewer:
+ * [G = nprobe * S][Q][R] packed, what mf_topk_merge_packed_deep takes.  1 <= R <= 1024 and nprobe * S * R <= 16,384.  Static
+ * LDS M KiB + 32 KiB + 16 B (M = d / dsub sub-vectors: 34 KiB at M = 2, 96 KiB at M = 64).  One launch each, no atomics,
+ * nothing to clear, no host read, capturable.  Refused before any launch: mf_pq_scan's refusals (then mf_pq_scan_allow's) in
+ * their order and words, with "R = .. outside 1..1024" in the place of the 256 limit and the 16,384 keys of the deep merge
+ * behind "nprobe * S * R too large".
+ * mf_pq_deep_plan / mf_pq_deep_ws_bytes: the rule of mf_pq_plan / mf_pq_ws_bytes with R <= 1024.
+ * mf_pq_refine_deep: mf_pq_refine for 1 <= k <= 1024 and k <= R <= 1024, the same arguments and arithmetic: one 256-thread
+ * workgroup per query, a thread scores up to four candidates, the keys are sorted in 8 KiB of LDS and the k best leave with
+ * the -inf / -1 tail.  The candidates of a query are distinct rows (the merge's output; -1 and rows outside [idx_base,
+ * idx_base + N) are no candidates).  Refused before any launch, in this order: MF_EINVAL "bad argument"; MF_ENOTSUP k outside
+ * 1..1024; MF_ENOTSUP R outside k..1024; MF_EINVAL a width outside {32, 64, 128, 256}; MF_ENOTSUP "item indices must fit 32
+ * bits". */
+size_t mf_pq_deep_ws_bytes(int64_t Q, int nprobe, int R, int64_t max_cell_blocks);
+int mf_pq_deep_plan(int64_t Q, int nprobe, int R, int64_t max_cell_blocks, int64_t* out4);
+int mf_pq_scan_deep(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+                    const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks, const int64_t* probes,
+                    const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off, const int64_t* excl_idx,
+                    int64_t idx_base, void* ws, size_t ws_bytes, mf_stream_t stream);
+int mf_pq_scan_deep_allow(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+                          const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks,
+                          const int64_t* probes, const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off,
+                          const int64_t* excl_idx, int64_t idx_base, const uint64_t* allow, int64_t n_masks, const int64_t* allow_of,
+                          void* ws, size_t ws_bytes, mf_stream_t stream);
+int mf_pq_refine_deep(const float* q, int64_t Q, const float* items, int64_t N, int d, const int64_t* cand, int R, int k,
+                      int64_t idx_base, float* out_scores, int64_t* out_idx, mf_stream_t stream);
 
 /* Retrieval metrics @k on device, straight from the top-k output.  Replaces the
  * per-example torchmetrics updates of `update_metrics` / `get_metrics` (xfmr_rec/lightning.py:149-187,

@@ -124,6 +124,13 @@ SIGNATURES = {
     "mf_pq_scan_allow": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_int,
                                  c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "mf_pq_refine": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp]),
+    "mf_pq_deep_ws_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
+    "mf_pq_deep_plan": (c_int, [c_i64, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]),
+    "mf_pq_scan_deep": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_int,
+                                c_vp, c_vp, c_i64, c_vp, c_sz, c_vp]),
+    "mf_pq_scan_deep_allow": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_int, c_int,
+                                      c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "mf_pq_refine_deep": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp]),
     "mf_target_positions_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_target_positions_min_ws_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "mf_target_positions": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp,

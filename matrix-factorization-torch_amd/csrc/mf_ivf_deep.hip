@@ -17,7 +17,10 @@
 //     n / 8 or less stays inside a quarter, and the LDS executes one wave's operations in order -- so of the log2(n) (log2(n) +
 //     1) / 2 stages only the three with distance n / 4 or n / 2 need workgroup barriers (66 stages at n = 2,048, 78 at 4,096).
 //   * ivf_scan_deep_allow_kernel: the same text reading an allow bitmap (mf_ivf_scan_allow's, a scalar load a block ahead).
+//   * pq_deep_scan_kernel / pq_deep_scan_allow_kernel (mf_pq_deep_scan.inc, at the end): the same keeping over the quantised
+//     cells of mf_pq.hip -- its tables and scoring, lists of up to 1,024 candidates for mf_pq_refine_deep.
 #include "mf_cells.h"
+#include "mf_pq_tables.h"
 #include "mf_select.h"
 
 // ---- the buffer's constants (tests/test_ivf_deep_cpu.py reads them from here)
@@ -140,4 +143,75 @@ extern "C" int mf_ivf_scan_deep_allow(const float* q, int64_t Q, const float* bl
                                       int64_t n_masks, const int64_t* allow_of, void* ws, size_t ws_bytes, mf_stream_t stream) {
     return ivf_scan_deep_run("mf_ivf_scan_deep_allow", q, Q, blocked, cell_blk, row_of, Npad, N, C, d, max_cell_blocks, probes, nprobe, k, S,
                              excl_off, excl_idx, idx_base, true, allow, n_masks, allow_of, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------- deep lists from the quantised cells ----
+// The scan of mf_pq.hip with the keeping above: lists of R <= 1,024 candidates, G * R of a query within the deep merge's keys.
+// Static LDS: the query's tables, M KiB, beside the buffer -- M * 1024 + IVFD_BUF * 8 + 16 bytes, 34 KiB at M = 2, 96 KiB + 16
+// at M = 64 (a CU's 160 KiB hold two workgroups at M = 32, one at M = 64).
+static constexpr MfCellsLimits PQD_LISTS{MF_TOPK_DEEP_MAX_K, MF_TOPK_MERGE_DEEP_MAX_KEYS, 'R'};
+
+#define MF_SCAN_KERNEL pq_deep_scan_kernel
+#define MF_SCAN_ALLOW false
+#include "mf_pq_deep_scan.inc"
+#undef MF_SCAN_KERNEL
+#undef MF_SCAN_ALLOW
+#define MF_SCAN_KERNEL pq_deep_scan_allow_kernel
+#define MF_SCAN_ALLOW true
+#include "mf_pq_deep_scan.inc"
+#undef MF_SCAN_KERNEL
+#undef MF_SCAN_ALLOW
+
+extern "C" int mf_pq_deep_plan(int64_t Q, int nprobe, int R, int64_t max_cell_blocks, int64_t* out4) {
+    return mf_cells_plan("mf_pq_deep_plan", PQD_LISTS, Q, nprobe, R, max_cell_blocks, out4);
+}
+
+extern "C" size_t mf_pq_deep_ws_bytes(int64_t Q, int nprobe, int R, int64_t max_cell_blocks) {
+    return mf_cells_ws_bytes(PQD_LISTS, Q, nprobe, R, max_cell_blocks);
+}
+
+// Both exports: mf_pq_scan's checks in its order and words, with the deep limits.
+static int pq_scan_deep_run(const char* who, const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub,
+                            const int64_t* cell_blk, const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks,
+                            const int64_t* probes, const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off,
+                            const int64_t* excl_idx, int64_t idx_base, bool with_allow, const uint64_t* allow, int64_t n_masks,
+                            const int64_t* allow_of, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    const bool pointers = q && codes && codebooks && cell_blk && row_of && probes && probe_scores && ws;
+    if (const int rc = mf_cells_check_shape(who, PQD_LISTS, pointers, Q, Npad, N, C, d, max_cell_blocks, nprobe, R, S)) return rc;
+    if (!pq_dsub_ok(dsub) || d / dsub > PQ_MAX_M)
+        return mf_set_error(MF_ENOTSUP, "%s: sub-vector length %d not in {4,8,16} or more than %d sub-vectors", who, dsub, PQ_MAX_M);
+    if (const int rc = mf_cells_check_lists(who, PQD_LISTS, Q, Npad, N, max_cell_blocks, nprobe, R, S, excl_off, excl_idx, idx_base, ws_bytes))
+        return rc;
+    if (with_allow)
+        if (const int rc = mf_cells_check_allow(who, allow, n_masks, allow_of, Npad)) return rc;
+    const int64_t G = (int64_t)nprobe * S;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PqScanParams p{q, codebooks, static_cast<const unsigned char*>(codes), cell_blk, row_of, probes, probe_scores, Q, C, nprobe, S, R,
+                   excl_off, excl_idx, idx_base, static_cast<long long*>(ws),
+                   {reinterpret_cast<const unsigned long long*>(allow), allow_of, n_masks, Npad / 64}};
+    const int kp = ivfd_kept(R);
+    const dim3 grid((unsigned)(Q * G));
+    if (with_allow) {
+        PQ_DISPATCH(d, dsub, { MF_TIMED("pq_scan_deep_allow", s, { pq_deep_scan_allow_kernel<M, DSUB><<<grid, IVFD_PASS, 0, s>>>(p, kp); }); });
+    } else {
+        PQ_DISPATCH(d, dsub, { MF_TIMED("pq_scan_deep", s, { pq_deep_scan_kernel<M, DSUB><<<grid, IVFD_PASS, 0, s>>>(p, kp); }); });
+    }
+    return mf_check_launch(who);
+}
+
+extern "C" int mf_pq_scan_deep(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+                               const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks,
+                               const int64_t* probes, const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off,
+                               const int64_t* excl_idx, int64_t idx_base, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    return pq_scan_deep_run("mf_pq_scan_deep", q, Q, codes, codebooks, dsub, cell_blk, row_of, Npad, N, C, d, max_cell_blocks, probes,
+                            probe_scores, nprobe, R, S, excl_off, excl_idx, idx_base, false, nullptr, 0, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int mf_pq_scan_deep_allow(const float* q, int64_t Q, const void* codes, const float* codebooks, int dsub, const int64_t* cell_blk,
+                                     const int64_t* row_of, int64_t Npad, int64_t N, int64_t C, int d, int64_t max_cell_blocks,
+                                     const int64_t* probes, const float* probe_scores, int nprobe, int R, int S, const int64_t* excl_off,
+                                     const int64_t* excl_idx, int64_t idx_base, const uint64_t* allow, int64_t n_masks,
+                                     const int64_t* allow_of, void* ws, size_t ws_bytes, mf_stream_t stream) {
+    return pq_scan_deep_run("mf_pq_scan_deep_allow", q, Q, codes, codebooks, dsub, cell_blk, row_of, Npad, N, C, d, max_cell_blocks, probes,
+                            probe_scores, nprobe, R, S, excl_off, excl_idx, idx_base, true, allow, n_masks, allow_of, ws, ws_bytes, stream);
 }

@@ -34,63 +34,19 @@
 //     (mf_filter_cell_bits): a row whose bit is clear has key 0 before it meets the bound -- mf_pq_scan_allow.
 //   * pq_refine_kernel: a workgroup per query, a thread per merged candidate: the chain on the original row, then the
 //     top_k <= 64 by mf_row_topk (as the join of ivf_scan_kernel), stored with the standard tail.
+//   * pq_refine_deep_kernel: the refine of the deep lists (mf_ivf_deep.hip: pq_deep_scan_kernel, up to 1,024 candidates): a
+//     thread scores up to four candidates with the same chain, the keys are sorted in LDS (pq_sort_desc), the first k leave.
+// The geometry's dispatch, the sub-vector chain and the scans' parameters are mf_pq_tables.h's, shared with the deep scan.
 #include "mf_cells.h"
+#include "mf_pq_tables.h"
 #include "mf_select.h"
 
 static constexpr int PQ_THREADS = 64 * MF_CELLS_NW;
 static constexpr int PQ_MAX_K = 64;            // one wavefront holds the result
 static constexpr int PQ_MAX_R = PQ_THREADS;    // candidates per query: a thread each in the refine
-static constexpr int PQ_MAX_M = 64;            // 64 KiB of tables
 static constexpr int PQ_BUF = 1024;            // keys of the workgroup's buffer: PQ_MAX_R kept, then the waiting ones
 // lists of R <= 256 entries, G * R of a query within the keys mf_topk_merge_packed_deep holds in LDS
 static constexpr MfCellsLimits PQ_LISTS{PQ_MAX_R, MF_TOPK_MERGE_DEEP_MAX_KEYS, 'R'};
-
-static inline bool pq_dsub_ok(int dsub) { return dsub == 4 || dsub == 8 || dsub == 16; }
-
-#define PQ_DISPATCH_M(DS, d, ...)                                                          \
-    switch (d) {                                                                           \
-        case 32: { constexpr int M = 32 / DS, DSUB = DS; __VA_ARGS__; } break;              \
-        case 64: { constexpr int M = 64 / DS, DSUB = DS; __VA_ARGS__; } break;              \
-        case 128: { constexpr int M = 128 / DS, DSUB = DS; __VA_ARGS__; } break;            \
-        default: { constexpr int M = 256 / DS, DSUB = DS; __VA_ARGS__; } break;             \
-    }
-// (d in {32, 64, 128, 256} and dsub in {4, 8, 16} were checked: twelve pairs, M = 2 .. 64)
-#define PQ_DISPATCH(d, dsub, ...)                                                     \
-    switch (dsub) {                                                                        \
-        case 4: PQ_DISPATCH_M(4, d, __VA_ARGS__) break;                                    \
-        case 8: PQ_DISPATCH_M(8, d, __VA_ARGS__) break;                                    \
-        default: PQ_DISPATCH_M(16, d, __VA_ARGS__) break;                                  \
-    }
-
-// the chain over one sub-vector: mf_dot_chain's order for 8 and 16 channels, ascending for 4
-template <int DSUB, class A, class B>
-__device__ __forceinline__ float pq_chain(const A& a, const B& b) {
-    float acc = 0.f;
-    if constexpr (DSUB == 4) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc = __builtin_fmaf(a[t], b[t], acc);
-    } else {
-#pragma unroll
-        for (int g = 0; g < DSUB; g += 8) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                acc = __builtin_fmaf(a[g + t], b[g + t], acc);
-                acc = __builtin_fmaf(a[g + 4 + t], b[g + 4 + t], acc);
-            }
-        }
-    }
-    return acc;
-}
-
-template <int DSUB>
-__device__ __forceinline__ void pq_load_sub(float (&v)[DSUB], const float* __restrict__ src) {
-#pragma unroll
-    for (int c = 0; c < DSUB / 4; ++c) {
-        const f32x4 x = reinterpret_cast<const f32x4*>(src)[c];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) v[4 * c + t] = x[t];
-    }
-}
 
 // ---------------------------------------------------------------------- encode ----
 struct PqEncodeParams {
@@ -172,22 +128,6 @@ extern "C" int mf_pq_encode(const float* rows, int64_t N, int d, const float* ce
 }
 
 // ------------------------------------------------------------------------ scan ----
-struct PqScanParams {
-    const float* q;             // [Q][D]
-    const float* codebooks;     // [M][256][DSUB]
-    const unsigned char* codes; // the cell-ordered layout above
-    const int64_t* cell_blk;    // [C + 1]
-    const int64_t* row_of;      // [Npad]
-    const int64_t* probes;      // [Q][nprobe]
-    const float* probe_scores;  // [Q][nprobe]: chain(q, centroid of the probe)
-    int64_t Q, C;
-    int nprobe, S, R;
-    const int64_t *excl_off, *excl_idx;     // nullable
-    int64_t idx_base;
-    long long* out;             // [nprobe * S][Q][R] packed entries (mf_topk_io.h) of the approximate scores
-    MfCellsAllow allow;         // the ALLOW kernels' bitmap (mf_cells.h); the others never look at it
-};
-
 // buf[0, n) in descending order, n a power of two <= PQ_BUF; every thread of the workgroup calls it
 __device__ __forceinline__ void pq_sort_desc(unsigned long long* buf, int n) {
     const int tid = threadIdx.x;
@@ -320,4 +260,61 @@ extern "C" int mf_pq_refine(const float* q, int64_t Q, const float* items, int64
     hipStream_t s = static_cast<hipStream_t>(stream);
     MF_DISPATCH_D(d, { MF_TIMED("pq_refine", s, { pq_refine_kernel<D><<<dim3((unsigned)Q), PQ_THREADS, 0, s>>>(q, items, cand, R, k, N, idx_base, out_scores, out_idx); }); });
     return mf_check_launch("mf_pq_refine");
+}
+
+// ----------------------------------------------------------------- deep refine ----
+// The same refine for the lists of mf_pq_scan_deep: k and R up to PQ_BUF = MF_TOPK_DEEP_MAX_K.  A workgroup per query; thread t
+// scores candidates t, t + 256, .. (four at most) with pq_refine_kernel's arithmetic -- the canonical chain on the original row,
+// the key by the global row, key 0 for a -1 or out-of-range candidate --, the keys go to an LDS buffer of the power of two >= R
+// (64 at least), pq_sort_desc orders it, and the first k entries leave with the standard tail.  The candidates of a query are
+// distinct rows by contract (the merge's output): equal keys would be written twice.
+template <int D>
+__global__ __launch_bounds__(PQ_THREADS) void pq_refine_deep_kernel(const float* __restrict__ q, const float* __restrict__ items,
+                                                                    const int64_t* __restrict__ cand, int R, int k, int64_t N,
+                                                                    int64_t idx_base, float* __restrict__ out_scores,
+                                                                    int64_t* __restrict__ out_idx) {
+    __shared__ unsigned long long keys[PQ_BUF];
+    const int tid = threadIdx.x;
+    const int64_t qi = blockIdx.x;
+    int n = 64;
+    while (n < R) n <<= 1;                                         // (R <= PQ_BUF was checked)
+    mf_const_f32 qc = (mf_const_f32)q + (size_t)qi * D;
+    for (int c = tid; c < n; c += PQ_THREADS) {
+        unsigned long long key = 0ull;
+        if (c < R) {
+            const int64_t grow = cand[qi * R + c], local = grow - idx_base;
+            if (grow >= 0 && local >= 0 && local < N) {
+                const f32x4* x = reinterpret_cast<const f32x4*>(items + local * D);
+                float acc = 0.f;
+#pragma unroll 4
+                for (int g = 0; g < D / 8; ++g) {
+                    const f32x4 a = x[2 * g], b = x[2 * g + 1];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {                  // k order of mf_dot_chain
+                        acc = __builtin_fmaf(a[t], qc[8 * g + t], acc);
+                        acc = __builtin_fmaf(b[t], qc[8 * g + 4 + t], acc);
+                    }
+                }
+                key = mf_key_retrieval(acc, (unsigned)grow);
+            }
+        }
+        keys[c] = key;
+    }
+    __syncthreads();
+    pq_sort_desc(keys, n);                                         // (a barrier behind its last stage)
+    for (int i = tid; i < k; i += PQ_THREADS) mf_store_topk(out_scores, out_idx, qi, k, i, keys[i], 0);
+}
+
+extern "C" int mf_pq_refine_deep(const float* q, int64_t Q, const float* items, int64_t N, int d, const int64_t* cand, int R, int k,
+                                 int64_t idx_base, float* out_scores, int64_t* out_idx, mf_stream_t stream) {
+    if (!q || !items || !cand || !out_scores || !out_idx || Q <= 0 || N <= 0 || Q >= (1ll << 31))
+        return mf_set_error(MF_EINVAL, "mf_pq_refine_deep: bad argument");
+    if (k <= 0 || k > PQ_BUF) return mf_set_error(MF_ENOTSUP, "mf_pq_refine_deep: k = %d outside 1..%d", k, PQ_BUF);
+    if (R < k || R > PQ_BUF) return mf_set_error(MF_ENOTSUP, "mf_pq_refine_deep: R = %d outside k..%d", R, PQ_BUF);
+    if (!mf_width_ok(d)) return mf_set_error(MF_EINVAL, "mf_pq_refine_deep: embedding width %d not in {32,64,128,256}", d);
+    if (N >= (1ll << 31) || idx_base < 0 || idx_base + N > (1ll << 32))
+        return mf_set_error(MF_ENOTSUP, "mf_pq_refine_deep: item indices must fit 32 bits");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MF_DISPATCH_D(d, { MF_TIMED("pq_refine_deep", s, { pq_refine_deep_kernel<D><<<dim3((unsigned)Q), PQ_THREADS, 0, s>>>(q, items, cand, R, k, N, idx_base, out_scores, out_idx); }); });
+    return mf_check_launch("mf_pq_refine_deep");
 }

@@ -28,7 +28,7 @@ from . import losses as mf_losses
 from . import fused, models, optim
 from .logq import StreamingLogQ
 from .params import INDEX_PATH, LOGQ_PATH, PROCESSORS_JSON, TOP_K, TOWERS_PATH
-from .retrieval import ItemProcessor, PartitionedIndex, PositionMetrics, QuantizedIndex, RetrievalMetrics
+from .retrieval import MERGE_DEEP_MAX_KEYS, ItemProcessor, PartitionedIndex, PositionMetrics, QuantizedIndex, RetrievalMetrics
 
 FEATURE_BAGS_PATH = "feature_bags.safetensors"     # the feature towers' registered bags (save / load)
 ITEM_TAGS_PATH = "item_tags.safetensors"           # the items' tag words, written only when tags are set
@@ -99,10 +99,24 @@ class MatrixFactorizationLitConfig(models.ModelConfig):
         if not 1 <= self.refine_factor <= QuantizedIndex.MAX_CANDIDATES:
             msg = f"refine_factor must be in 1..{QuantizedIndex.MAX_CANDIDATES}: {self.refine_factor}"
             raise ValueError(msg)
-        if self.index_type == "quantized" and self.refine_factor * self.top_k > QuantizedIndex.MAX_CANDIDATES:
-            msg = (f"a quantized index refines at most {QuantizedIndex.MAX_CANDIDATES} candidates per query: "
-                   f"refine_factor * top_k = {self.refine_factor * self.top_k}")
-            raise ValueError(msg)
+        if self.index_type == "quantized" and self.top_k <= QuantizedIndex.TILE_MAX_K:
+            if self.refine_factor * self.top_k > QuantizedIndex.MAX_CANDIDATES:
+                msg = (f"a quantized index refines at most {QuantizedIndex.MAX_CANDIDATES} candidates per query: "
+                       f"refine_factor * top_k = {self.refine_factor * self.top_k}")
+                raise ValueError(msg)
+        elif self.index_type == "quantized":         # beyond 64 rows: the deep search (QuantizedIndex.serving_path), its limits
+            candidates = self.refine_factor * self.top_k
+            if self.top_k > QuantizedIndex.DEEP_MAX_K:
+                msg = f"a quantized index returns at most {QuantizedIndex.DEEP_MAX_K} rows per query: top_k = {self.top_k}"
+                raise ValueError(msg)
+            if candidates > QuantizedIndex.DEEP_MAX_CANDIDATES:
+                msg = (f"a quantized index refines at most {QuantizedIndex.DEEP_MAX_CANDIDATES} candidates per query beyond "
+                       f"{QuantizedIndex.TILE_MAX_K} rows: refine_factor * top_k = {candidates}")
+                raise ValueError(msg)
+            if self.num_probes * candidates > MERGE_DEEP_MAX_KEYS:
+                msg = (f"a quantized index merges at most {MERGE_DEEP_MAX_KEYS} candidates of a query's probes: "
+                       f"num_probes * refine_factor * top_k = {self.num_probes * candidates}")
+                raise ValueError(msg)
         if self.num_partitions is not None and self.num_partitions < 1:
             msg = f"num_partitions must be None (the default for the catalog's size) or at least 1: {self.num_partitions}"
             raise ValueError(msg)
@@ -463,7 +477,7 @@ class MatrixFactorizationLitModule(_Base):
             metric.update(pos, off, rating, ncand)
             return metric.compute()
         index = self.item_processor.index
-        _, rows = index.search(queries, self.config.top_k, exclude_csr=batch.get("history"), path=index.default_path(self.config.top_k))
+        _, rows = index.search(queries, self.config.top_k, exclude_csr=batch.get("history"), path=index.serving_path(self.config.top_k))
         metric.update(rows, off, ids, rating)
         return metric.compute()
 
@@ -490,7 +504,7 @@ class MatrixFactorizationLitModule(_Base):
         """``(scores, item rows)`` [Q, top_k] of the batch's users, histories excluded."""
         queries = self._queries(batch)
         index = self.item_processor.index
-        return index.search(queries, self.config.top_k, exclude_csr=batch.get("history"), path=index.default_path(self.config.top_k))
+        return index.search(queries, self.config.top_k, exclude_csr=batch.get("history"), path=index.serving_path(self.config.top_k))
 
     def training_step(self, batch, _: int = 0) -> torch.Tensor:
         losses = self.compute_losses(batch, step_name="train")

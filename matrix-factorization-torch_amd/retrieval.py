@@ -408,7 +408,13 @@ class ItemIndex:
         predictions): ``"auto"`` here, the cell scan that serves the depth on a ``PartitionedIndex``, ``"pq"`` on a quantised one."""
         return "auto"
 
-    # engine -> (workspace-size export, search export, workspace key, the source tensors behind the queries)
+    def serving_path(self, top_k: int) -> str:
+        """The ``path`` that serves ``top_k`` rows at every depth the index has a search for -- what ``ItemProcessor.search``, the
+        module's metrics and its predictions pass.  ``default_path`` here and on a ``PartitionedIndex``; a ``QuantizedIndex`` sends
+        lists beyond ``TILE_MAX_K`` rows to its deep search."""
+        return self.default_path(top_k)
+
+    # engine ->(workspace-size export, search export, workspace key, the source tensors behind the queries)
     _ENGINES = {
         "deep": ("mf_topk_deep_ws_bytes", "mf_topk_deep", "deep", lambda self: (self.embeddings,)),
         "scan": ("mf_topk_small_ws_bytes", "mf_topk_small", "small", lambda self: (self.blocked(),)),
@@ -781,6 +787,7 @@ class QuantizedIndex(PartitionedIndex):
     csrc/mf_pq.hip, DESIGN.md "Quantised cells".  ``path="cells"`` and ``path="exact"`` stay the parent's."""
 
     MAX_CANDIDATES = 256       # refine_factor * top_k: a thread each in mf_pq_refine
+    DEEP_MAX_CANDIDATES = 1024  # the same on path="pq_deep": mf_pq_scan_deep's lists, four candidates a thread in mf_pq_refine_deep
     SUB_LENGTHS = (4, 8, 16)   # channels per sub-vector
     MAX_SUB_VECTORS = 64       # 64 KiB of lookup tables
     TRAIN_ROWS = 65536         # rows the codebooks are trained on
@@ -831,6 +838,10 @@ class QuantizedIndex(PartitionedIndex):
     def default_path(self, top_k: int) -> str:  # noqa: ARG002
         """``"pq"``: the quantiser's own search at every depth it serves (``refine_factor * top_k <= MAX_CANDIDATES``)."""
         return "pq"
+
+    def serving_path(self, top_k: int) -> str:
+        """``"pq"`` up to ``TILE_MAX_K`` rows (where ``default_path`` and every limit stay what they were), ``"pq_deep"`` beyond."""
+        return "pq" if int(top_k) <= self.TILE_MAX_K else "pq_deep"
 
     @classmethod
     def _geometry(cls, d: int, m: int) -> tuple[int, int]:
@@ -919,32 +930,59 @@ class QuantizedIndex(PartitionedIndex):
             raise ValueError(msg)
         return rf * top_k
 
+    def _deep_candidates_of(self, top_k: int, refine_factor: int | None, nprobe: int) -> int:
+        """``path="pq_deep"``'s candidate depth: ``top_k`` in 1..``DEEP_MAX_K``, ``refine_factor * top_k`` within
+        ``DEEP_MAX_CANDIDATES``, and a list per probe at least within the deep merge's keys."""
+        rf = self.refine_factor if refine_factor is None else self._refine_factor(refine_factor)
+        top_k = int(top_k)
+        if not 1 <= top_k <= self.DEEP_MAX_K:
+            msg = f"the deep quantised search returns 1..{self.DEEP_MAX_K} rows per query: {top_k = }"
+            raise ValueError(msg)
+        if rf * top_k > self.DEEP_MAX_CANDIDATES:
+            msg = f"refine_factor * top_k must not exceed {self.DEEP_MAX_CANDIDATES} on path='pq_deep': {rf = }, {top_k = }"
+            raise ValueError(msg)
+        if nprobe * rf * top_k > MERGE_DEEP_MAX_KEYS:
+            msg = (f"nprobe * refine_factor * top_k must not exceed {MERGE_DEEP_MAX_KEYS} (the keys the merge of the lists holds): "
+                   f"{nprobe = }, {rf = }, {top_k = }")
+            raise ValueError(msg)
+        return rf * top_k
+
     def plan(self, num_queries: int, top_k: int = TOP_K, nprobe: int | None = None, refine_factor: int | None = None,
              path: str = "pq") -> dict[str, int]:
-        """The geometry ``search`` runs with (``mf_pq_plan`` for ``refine_factor * top_k`` candidates; ``path="cells"``: the
-        parent's): slices per cell, partial lists per query, workgroups."""
-        if path != "pq":
+        """The geometry ``search`` runs with (``mf_pq_plan`` for ``refine_factor * top_k`` candidates; ``path="pq_deep"``:
+        ``mf_pq_deep_plan``; ``path="cells"``: the parent's): slices per cell, partial lists per query, workgroups."""
+        if path not in ("pq", "pq_deep"):
             return super().plan(num_queries, top_k, nprobe, "cells_deep" if path == "cells_deep" else "cells")
-        r, nprobe = self._candidates_of(top_k, refine_factor), self._nprobe(nprobe)
+        if path == "pq_deep":
+            nprobe = self._nprobe(nprobe)
+            r = self._deep_candidates_of(top_k, refine_factor, nprobe)
+        else:
+            r, nprobe = self._candidates_of(top_k, refine_factor), self._nprobe(nprobe)
         if int(num_queries) < 1:
             msg = f"num_queries must be at least 1: {num_queries = }"
             raise ValueError(msg)
-        return self._plan(_lib.lib().mf_pq_plan, num_queries, nprobe, r)
+        return self._plan(_lib.lib().mf_pq_deep_plan if path == "pq_deep" else _lib.lib().mf_pq_plan, num_queries, nprobe, r)
 
     def candidates(self, queries: torch.Tensor, num_candidates: int, *, exclude: Sequence[Sequence[int]] | None = None,
                    exclude_csr: tuple[torch.Tensor, torch.Tensor] | None = None,
                    nprobe: int | None = None, slices: int | None = None, allow=None,
-                   allow_of=None) -> tuple[torch.Tensor, torch.Tensor]:
+                   allow_of=None, path: str = "pq") -> tuple[torch.Tensor, torch.Tensor]:
         """``(approximate scores [Q, R] fp32, GLOBAL rows [Q, R] int64)``: the ``R = num_candidates`` (1..``MAX_CANDIDATES``)
         admissible rows of the probed cells that the quantiser ranks first -- approximate score descending, row ascending,
         the -inf / -1 tail --, what ``search`` refines.  Three stages, none with a host read: the cells, ``mf_pq_scan``,
         ``mf_topk_merge_packed_deep``.  ``slices``: into how many workgroups a probed cell is cut (None: the plan's number;
         1..the largest cell's blocks, ``nprobe * slices * R`` within the merge's ``MERGE_DEEP_MAX_KEYS``) -- the lists are the
         same for every value.  ``allow`` / ``allow_of``: as in ``search`` (``mf_pq_scan_allow``) -- the candidates of the same call
-        with every inadmissible row on every query's exclusion list."""
+        with every inadmissible row on every query's exclusion list.  ``path="pq_deep"``: the same lists for ``R`` in
+        1..``DEEP_MAX_CANDIDATES`` from ``mf_pq_scan_deep`` -- for an ``R`` both paths take, the same bits."""
         r = int(num_candidates)
-        if not 1 <= r <= self.MAX_CANDIDATES:
-            msg = f"num_candidates must be in 1..{self.MAX_CANDIDATES}: {r = }"
+        if path not in ("pq", "pq_deep"):
+            msg = f"candidates come from the quantised scans, path in ('pq', 'pq_deep'): {path = }"
+            raise ValueError(msg)
+        deep = path == "pq_deep"
+        most = self.DEEP_MAX_CANDIDATES if deep else self.MAX_CANDIDATES
+        if not 1 <= r <= most:
+            msg = f"num_candidates must be in 1..{most}: {r = }"
             raise ValueError(msg)
         nprobe = self._nprobe(nprobe)
         if slices is not None and (not 1 <= int(slices) <= self.max_cell_blocks or nprobe * int(slices) * r > MERGE_DEEP_MAX_KEYS):
@@ -955,26 +993,29 @@ class QuantizedIndex(PartitionedIndex):
         self._allow_route(allow, allow_of, None, "pq", ("pq",))
         mask, allow_of = self._allow_masks(allow, allow_of, q.shape[0])
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, q.shape[0], q.device)
-        return self._candidates(q, r, nprobe, off, ids, 0 if slices is None else int(slices), mask, allow_of)
+        return self._candidates(q, r, nprobe, off, ids, 0 if slices is None else int(slices), mask, allow_of, deep)
 
     def _candidates(self, q: torch.Tensor, r: int, nprobe: int, off, ids, slices: int = 0, mask: CellMask | None = None,
-                    allow_of: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+                    allow_of: torch.Tensor | None = None, deep: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         base, probes = self.coarse.search(q, nprobe)
         lib = _lib.lib()
-        planned = self._plan(lib.mf_pq_plan, nq, nprobe, r)["lists"]
+        plan, ws_bytes, scan_plain, scan_allow = (
+            (lib.mf_pq_deep_plan, lib.mf_pq_deep_ws_bytes, lib.mf_pq_scan_deep, lib.mf_pq_scan_deep_allow) if deep else
+            (lib.mf_pq_plan, lib.mf_pq_ws_bytes, lib.mf_pq_scan, lib.mf_pq_scan_allow))
+        planned = self._plan(plan, nq, nprobe, r)["lists"]
         lists = nprobe * slices if slices else planned
-        ws = self._workspace(("pq", nq, nprobe, r, slices), max(lists * nq * r * 8, lib.mf_pq_ws_bytes(nq, nprobe, r, self.max_cell_blocks)))
+        ws = self._workspace(("pq_deep" if deep else "pq", nq, nprobe, r, slices),
+                             max(lists * nq * r * 8, ws_bytes(nq, nprobe, r, self.max_cell_blocks)))
         approx = torch.empty(nq, r, dtype=torch.float32, device=q.device)
         rows = torch.empty(nq, r, dtype=torch.int64, device=q.device)
         scan = (q.data_ptr(), nq, self.codes().data_ptr(), self.codebooks.data_ptr(), self.dsub, self.cell_blk.data_ptr(), self.row_of.data_ptr(),
                 self.row_of.numel(), n, self.num_partitions, d, self.max_cell_blocks, probes.data_ptr(), base.data_ptr(), nprobe, r, slices,
                 _lib.ptr(off), _lib.ptr(ids), self.idx_base)
         if mask is None:
-            _lib.check(lib.mf_pq_scan(*scan, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+            _lib.check(scan_plain(*scan, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
         else:
-            _lib.check(lib.mf_pq_scan_allow(*scan, mask.words.data_ptr(), mask.num_masks, _lib.ptr(allow_of), ws.data_ptr(), ws.numel(),
-                                            _lib.stream_ptr()))
+            _lib.check(scan_allow(*scan, mask.words.data_ptr(), mask.num_masks, _lib.ptr(allow_of), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
         _lib.check(lib.mf_topk_merge_packed_deep(ws.data_ptr(), lists, nq, r, approx.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
         return approx, rows
 
@@ -990,25 +1031,35 @@ class QuantizedIndex(PartitionedIndex):
         parent's.  ``where``: refused (``filtered``) -- the filter this index takes is ``allow``: a ``CellMask`` or anything
         ``cell_mask`` takes (``allow_of``: each query's mask among several), on ``path="pq"`` (``mf_pq_scan_allow``: a row the
         mask does not admit never becomes a candidate, so the refine only sees admitted rows) and on the parent's
-        ``path="cells"`` -- bit for bit the same search with the inadmissible rows on every query's exclusion list."""
-        self._allow_route(allow, allow_of, where, path, ("pq", "cells", "cells_deep"))
+        ``path="cells"`` -- bit for bit the same search with the inadmissible rows on every query's exclusion list.
+        ``path="pq_deep"``: the same contract and the same four stages for ``1 <= top_k <= DEEP_MAX_K`` with ``refine_factor *
+        top_k`` within ``DEEP_MAX_CANDIDATES`` and ``nprobe`` times that within ``MERGE_DEEP_MAX_KEYS`` (``mf_pq_scan_deep`` /
+        ``mf_pq_scan_deep_allow``, ``mf_pq_refine_deep``) -- where ``"pq"`` takes the shape too, the same bits.
+        ``serving_path(top_k)`` names the one of the two that serves a depth."""
+        self._allow_route(allow, allow_of, where, path, ("pq", "pq_deep", "cells", "cells_deep"))
         if where is not None:
             self.filtered(where)
-        if path != "pq":
+        if path not in ("pq", "pq_deep"):
             return super().search(queries, top_k, exclude=exclude, exclude_csr=exclude_csr, nprobe=nprobe, path=path, allow=allow,
                                   allow_of=allow_of)
-        r = self._candidates_of(top_k, refine_factor)
+        deep = path == "pq_deep"
+        if deep:
+            nprobe = self._nprobe(nprobe)
+            r = self._deep_candidates_of(top_k, refine_factor, nprobe)
+        else:
+            r = self._candidates_of(top_k, refine_factor)
+            nprobe = self._nprobe(nprobe)
         top_k = int(top_k)
-        nprobe = self._nprobe(nprobe)
         q = self._queries(queries)
         nq, n, d = q.shape[0], self.num_items, self.embeddings.shape[1]
         mask, allow_of = self._allow_masks(allow, allow_of, nq)
         off, ids = exclude_csr if exclude_csr is not None else _csr(exclude, nq, q.device)
-        _, cand = self._candidates(q, r, nprobe, off, ids, 0, mask, allow_of)
+        _, cand = self._candidates(q, r, nprobe, off, ids, 0, mask, allow_of, deep)
         scores = torch.empty(nq, top_k, dtype=torch.float32, device=q.device)
         rows = torch.empty(nq, top_k, dtype=torch.int64, device=q.device)
-        _lib.check(_lib.lib().mf_pq_refine(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, cand.data_ptr(), r, top_k, self.idx_base,
-                                           scores.data_ptr(), rows.data_ptr(), _lib.stream_ptr()))
+        refine = _lib.lib().mf_pq_refine_deep if deep else _lib.lib().mf_pq_refine
+        _lib.check(refine(q.data_ptr(), nq, self.embeddings.data_ptr(), n, d, cand.data_ptr(), r, top_k, self.idx_base, scores.data_ptr(),
+                          rows.data_ptr(), _lib.stream_ptr()))
         return scores, rows
 
 
@@ -1298,7 +1349,7 @@ class ItemProcessor:
             raise ValueError(msg)
         q = torch.as_tensor(np.asarray(embedding), dtype=torch.float32).reshape(1, -1).to(self.index.embeddings.device)
         rows = [self._row_of_id[i] for i in (exclude_item_ids or []) if i in self._row_of_id]
-        path = self.index.default_path(top_k)          # (a partitioned index: the deep cell scan beyond 64 rows)
+        path = self.index.serving_path(top_k)          # (the deep cell scan / the deep quantised search beyond 64 rows)
         if where is None:
             scores, idx = self.index.search(q, top_k, exclude=[rows], path=path)
         elif self.filter_mode == "mask":

@@ -3,6 +3,7 @@
 quantiser costs in recall and saves in memory.  The companion of tools/ivf_probe.py, whose helpers it shares.
 
     python tools/ivf_pq_probe.py [--out profiles/ivf_pq_probe.json]
+    python tools/ivf_pq_probe.py --deep [--catalogs 62423,4194304] [--out profiles/ivf_pq_deep_probe.json]     # path="pq_deep": deep_main
 
 Time.  Catalogs 62,423 x 128 and 2^22 x 128 (unit rows), each with the reference's default partition count and
 num_sub_vectors = 16 (the reference's width // 8), built by ``QuantizedIndex.build`` (10 + 10 iterations).  Per cell -- Q in
@@ -159,11 +160,124 @@ def recall(mf, name: str, rows: torch.Tensor, queries: torch.Tensor, res: dict) 
     print(json.dumps(entry), flush=True)
 
 
+# ------------------------------------------------------------------------------- --deep: path="pq_deep" beside its neighbours ----
+DEEP_QS, DEEP_DEPTHS, DEEP_NPROBES, DEEP_SHALLOW = (1, 32, 1024), ((100, 4), (256, 4), (1000, 1)), (1, 8, 16), ((20, 4), (64, 4))
+DEEP_WARMUP, DEEP_MAX_ITERS, DEEP_REGION_US = 3, 20, 20_000.0
+
+
+def deep_alternate(arms: dict, regions: int = base.REGIONS) -> dict:
+    """``ivf_probe.alternate`` with the calls of a region chosen per cell: a region of the slowest arm lasts about DEEP_REGION_US."""
+    for fn in arms.values():
+        for _ in range(DEEP_WARMUP):
+            fn()
+    torch.cuda.synchronize()
+    slowest = max(base.region_us(fn, 1) for fn in arms.values())
+    iters = int(min(DEEP_MAX_ITERS, max(1, DEEP_REGION_US // max(slowest, 1.0))))
+    return base.alternate(arms, iters=iters, regions=regions, warmup=0)
+
+
+def deep_stages(mf, index, q, csr, nprobe: int, k: int, rf: int) -> dict:
+    """The four stages of ``path="pq_deep"`` one by one, each on the inputs the search hands it."""
+    lib, L = mf._lib.lib(), mf._lib
+    nq, r = q.shape[0], rf * k
+    off, ids = csr if csr is not None else (None, None)
+    probe_scores, probes = index.coarse.search(q, nprobe)
+    probe_scores, probes = probe_scores.clone(), probes.clone()
+    lists = index.plan(nq, k, nprobe, rf, path="pq_deep")["lists"]
+    ws = L.workspace(lib.mf_pq_deep_ws_bytes(nq, nprobe, r, index.max_cell_blocks), q.device)
+    approx = torch.empty(nq, r, dtype=torch.float32, device=DEV)
+    cand = torch.empty(nq, r, dtype=torch.int64, device=DEV)
+    scores = torch.empty(nq, k, dtype=torch.float32, device=DEV)
+    rows = torch.empty(nq, k, dtype=torch.int64, device=DEV)
+    n, d = index.embeddings.shape
+
+    def scan():
+        L.check(lib.mf_pq_scan_deep(q.data_ptr(), nq, index.codes().data_ptr(), index.codebooks.data_ptr(), index.dsub, index.cell_blk.data_ptr(),
+                                    index.row_of.data_ptr(), index.row_of.numel(), n, index.num_partitions, d, index.max_cell_blocks,
+                                    probes.data_ptr(), probe_scores.data_ptr(), nprobe, r, 0, L.ptr(off), L.ptr(ids), index.idx_base,
+                                    ws.data_ptr(), ws.numel(), L.stream_ptr()))
+
+    def merge():
+        L.check(lib.mf_topk_merge_packed_deep(ws.data_ptr(), lists, nq, r, approx.data_ptr(), cand.data_ptr(), L.stream_ptr()))
+
+    def refine():
+        L.check(lib.mf_pq_refine_deep(q.data_ptr(), nq, index.embeddings.data_ptr(), n, d, cand.data_ptr(), r, k, index.idx_base,
+                                      scores.data_ptr(), rows.data_ptr(), L.stream_ptr()))
+
+    scan()
+    merge()
+    out = deep_alternate({"cells": lambda: index.coarse.search(q, nprobe), "scan": scan, "merge": merge, "refine": refine}, regions=STAGE_REGIONS)
+    return {name: v["us"] for name, v in out.items()}
+
+
+def deep_catalog(mf, n: int, res: dict, out_path: pathlib.Path) -> None:
+    rows = base.unit_rows(n, D, seed=n % 1000)
+    index, info = timed_build(mf, rows)
+    res["builds"].append(info)
+    print(json.dumps(info), flush=True)
+    exact = mf.retrieval.ItemIndex(rows)
+    queries = base.unit_rows(max(DEEP_QS), D, seed=7)
+    g = np.random.default_rng(1)
+    for nq in DEEP_QS:
+        q = queries[:nq].contiguous()
+        lists = {0: None, 150: mf.retrieval._csr([distinct_rows(g, n, 150) for _ in range(nq)], nq, DEV)}
+        for nprobe in DEEP_NPROBES:
+            for k, rf in DEEP_SHALLOW:                         # where both quantised paths serve the shape
+                cell = {"N": n, "Q": nq, "k": k, "refine_factor": rf, "nprobe": nprobe}
+                cell.update(deep_alternate({"pq_deep": lambda: index.search(q, k, nprobe=nprobe, refine_factor=rf, path="pq_deep"),
+                                            "pq": lambda: index.search(q, k, nprobe=nprobe, refine_factor=rf, path="pq")}))
+                cell["pq_deep_over_pq"] = cell["pq_deep"]["us"] / cell["pq"]["us"]
+                res["shallow"].append(cell)
+                print(json.dumps(cell), flush=True)
+            for k, rf in DEEP_DEPTHS:
+                for excluded in EXCLUDED:
+                    csr = lists[excluded]
+                    cell = {"N": n, "Q": nq, "k": k, "refine_factor": rf, "nprobe": nprobe, "excluded_per_query": excluded,
+                            "slices": index.plan(nq, k, nprobe, rf, path="pq_deep")["slices"],
+                            "slices_cells_deep": index.plan(nq, k, nprobe, path="cells_deep")["slices"]}
+                    cell.update(deep_alternate({
+                        "pq_deep": lambda: index.search(q, k, exclude_csr=csr, nprobe=nprobe, refine_factor=rf, path="pq_deep"),
+                        "cells_deep": lambda: index.search(q, k, exclude_csr=csr, nprobe=nprobe, path="cells_deep"),
+                        "deep": lambda: exact.search(q, k, exclude_csr=csr, path="deep")}))
+                    cell["cells_deep_over_pq_deep"] = cell["cells_deep"]["us"] / cell["pq_deep"]["us"]
+                    cell["deep_over_pq_deep"] = cell["deep"]["us"] / cell["pq_deep"]["us"]
+                    cell["pq_deep_slower_than_cells_deep"] = bool(cell["pq_deep"]["us"] > cell["cells_deep"]["us"])
+                    cell["pq_deep_slower_than_deep"] = bool(cell["pq_deep"]["us"] > cell["deep"]["us"])
+                    cell["stages_us"] = deep_stages(mf, index, q, csr, nprobe, k, rf)
+                    res["cells"].append(cell)
+                    print(json.dumps(cell), flush=True)
+                    out_path.write_text(json.dumps(res, indent=1) + "\n")
+
+
+def deep_main(mf, args) -> None:
+    """``--deep``: ``path="pq_deep"`` beside ``path="cells_deep"`` of the same index (the parent's exact scan of the same cells,
+    which builds the cell-ordered fp32 copy) and ``ItemIndex.search(path="deep")`` on the same rows -- Q in {1, 32, 1024} x
+    (top_k, refine_factor) in {(100, 4), (256, 4), (1000, 1)} x nprobe in {1, 8, 16} x {no exclusions, 150 per query}, the arms
+    alternating in one process, 7 regions per arm, the calls of a region chosen per cell; the four stages one by one; and at
+    (20, 4) and (64, 4) ``pq_deep`` beside ``pq``."""
+    out_path = pathlib.Path(args.out if args.out else ROOT / "profiles" / "ivf_pq_deep_probe.json")
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    res = {"protocol": {"regions": base.REGIONS, "warmup": DEEP_WARMUP, "stage_regions": STAGE_REGIONS,
+                        "iters": f"1..{DEEP_MAX_ITERS}, a region of the slowest arm about {DEEP_REGION_US:.0f} us",
+                        "arms": "alternate region by region", "cells_deep": "QuantizedIndex.search(path='cells_deep'): the parent's deep cell scan",
+                        "deep": "ItemIndex.search(path='deep') of the same library"},
+           "device": torch.cuda.get_device_name(0), "builds": [], "shallow": [], "cells": []}
+    for n in map(int, args.catalogs.split(",")):
+        deep_catalog(mf, n, res, out_path)
+    out_path.write_text(json.dumps(res, indent=1) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "ivf_pq_probe.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--deep", action="store_true", help="time path='pq_deep' (profiles/ivf_pq_deep_probe.json)")
+    ap.add_argument("--catalogs", default=",".join(map(str, CATALOGS)), help="with --deep: the catalog sizes to time")
     args = ap.parse_args()
     mf = importlib.import_module("matrix-factorization-torch_amd")
+    if args.deep:
+        deep_main(mf, args)
+        return
+    args.out = args.out or str(ROOT / "profiles" / "ivf_pq_probe.json")
     res = {"protocol": {"k": K, "refine_factor": REFINE, "iters": base.ITERS, "regions": base.REGIONS, "warmup": base.WARMUP,
                         "stage_regions": STAGE_REGIONS, "arms": "alternate region by region",
                         "cells": "QuantizedIndex.search(path='cells'): PartitionedIndex.search of the same library",
